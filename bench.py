@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: query image pairs / second through forward(grd, sat) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py starts its N ranks itself (one child
 process per GPU, before anything touches HIP) and relays rank 0's JSON line; it also runs under
@@ -15,7 +15,18 @@ or checkpoints).  One step = one forward over the batch + device-side post-proce
 cos/sin lookup) + the only collective of the path, an all_gather of the 20-byte-per-query results.
 Weak scaling: every rank processes its own batch; value = all ranks' queries / max-over-ranks time.
 
-Besides the contract line rank 0 prints (N = 1 only for everything but `roofline`):
+A plain run sets up, warms up, times --steps steps and prints one JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, plus the run's configuration).
+
+  --dump-outputs DIR  after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32):
+                      `rows` = the step's result (the gathered [N*B, 5] post-processing rows) and the forward's nine outputs
+                      (logits, heatmap, ori, ms1..ms6).  An output of more than 2^20 elements is stored as a fixed sample
+                      of its flattened values (the same seeded positions in every run, in ascending order), so the dump
+                      stays under 64 MB; inputs and weights are seeded, so two builds can be compared file by file.
+  --full              also measures the sub-results below and adds them to rank 0's line (N = 1 only for everything but
+                      `roofline`; --no-extra / --no-alt-precision / --no-cpu-baseline leave parts out).
+
+Added with --full:
   roofline       dominant MFMA kernel, timed per launch with hipEvents on the launch stream in one serial profiled
                  step after the timed region.  `achieved` / `frac` = FLOPs the kernel ISSUES on the matrix pipe
                  (tile padding included; Winograd F(2x2,3x3) issues 16 products per 2x2 tile) over its time and
@@ -46,6 +57,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0    # dense bf16 MFMA (bf16x3 mode only)
 PEAK_HBM_GBS = 8000.0
 GFLOP_PER_QUERY = {"vigor_samearea_fov360_b32": 56.37, "vigor_samearea_fov108_noise72": 54.13, "kitti_test1": 54.45,
                    "oxford_stream": 53.66}   # SURVEY 8d / BASELINE.md section 3
+DUMP_SAMPLE = 1 << 20     # --dump-outputs: elements kept of a larger output (10 files x 4 MB at most)
+DUMP_SEED = 0
 
 WORKLOADS = {
     # name: (variant, ctor kwargs, fov)
@@ -66,12 +79,16 @@ def parse_args():
     ap.add_argument("--workload", default="vigor_samearea_fov360_b32", choices=list(WORKLOADS))
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="fp32 = exact fp32 MFMA (default, the headline); bf16x3 = 3-term bf16 split (opt-in, ~1e-5 rel.)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-precision", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the batch-1 and config 3-5 sub-results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; large outputs as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, batch 1, pipeline, configs 3-5, bf16x3 and the CPU baseline (off: headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt-precision", action="store_true", help="with --full: skip the bf16x3 sub-result")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the batch-1, pipeline and config 3-5 sub-results")
     ap.add_argument("--cached-aerial", action="store_true",
                     help="streaming mode: the aerial tile is encoded once (outside the timed region) and every step runs forward_cached")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-launch profile table to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="print the per-launch profile table to stderr (runs the roofline step)")
     ap.add_argument("--dry-run", action="store_true",
                     help="test rigs only: exercise rank start-up, rendezvous (gloo), the per-step gather and the single-line "
                          "report on the CPU with fake result rows - measures nothing, prints no metric value")
@@ -251,8 +268,23 @@ def main() -> int:
         def step():
             outs = m.forward_cached(gg, cc) if cc is not None else m(gg, ss)
             rows = m.postprocess_rows(outs[1], outs[2])   # [B, 5] float rows written by the post-processing launch itself
-            return D.gather_results(rows)
+            return outs, D.gather_results(rows)
         return step
+
+    def dump_outputs(path, outs, res):
+        """The last timed step's result rows and forward outputs as float32 .npy files (see --dump-outputs)."""
+        import numpy as np
+        os.makedirs(path, exist_ok=True)
+        arrays = {"rows": res}
+        arrays.update(zip(["logits", "heatmap", "ori", "ms1", "ms2", "ms3", "ms4", "ms5", "ms6"], outs))
+        for name, t in arrays.items():
+            a = t.detach()
+            if a.numel() > DUMP_SAMPLE:   # flattened: one seeded position in each of DUMP_SAMPLE equal strata, the same in every run
+                gen = torch.Generator().manual_seed(DUMP_SEED)
+                edges = torch.arange(DUMP_SAMPLE + 1, dtype=torch.int64) * a.numel() // DUMP_SAMPLE
+                pos = edges[:-1] + (torch.rand(DUMP_SAMPLE, generator=gen, dtype=torch.float64) * (edges[1:] - edges[:-1])).long()
+                a = a.reshape(-1)[pos.to(a.device)]
+            np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
 
     step = make_step(model, grd, sat, cache)
     # first call of the headline plan: weight ingestion + plan build (+ measuring whatever launches the tuning table does not know)
@@ -270,12 +302,15 @@ def main() -> int:
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        res = step()
+        outs, res = step()
     torch.cuda.synchronize(dev)
     D.barrier()
     dt = time.perf_counter() - t0
     dt = D.max_over_ranks(dt, dev)
     assert res.shape[0] == world * args.batch
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs, res)
+    del outs
 
     total_queries = world * args.batch * args.steps
     two_streams = not (os.environ.get("CCVPE_STREAMS") == "1")
@@ -388,7 +423,7 @@ def main() -> int:
                 "stages": "uint8 1024x2048 + 640x640 (HBM resident) -> preprocess_resize -> forward -> postprocess -> eval_metrics -> gather",
                 "input_bytes_per_query": 1024 * 2048 * 3 + 640 * 640 * 3}
 
-    if rank == 0:
+    if rank == 0 and (args.full or args.breakdown):
         peak = PEAK_FP32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
         # ---- roofline of the dominant kernel: one extra profiled step, hipEvents around every launch ----
         rows = model.profile(grd, sat)
@@ -463,7 +498,8 @@ def main() -> int:
                       f"{by_ / (ms_ * 1e-3) / 1e9 if ms_ > 0 else 0:9.1f}", file=sys.stderr)
             for k, v in sorted(groups.items(), key=lambda kv: -kv[1][0]):
                 print(f"  group {k:28s} {v[0]:9.3f} ms  {100 * v[0] / total_ms:5.1f}%  n={v[3]}", file=sys.stderr)
-        extras = world == 1 and args.precision == "fp32" and not args.cached_aerial
+    if rank == 0:
+        extras = args.full and world == 1 and args.precision == "fp32" and not args.cached_aerial
         if extras and not args.no_extra:
             # BASELINE.json metric asks batch 1 AND 32; BASELINE.md section 5 lists configs 3-5
             line["batch1"] = latency_run(model, grd[:1].contiguous(), sat[:1].contiguous())
@@ -500,7 +536,7 @@ def main() -> int:
                                      "note": "fp32 operands split into 2 bf16, 3 bf16 MFMAs per product, fp32 accumulate; not the headline"}
             del alt
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(variant, kw, fov)
         print(json.dumps(line), flush=True)
     D.barrier()

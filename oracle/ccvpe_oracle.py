@@ -7,10 +7,9 @@ library.
 This is an independent fp32 PyTorch-CPU restatement of the reference algorithm, structured our
 way (functional, state_dict-driven, aerial descriptor map as one k2/s2 convolution, rolling match
 as a gather-correlation).  Each function cites the reference lines it follows.  Pinning:
-tests/test_oracle_vs_reference.py compares it tensor-for-tensor with the reference imported from
-/root/reference (in the build container only), and tests/test_oracle_golden.py checks it against
-the committed golden vectors under tests/golden/ that oracle/make_golden.py captured from the
-reference itself.  The reference ships no tests or golden vectors of its own.
+tests/test_oracle_vs_reference.py and tests/test_oracle_golden.py check it against the committed
+golden vectors under tests/golden/ that oracle/make_reference_golden.py and oracle/make_golden.py
+captured from the reference itself.  The reference ships no tests or golden vectors of its own.
 """
 from __future__ import annotations
 

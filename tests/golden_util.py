@@ -19,34 +19,45 @@ CONFIGS = {
     "vigor_prior180_b2": dict(variant="vigor_ori_prior", circular=True, ori_noise=180.0, fov=360.0, batch=2, seed=3),
 }
 
+# tests/test_oracle_vs_reference.py: (variant, circular, ori_noise, fov) at batch 1, seed 5 - all four model classes of the
+# reference; fixtures tests/golden/reference_<variant>.npz (oracle/make_reference_golden.py)
+REFERENCE_CASES = [
+    ("vigor_ori_prior", True, 36.0, 360.0),
+    ("vigor", True, None, 360.0),
+    ("kitti", False, None, 360.0),
+    ("oxford", False, None, 360.0),
+]
+REFERENCE_SEED = 5
+REFERENCE_LATTICE = 16384
+
 OUTPUT_NAMES = ["logits", "heatmap", "ori", "ms1", "ms2", "ms3", "ms4", "ms5", "ms6"]
 FULL_LIMIT = 32768
 LATTICE_TARGET = 16384
 
 
-def lattice(numel: int) -> np.ndarray:
+def lattice(numel: int, target: int = LATTICE_TARGET, full: int = FULL_LIMIT) -> np.ndarray:
     """Deterministic sample positions in a flattened tensor: everything for small tensors, otherwise
-    ~16k positions on an odd stride (odd => not aligned with the power-of-two image widths)."""
-    if numel <= FULL_LIMIT:
+    ~`target` (default 16k) positions on an odd stride (odd => not aligned with the power-of-two image widths)."""
+    if numel <= full:
         return np.arange(numel, dtype=np.int64)
-    stride = (numel + LATTICE_TARGET - 1) // LATTICE_TARGET
+    stride = (numel + target - 1) // target
     stride |= 1
     return np.arange(0, numel, stride, dtype=np.int64)
 
 
-def summarize(name: str, a: np.ndarray) -> Dict[str, np.ndarray]:
+def summarize(name: str, a: np.ndarray, target: int = LATTICE_TARGET, full: int = FULL_LIMIT) -> Dict[str, np.ndarray]:
     a = np.ascontiguousarray(a, dtype=np.float32)
     flat = a.reshape(-1)
     a64 = flat.astype(np.float64)
     return {
         f"{name}/shape": np.array(a.shape, dtype=np.int64),
-        f"{name}/values": flat[lattice(flat.size)].copy(),
+        f"{name}/values": flat[lattice(flat.size, target, full)].copy(),
         f"{name}/stats": np.array([a64.sum(), np.abs(a64).sum(), np.sqrt((a64 * a64).sum()), np.abs(a64).max()]),
         f"{name}/argmax": np.array([int(np.argmax(flat))], dtype=np.int64),
     }
 
 
-def compare(name: str, fx, got: np.ndarray, rtol: float) -> float:
+def compare(name: str, fx, got: np.ndarray, rtol: float, target: int = LATTICE_TARGET, full: int = FULL_LIMIT) -> float:
     """Assert `got` matches the fixture entry `name`; returns the scale-relative max error.
     Error is measured relative to the tensor's max |value| (fixture stats[3])."""
     got = np.ascontiguousarray(got, dtype=np.float32)
@@ -54,7 +65,7 @@ def compare(name: str, fx, got: np.ndarray, rtol: float) -> float:
     assert tuple(got.shape) == shape, f"{name}: shape {got.shape} != fixture {shape}"
     flat = got.reshape(-1)
     exp = fx[f"{name}/values"]
-    idx = lattice(flat.size)
+    idx = lattice(flat.size, target, full)
     assert idx.size == exp.size
     scale = float(fx[f"{name}/stats"][3])
     err = float(np.abs(flat[idx].astype(np.float64) - exp.astype(np.float64)).max()) / max(scale, 1e-30)

@@ -1,4 +1,4 @@
-"""Dev tool (GPU box): batch-1 latency exactly as bench.py reports it (`batch1` / `config5`): p50 / p99 of a synchronised step
+"""Dev tool (GPU box): batch-1 latency exactly as `bench.py --full` reports it (`batch1` / `config5`): p50 / p99 of a synchronised step
 (forward + device post-processing) and the back-to-back rate, for the VIGOR headline model and the Oxford streaming model.
 usage: python tools/b1_latency.py [n]      (environment switches such as CCVPE_SE_TICKET=0 apply)"""
 import os
