@@ -32,6 +32,74 @@ __global__ __launch_bounds__(256) void checksum_kernel(const uint32_t* __restric
 
 
 // ------------------------------------------------------------------------------------------------
+// environment switches: the library's only reader of the environment (INTEGRATION.md lists the variables)
+// ------------------------------------------------------------------------------------------------
+Switches read_switches() {
+    Switches s;
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    auto off = [](const char* name) { const char* e = getenv(name); return e && std::atoi(e) == 0; };   // set to 0
+    if (const char* e = getenv("CCVPE_AUTOTUNE")) s.autotune = std::atoi(e) != 0;
+    if (const char* e = getenv("CCVPE_FUSE_MBCONV")) s.fuse_mbconv = std::atoi(e);
+    if (const char* e = getenv("CCVPE_FUSE_L1")) s.fuse_level1 = std::atoi(e) != 0;
+    if (const char* e = getenv("CCVPE_WINOGRAD")) s.wino = std::atoi(e) != 0;
+    if (const char* e = getenv("CCVPE_GRAPH")) s.graph_mode = std::atoi(e) != 0;
+    if (const char* e = getenv("CCVPE_STREAMS")) s.two_streams = std::atoi(e) >= 2;
+    if (const char* e = getenv("CCVPE_PRECISION")) s.precision = (std::string(e) == "bf16x3") ? 1 : 0;
+    s.stem_dw = !off("CCVPE_STEM_DW");
+    if (const char* e = getenv("CCVPE_FRONT_SPREAD")) s.front_spread = std::atoi(e);
+    s.mbconv_image = !off("CCVPE_MBCONV_IMAGE");
+    s.se_ticket = !off("CCVPE_SE_TICKET");
+    if (const char* e = getenv("CCVPE_SE_PROLOGUE")) s.se_prologue = std::atoi(e) == 1;
+    s.split_planes = !set("CCVPE_NO_SPLIT_PLANES");
+    s.match_prep_early = !off("CCVPE_MATCH_PREP_EARLY");
+    s.match_wide = !off("CCVPE_MATCH_WIDE");
+    s.issue_interleaved = !off("CCVPE_ISSUE_ORDER");
+    s.log_schedule = set("CCVPE_LOG_SCHEDULE");
+    s.no_reuse = set("CCVPE_NO_REUSE");
+    s.tune_prefer_pw = set("CCVPE_TUNE_PREFER_PW");
+    if (const char* e = getenv("CCVPE_TUNE_PREFER_PROJ")) { s.tune_prefer_proj = true; s.tune_prefer_lat = std::strcmp(e, "lat") == 0; }
+    if (const char* e = getenv("CCVPE_TUNE_SPLITK")) s.tune_splitk = std::atoi(e);
+    s.tune_no_bf16x3 = set("CCVPE_TUNE_NO_BF16X3");
+    s.no_pw = set("CCVPE_NO_PW");
+    s.tune_ignore_table = set("CCVPE_TUNE_IGNORE_TABLE");
+    s.tune_lat_rows = set("CCVPE_TUNE_LAT_ROWS");
+    s.tune_lat_split = set("CCVPE_TUNE_LAT_SPLIT");
+    s.tune_no_fused_split = set("CCVPE_TUNE_NO_FUSED_SPLIT");
+    if (const char* e = getenv("CCVPE_TUNE_VERBOSE")) s.tune_verbose = e;
+    s.no_proj = set("CCVPE_NO_PROJ");
+    if (const char* e = getenv("CCVPE_WINO4_MIN_N")) s.wino4_min_n = std::atoi(e);
+    s.no_wino4 = set("CCVPE_NO_WINO4");
+    s.no_wino4x = set("CCVPE_NO_WINO4X");
+    s.pad_concat = !off("CCVPE_PAD_CONCAT");
+    if (const char* e = getenv("CCVPE_DIAG_SYNC_BEFORE")) s.diag_sync = e;
+    if (const char* e = getenv("CCVPE_DIAG_SNAP")) s.diag_snap = e;
+    return s;
+}
+
+// Largest micro-batch whose plan keeps every tensor below 2 GiB, under the switches `sw`.  A device-less stand-in handle: build_plan
+// only sizes tensors and records launches, it never touches HIP.  fuse_mbconv = 0 sizes the unfused (largest) form of every MBConv
+// block, fuse_level1 = false the unfused last decoder level (a handle may run with CCVPE_FUSE_L1=0 or a level-1 input the fused kernel
+// does not take), so the bound holds whatever flags the real handle has.
+static int max_micro_batch(const Switches& sw, int variant, float ori_noise, int grd_h, int grd_w) {
+    if (variant < 0 || variant > 3) return ccvpe_fail(CCVPE_EINVAL, "unknown variant %d", variant);
+    ccvpe_handle_s tmp;
+    tmp.cfg.variant = variant; tmp.cfg.ori_noise = ori_noise; tmp.cfg.micro_batch = 1;
+    tmp.vs = make_variant(variant);
+    tmp.sw = sw;
+    tmp.sw.fuse_mbconv = 0; tmp.sw.fuse_level1 = false; tmp.sw.two_streams = false; tmp.sw.graph_mode = 0;
+    const int n = (int)(ori_noise / 18.f);
+    for (int k = 0; k < 6; ++k) tmp.rolls[k] = (variant == CCVPE_VARIANT_VIGOR_ORI_PRIOR && k > 0) ? 2 * n + 1 : tmp.vs.n_rolls;
+    int lo = 0, hi = 1024;   // invariant: lo fits (0 = nothing fits / bad geometry), hi does not
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        Plan pl;
+        if (build_plan(&tmp, pl, mid, grd_h, grd_w) == 0) lo = mid; else hi = mid;
+    }
+    if (lo == 0) return ccvpe_fail(CCVPE_EINVAL, "ground size %d x %d is not valid for variant %d: %s", grd_h, grd_w, variant, ccvpe_err().c_str());
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
 extern "C" {
@@ -56,18 +124,8 @@ int ccvpe_create(const ccvpe_config* cfg, ccvpe_handle* out) {
     h->cfg = *cfg;
     if (h->cfg.micro_batch <= 0) h->cfg.micro_batch = 32;
     h->vs = make_variant(cfg->variant);
-    if (const char* e = getenv("CCVPE_AUTOTUNE")) h->autotune = std::atoi(e) != 0;
-    // the candidate-filter switches are diagnostics: with one of them set every plan is measured under it, table or not
-    for (const char* sw : {"CCVPE_TUNE_PREFER_PW", "CCVPE_TUNE_PREFER_PROJ", "CCVPE_TUNE_SPLITK", "CCVPE_TUNE_NO_BF16X3", "CCVPE_TUNE_BF16_ONLY", "CCVPE_NO_PW", "CCVPE_TUNE_IGNORE_TABLE"})
-        if (getenv(sw)) h->tuning_lookup = false;
-    if (const char* e = getenv("CCVPE_GRAPH")) h->graph_mode = std::atoi(e) != 0;
-    if (const char* e = getenv("CCVPE_FUSE_L1")) h->fuse_level1 = std::atoi(e) != 0;
-    if (const char* e = getenv("CCVPE_WINOGRAD")) h->wino = std::atoi(e) != 0;
-    if (const char* e = getenv("CCVPE_STREAMS")) h->two_streams = std::atoi(e) >= 2;
-    if (const char* e = getenv("CCVPE_FUSE_MBCONV")) h->fuse_mbconv = std::atoi(e);
-    if (const char* e = getenv("CCVPE_DIAG_SYNC_BEFORE")) h->diag_sync = e;
-    if (const char* e = getenv("CCVPE_DIAG_SNAP")) h->diag_snap = e;
-    if (const char* e = getenv("CCVPE_PRECISION")) h->cfg.reserved[0] = (std::string(e) == "bf16x3") ? 1 : 0;
+    h->sw = read_switches();
+    if (h->sw.precision) h->cfg.reserved[0] = *h->sw.precision;
     if (h->cfg.reserved[0] != 0 && h->cfg.reserved[0] != 1) { delete h; return ccvpe_fail(CCVPE_EINVAL, "unknown precision mode %d", cfg->reserved[0]); }
     const int n = (int)(cfg->ori_noise / 18.f);
     for (int k = 0; k < 6; ++k)
@@ -82,25 +140,7 @@ int ccvpe_create(const ccvpe_config* cfg, ccvpe_handle* out) {
 }
 
 int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t grd_h, int32_t grd_w) {
-    if (variant < 0 || variant > 3) return ccvpe_fail(CCVPE_EINVAL, "unknown variant %d", variant);
-    // a device-less stand-in handle: build_plan only sizes tensors and records launches, it never touches HIP.
-    // fuse_mbconv = 0 sizes the unfused (largest) form of every MBConv block, so the bound holds for every plan.
-    ccvpe_handle_s tmp;
-    tmp.cfg.variant = variant; tmp.cfg.ori_noise = ori_noise; tmp.cfg.micro_batch = 1;
-    tmp.vs = make_variant(variant);
-    // fuse_level1 = false sizes the unfused last decoder level too (a handle may run with CCVPE_FUSE_L1=0 or a level-1 input the
-    // fused kernel does not take), so the cap holds whatever flags the real handle has
-    tmp.fuse_mbconv = 0; tmp.fuse_level1 = false; tmp.two_streams = false; tmp.graph_mode = 0;
-    const int n = (int)(ori_noise / 18.f);
-    for (int k = 0; k < 6; ++k) tmp.rolls[k] = (variant == CCVPE_VARIANT_VIGOR_ORI_PRIOR && k > 0) ? 2 * n + 1 : tmp.vs.n_rolls;
-    int lo = 0, hi = 1024;   // invariant: lo fits (0 = nothing fits / bad geometry), hi does not
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        Plan pl;
-        if (build_plan(&tmp, pl, mid, grd_h, grd_w) == 0) lo = mid; else hi = mid;
-    }
-    if (lo == 0) return ccvpe_fail(CCVPE_EINVAL, "ground size %d x %d is not valid for variant %d: %s", grd_h, grd_w, variant, ccvpe_err().c_str());
-    return lo;
+    return max_micro_batch(read_switches(), variant, ori_noise, grd_h, grd_w);
 }
 
 int ccvpe_destroy(ccvpe_handle h) {
@@ -172,8 +212,8 @@ static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
         const size_t i = pl.issue_order.size() == n ? (size_t)pl.issue_order[k] : k;
         Op& op = pl.ops[i];
         for (int d : op.wait_on) HIPCHK(hipStreamWaitEvent(st[op.stream], pl.events[d], 0));
-        if (!h->diag_sync.empty() && op.name.find(h->diag_sync) != std::string::npos) HIPCHK(hipDeviceSynchronize());
-        const bool snap = !h->diag_snap.empty() && op.name == h->diag_snap;
+        if (!h->sw.diag_sync.empty() && op.name.find(h->sw.diag_sync) != std::string::npos) HIPCHK(hipDeviceSynchronize());
+        const bool snap = !h->sw.diag_snap.empty() && op.name == h->sw.diag_snap;
         auto take_snap = [&](int which) -> int {
             if (!h->snap[0]) {
                 h->snap_layout.clear();
@@ -214,7 +254,7 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         auto it = h->mb_cap.find({gh, gw});
         if (it == h->mb_cap.end()) {
             const std::string keep = ccvpe_err();
-            const int cap = ccvpe_max_micro_batch(h->cfg.variant, h->cfg.ori_noise, gh, gw);
+            const int cap = max_micro_batch(h->sw, h->cfg.variant, h->cfg.ori_noise, gh, gw);
             ccvpe_err() = keep;
             it = h->mb_cap.emplace(std::make_pair(gh, gw), cap).first;
         }
@@ -565,7 +605,7 @@ int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
     }
     if (h->snap[0]) {   // CCVPE_DIAG_SNAP: what the named launch's tensors held right before / right after it, in stream order
         for (int which = 0; which < 2; ++which) {
-            std::fprintf(f, "snap_%s %s", which ? "after" : "before", h->diag_snap.c_str());
+            std::fprintf(f, "snap_%s %s", which ? "after" : "before", h->sw.diag_snap.c_str());
             for (auto& e : h->snap_layout) {
                 unsigned long long* dd = nullptr;
                 unsigned long long v = 0;
@@ -602,7 +642,8 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
     std::vector<float> hw(nw), hb(Cout, 0.f);
     HIPCHK(hipMemcpy(hw.data(), w, nw * sizeof(float), hipMemcpyDefault));
     if (bias) HIPCHK(hipMemcpy(hb.data(), bias, Cout * sizeof(float), hipMemcpyDefault));
-    ccvpe_handle_s tmp;   // only its dev_allocs list / precision flag are used by the packer
+    ccvpe_handle_s tmp;   // only its dev_allocs list, precision flag and packer switches are used by the packer
+    tmp.sw = read_switches();
     tmp.cfg.reserved[0] = 1;   // also pack the bf16x3 planes so every tile id can be exercised
     PackedConv pc;
     const int taps = KH * KW;
@@ -629,14 +670,6 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
         tmp.dev_allocs.push_back(d);
         tmp.dev_alloc_bytes.push_back(fl * sizeof(float));
         p.partial = (float*)d; p.partial_floats = fl;
-    }
-    if (conv_igemm_tile_is_wino4p(tile) && H % 16 == 0 && W % 16 == 0) {   // split Winograd form: scratch for V = B^T d B
-        const size_t fl = (size_t)B * (H / 16) * (W / 16) * ((Cin + 15) / 16) * 9216;
-        void* d = nullptr;
-        if (hipMalloc(&d, fl * sizeof(float)) != hipSuccess) { cleanup(); return ccvpe_fail(CCVPE_ENOMEM, "Winograd V scratch"); }
-        tmp.dev_allocs.push_back(d);
-        tmp.dev_alloc_bytes.push_back(fl * sizeof(float));
-        p.wino4_v = (float*)d; p.wino4_v_floats = fl;
     }
     if (conv_igemm_tile_is_wino(tile) && !conv_wino_tile_supported(p, tile)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "layer is not Winograd-shaped (3x3, stride 1, pad 1, W %% 16 == 0, H %% 16 == 0, output channels a multiple of 4; F(4x4): >= 40 of them)"); }
     if (launch_conv_igemm(p, tile, st) != 0) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "unsupported conv geometry (KH*KW <= 16, Cin %% 8 == 0)"); }

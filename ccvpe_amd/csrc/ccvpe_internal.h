@@ -16,6 +16,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <optional>
 #include <set>
 #include <string>
 #include <type_traits>
@@ -105,11 +106,77 @@ static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 // when a pixel's piece is not a whole number of 64-byte lines (tools/ubench_strided_write.py: 40 of 56 channels 3.4 TB/s against 5.3
 // dense): the localisation decoder's level 2 (40 + 16 channels) is therefore laid out as [40 | 8 zero | 16] - 64 channels, pieces of
 // 192 and 64 bytes; the transposed conv has eight zero output columns (it writes the zeros), conv2.0 eight zero input columns.
-// CCVPE_PAD_CONCAT=0: the reference's widths.  Every other level of every variant already ends on a line.
-static int deconv_width(const DecLevel& l) {
-    static const bool pad = !(getenv("CCVPE_PAD_CONCAT") && std::atoi(getenv("CCVPE_PAD_CONCAT")) == 0);
+// pad = false (CCVPE_PAD_CONCAT=0): the reference's widths.  Every other level of every variant already ends on a line.
+static int deconv_width(const DecLevel& l, bool pad) {
     return (pad && l.skip > 0 && (l.dout * 4) % 64 != 0) ? round_up(l.dout, 16) : l.dout;
 }
+
+// ------------------------------------------------------------------------------------------------
+// environment switches: read once per handle by read_switches() (ccvpe_api.hip) at ccvpe_create.  Defaults are the
+// library's behaviour with nothing set; the comment of each field names its variable and the setting that changes it.
+// ------------------------------------------------------------------------------------------------
+struct Switches {
+    // handle
+    bool autotune = true;                 // CCVPE_AUTOTUNE=0: plans the tuning table does not cover run the shape heuristic's tiles
+    int fuse_mbconv = 1;                  // CCVPE_FUSE_MBCONV: 0 never, 1 where measured profitable (3x3 blocks), 2 every supported block
+    bool fuse_level1 = true;              // CCVPE_FUSE_L1=0 falls back to deconv / conv / tail launches
+    // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
+    // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
+    bool wino = true;
+    int graph_mode = 0;                   // 1: plans replay a captured hipGraph (CCVPE_GRAPH=1; opt-in since round 4, see build_plan), 0 eager launches
+    bool two_streams = true;              // CCVPE_STREAMS=1 issues everything on the caller's stream
+    std::optional<int> precision;         // CCVPE_PRECISION: 1 for "bf16x3", 0 for anything else; unset: the config's
+    // plan
+    bool stem_dw = true;                  // CCVPE_STEM_DW=0: stem and block 0's depthwise conv as two launches
+    std::optional<int> front_spread;      // CCVPE_FRONT_SPREAD: work items a fused MBConv front may spread to (unset: by encoder)
+    bool mbconv_image = true;             // CCVPE_MBCONV_IMAGE=0: no image-resident MBConv front
+    bool se_ticket = true;                // CCVPE_SE_TICKET=0: squeeze-excite as launches of its own
+    bool se_prologue = false;             // CCVPE_SE_PROLOGUE=1: squeeze-excite in the latency-form project GEMM's prologue
+    bool split_planes = true;             // CCVPE_NO_SPLIT_PLANES: bf16x3 plans keep every tensor fp32
+    bool match_prep_early = true;         // CCVPE_MATCH_PREP_EARLY=0: each matching level prepares inside its own launch
+    bool match_wide = true;               // CCVPE_MATCH_WIDE=0: the batch-32 form of the matching kernels at every batch
+    bool issue_interleaved = true;        // CCVPE_ISSUE_ORDER=0: two-stream plans are issued in plan order
+    bool log_schedule = false;            // CCVPE_LOG_SCHEDULE: print the two-stream schedule to stderr
+    bool no_reuse = false;                // CCVPE_NO_REUSE: every tensor keeps its memory
+    // tuner candidate filters (tests and diagnostics)
+    bool tune_prefer_pw = false;          // CCVPE_TUNE_PREFER_PW: pointwise tiles wherever they apply
+    bool tune_prefer_proj = false;        // CCVPE_TUNE_PREFER_PROJ: the deep-K project GEMM wherever it applies ...
+    bool tune_prefer_lat = false;         // ... =lat: its latency form only
+    std::optional<int> tune_splitk;       // CCVPE_TUNE_SPLITK=0: no split-K candidates
+    bool tune_no_bf16x3 = false;          // CCVPE_TUNE_NO_BF16X3
+    bool no_pw = false;                   // CCVPE_NO_PW: neither the pointwise nor the deep-K project tiles
+    bool tune_ignore_table = false;       // CCVPE_TUNE_IGNORE_TABLE: measure every plan
+    bool tune_lat_rows = false;           // CCVPE_TUNE_LAT_ROWS: also time the multi-row latency tiles
+    bool tune_lat_split = false;          // CCVPE_TUNE_LAT_SPLIT: also time split-K latency tiles
+    bool tune_no_fused_split = false;     // CCVPE_TUNE_NO_FUSED_SPLIT: no self-reducing split-K candidates
+    std::string tune_verbose;             // CCVPE_TUNE_VERBOSE=<name part>: print every candidate of the matching launches
+    // packer (part of the packed-weight cache key: pack_group())
+    bool no_proj = false;                 // CCVPE_NO_PROJ
+    int wino4_min_n = 40;                 // CCVPE_WINO4_MIN_N
+    bool no_wino4 = false;                // CCVPE_NO_WINO4
+    bool no_wino4x = false;               // CCVPE_NO_WINO4X
+    bool pad_concat = true;               // CCVPE_PAD_CONCAT=0 (deconv_width)
+    // diagnostics: CCVPE_DIAG_SYNC_BEFORE=<name part> drains the device before matching launches; CCVPE_DIAG_SNAP=<launch name> copies
+    // that launch's tensors aside (stream ordered) right before and right after it
+    std::string diag_sync, diag_snap;
+
+    // a candidate filter is set: plans are measured under it, table or not, and their choices are not recorded (ccvpe_tune.hip)
+    bool tune_filtered() const {
+        return tune_prefer_pw || tune_prefer_proj || tune_splitk || tune_no_bf16x3 || no_pw || tune_ignore_table || tune_lat_rows || tune_lat_split ||
+               tune_no_fused_split;
+    }
+    // the packer switches that differ from their defaults, as "NAME=value;" in a fixed order ("" when none does)
+    std::string pack_group() const {
+        std::string s;
+        if (no_proj) s += "CCVPE_NO_PROJ=1;";
+        if (wino4_min_n != 40) s += "CCVPE_WINO4_MIN_N=" + std::to_string(wino4_min_n) + ";";
+        if (no_wino4) s += "CCVPE_NO_WINO4=1;";
+        if (no_wino4x) s += "CCVPE_NO_WINO4X=1;";
+        if (!pad_concat) s += "CCVPE_PAD_CONCAT=0;";
+        return s;
+    }
+};
+Switches read_switches();
 
 // ------------------------------------------------------------------------------------------------
 // weights
@@ -167,8 +234,6 @@ struct Ctx {
     ccvpe_outputs out{};
     float* splitk_scratch = nullptr;
     size_t splitk_floats = 0;
-    float* wino_v = nullptr;           // pre-transformed input of the split Winograd form (kernels_wino4p.hip), per stream
-    size_t wino_v_floats = 0;
     unsigned* tickets = nullptr;       // the plan's last-arriver counters (ticket.h); every launch that draws tickets owns a range
     const float* cache_in = nullptr;   // aerial cache consumed by a "cached" plan
     float* cache_out = nullptr;        // aerial cache produced by an "encode" plan
@@ -180,8 +245,6 @@ struct Ctx {
         p.tickets = tickets ? tickets + conv_tick_off : nullptr;
         p.partial = splitk_scratch;
         p.partial_floats = splitk_floats;
-        p.wino4_v = wino_v;
-        p.wino4_v_floats = wino_v_floats;
         if (launch_conv_igemm(p, cfg, stream) != 0) ++conv_errors;
     }
 };
@@ -240,9 +303,9 @@ struct Plan {
     // tensor its own memory (lifetime-based reuse would add hidden dependencies between the streams).
     bool two_streams = false;
     Tensor scratch2;              // split-K slab scratch of the second stream
-    Tensor vscratch, vscratch2;   // V = B^T d B of the split Winograd F(4x4) form, one per stream (whole-plan lifetime)
     std::vector<hipEvent_t> events;   // one per signalling op + fork + join, created on first use
     std::vector<int> issue_order;     // two-stream plans: the order the launches are handed to the two streams (schedule())
+    bool issue_interleaved = true, log_schedule = false, no_reuse = false;   // the handle's switches of the same names (build_plan)
     ~Plan() {
         if (exec) (void)hipGraphExecDestroy(exec);
         for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
@@ -281,8 +344,7 @@ struct Plan {
             for (int i = 0; i < (int)ops.size(); ++i) q[ops[i].stream].push_back(i);
             size_t p[2] = {0, 0};
             std::vector<bool> issued(ops.size(), false);
-            static const bool plan_order = getenv("CCVPE_ISSUE_ORDER") && std::atoi(getenv("CCVPE_ISSUE_ORDER")) == 0;   // A/B switch: plan order
-            while (!plan_order && (p[0] < q[0].size() || p[1] < q[1].size())) {
+            while (issue_interleaved && (p[0] < q[0].size() || p[1] < q[1].size())) {
                 auto ready = [&](int s) {
                     if (p[s] >= q[s].size()) return false;
                     for (int d : ops[q[s][p[s]]].wait_on) if (!issued[d]) return false;
@@ -299,7 +361,7 @@ struct Plan {
             }
             if (issue_order.size() != ops.size()) { issue_order.resize(ops.size()); for (int i = 0; i < (int)ops.size(); ++i) issue_order[i] = i; }
         }
-        if (getenv("CCVPE_LOG_SCHEDULE"))
+        if (log_schedule)
             for (int i = 0; i < (int)ops.size(); ++i) {
                 std::fprintf(stderr, "op %3d s%d %-28s wait=%d uses=", i, ops[i].stream, ops[i].name.c_str(), ops[i].wait_on.empty() ? -1 : ops[i].wait_on[0]);
                 for (int id : ops[i].uses) std::fprintf(stderr, "%d ", id);
@@ -307,12 +369,9 @@ struct Plan {
             }
     }
     static constexpr size_t SPLITK_FLOATS = 32u << 20;   // 128 MiB: 16 slabs of M*N <= 2M outputs
-    static constexpr size_t WINO_V_FLOATS = 64u << 20;   // 256 MiB: upper bound of a V scratch (kernels_wino4p.hip)
     void set_scratch(Ctx& c, int stream) const {         // per-stream scratch pointers of a launch context
         const Tensor& sk = stream ? scratch2 : scratch;
-        const Tensor& vv = stream ? vscratch2 : vscratch;
         c.splitk_scratch = c.ptr(sk); c.splitk_floats = SPLITK_FLOATS;
-        c.wino_v = vv.id >= 0 ? c.ptr(vv) : nullptr; c.wino_v_floats = vv.id >= 0 ? (size_t)vv.C : 0;
     }
 
     // every kernel addresses a tensor with 32-bit byte offsets (raw buffer loads, `unsigned in_bytes`, the 0x80000000
@@ -357,11 +416,10 @@ struct Plan {
                 first[id] = std::min(first[id], i); last[id] = std::max(last[id], i);
                 smask[id] |= 1 << (two_streams ? ops[i].stream : 0);
             }
-        static const bool no_reuse = getenv("CCVPE_NO_REUSE") != nullptr;   // diagnostic: every tensor keeps its memory
         std::vector<bool> pinned(n, false);
         auto pin = [&](const Tensor& t) { if (t.id >= 0) { pinned[t.id] = true; first[t.id] = 0; last[t.id] = 1 << 30; } };
         if (debug || no_reuse) for (int i = 0; i < n; ++i) if (last[i] >= 0) pinned[i] = true;
-        pin(scratch); pin(scratch2); pin(vscratch); pin(vscratch2); pin(tune_cache);
+        pin(scratch); pin(scratch2); pin(tune_cache);
         if (use_graph)
             for (const Tensor* t : {&io_grd, &io_sat, &io_logits, &io_heat, &io_ori, &io_ms[0], &io_ms[1], &io_ms[2], &io_ms[3], &io_ms[4], &io_ms[5]}) pin(*t);
         for (int i = 0; i < n; ++i) if (smask[i] == 3) pinned[i] = true;
@@ -409,16 +467,9 @@ struct ccvpe_handle_s {
     std::set<std::string> skipped;
     bool finalized = false;
     bool debug = false;
-    bool autotune = true;
-    int fuse_mbconv = 1;          // CCVPE_FUSE_MBCONV: 0 never, 1 where measured profitable (3x3 blocks), 2 every supported block
-    bool fuse_level1 = true;      // CCVPE_FUSE_L1=0 falls back to deconv / conv / tail launches
-    // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
-    // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
-    bool wino = true;
-    int graph_mode = 0;           // 1: plans replay a captured hipGraph (CCVPE_GRAPH=1; opt-in since round 4, see build_plan), 0 eager launches
+    Switches sw;                  // environment switches, read at ccvpe_create
     hipStream_t capture_stream = nullptr;
     hipStream_t aux_stream = nullptr;   // second stream of two-stream plans
-    bool two_streams = true;      // CCVPE_STREAMS=1 issues everything on the caller's stream
     bool serial_issue = false;    // ccvpe_set_streams(h, 1): run two-stream plans in program order on one stream
     std::vector<void*> dev_allocs;
     std::vector<size_t> dev_alloc_bytes;   // parallel to dev_allocs (packed-weight cache: ccvpe_save_packed)
@@ -429,17 +480,13 @@ struct ccvpe_handle_s {
     DecoderW loc, ori;
     std::vector<std::unique_ptr<Plan>> plans;
     Plan* last_plan = nullptr;    // plan of the most recent forward (ccvpe_debug_dump_plan)
-    // diagnostics (environment, read at ccvpe_create): CCVPE_DIAG_SYNC_BEFORE=<name part> drains the device before matching
-    // launches; CCVPE_DIAG_SNAP=<launch name> copies that launch's tensors aside (stream ordered) right before and right after it
-    std::string diag_sync, diag_snap;
-    float* snap[2] = {nullptr, nullptr};
+    float* snap[2] = {nullptr, nullptr};   // CCVPE_DIAG_SNAP: the named launch's tensors before / after it
     size_t snap_floats = 0;
     std::vector<std::pair<int, size_t>> snap_layout;   // (tensor id, float offset inside a snapshot buffer)
     std::map<std::pair<int, int>, int> mb_cap;   // ground size -> ccvpe_max_micro_batch (2 GiB tensor bound)
     // tuning table (ccvpe_tune.hip): launch key -> (tile name, split-K code); launches found here are not measured again
     std::map<std::string, std::pair<std::string, int>> tuning;
     int tuned_plans = 0;          // plans this handle has (partly) tuned by measurement (ccvpe_tuning_generation)
-    bool tuning_lookup = true;    // false while a CCVPE_TUNE_* / CCVPE_NO_PW diagnostic switch is set
     float* arena = nullptr;
     size_t arena_floats = 0;
     void* post_scratch = nullptr;   // launch_postprocess: partial pairs and ticket counters for post_batch samples

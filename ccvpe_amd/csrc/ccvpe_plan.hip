@@ -44,8 +44,8 @@ static void plan_encoder(ccvpe_handle_s* h, Plan& pl, const EncoderW& ew, bool i
     static_pad(3, 2, lo, hi);
     int ch = conv_out(H, 3, 2), cw = conv_out(W, 3, 2);
     // stem + the depthwise conv of block 0 in one launch (block 0 has no expand conv; kernels_encoder.hip): the half-resolution 32-channel
-    // stem output never reaches HBM.  CCVPE_STEM_DW=0: two launches (read per plan: tests toggle it)
-    const bool stem_dw = !(getenv("CCVPE_STEM_DW") && std::atoi(getenv("CCVPE_STEM_DW")) == 0) && B0[0].e == 1 && B0[0].k == 3 && B0[0].s == 1 && B0[0].cin == 32 &&
+    // stem output never reaches HBM.  CCVPE_STEM_DW=0: two launches
+    const bool stem_dw = h->sw.stem_dw && B0[0].e == 1 && B0[0].k == 3 && B0[0].s == 1 && B0[0].cin == 32 &&
                          (size_t)B * 3 * H * W * sizeof(float) < ((size_t)1 << 31);   // (the kernel addresses its input through one 32-bit buffer descriptor)
     StemParams stem_sp{};
     stem_sp.B = B; stem_sp.H = H; stem_sp.W = W; stem_sp.OH = ch; stem_sp.OW = cw; stem_sp.pad_t = lo; stem_sp.pad_l = lo; stem_sp.circular = circular;
@@ -79,19 +79,18 @@ static void plan_encoder(ccvpe_handle_s* h, Plan& pl, const EncoderW& ew, bool i
         {
             const double share = (double)H * W / ((double)H * W + (double)CCVPE_SAT_HW * CCVPE_SAT_HW);
             const int dflt = is_grd ? std::max(64, std::min(128, (int)(256.0 * share / 16.0 + 0.5) * 16)) : 144;
-            mp.spread = getenv("CCVPE_FRONT_SPREAD") ? std::atoi(getenv("CCVPE_FRONT_SPREAD")) : dflt;   // (read per plan: tests toggle it)
+            mp.spread = h->sw.front_spread.value_or(dflt);
         }
         // small-spatial blocks: the whole expanded image of 16 channels lives in LDS (kernels_mbimg.hip); CCVPE_FUSE_MBCONV=0 / CCVPE_MBCONV_IMAGE=0 turn it off
-        const bool image_off = getenv("CCVPE_MBCONV_IMAGE") && std::atoi(getenv("CCVPE_MBCONV_IMAGE")) == 0;   // read per plan: tests toggle it
-        const bool image = b.e != 1 && bw.exp_lin != nullptr && h->fuse_mbconv != 0 && !image_off && mbconv_image_supported(mp);
+        const bool image = b.e != 1 && bw.exp_lin != nullptr && h->sw.fuse_mbconv != 0 && h->sw.mbconv_image && mbconv_image_supported(mp);
         const bool fused = image || (b.e != 1 && bw.exp_lin != nullptr && mbconv_front_supported(b.k, b.s, b.cin, mid) &&
-                           (h->fuse_mbconv == 2 || (h->fuse_mbconv == 1 && mbconv_front_profitable(b.k))));
+                           (h->sw.fuse_mbconv == 2 || (h->sw.fuse_mbconv == 1 && mbconv_front_profitable(b.k))));
         Tensor d = pl.alloc(B, oh, ow, mid);
         const bool with_stem = stem_dw && i == 0;
         // Squeeze-excite by ticket (round 4, ticket.h; model.py:113-118): the front kernel's last-arriving workgroup of a sample reduces the
-        // pooling partials and computes the gates - no launch of its own.  CCVPE_SE_TICKET=0 keeps the separate launches (read per plan:
-        // tests toggle it); kernels that take no ticket (plain depthwise, the workgroup form of the tile kernel) keep them too.
-        const bool ticket_on = !(getenv("CCVPE_SE_TICKET") && std::atoi(getenv("CCVPE_SE_TICKET")) == 0) && mid <= 1152 && bw.sq <= 64;
+        // pooling partials and computes the gates - no launch of its own.  CCVPE_SE_TICKET=0 keeps the separate launches; kernels that
+        // take no ticket (plain depthwise, the workgroup form of the tile kernel) keep them too.
+        const bool ticket_on = h->sw.se_ticket && mid <= 1152 && bw.sq <= 64;
         const int trows = !ticket_on ? 0 : with_stem ? stem_dw_tiles(oh, ow) : image ? mbconv_image_ticket_rows(mp) : fused ? mbconv_front_ticket_rows(mp) : 0;
         // Opt-in (CCVPE_SE_PROLOGUE=1; measured, not the default): latency plans (batch <= 4, blocks of <= 4096 rows) without a ticket either -
         // the image-resident front leaves its per-item squeeze rows and the latency-form project GEMM computes the gates in its prologue,
@@ -100,7 +99,7 @@ static void plan_encoder(ccvpe_handle_s* h, Plan& pl, const EncoderW& ew, bool i
         // now in front of its MFMAs, and its 128-register waves cannot keep all four kinds of requests in flight at once): 1.41 against
         // 1.28 ms per batch-1 frame.
         bool sep = false;
-        if (trows > 0 && image && bw.project.proj != nullptr && h->cfg.reserved[0] == 0 && getenv("CCVPE_SE_PROLOGUE") && std::atoi(getenv("CCVPE_SE_PROLOGUE")) == 1) {
+        if (trows > 0 && image && bw.project.proj != nullptr && h->cfg.reserved[0] == 0 && h->sw.se_prologue) {
             ConvParams q = conv_params(bw.project, nullptr, mid, B, oh, ow, oh, ow, 1, 0, 0, ACT_NONE);
             q.M = B * oh * ow;
             q.se_rows = reinterpret_cast<const float*>(1); q.se_nrows = trows * (mid / 16); q.se_sq = bw.sq;
@@ -257,32 +256,14 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     const VariantSpec& vs = h->vs;
     pl.B = B; pl.gh = gh; pl.gw = gw; pl.debug = h->debug;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
-    pl.two_streams = h->two_streams && !h->debug;
+    pl.two_streams = h->sw.two_streams && !h->debug;
+    pl.issue_interleaved = h->sw.issue_interleaved; pl.log_schedule = h->sw.log_schedule; pl.no_reuse = h->sw.no_reuse;
     if (pl.two_streams) pl.scratch2 = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
-    if (h->wino && h->cfg.reserved[0] == 0 && getenv("CCVPE_WINO4P")) {
-        // split Winograd form (kernels_wino4p.hip), opt-in: measured equal to or slower than the fused form on every decoder layer
-        // (profiles/r03_wino4_forms.md), so plans neither reserve its scratch nor time its tiles by default.  Room for the largest
-        // pre-transformed layer input (36 KiB per 16 x 16 pixel block and 16-channel group) that stays below 256 MiB
-        auto vneed = [&](const DecLevel* lv) {
-            size_t best = 0;
-            for (int j = 0; j < 5; ++j) {
-                const size_t hout = (size_t)16 << j, mbl = (size_t)B * (hout / 16) * (hout / 16);
-                for (int cin : {deconv_width(lv[j]) + lv[j].skip, lv[j].mid}) {
-                    const size_t f = mbl * ((cin + 15) / 16) * 9216;
-                    if (f <= Plan::WINO_V_FLOATS) best = std::max(best, f);
-                }
-            }
-            return best;
-        };
-        const size_t v0 = std::max(vneed(vs.loc), vneed(vs.ori)), v1 = vneed(vs.ori);   // stream 0's also serves a serial issue of both chains
-        if (v0) pl.vscratch = pl.alloc(1, 1, 1, (int)v0);
-        if (pl.two_streams && v1) pl.vscratch2 = pl.alloc(1, 1, 1, (int)v1);
-    }
     // hipGraph replay: opt-in since round 4 (CCVPE_GRAPH=1).  Rounds 2-3 replayed plans of <= 4 samples: with ~330 launches per frame the
     // host could not keep up.  A batch-1 frame is 137 launches now; issued eagerly (interleaved over the two streams, Plan::schedule) the
     // GPU starts on the first while the host still hands over the rest, and a synchronised frame takes 1.31 ms against 1.44 ms replayed
     // (the replay's set-up precedes its first kernel); back to back both run at the GPU's pace.
-    pl.use_graph = !cached && h->graph_mode == 1;
+    pl.use_graph = !cached && h->sw.graph_mode == 1;
     if (pl.use_graph) {
         pl.io_grd = pl.alloc(B, 3, gh, gw);
         pl.io_sat = pl.alloc(B, 3, CCVPE_SAT_HW, CCVPE_SAT_HW);
@@ -313,11 +294,11 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     for (int j = 0; j < 6; ++j) {
         const int hw_in = 8 << j;
         loc_in[j] = pl.alloc(B, hw_in, hw_in, 8 + vs.match_ch[j]);
-        loc_cat[j] = pl.alloc(B, hw_in * 2, hw_in * 2, deconv_width(vs.loc[j]) + vs.loc[j].skip);
-        ori_cat[j] = pl.alloc(B, hw_in * 2, hw_in * 2, deconv_width(vs.ori[j]) + vs.ori[j].skip);
+        loc_cat[j] = pl.alloc(B, hw_in * 2, hw_in * 2, deconv_width(vs.loc[j], h->sw.pad_concat) + vs.loc[j].skip);
+        ori_cat[j] = pl.alloc(B, hw_in * 2, hw_in * 2, deconv_width(vs.ori[j], h->sw.pad_concat) + vs.ori[j].skip);
         // bf16x3 mode: tensors consumed only by convolutions live as pre-split bf16 planes (same bytes), so the
         // consumers' K loops carry no fp32->bf16 conversion; level 1 (j == 5) feeds the fp32 tail and stays fp32
-        if (h->cfg.reserved[0] == 1 && j < 5 && !getenv("CCVPE_NO_SPLIT_PLANES")) { loc_cat[j].split = true; ori_cat[j].split = true; }
+        if (h->cfg.reserved[0] == 1 && j < 5 && h->sw.split_planes) { loc_cat[j].split = true; ori_cat[j].split = true; }
     }
     ori_in6 = pl.alloc(B, 8, 8, rpad + D);
 
@@ -327,8 +308,8 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     TapDst td[5];
     for (int t = 0; t < 5; ++t) {
         td[t].n = 2;
-        td[t].t[0] = loc_cat[t]; td[t].coff[0] = deconv_width(vs.loc[t]);
-        td[t].t[1] = ori_cat[t]; td[t].coff[1] = deconv_width(vs.ori[t]);
+        td[t].t[0] = loc_cat[t]; td[t].coff[0] = deconv_width(vs.loc[t], h->sw.pad_concat);
+        td[t].t[1] = ori_cat[t]; td[t].coff[1] = deconv_width(vs.ori[t], h->sw.pad_concat);
     }
     size_t coff[6];
     cache_layout(vs, B, coff);
@@ -337,7 +318,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     } else {
         for (int t = 0; t < 5; ++t) {   // cached encoder taps -> skip halves of the decoder concat buffers
             Tensor lc = loc_cat[t], oc = ori_cat[t];
-            const int lcoff = deconv_width(vs.loc[t]), ocoff = deconv_width(vs.ori[t]);
+            const int lcoff = deconv_width(vs.loc[t], h->sw.pad_concat), ocoff = deconv_width(vs.ori[t], h->sw.pad_concat);
             const size_t src_off = coff[t + 1];
             const int C = TAP_C[t];
             const long long P = (long long)B * TAP_HW[t];
@@ -399,7 +380,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         const DecLevel& l = lv[j];
         {
             const PackedConv* pc = &dw.deconv[j];
-            const int cout = deconv_width(l);   // (columns past l.dout: zero weights and biases, written as zeros)
+            const int cout = deconv_width(l, h->sw.pad_concat);   // (columns past l.dout: zero weights and biases, written as zeros)
             pl.add_conv(tag + ".deconv", {din, cat}, B * hin * hin, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
                 ConvParams p = conv_params(*pc, c.ptr(din), din.C, B, hin, hin, hin, hin, 1, 0, 0, ACT_NONE);
                 p.mode = MODE_DECONV; p.deconv_cout = cout;
@@ -421,7 +402,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
             }, 2.0 * B * hout * hout * 9.0 * cat.C * l.mid, 4.0 * B * hout * hout * ((double)cat.C + l.mid));
             pl.ops.back().bf16x3_only = cat.split;
             pl.ops.back().conv_cin = cat.C;
-            pl.ops.back().wino_ok = pc->wino != nullptr && !cat.split && h->wino && h->cfg.reserved[0] == 0;
+            pl.ops.back().wino_ok = pc->wino != nullptr && !cat.split && h->sw.wino && h->cfg.reserved[0] == 0;
             pl.ops.back().wino4_ok = pl.ops.back().wino_ok && pc->wino4 != nullptr;
             pl.ops.back().wino4x_ok = pl.ops.back().wino_ok && pc->wino4x != nullptr;
         }
@@ -437,7 +418,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
             }, 2.0 * B * hout * hout * 9.0 * l.mid * l.out, 4.0 * B * hout * hout * ((double)l.mid + l.out));
             pl.ops.back().bf16x3_only = mid.split;
             pl.ops.back().conv_cin = mid.C;
-            pl.ops.back().wino_ok = pc->wino != nullptr && !mid.split && h->wino && h->cfg.reserved[0] == 0;
+            pl.ops.back().wino_ok = pc->wino != nullptr && !mid.split && h->sw.wino && h->cfg.reserved[0] == 0;
             pl.ops.back().wino4_ok = pl.ops.back().wino_ok && pc->wino4 != nullptr;
             pl.ops.back().wino4x_ok = pl.ops.back().wino_ok && pc->wino4x != nullptr;
         }
@@ -468,7 +449,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     // The preparation launch of every matching level (rolled descriptor / Gm, Mk) depends on the ground descriptor only: the six of them are
     // moved in front of the first matching level, where the localisation stream otherwise waits for the aerial encoder (batch 1: ~40 us off the
     // critical path).  CCVPE_MATCH_PREP_EARLY=0: inside each level's launch as before.
-    const bool prep_early = !(getenv("CCVPE_MATCH_PREP_EARLY") && std::atoi(getenv("CCVPE_MATCH_PREP_EARLY")) == 0);
+    const bool prep_early = h->sw.match_prep_early;
     size_t first_match_op = (size_t)-1;
     std::vector<std::function<MatchParams(const Ctx&)>> prep_fills;
     std::vector<Tensor> prep_uses;
@@ -493,7 +474,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         }
         mp.rpad = rpad;
         mp.P = match_pixels_per_block(hw, C);
-        mp.no_wide = (getenv("CCVPE_MATCH_WIDE") && std::atoi(getenv("CCVPE_MATCH_WIDE")) == 0) ? 1 : 0;   // (read per plan: tests toggle it)
+        mp.no_wide = h->sw.match_wide ? 0 : 1;
         mp.cat_max_ld = 8 + C;
         mp.cat_all_ld = rpad + C;
         Tensor xin = x, lin = loc_in[k];
@@ -522,7 +503,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         pl.add("match" + std::to_string(k + 1), uses, [=](const Ctx& c) { launch_match(fill(c), c.stream); },
                4.0 * B * hw * (double)R * L[k], 4.0 * B * hw * (2.0 * C + R + 8));
         pl.taps["loc_in" + std::to_string(6 - k)] = {lin, 0, lin.C};
-        if (k == 5 && h->fuse_level1) { plan_level1_fused(h->loc, lin, vs.loc[5].din, 1, false, Tensor{}, "loc1"); break; }
+        if (k == 5 && h->sw.fuse_level1) { plan_level1_fused(h->loc, lin, vs.loc[5].din, 1, false, Tensor{}, "loc1"); break; }
         Tensor o = plan_level(h->loc, vs.loc, k, lin, loc_cat[k], "loc" + std::to_string(6 - k));
         if (k < 5) { pl.taps["loc_level" + std::to_string(6 - k)] = {o, 0, o.C}; x = o; }
         else loc_mid = o;
@@ -537,7 +518,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         }, 0.0, 0.0);
         std::rotate(pl.ops.begin() + first_match_op, pl.ops.begin() + n0, pl.ops.end());
     }
-    if (!h->fuse_level1) {
+    if (!h->sw.fuse_level1) {
         Tensor m = loc_mid;
         const float* tw = h->loc.tail_w;
         const float tb = h->loc.tail_b[0];
@@ -565,7 +546,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         if (h->debug) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
         bool fused_done = false;
         for (int j = 0; j < 6; ++j) {
-            if (j == 5 && h->fuse_level1) { plan_level1_fused(h->ori, xo, vs.ori[5].din, 2, true, raw, "ori1"); fused_done = true; break; }
+            if (j == 5 && h->sw.fuse_level1) { plan_level1_fused(h->ori, xo, vs.ori[5].din, 2, true, raw, "ori1"); fused_done = true; break; }
             Tensor o = plan_level(h->ori, vs.ori, j, xo, ori_cat[j], "ori" + std::to_string(6 - j));
             if (j < 5) { pl.taps["ori_level" + std::to_string(6 - j)] = {o, 0, o.C}; xo = o; }
             else ori_mid = o;
@@ -598,6 +579,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
 static int build_aerial_plan(ccvpe_handle_s* h, Plan& pl, int B) {
     const VariantSpec& vs = h->vs;
     pl.B = B; pl.gh = 0; pl.gw = 0; pl.mode = 1; pl.debug = false;
+    pl.no_reuse = h->sw.no_reuse;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
     EncOut senc;
     plan_encoder(h, pl, h->sat_enc, false, B, CCVPE_SAT_HW, CCVPE_SAT_HW, false, nullptr, senc, "sat");

@@ -37,7 +37,7 @@ static int apply_tuning(ccvpe_handle_s* h, Plan& pl, std::vector<bool>& known) {
         Op& op = pl.ops[i];
         if (!op.tile) continue;
         int t = -1, split = 0;
-        if (h->tuning_lookup) {
+        if (!h->sw.tune_filtered()) {
             const std::string key = tuning_key(h, pl, op);
             auto e = key.empty() ? h->tuning.end() : h->tuning.find(key);
             if (e != h->tuning.end()) { t = tile_by_name(e->second.first); split = e->second.second; }
@@ -115,6 +115,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
     HIPCHK(hipEventCreate(&e1));
     launch_fill_random(h->arena, pl.total, 0x9e3779b9u, nullptr);
     const int nt = conv_igemm_num_tiles();
+    const Switches& sw = h->sw;
     for (size_t oi = 0; oi < pl.ops.size(); ++oi) {
         Op& op = pl.ops[oi];
         if (!op.tile || (known && (*known)[oi])) continue;   // launches the tuning table covers are not measured
@@ -125,35 +126,29 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
         const int nkt = op.gemm_kpad / 32;
         for (int t = 1; t <= nt; ++t) {
             if (conv_igemm_tile_util(q, t) < 0.45) continue;
-            if (conv_igemm_tile_is_bf16x3(t) && (h->cfg.reserved[0] != 1 || getenv("CCVPE_TUNE_NO_BF16X3"))) continue;
-            if (const char* only = getenv("CCVPE_TUNE_BF16_ONLY"))   // diagnostic: keep only bf16x3 tiles whose name contains the string
-                if (conv_igemm_tile_is_bf16x3(t) && !std::strstr(conv_igemm_tile_name(t), only)) continue;
+            if (conv_igemm_tile_is_bf16x3(t) && (h->cfg.reserved[0] != 1 || sw.tune_no_bf16x3)) continue;
             if (op.bf16x3_only && !conv_igemm_tile_is_bf16x3(t)) continue;
             if (conv_igemm_tile_is_wino(t) && !op.wino_ok) continue;
             if (conv_igemm_tile_is_wino4x(t)) { if (!op.wino4x_ok || conv_igemm_tile_wino4x_cfg(t) != conv_wino4x_config(op.gemm_n)) continue; }
             else if (conv_igemm_tile_is_wino4(t) && !op.wino4_ok) continue;
-            static const bool prefer_pw = getenv("CCVPE_TUNE_PREFER_PW") != nullptr;   // test hook: pointwise tiles wherever they apply
-            if (prefer_pw && op.is_pw && !op.bf16x3_only && !conv_igemm_tile_is_pw(t) && op.gemm_kpad <= 512) continue;
-            static const bool prefer_proj = getenv("CCVPE_TUNE_PREFER_PROJ") != nullptr;   // test hook: the deep-K project GEMM wherever it applies
-            if (prefer_proj && op.proj_ok && !conv_igemm_tile_is_proj(t)) continue;
-            static const bool prefer_lat = prefer_proj && std::strcmp(getenv("CCVPE_TUNE_PREFER_PROJ"), "lat") == 0;   // ... its latency form only
-            if (prefer_lat && op.proj_ok && op.gemm_m <= 4096 && conv_igemm_tile_proj_rt(t) < 100) continue;
+            if (sw.tune_prefer_pw && op.is_pw && !op.bf16x3_only && !conv_igemm_tile_is_pw(t) && op.gemm_kpad <= 512) continue;
+            if (sw.tune_prefer_proj && op.proj_ok && !conv_igemm_tile_is_proj(t)) continue;
+            if (sw.tune_prefer_lat && op.proj_ok && op.gemm_m <= 4096 && conv_igemm_tile_proj_rt(t) < 100) continue;
             if (conv_igemm_tile_is_proj(t)) {
                 const int rt = conv_igemm_tile_proj_rt(t);   // row tiles per workgroup; >= 100: the latency form (small M only)
-                if (!op.proj_ok || !conv_proj_has(rt, op.gemm_n) || getenv("CCVPE_NO_PW")) continue;
+                if (!op.proj_ok || !conv_proj_has(rt, op.gemm_n) || sw.no_pw) continue;
                 if (rt >= 100 && (op.gemm_m > 4096 || op.gemm_kpad > 10240)) continue;   // (conv_proj_supported has the exact rule)
                 // the multi-row forms (conv_projl_r2 / r4) win the level-6 transposed convs by 1 us when timed alone (17.7 against 18.8 us) and lose
                 // in the frame, where the two decoders run that layer at the same time: 2 x 256 sixteen-wave workgroups, one per CU - 31.7 us
                 // each in the traced frame against ~24 for the four-wave implicit GEMM.  CCVPE_TUNE_LAT_ROWS=1 times them all the same.
-                static const bool lat_rows = getenv("CCVPE_TUNE_LAT_ROWS") != nullptr;
-                if (rt > 104 && (!lat_rows || op.gemm_m > 1024)) continue;
+                if (rt > 104 && (!sw.tune_lat_rows || op.gemm_m > 1024)) continue;
             } else if (conv_igemm_tile_is_pw(t)) {
                 ConvParams qq{}; qq.M = 16; qq.N = 1 << 20;
                 const int bn = (int)(((long long)qq.N) / conv_igemm_tile_blocks(qq, t));   // the tile's column width
-                if (!op.is_pw || op.bf16x3_only || !conv_pw_fits(bn, op.gemm_kpad) || getenv("CCVPE_NO_PW")) continue;
+                if (!op.is_pw || op.bf16x3_only || !conv_pw_fits(bn, op.gemm_kpad) || sw.no_pw) continue;
             }
             const long long blocks = conv_igemm_tile_blocks(q, t);
-            static const bool no_split = getenv("CCVPE_TUNE_SPLITK") && std::atoi(getenv("CCVPE_TUNE_SPLITK")) == 0;
+            const bool no_split = sw.tune_splitk == 0;
             // the persistent Winograd grids also try odd split factors: 160 work items on 256 resident workgroups (conv6.0) are
             // 3 rounds of quarter items with split 4 but 2 rounds of thirds with split 3
             static const int SPLITS[] = {1, 255, 2, 3, 4, 5, 6, 8, 12, 16};   // 255: F(4x4) tail split (kernels_wino4.hip); before the rest, whose limits end the loop
@@ -165,8 +160,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
                 // the latency form can split K (self-reducing, layers without a gate) but never wins: a sixteen-wave workgroup is alone on its CU
                 // and lives ~6 us whatever its share of K, so S times as many workgroups are S times as many rounds (tools/time_lat_gemm.py:
                 // level-6 transposed conv 18 / 25 / 41 / 73 us at S = 1 / 2 / 4 / 8).  CCVPE_TUNE_LAT_SPLIT=1 times them all the same.
-                static const bool lat_split_on = getenv("CCVPE_TUNE_LAT_SPLIT") != nullptr;
-                const bool lat_split = lat_split_on && conv_igemm_tile_proj_rt(t) >= 100 && op.gemm_m <= 256;
+                const bool lat_split = sw.tune_lat_split && conv_igemm_tile_proj_rt(t) >= 100 && op.gemm_m <= 256;
                 if (split > 1 && conv_igemm_tile_is_pw(t) && !lat_split) break;   // the pointwise persistent tiles keep K whole
                 if (split > 1 && split != 255) {   // split-K only where the grid underfills the chip and K is deep enough
                     // (the persistent Winograd grid also splits when the tile count is an awkward multiple of the
@@ -176,7 +170,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
                     if ((size_t)split * op.gemm_m * op.gemm_n > Plan::SPLITK_FLOATS) break;
                 }
                 for (int fuse = (split > 1 && conv_igemm_tile_is_pw(t)) ? 1 : 0; fuse < 2; ++fuse) {   // a split launch: with the reduce launch, and reducing itself (ticket.h) where the kernel can
-                if (fuse && (split <= 1 || split == 255 || !conv_igemm_tile_can_fuse_split(t) || pl.tickets == nullptr || getenv("CCVPE_TUNE_NO_FUSED_SPLIT"))) break;
+                if (fuse && (split <= 1 || split == 255 || !conv_igemm_tile_can_fuse_split(t) || pl.tickets == nullptr || sw.tune_no_fused_split)) break;
                 const int cfg = t | ((fuse ? split + SPLIT_FUSED : split) << 8);
                 *op.tile = cfg;
                 op.fn(c);   // warm-up (also sets the dynamic-LDS attribute on first use)
@@ -195,8 +189,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
                     HIPCHK(hipEventElapsedTime(&t, e0, e1));
                     ms = std::min(ms, t);
                 }
-                static const char* verbose = getenv("CCVPE_TUNE_VERBOSE");   // dev: print every candidate of the launches whose name contains the string
-                if (verbose && op.name.find(verbose) != std::string::npos)
+                if (!sw.tune_verbose.empty() && op.name.find(sw.tune_verbose) != std::string::npos)
                     std::fprintf(stderr, "tune %-28s %-28s split %3d%s: %8.1f us\n", op.name.c_str(), conv_igemm_tile_name(t), split, fuse ? " self-reducing" : "", 500.0 * ms);
                 if (ms < best_ms) { best_ms = ms; best = cfg; }
                 }
@@ -236,13 +229,12 @@ int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode) {
         HIPCHK(hipMemset(pl->tickets, 0, pl->ticket_words * sizeof(unsigned)));
     }
     std::vector<bool> known;
-    if (apply_tuning(h, *pl, known) > 0 && h->autotune) {
+    if (apply_tuning(h, *pl, known) > 0 && h->sw.autotune) {
         int rc2 = autotune_plan(h, *pl, &known);
         if (rc2) return rc2;
-        // choices made under a candidate-filter switch (CCVPE_TUNE_PREFER_*, CCVPE_NO_PW, CCVPE_TUNE_SPLITK ...) stay in this plan:
-        // the key does not name the switch, so recording them would hand the filtered tiles to every later default process
-        // through ccvpe_export_tuning / the user cache
-        if (h->tuning_lookup) {
+        // choices made under a candidate-filter switch (Switches::tune_filtered) stay in this plan: the key does not name the switch,
+        // so recording them would hand the filtered tiles to every later default process through ccvpe_export_tuning / the user cache
+        if (!h->sw.tune_filtered()) {
             record_tuning(h, *pl);
             h->tuned_plans++;
         }

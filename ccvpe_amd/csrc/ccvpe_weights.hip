@@ -69,14 +69,11 @@ static int upload(ccvpe_handle_s* h, const std::vector<float>& v, float** out) {
     return 0;
 }
 
-// Environment switches the packer branches on: ONE list, read by pack_conv's callers' cache key (ccvpe_pack_switches) - a packed-weight
-// file written under one setting must never be loaded under another (ccvpe_load_packed restores every descriptor from the file).
-static const char* const PACK_SWITCHES[] = {"CCVPE_NO_PROJ", "CCVPE_WINO4_MIN_N", "CCVPE_NO_WINO4", "CCVPE_NO_WINO4X", "CCVPE_PAD_CONCAT"};
+// The switches the packer branches on (Switches::pack_group): part of the caller's cache key, and recorded in a packed-weight file - a file
+// written under one setting must never be loaded under another (ccvpe_load_packed restores every descriptor from the file).
 extern "C" const char* ccvpe_pack_switches(void) {
     static thread_local std::string s;
-    s.clear();
-    for (const char* k : PACK_SWITCHES)
-        if (const char* v = getenv(k)) s += std::string(k) + "=" + v + ";";
+    s = read_switches().pack_group();
     return s.c_str();
 }
 
@@ -93,7 +90,7 @@ int pack_conv(ccvpe_handle_s* h, PackedConv& pc, int N, int taps, int cin, int c
     pc.N = N; pc.Kpad = kpad; pc.nchunks = K / 8; pc.cinp = cinp; pc.KH = KH; pc.KW = KW;
     int rc = upload(h, w, &pc.w);
     if (rc) return rc;
-    if (((KH == 1 && KW == 1 && taps == 1 && cin == cinp && conv_proj_wanted(N, cin)) || conv_proj_lat_wanted(taps, KH, KW, cinp)) && !getenv("CCVPE_NO_PROJ")) {
+    if (((KH == 1 && KW == 1 && taps == 1 && cin == cinp && conv_proj_wanted(N, cin)) || conv_proj_lat_wanted(taps, KH, KW, cinp)) && !h->sw.no_proj) {
         // fragment-order copy for kernels_proj.hip; columns follow the packed channel positions (cmap: the [8 | C] layout of the
         // decoder's transposed convs has zero columns where the score padding sits)
         std::vector<int> inv(cinp, -1);
@@ -111,15 +108,14 @@ int pack_conv(ccvpe_handle_s* h, PackedConv& pc, int N, int taps, int cin, int c
         // F(4x4,3x3) pays where the layer fills at least three of a workgroup's four 16-channel slices: measured faster than
         // every F(2x2) tile down to 40 output channels (conv2: 0.52 vs 0.64 ms), slower at 32 (conv2_ori: 0.41 vs 0.37);
         // 4x the direct weights, ~0.5 GB for the layers that qualify
-        static const int wino4_min_n = getenv("CCVPE_WINO4_MIN_N") ? std::atoi(getenv("CCVPE_WINO4_MIN_N")) : 40;
-        if (N >= wino4_min_n && (size_t)((cin + 15) / 16) * 4 * 9 * ((N + 15) / 16) * 1024 < (1u << 31) && !getenv("CCVPE_NO_WINO4")) {
+        if (N >= h->sw.wino4_min_n && (size_t)((cin + 15) / 16) * 4 * 9 * ((N + 15) / 16) * 1024 < (1u << 31) && !h->sw.no_wino4) {
             std::vector<float> u4;
             conv_wino4_pack(N, cin, get, u4);
             pc.wino4_bytes = u4.size() * sizeof(float);
             if ((rc = upload(h, u4, &pc.wino4))) return rc;
         }
         // xi-split F(4x4,3x3) for the narrow layers (one n-block of <= 128 channels; kernels_wino4x.hip)
-        if (N >= 24 && conv_wino4x_config(N) >= 0 && !getenv("CCVPE_NO_WINO4X")) {
+        if (N >= 24 && conv_wino4x_config(N) >= 0 && !h->sw.no_wino4x) {
             std::vector<float> ux;
             conv_wino4x_pack(N, cin, get, ux, &pc.wino4x_cfg);
             pc.wino4x_bytes = ux.size() * sizeof(float);
@@ -230,7 +226,7 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
         {   // ConvTranspose2d weight [cin][cout][2][2] -> rows n = (dy*2+dx)*cout + o
             const auto& w = h->host["deconv" + n + sfx + ".weight"];
             const auto& b = h->host["deconv" + n + sfx + ".bias"];
-            const int cin = lv[j].din, cout = lv[j].dout, cw = deconv_width(lv[j]);   // cw >= cout: zero columns (ccvpe_internal.h)
+            const int cin = lv[j].din, cout = lv[j].dout, cw = deconv_width(lv[j], h->sw.pad_concat);   // cw >= cout: zero columns (ccvpe_internal.h)
             int nscore = 0;
             if (every_level_scored) nscore = 1;
             else if (j == 0) nscore = nscore_l6;
@@ -270,7 +266,7 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
         }
         {
             const auto& w = h->host["conv" + n + sfx + ".0.weight"];
-            const int dout = lv[j].dout, cw = deconv_width(lv[j]);
+            const int dout = lv[j].dout, cw = deconv_width(lv[j], h->sw.pad_concat);
             const int cin = dout + lv[j].skip, cinw = cw + lv[j].skip, cout = lv[j].mid;   // cinw: with the zero columns behind the transposed conv's channels
             if ((rc = pack_conv(h, d.conva[j], cout, 9, cinw, cinw, identity_map(cinw),
                                 [&](int nn, int t, int c) {
@@ -312,8 +308,9 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
 // ingestion and the packing entirely.  The caller keys the file (ccvpe_amd/models.py: sha256 of the state_dict bytes,
 // variant, precision, library build digest); the header carries variant / precision / struct sizes and is checked.
 struct PackedHeader {
-    char magic[8];                 // "CCVPEPK3"
+    char magic[8];                 // "CCVPEPK4"
     int32_t variant, precision, circular, fuse_level1;
+    char pack_group[128];          // Switches::pack_group() of the handle that packed the weights
     uint64_t n_allocs, sz_encoder, sz_decoder, sz_conv;
     uint64_t n_relocs;             // (descriptor word index, buffer index) pairs behind the descriptor structs
 };
@@ -398,7 +395,7 @@ int ccvpe_finalize_weights(ccvpe_handle h) {
     if ((rc = build_decoder(h, h->loc, h->vs.loc, "", 1, true))) return rc;
     if ((rc = build_decoder(h, h->ori, h->vs.ori, "_ori", h->vs.n_rolls, false))) return rc;
     h->host.clear();
-    if (!level1_supported(h->loc.l1_cxp) || !level1_supported(h->ori.l1_cxp)) h->fuse_level1 = false;   // > 64 input channels
+    if (!level1_supported(h->loc.l1_cxp) || !level1_supported(h->ori.l1_cxp)) h->sw.fuse_level1 = false;   // > 64 input channels
     h->finalized = true;
     return 0;
 }
@@ -432,8 +429,9 @@ int ccvpe_save_packed(ccvpe_handle h, const char* path) {
         word0 += n / 8;
     });
     PackedHeader hd{};
-    std::memcpy(hd.magic, "CCVPEPK3", 8);
-    hd.variant = h->cfg.variant; hd.precision = h->cfg.reserved[0]; hd.circular = h->cfg.circular_padding; hd.fuse_level1 = h->fuse_level1 ? 1 : 0;
+    std::memcpy(hd.magic, "CCVPEPK4", 8);
+    std::snprintf(hd.pack_group, sizeof(hd.pack_group), "%s", h->sw.pack_group().c_str());   // (at most ~100 characters)
+    hd.variant = h->cfg.variant; hd.precision = h->cfg.reserved[0]; hd.circular = h->cfg.circular_padding; hd.fuse_level1 = h->sw.fuse_level1 ? 1 : 0;
     hd.n_allocs = h->dev_allocs.size(); hd.sz_encoder = sizeof(EncoderW); hd.sz_decoder = sizeof(DecoderW); hd.sz_conv = sizeof(PackedConv);
     hd.n_relocs = relocs.size() / 2;
     bool ok = std::fwrite(&hd, sizeof(hd), 1, f) == 1;
@@ -458,8 +456,10 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
     if (!f) return ccvpe_fail(CCVPE_EINVAL, "cannot open %s", path);
     PackedHeader hd{};
     auto bad = [&](const char* why) { std::fclose(f); return ccvpe_fail(CCVPE_EINVAL, "%s: %s", path, why); };
-    if (std::fread(&hd, sizeof(hd), 1, f) != 1 || std::memcmp(hd.magic, "CCVPEPK3", 8) != 0) return bad("not a packed-weight file of this library version");
+    if (std::fread(&hd, sizeof(hd), 1, f) != 1 || std::memcmp(hd.magic, "CCVPEPK4", 8) != 0) return bad("not a packed-weight file of this library version");
     if (hd.variant != h->cfg.variant || hd.precision != h->cfg.reserved[0] || hd.circular != h->cfg.circular_padding) return bad("packed for a different variant / precision / padding mode");
+    hd.pack_group[sizeof(hd.pack_group) - 1] = 0;
+    if (h->sw.pack_group() != hd.pack_group) return bad("packed under other packer switches (CCVPE_NO_PROJ, CCVPE_WINO4_MIN_N, CCVPE_NO_WINO4, CCVPE_NO_WINO4X, CCVPE_PAD_CONCAT)");
     if (hd.sz_encoder != sizeof(EncoderW) || hd.sz_decoder != sizeof(DecoderW) || hd.sz_conv != sizeof(PackedConv)) return bad("descriptor layout mismatch");
     if (hd.n_allocs == 0 || hd.n_allocs > 100000 || hd.n_relocs > 100000) return bad("implausible buffer / relocation counts");
     for (void* p : h->dev_allocs) (void)hipFree(p);
@@ -508,7 +508,7 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
         return ccvpe_fail(CCVPE_EINVAL, "%s: layer sizes do not match this variant", path);
     }
     h->host.clear();
-    h->fuse_level1 = hd.fuse_level1 != 0 && h->fuse_level1;
+    h->sw.fuse_level1 = hd.fuse_level1 != 0 && h->sw.fuse_level1;
     h->finalized = true;
     return 0;
 }

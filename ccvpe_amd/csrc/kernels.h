@@ -106,9 +106,6 @@ struct ConvParams {
     // deep-K / narrow-N project GEMM (kernels_proj.hip): the 1x1 weights in MFMA fragment order, null = not packed
     const float* proj_w;       // [Cin / 16 steps][ceil(N / 16) column tiles][64 lanes][4]
     unsigned proj_bytes;
-    // split F(4x4) form (kernels_wino4p.hip): per-stream scratch for the pre-transformed input V = B^T d B (null = unavailable)
-    float* wino4_v;
-    size_t wino4_v_floats;
     // Squeeze-excite in the prologue of the latency-form project GEMM (kernels_proj.hip, batch <= 4; model.py:113-118): instead of a gate
     // vector the launch gets the fused front kernel's per-item squeeze rows (ticket.h: SeTicket::sqpart) and the excite weights, and
     // every wave computes the gates of ITS K slice while its operands are in flight.  se_rows == null: `gate` as usual.
@@ -137,7 +134,7 @@ void launch_splitk_reduce(const ConvParams& p, hipStream_t s);
 struct Bf16x3Tile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); };
 int bf16x3_num_tiles();
 const Bf16x3Tile* bf16x3_tile(int i);
-struct WinoTile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); int f; bool pre; int xcfg; };   // f: output tile edge, 2 or 4; pre: split form (V pre-transformed); xcfg >= 0: xi-split configuration
+struct WinoTile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); int f; int xcfg; };   // f: output tile edge, 2 or 4; xcfg >= 0: xi-split configuration
 int wino_num_tiles();
 const WinoTile* wino_tile(int i);
 bool conv_wino_supported(const ConvParams& p);
@@ -147,11 +144,6 @@ bool conv_igemm_tile_is_wino4(int tile);
 void launch_wino4_64(const ConvParams& p, hipStream_t s);
 void launch_wino4_128(const ConvParams& p, hipStream_t s);
 bool conv_wino4_tail_applied();
-void launch_wino4p_64(const ConvParams& p, hipStream_t s);    // split form: input transform kernel + matrix kernel
-void launch_wino4p_128(const ConvParams& p, hipStream_t s);
-bool conv_wino4p_tail_applied();
-bool conv_wino4p_supported(const ConvParams& p);
-bool conv_igemm_tile_is_wino4p(int tile);
 bool conv_igemm_tile_is_wino4x(int tile);
 int conv_igemm_tile_wino4x_cfg(int tile);   // xi-split configuration of the tile, -1 for other tiles
 void launch_wino4x(const ConvParams& p, hipStream_t s);       // xi-split form (kernels_wino4x.hip)

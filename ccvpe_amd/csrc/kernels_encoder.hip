@@ -7,7 +7,6 @@
 #include "kernels.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace ccvpe {
 
@@ -17,62 +16,10 @@ __device__ __forceinline__ float swishf(float v) { return v * __builtin_amdgcn_r
 
 // ------------------------------------------------------------------------------------------------
 // Stem: 3x3 stride 2, 3 -> 32 channels, NCHW input -> NHWC output, BN + swish.
-// thread = (output pixel, group of 4 output channels); 8 consecutive lanes share a pixel so the
-// 27 input taps are broadcast loads and the store is a fully coalesced 16 B/lane stream.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stem_kernel(const StemParams p) {
-    // The grid stride is a multiple of 8, so a thread keeps its channel group for the whole launch and
-    // holds its 27 x 4 weights in registers (the LDS broadcast reads were the bottleneck before).
-    const int cg = threadIdx.x & 7;
-    float4 w[27];
-#pragma unroll
-    for (int i = 0; i < 27; ++i) w[i] = *reinterpret_cast<const float4*>(p.w + i * 32 + cg * 4);
-    const float4 bias = *reinterpret_cast<const float4*>(p.bias + cg * 4);
-    const long long total = (long long)p.B * p.OH * p.OW * 8;
-    for (long long it = (long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (long long)gridDim.x * 256) {
-        long long pix = it >> 3;
-        const int ox = (int)(pix % p.OW);
-        long long t = pix / p.OW;
-        const int oy = (int)(t % p.OH);
-        const int b = (int)(t / p.OH);
-        float4 acc = bias;
-        const float* inb = p.in + (size_t)b * 3 * p.H * p.W;
-        const int plane = p.H * p.W;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = oy * 2 - p.pad_t + ky;
-            const bool oky = (unsigned)iy < (unsigned)p.H;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                int ix = ox * 2 - p.pad_l + kx;
-                bool ok = oky;
-                if (p.circular) {
-                    if (ix < 0) ix += p.W;
-                    if (ix >= p.W) ix -= p.W;
-                } else {
-                    ok = ok & ((unsigned)ix < (unsigned)p.W);
-                }
-                const int o = ok ? iy * p.W + ix : 0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float v = inb[c * plane + o];
-                    v = ok ? v : 0.f;
-                    const float4 wv = w[(c * 3 + ky) * 3 + kx];
-                    acc.x = fmaf(v, wv.x, acc.x);
-                    acc.y = fmaf(v, wv.y, acc.y);
-                    acc.z = fmaf(v, wv.z, acc.z);
-                    acc.w = fmaf(v, wv.w, acc.w);
-                }
-            }
-        }
-        acc.x = swishf(acc.x); acc.y = swishf(acc.y); acc.z = swishf(acc.z); acc.w = swishf(acc.w);
-        *reinterpret_cast<float4*>(p.out + pix * 32 + cg * 4) = acc;
-    }
-}
-
-// Stem, tile form (default): a workgroup owns 32 x 8 output pixels x all 32 channels.  The (65 x 17 x 3)-float input patch is
-// staged in LDS once (coalesced rows; zero / wrapped outside the image), so the 27 taps of an output are LDS reads instead
-// of 27 global loads each touching 8 addresses (the pixel form above sat at ~2 TB/s on load issue).  Thread = (channel quad,
+// Tile form: a workgroup owns 32 x 8 output pixels x all 32 channels.  The (65 x 17 x 3)-float input patch is staged in LDS
+// once (coalesced rows; zero / wrapped outside the image), so the 27 taps of an output are LDS reads instead of 27 global loads
+// each touching 8 addresses (a pixel-per-thread form, removed after round 2, sat at ~2 TB/s on load issue).  Thread = (channel quad,
 // column of the tile): its 8 output rows share input rows (17 x 9 = 153 reads for 8 outputs), the 27 x 4 weights stay in
 // registers, stores are 16 B per lane with the 8 quads of a pixel contiguous.  Persistent grid.
 typedef float f32x4s __attribute__((ext_vector_type(4)));
@@ -166,16 +113,8 @@ __global__ __launch_bounds__(256) void stem_tile_kernel(const StemParams p) {
 }
 
 void launch_stem(const StemParams& p, hipStream_t s) {
-    static const bool pixel_form = getenv("CCVPE_STEM_TILE") && std::atoi(getenv("CCVPE_STEM_TILE")) == 0;   // A/B switch
-    if (!pixel_form) {
-        const int tiles = p.B * ((p.OW + ST_TW - 1) / ST_TW) * ((p.OH + ST_TH - 1) / ST_TH);
-        CCVPE_LAUNCH(stem_tile_kernel, dim3(std::min(tiles, 256 * 6)), dim3(256), 0, s, p);
-        return;
-    }
-    long long total = (long long)p.B * p.OH * p.OW * 8;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    CCVPE_LAUNCH(stem_kernel, dim3(blocks), dim3(256), 0, s, p);
+    const int tiles = p.B * ((p.OW + ST_TW - 1) / ST_TW) * ((p.OH + ST_TH - 1) / ST_TH);
+    CCVPE_LAUNCH(stem_tile_kernel, dim3(std::min(tiles, 256 * 6)), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------

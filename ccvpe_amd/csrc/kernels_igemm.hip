@@ -379,21 +379,19 @@ int conv_proj_lat_tile() {
     return 0;
 }
 bool conv_igemm_tile_is_wino4(int tile) { return conv_igemm_tile_is_wino(tile) && wino_tile((tile & 0xff) - NTILES - bf16x3_num_tiles() - 1)->f == 4; }
-bool conv_igemm_tile_is_wino4p(int tile) { return conv_igemm_tile_is_wino4(tile) && wino_tile((tile & 0xff) - NTILES - bf16x3_num_tiles() - 1)->pre; }
 static int wino4x_cfg_of(int tile) { return conv_igemm_tile_is_wino(tile) ? wino_tile((tile & 0xff) - NTILES - bf16x3_num_tiles() - 1)->xcfg : -1; }
 bool conv_igemm_tile_is_wino4x(int tile) { return wino4x_cfg_of(tile) >= 0; }
 int conv_igemm_tile_wino4x_cfg(int tile) { return wino4x_cfg_of(tile); }
 bool conv_wino_tile_supported(const ConvParams& p, int tile) {
     if (!conv_igemm_tile_is_wino(tile)) return false;
     if (conv_igemm_tile_is_wino4x(tile)) return conv_wino4x_supported(p) && p.wino4x_cfg == wino4x_cfg_of(tile);
-    if (conv_igemm_tile_is_wino4p(tile)) return conv_wino4p_supported(p);
     return conv_igemm_tile_is_wino4(tile) ? conv_wino4_supported(p) : conv_wino_supported(p);
 }
 bool conv_igemm_tile_is_bf16x3(int tile) { tile &= 0xff; return tile > NTILES && tile <= NTILES + bf16x3_num_tiles(); }
 // kernels that can reduce their own split-K (split code SPLIT_FUSED + S): the fp32 implicit GEMM and the fused F(4x4) / F(2x2) Winograd kernels
 bool conv_igemm_tile_can_fuse_split(int tile) {
     tile &= 0xff;
-    return (tile >= 1 && tile <= NTILES) || (conv_igemm_tile_is_wino(tile) && !conv_igemm_tile_is_wino4p(tile) && !conv_igemm_tile_is_wino4x(tile)) ||
+    return (tile >= 1 && tile <= NTILES) || (conv_igemm_tile_is_wino(tile) && !conv_igemm_tile_is_wino4x(tile)) ||
            conv_igemm_tile_proj_rt(tile) >= 100;   // (the latency form of the deep-K GEMM: layers without a gate)
 }
 static void tile_dims(int tile, int& bm, int& bn) {
@@ -545,7 +543,7 @@ int launch_conv_igemm(const ConvParams& p_in, int tile, hipStream_t s) {
     else if (conv_igemm_tile_is_pw(tile)) pw_tile(pw_index(tile))->launch(p, s);
     else if (conv_igemm_tile_is_wino(tile)) wino_tile(tile - NTILES - bf16x3_num_tiles() - 1)->launch(p, s);
     else (*bf16x3_tile(tile - NTILES - 1)).launch(p, s);
-    if (splitk == 255 && !(conv_igemm_tile_is_wino4p(tile) ? conv_wino4p_tail_applied() : conv_wino4_tail_applied())) g_last_tile = tile | (1 << 8);   // the tail split did not apply: a plain launch
+    if (splitk == 255 && !conv_wino4_tail_applied()) g_last_tile = tile | (1 << 8);   // the tail split did not apply: a plain launch
     return 0;
 }
 

@@ -12,7 +12,6 @@
 // [max | 7 zero pad | x/||x||] and optionally (c) the orientation concat buffer [scores | pad | x/||x||].
 #include "kernels.h"
 
-#include <cstdlib>
 
 namespace ccvpe {
 
@@ -405,13 +404,8 @@ int match_pixels_per_block(int HW, int C) {
     return P;
 }
 
-static bool match_use_mfma(const MatchParams& p) {
-    static const bool no_mfma = getenv("CCVPE_MATCH_MFMA") && std::atoi(getenv("CCVPE_MATCH_MFMA")) == 0;
-    return !no_mfma && match_mfma_supported(p);
-}
-
 void launch_match_prep(const MatchParams& p, hipStream_t s) {
-    if (match_use_mfma(p)) CCVPE_LAUNCH(match_mfma_prep_kernel, dim3(p.B, 8), dim3(256), 0, s, p, p.gg_scratch);
+    if (match_mfma_supported(p)) CCVPE_LAUNCH(match_mfma_prep_kernel, dim3(p.B, 8), dim3(256), 0, s, p, p.gg_scratch);
     else if (p.gg_scratch && match_small_supported(p)) CCVPE_LAUNCH(match_prep_kernel, dim3(p.B), dim3(256), 0, s, p, p.gg_scratch);
 }
 
@@ -420,14 +414,14 @@ void launch_match_prep_all(const MatchParams* ps, int n, hipStream_t s) {
     bool any = false;
     for (int i = 0; i < n && i < 6; ++i) {
         a.p[i] = ps[i];
-        a.form[i] = match_use_mfma(ps[i]) ? 2 : (ps[i].gg_scratch && match_small_supported(ps[i])) ? 1 : 0;
+        a.form[i] = match_mfma_supported(ps[i]) ? 2 : (ps[i].gg_scratch && match_small_supported(ps[i])) ? 1 : 0;
         any = any || a.form[i] != 0;
     }
     if (any) CCVPE_LAUNCH(match_prep_all_kernel, dim3(ps[0].B, 8, std::min(n, 6)), dim3(256), 0, s, a);
 }
 
 void launch_match(const MatchParams& p, hipStream_t s) {
-    if (match_use_mfma(p)) {
+    if (match_mfma_supported(p)) {
         if (!p.prep_done) CCVPE_LAUNCH(match_mfma_prep_kernel, dim3(p.B, 8), dim3(256), 0, s, p, p.gg_scratch);
         const size_t lds = ((size_t)16 * (p.C + 4) + 4 * 2 * 2 * 256 + 32 * 16) * sizeof(float);
         const size_t lds16 = ((size_t)16 * (p.C + 4) + 16 * 2 * 2 * 256 + 32 * 16) * sizeof(float);

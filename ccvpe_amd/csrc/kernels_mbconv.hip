@@ -15,7 +15,6 @@
 #include "kernels.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace ccvpe {
 
@@ -392,8 +391,7 @@ bool mbconv_front_supported(int k, int s, int cin, int mid) {
 bool mbconv_front_profitable(int k) { return k == 3; }
 
 static bool wave_form_serves(const MbFrontParams& p) {
-    static const bool wave_form = !(getenv("CCVPE_MBCONV_WAVE") && std::atoi(getenv("CCVPE_MBCONV_WAVE")) == 0);   // CCVPE_MBCONV_WAVE=0: workgroup form
-    return wave_form && p.k == 3 && p.cinp <= 48 && p.cinp % 16 == 0 && p.mid % 16 == 0;
+    return p.k == 3 && p.cinp <= 48 && p.cinp % 16 == 0 && p.mid % 16 == 0;
 }
 
 // only the wave-local form takes a squeeze-excite ticket (four tiles per workgroup share a pooling partial row)

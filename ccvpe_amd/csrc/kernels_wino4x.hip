@@ -17,7 +17,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <thread>
 #include <type_traits>
 
@@ -458,8 +457,7 @@ static void launch_wino4x_cfg(const ConvParams& p_in, hipStream_t s) {
     auto kern = conv_wino4x_kernel<NW, S0, S1>;
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(kern), lds);
     const int mblocks = p.B * (p.W >> 4) * (p.H >> 4);
-    static const int grid_override = getenv("CCVPE_X4_GRID") ? std::atoi(getenv("CCVPE_X4_GRID")) : 0;   // dev: workgroups of the persistent grid
-    const int resident = grid_override > 0 ? grid_override : (NW == 4 ? 2 : 1) * 256 / (p.splitk > 1 ? p.splitk : 1);
+    const int resident = (NW == 4 ? 2 : 1) * 256 / (p.splitk > 1 ? p.splitk : 1);
     dim3 grid(std::min(mblocks, std::max(resident, 8)), 1, p.splitk > 1 ? p.splitk : 1);
     CCVPE_LAUNCH(kern, grid, dim3(NW * 64), lds, s, p);
 #if CCVPE_X4_CLOCK

@@ -118,12 +118,14 @@ int ccvpe_finalize_weights(ccvpe_handle h);
  * ccvpe_finalize_weights, ccvpe_save_packed writes the folded / repacked / Winograd-transformed device weights to `path`;
  * in a later process ccvpe_load_packed(h, path) on a handle created with the same config replaces the 818 ccvpe_set_weight
  * calls and ccvpe_finalize_weights.  The caller keys the file by the checkpoint's content (see ccvpe_amd/models.py).
- * CCVPE_EINVAL if the file is missing, truncated, or was packed for another variant / precision / library build. */
+ * CCVPE_EINVAL if the file is missing, truncated, or was packed for another variant / precision / library build or under other
+ * packer switches than the loading handle's (ccvpe_pack_switches). */
 int ccvpe_save_packed(ccvpe_handle h, const char* path);
 int ccvpe_load_packed(ccvpe_handle h, const char* path);
-/* The environment switches that change what the packer emits, as "NAME=value;" pairs in a fixed order ("" when none is set;
- * thread-local storage, valid until the thread's next call): part of the caller's cache key, so a file packed under one setting
- * is never loaded under another.  No reference counterpart. */
+/* The environment switches that change what the packer emits and differ from their defaults, as "NAME=value;" pairs in a fixed
+ * order ("" when none does; thread-local storage, valid until the thread's next call): part of the caller's cache key, so a file
+ * packed under one setting is never loaded under another.  Read from the environment at the call, as ccvpe_create reads it for a
+ * handle.  No reference counterpart. */
 const char* ccvpe_pack_switches(void);
 
 /* Tuning table.  The first forward of a new (batch, ground size) measures every tiled launch of its plan with each candidate

@@ -63,3 +63,23 @@ def test_micro_batch_bound_is_host_arithmetic():
     assert lib.ccvpe_max_micro_batch(2, 0.0, 250, 1024) < 0          # 7 feature rows: not a KITTI-shaped ground image
     assert b"feature volume" in lib.ccvpe_last_error()
     assert lib.ccvpe_max_micro_batch(7, 0.0, 320, 640) < 0
+
+
+def test_environment_is_read_only_by_read_switches():
+    """Every environment switch of the library is read once per handle, at ccvpe_create, by read_switches() (ccvpe_api.hip):
+    no other function under ccvpe_amd/csrc calls getenv - a switch latched elsewhere (a function-local static, a plan builder) would
+    give the process, a plan or the packed-weight cache key a different value than the handle."""
+    csrc = os.path.join(ROOT, "ccvpe_amd", "csrc")
+    offenders, readers = [], 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())
+        m = re.search(r"^Switches read_switches\(\) \{\n.*?^\}\n", text, flags=re.S | re.M)
+        if m:
+            readers += 1
+            assert re.search(r"\bgetenv\s*\(", m.group(0))
+            text = text[:m.start()] + text[m.end():]
+        offenders += [f"{f}: {line.strip()}" for line in text.splitlines() if re.search(r"\bgetenv\s*\(", line)]
+    assert readers == 1, "read_switches() is defined once"
+    assert not offenders, "getenv outside read_switches():\n" + "\n".join(offenders)

@@ -52,6 +52,18 @@ def ori_weighted_error(a, b, mag):
     return ((a.cpu() - b.cpu()).abs() * mag).max().item() / mag.max().item()
 
 
+def launch_tiles(m, g, s):
+    """Launch name -> tile of every tiled launch of the model's plan for (g, s), from its profile rows ("name|tile")."""
+    return dict(row[0].split("|", 1) for row in m.profile(g, s) if "|" in row[0])
+
+
+def assert_hook_moved(forced, default, family):
+    """A candidate-filter hook took effect: at least one launch runs a tile of `family` under it that the default plan of the same
+    model does not run there (the hook not honoured: the same tuner, the same choices)."""
+    moved = [op for op, t in forced.items() if t.startswith(family) and not default.get(op, "").startswith(family)]
+    assert moved, f"no launch moved onto a {family} tile: {forced}"
+
+
 def check_against_fixture(fx, outs, rtol):
     worst = 0.0
     for n, t in zip(gu.OUTPUT_NAMES, outs):
@@ -257,6 +269,11 @@ def test_pointwise_persistent_tiles_everywhere_match_golden(name, monkeypatch):
     # choices measured under a candidate filter stay in the handle's plans: nothing is recorded, exported or written to the shared cache
     from ccvpe_amd import _lib
     assert _lib.load().ccvpe_tuning_generation(m._handle) == 0
+    # the hook took effect (pointwise family: conv_pw_* and the deep-K conv_proj* tiles)
+    forced = launch_tiles(m, g, s)
+    monkeypatch.delenv("CCVPE_TUNE_PREFER_PW")
+    default = launch_tiles(build_model(cfg), g, s)
+    assert_hook_moved(forced, default, "conv_pw_")
 
 
 @pytest.mark.parametrize("name,batch", [("vigor_prior180_circ", 1), ("kitti", 1), ("oxford", 3)])
@@ -276,17 +293,22 @@ def test_deep_k_project_gemm_everywhere_matches_golden(name, batch, monkeypatch)
         if name == "vigor_prior180_circ":
             for tap in ["sat_block4", "sat_block10", "sat_block15"]:
                 gu.compare("tap_" + tap, fx, m.read_tap(tap).numpy(), RTOL)
+        monkeypatch.delenv("CCVPE_TUNE_PREFER_PROJ")
+        ref_model = build_model(cfg)
     else:   # a batch the goldens do not hold: against the default plan of the same model
         g, s = inputs(cfg, batch=batch)
         out = [t.clone() for t in m(g, s)]
         monkeypatch.delenv("CCVPE_TUNE_PREFER_PROJ")
-        ref = build_model(cfg)(g, s)
+        ref_model = build_model(cfg)
+        ref = ref_model(g, s)
         mag = raw_ori_magnitude(cfg, g, s)
         for i, (a, b) in enumerate(zip(ref, out)):
             if i == 2:
                 assert ori_weighted_error(a, b, mag) <= 1e-4
             else:
                 assert (a - b).abs().max().item() <= 1e-4 * max(a.abs().max().item(), 1e-30), gu.OUTPUT_NAMES[i]
+    # the hook took effect: the deep-K GEMM (conv_proj_r*, or its latency form conv_projl_*) on launches the default plan runs elsewhere
+    assert_hook_moved(launch_tiles(m, g, s), launch_tiles(ref_model, g, s), "conv_proj")
 
 
 @pytest.mark.parametrize("name,batch", [("vigor_prior180_circ", 1), ("kitti", 1), ("oxford", 1), ("oxford", 3), ("vigor_prior180_b2", 2)])
@@ -309,6 +331,12 @@ def test_latency_form_project_gemm_matches_golden(name, batch, monkeypatch):
     else:
         g, s = inputs(cfg, batch=batch)
         out = [t.clone() for t in m(g, s)]
+    # the hook took effect: the latency form runs, and no gated project conv it covers (every one the deep-K GEMM takes: blocks 5-15,
+    # at most 4096 rows at these batches) runs the throughput form conv_proj_r*
+    forced = launch_tiles(m, g, s)
+    assert any(t.startswith("conv_projl_") for t in forced.values()), forced
+    assert not [op for op, t in forced.items() if op.endswith(".project") and t.startswith("conv_proj_r")], forced
+    if batch != cfg["batch"]:
         monkeypatch.delenv("CCVPE_TUNE_PREFER_PROJ")
         ref = build_model(cfg)(g, s)
         mag = raw_ori_magnitude(cfg, g, s)
