@@ -59,6 +59,12 @@ SYMBOLS = [
                                    C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_void_p, C.c_void_p]),
     ("ccvpe_preprocess_resize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                           C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ccvpe_preprocess_affine", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3),
+                                          C.c_void_p, C.c_void_p]),
+    ("ccvpe_preprocess_window_resize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     ("ccvpe_set_debug", C.c_int, [C.c_void_p, C.c_int32]),
     ("ccvpe_set_streams", C.c_int, [C.c_void_p, C.c_int32]),
     ("ccvpe_read_tap", C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
@@ -126,6 +132,57 @@ def preprocess_resize(img_u8_hwc, out_hw, shift=None, crop_w=None, mean=IMAGENET
                                      crop_w, C.byref(m), C.byref(s), C.c_void_p(scratch.data_ptr()) if scratch is not None else None,
                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream))
     check(rc, "ccvpe_preprocess_resize")
+    return out
+
+
+RESAMPLE = {"nearest": 0, "bilinear": 2}   # CCVPE_RESAMPLE_* = PIL.Image.NEAREST / BILINEAR
+
+
+def preprocess_affine(img_u8_hwc, matrices, filters, crop, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """uint8 [B,H,W,3] cuda tensor -> chain of PIL affine resamplings (matrices [B,n,6] float64 PIL `data` tuples, filters [n] of
+    "nearest" / "bilinear" or PIL's 0 / 2) -> crop = (top, left, out_h, out_w) of the last canvas -> ToTensor + Normalize ->
+    float32 NCHW [B,3,out_h,out_w] (ccvpe_preprocess_affine; KITTI datasets.py:577-598)."""
+    import torch
+    lib = load()
+    assert img_u8_hwc.is_cuda and img_u8_hwc.dtype == torch.uint8 and img_u8_hwc.dim() == 4 and img_u8_hwc.shape[3] == 3
+    img = img_u8_hwc.contiguous()
+    B, H, W, _ = img.shape
+    mat = torch.as_tensor(matrices, dtype=torch.float64).to(img.device).contiguous()
+    n = len(filters)
+    assert mat.shape == (B, n, 6), (tuple(mat.shape), B, n)
+    flt = (C.c_int32 * n)(*[RESAMPLE[f] if isinstance(f, str) else int(f) for f in filters])
+    top, left, out_h, out_w = (int(v) for v in crop)
+    out = torch.empty((B, 3, max(out_h, 0), max(out_w, 0)), dtype=torch.float32, device=img.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    stream = torch.cuda.current_stream(img.device).cuda_stream
+    rc = lib.ccvpe_preprocess_affine(C.c_void_p(img.data_ptr()), B, H, W, C.c_void_p(mat.data_ptr()), flt, n, top, left, out_h, out_w,
+                                     C.byref(m), C.byref(s), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+    check(rc, "ccvpe_preprocess_affine")
+    return out
+
+
+def preprocess_window_resize(map_u8_hwc, origins, win_hw, out_hw, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """ONE uint8 map [map_h,map_w,3] cuda tensor -> per sample the win_hw window at origins[b] = (x0, y0) (zeros outside the map,
+    PIL crop) -> PIL-exact bilinear resize to out_hw -> ToTensor + Normalize -> float32 NCHW [B,3,out_h,out_w]
+    (ccvpe_preprocess_window_resize; Oxford datasets.py:306-321)."""
+    import torch
+    lib = load()
+    assert map_u8_hwc.is_cuda and map_u8_hwc.dtype == torch.uint8 and map_u8_hwc.dim() == 3 and map_u8_hwc.shape[2] == 3
+    mp = map_u8_hwc.contiguous()
+    org = torch.as_tensor(origins, dtype=torch.int32).reshape(-1, 2).to(mp.device).contiguous()
+    B = org.shape[0]
+    win_h, win_w = int(win_hw[0]), int(win_hw[1])
+    out_h, out_w = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((B, 3, max(out_h, 0), max(out_w, 0)), dtype=torch.float32, device=mp.device)
+    scratch = torch.empty((max(B * win_h * out_w * 3, 1),), dtype=torch.uint8, device=mp.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    stream = torch.cuda.current_stream(mp.device).cuda_stream
+    rc = lib.ccvpe_preprocess_window_resize(C.c_void_p(mp.data_ptr()), mp.shape[0], mp.shape[1], C.c_void_p(org.data_ptr()), B, win_h, win_w,
+                                            out_h, out_w, C.byref(m), C.byref(s), C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(stream))
+    check(rc, "ccvpe_preprocess_window_resize")
     return out
 
 

@@ -1,0 +1,211 @@
+"""Aerial-side input preparation of the KITTI and Oxford test loops on device.
+
+The datasets prepare the aerial image with Pillow on the host (reference datasets.py:306-321 Oxford, datasets.py:577-598 KITTI) and
+build a 512 x 512 float32 Gaussian ground-truth map per sample only for the test loop to take its argmax (train_KITTI.py:312,
+train_OxfordRobotCar.py:220).  This module restates the dataset arithmetic - the parameters of every Pillow call, the crop
+boxes, the ground-truth offsets and orientation - and hands the pixel work to ccvpe_preprocess_affine /
+ccvpe_preprocess_window_resize, whose output equals the reference's satmap tensor bit for bit.  The ground-truth helpers return
+exactly what the test loop reads off the maps: the flat argmax index (ties broken as np.argmax does), the (cos, sin) at that pixel
+and the heading in degrees, ready for `model.evaluate`.
+
+Host scalars follow the reference's own operations (Python floats, np.cos / np.sin, Python's round), so they are the same doubles.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+SAT_HW = 512                       # SatMap_process_sidelength (datasets.py:359) = Resize([512, 512]) of the Oxford transform
+NEAREST, BILINEAR = 0, 2           # PIL.Image.NEAREST / BILINEAR = CCVPE_RESAMPLE_*
+
+# KITTI (datasets.py:355-374)
+DEFAULT_LAT = 49.015
+SATMAP_ZOOM = 18
+CAMERA_GPS_SHIFT_LEFT = (1.08, 0.26)
+KITTI_FILTERS = (NEAREST, BILINEAR, BILINEAR, NEAREST)
+
+# Oxford (datasets.py:306-321): 800 x 800 windows on a 400-px grid
+OXFORD_GRID = 400
+OXFORD_WIN = 800
+
+
+def get_meter_per_pixel(lat: float = DEFAULT_LAT, zoom: int = SATMAP_ZOOM, scale: float = 1.0) -> float:
+    """datasets.py:366-371; the datasets use scale=1 (datasets.py:375, 459)."""
+    meter_per_pixel = 156543.03392 * np.cos(lat * np.pi / 180.) / (2 ** zoom)
+    meter_per_pixel /= 2
+    meter_per_pixel /= scale
+    return meter_per_pixel
+
+
+def rotate_matrix(angle_deg: float, width: int, height: int) -> Tuple[float, ...]:
+    """The affine `data` PIL.Image.rotate(angle_deg) passes to Image.transform with default arguments (NEAREST, centre
+    (w/2, h/2), no translation, no expand).  Its shortcuts (copy at 0, transposes at 180 and at 90/270 on square images) give the
+    same bytes as the fixed-point NEAREST path fed this matrix."""
+    angle = angle_deg % 360.0
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    cx, cy = width / 2.0, height / 2.0
+    m[2] = m[0] * -cx + m[1] * -cy + m[2]
+    m[5] = m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def center_crop_box(height: int, width: int, size: int = SAT_HW) -> Tuple[int, int]:
+    """torchvision center_crop on a PIL image: (top, left) = (int(round((H - size) / 2.0)), int(round((W - size) / 2.0)))."""
+    return int(round((height - size) / 2.0)), int(round((width - size) / 2.0))
+
+
+def _vec(v, n=None) -> np.ndarray:
+    a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    return a if n is None else np.broadcast_to(a, (n,))
+
+
+def kitti_matrices(heading_rad, gt_shift_x, gt_shift_y, theta, tile_hw: Sequence[int], shift_range_lat: float = 20,
+                   shift_range_lon: float = 20, rotation_range: float = 10) -> Tuple[np.ndarray, Tuple[int, ...]]:
+    """The four Pillow calls of SatGrdDatasetTest.__getitem__ (datasets.py:577-594) as affine `data` tuples, per sample.
+
+    heading_rad: oxts field 5; gt_shift_x, gt_shift_y, theta: the test-split file's values AS READ (the dataset negates the shifts
+    itself, datasets.py:585-586); tile_hw: the satellite tile's (H, W).  shift_range_* / rotation_range are the dataset's
+    constructor arguments (train_KITTI.py passes its --shift_range_lat/lon and --rotation_range).  Returns (matrices [B,4,6]
+    float64, filters): rotate(-heading), camera-GPS shift (BILINEAR), ground-truth shift (BILINEAR), rotate(theta * range)."""
+    heading = _vec(heading_rad)
+    B = heading.shape[0]
+    sx, sy, th = _vec(gt_shift_x, B), _vec(gt_shift_y, B), _vec(theta, B)
+    H, W = int(tile_hw[0]), int(tile_hw[1])
+    mpp = get_meter_per_pixel(scale=1)
+    pix_lat = shift_range_lat / mpp
+    pix_lon = shift_range_lon / mpp
+    cam = (1, 0, CAMERA_GPS_SHIFT_LEFT[0] / mpp, 0, 1, CAMERA_GPS_SHIFT_LEFT[1] / mpp)
+    out = np.empty((B, 4, 6), dtype=np.float64)
+    for b in range(B):
+        shift_x = -float(sx[b])
+        shift_y = -float(sy[b])
+        out[b, 0] = rotate_matrix(-float(heading[b]) / np.pi * 180, W, H)
+        out[b, 1] = cam
+        out[b, 2] = (1, 0, shift_x * pix_lon, 0, 1, -shift_y * pix_lat)
+        out[b, 3] = rotate_matrix(float(th[b]) * rotation_range, W, H)
+    return out, KITTI_FILTERS
+
+
+def kitti_aerial(sat_u8, heading_rad, gt_shift_x, gt_shift_y, theta, shift_range_lat: float = 20, shift_range_lon: float = 20,
+                 rotation_range: float = 10, mean=_lib.IMAGENET_MEAN, std=_lib.IMAGENET_STD):
+    """uint8 satellite tiles [B,H,W,3] (cuda, as decoded, H and W >= 512) -> the KITTI test split's `sat_map` tensor [B,3,512,512]
+    (datasets.py:577-598 + satmap_transform, train_KITTI.py:60-64), in one launch."""
+    H, W = int(sat_u8.shape[1]), int(sat_u8.shape[2])
+    mats, filters = kitti_matrices(heading_rad, gt_shift_x, gt_shift_y, theta, (H, W), shift_range_lat, shift_range_lon, rotation_range)
+    top, left = center_crop_box(H, W)
+    return _lib.preprocess_affine(sat_u8, mats, filters, (top, left, SAT_HW, SAT_HW), mean, std)
+
+
+def gt_argmax(x_offset: int, y_offset: int, size: int = SAT_HW) -> int:
+    """Flat index of np.argmax of the reference's float32 Gaussian map, built from
+    np.meshgrid(np.linspace(-256 + x_offset, 256 + x_offset, 512), np.linspace(-256 + y_offset, 256 + y_offset, 512)),
+    d = sqrt(x^2 + y^2), exp(-(d^2) / 32) (datasets.py:323-329, 600-606), without building it: the map falls off with |x| and |y|
+    separately, so the maximum lies at the grid line nearest 0 of each axis; the 3 x 3 window around it is evaluated with the
+    reference's formula and scanned in np.argmax's order, which settles exact ties (offset 0 puts two lines at +-256/511).
+    Offsets beyond +-255 (peak off the map) are refused."""
+    xo, yo = int(x_offset), int(y_offset)
+    half = size // 2
+    if abs(xo) > half - 1 or abs(yo) > half - 1:
+        raise ValueError(f"ground-truth offset ({xo}, {yo}) outside +-{half - 1}: the Gaussian's peak is not on the map")
+    xs = np.linspace(-half + xo, half + xo, size)
+    ys = np.linspace(-half + yo, half + yo, size)
+    cx, cy = int(np.argmin(np.abs(xs))), int(np.argmin(np.abs(ys)))
+    cols = np.arange(max(cx - 1, 0), min(cx + 2, size))
+    rows = np.arange(max(cy - 1, 0), min(cy + 2, size))
+    x, y = np.meshgrid(xs[cols], ys[rows])
+    d = np.sqrt(x * x + y * y)
+    sigma, mu = 4, 0.0
+    g = np.exp(-((d - mu) ** 2 / (2.0 * sigma ** 2))).astype(np.float32)
+    k = int(np.argmax(g))
+    return int(rows[k // len(cols)]) * size + int(cols[k % len(cols)])
+
+
+def _cos_sin_f32(angle_deg: np.ndarray) -> np.ndarray:
+    """torch.full([2, H, W], np.cos(a * np.pi / 180)) + [1] = np.sin(...): the float32 values the test loop reads at the GT pixel."""
+    out = np.empty((len(angle_deg), 2), dtype=np.float32)
+    for b, a in enumerate(angle_deg):                  # scalar calls, as the dataset makes them
+        out[b] = (np.cos(float(a) * np.pi / 180), np.sin(float(a) * np.pi / 180))
+    return out
+
+
+def kitti_ground_truth(gt_shift_x, gt_shift_y, theta, shift_range_lat: float = 20, shift_range_lon: float = 20,
+                       rotation_range: float = 10) -> Dict[str, np.ndarray]:
+    """Ground-truth side of a KITTI test sample (datasets.py:600-634) from the split file's values as read: gt_index [B] int32 =
+    flat argmax of `gt`, gt_cos_sin [B,2] float32 = `orientation_map` at that pixel, heading_deg [B] float64 =
+    `orientation_angle`.  With meter_per_pixel = get_meter_per_pixel(scale=1) these are the arguments of model.evaluate."""
+    sx, sy, th = _vec(gt_shift_x), _vec(gt_shift_y), _vec(theta)
+    B = max(sx.shape[0], sy.shape[0], th.shape[0])
+    sx, sy, th = np.broadcast_to(sx, (B,)), np.broadcast_to(sy, (B,)), np.broadcast_to(th, (B,))
+    mpp = get_meter_per_pixel(scale=1)
+    pix_lat = shift_range_lat / mpp
+    pix_lon = shift_range_lon / mpp
+    idx = np.empty(B, dtype=np.int32)
+    heading = np.empty(B, dtype=np.float64)
+    for b in range(B):
+        shift_x = -float(sx[b])
+        shift_y = -float(sy[b])
+        random_ori = float(th[b]) * rotation_range
+        x_offset = int(shift_x * pix_lon * np.cos(random_ori / 180 * np.pi) - shift_y * pix_lat * np.sin(random_ori / 180 * np.pi))
+        y_offset = int(-shift_y * pix_lat * np.cos(random_ori / 180 * np.pi) - shift_x * pix_lon * np.sin(random_ori / 180 * np.pi))
+        idx[b] = gt_argmax(x_offset, y_offset)
+        orientation_angle = 90 - random_ori
+        if orientation_angle < 0:
+            orientation_angle = orientation_angle + 360
+        elif orientation_angle > 360:
+            orientation_angle = orientation_angle - 360
+        heading[b] = orientation_angle
+    return {"gt_index": idx, "gt_cos_sin": _cos_sin_f32(heading), "heading_deg": heading}
+
+
+def oxford_window(image_coord) -> Dict[str, np.ndarray]:
+    """Test / val window of OxfordRobotCarDataset (datasets.py:306-321) for pixel coordinates image_coord [B,2] = (col, row):
+    origin [B,2] int32 = (x0, y0) of the 800 x 800 crop box on the 400-px grid, offset [B,2] int = (col_offset_resized,
+    row_offset_resized) of the ground-truth Gaussian."""
+    ic = np.asarray(image_coord, dtype=np.float64).reshape(-1, 2)
+    B = ic.shape[0]
+    origin = np.empty((B, 2), dtype=np.int32)
+    offset = np.empty((B, 2), dtype=np.int64)
+    for b in range(B):
+        col_split = int((ic[b, 0]) // OXFORD_GRID)
+        if np.round(ic[b, 0] - OXFORD_GRID * col_split) < 200:
+            col_split -= 1
+        col_pixel = int(np.round(ic[b, 0] - OXFORD_GRID * col_split))
+        row_split = int((ic[b, 1]) // OXFORD_GRID)
+        if np.round(ic[b, 1] - OXFORD_GRID * row_split) < 200:
+            row_split -= 1
+        row_pixel = int(np.round(ic[b, 1] - OXFORD_GRID * row_split))
+        origin[b] = (col_split * OXFORD_GRID, row_split * OXFORD_GRID)
+        offset[b] = (int(-(col_pixel / 800 * 512 - 256)), int(-(row_pixel / 800 * 512 - 256)))
+    return {"origin": origin, "offset": offset}
+
+
+def oxford_aerial(map_u8, image_coords, mean=_lib.IMAGENET_MEAN, std=_lib.IMAGENET_STD):
+    """The resident satellite map [map_h,map_w,3] (cuda uint8) -> the Oxford test split's `sat` tensors [B,3,512,512] for ground
+    images at image_coords [B,2] (datasets.py:306-321 crop + transform_sat, train_OxfordRobotCar.py:56-60), in two launches."""
+    win = oxford_window(image_coords)
+    return _lib.preprocess_window_resize(map_u8, win["origin"], (OXFORD_WIN, OXFORD_WIN), (SAT_HW, SAT_HW), mean, std)
+
+
+def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
+    """Ground-truth side of an Oxford test sample (datasets.py:323-351): gt_index [B] int32 = flat argmax of `gt`, gt_cos_sin [B,2]
+    float32 = `orientation` at that pixel, heading_deg [B] float64 = `orientation_angle` (yaw: grdYaw, radians)."""
+    win = oxford_window(image_coords)
+    yaw = _vec(yaw, win["origin"].shape[0])
+    B = yaw.shape[0]
+    idx = np.empty(B, dtype=np.int32)
+    heading = np.empty(B, dtype=np.float64)
+    for b in range(B):
+        col_off, row_off = (int(v) for v in win["offset"][b])
+        idx[b] = gt_argmax(col_off, row_off)
+        orientation_angle = (float(yaw[b]) / np.pi * 180) - 90
+        if orientation_angle < 0:
+            orientation_angle = orientation_angle + 360
+        heading[b] = orientation_angle
+    return {"gt_index": idx, "gt_cos_sin": _cos_sin_f32(heading), "heading_deg": heading}

@@ -571,6 +571,51 @@ int ccvpe_preprocess_resize(const uint8_t* hwc, int32_t batch, int32_t in_h, int
     return 0;
 }
 
+int ccvpe_preprocess_affine(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const double* matrices, const int32_t* filters,
+                            int32_t n_stages, int32_t top, int32_t left, int32_t out_h, int32_t out_w, const float mean[3],
+                            const float stdv[3], float* out_nchw, void* stream) {
+    if (!hwc || !matrices || !filters || !mean || !stdv || !out_nchw) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (n_stages < 1 || n_stages > WARP_MAX_STAGES) return ccvpe_fail(CCVPE_EINVAL, "%d stages (1..%d are supported)", n_stages, WARP_MAX_STAGES);
+    unsigned bil = 0;
+    int n_bil = 0;
+    for (int s = 0; s < n_stages; ++s) {
+        if (filters[s] == CCVPE_RESAMPLE_BILINEAR) { bil |= 1u << s; ++n_bil; }
+        else if (filters[s] != CCVPE_RESAMPLE_NEAREST) return ccvpe_fail(CCVPE_EINVAL, "stage %d: unknown filter %d (NEAREST 0 or BILINEAR 2)", s, filters[s]);
+    }
+    if (n_bil > WARP_MAX_BILINEAR) return ccvpe_fail(CCVPE_EINVAL, "%d BILINEAR stages (at most %d)", n_bil, WARP_MAX_BILINEAR);
+    if (batch <= 0 || batch > 65535) return ccvpe_fail(CCVPE_EINVAL, "batch %d out of range (1..65535)", batch);
+    if (H <= 0 || W <= 0 || H > 16384 || W > 16384) return ccvpe_fail(CCVPE_EINVAL, "canvas %d x %d out of range (1..16384 per side)", H, W);
+    if (out_h <= 0 || out_w <= 0 || top < 0 || left < 0 || top > H - out_h || left > W - out_w)
+        return ccvpe_fail(CCVPE_EINVAL, "crop (top %d, left %d, %d x %d) outside the %d x %d canvas", top, left, out_h, out_w, H, W);
+    WarpParams p{};
+    p.in = hwc; p.mat = matrices; p.B = batch; p.H = H; p.W = W; p.n = n_stages; p.bilinear = bil;
+    p.top = top; p.left = left; p.out_h = out_h; p.out_w = out_w; p.out = out_nchw;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
+    if (launch_warp(p, (hipStream_t)stream) != 0) return ccvpe_fail(CCVPE_EINVAL, "no kernel for this stage pattern");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "affine launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int ccvpe_preprocess_window_resize(const uint8_t* map_hwc, int32_t map_h, int32_t map_w, const int32_t* origins, int32_t batch,
+                                   int32_t win_h, int32_t win_w, int32_t out_h, int32_t out_w, const float mean[3], const float stdv[3],
+                                   uint8_t* scratch, float* out_nchw, void* stream) {
+    if (!map_hwc || !origins || !mean || !stdv || !scratch || !out_nchw) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (map_h <= 0 || map_w <= 0 || batch <= 0 || win_h <= 0 || win_w <= 0 || out_h <= 0 || out_w <= 0) return ccvpe_fail(CCVPE_EINVAL, "bad geometry");
+    if (win_w > 8 * out_w || win_h > 8 * out_h)
+        return ccvpe_fail(CCVPE_EINVAL, "down-scaling factors above 8 are not supported (%dx%d -> %dx%d)", win_h, win_w, out_h, out_w);
+    if ((double)batch * win_h * out_w * 3 >= 2147483647.0 * 2 || (double)batch * 3 * out_h * out_w >= 2147483647.0 * 2)
+        return ccvpe_fail(CCVPE_EINVAL, "window batch too large");
+    ResizeParams p{};
+    p.in = map_hwc; p.B = batch; p.IH = win_h; p.IW = win_w; p.OH = out_h; p.OW = out_w; p.crop_w = out_w; p.tmp = scratch; p.out = out_nchw;
+    p.origin = origins; p.map_h = map_h; p.map_w = map_w;
+    for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
+    if (launch_resize(p, (hipStream_t)stream) != 0) return ccvpe_fail(CCVPE_EINVAL, "down-scaling factors above 8 are not supported");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "window resize launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
 int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
     if (!h || !path) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     Plan* pl = h->last_plan;

@@ -364,8 +364,26 @@ struct ResizeParams {
     const int* shift;          // [B] roll in output pixels or null
     float mean[3], stdv[3];
     float* out;                // [B][3][OH][crop_w] fp32
+    // window mode (origin != null): `in` is ONE map [map_h][map_w][3]; sample b resizes the IH x IW window whose top-left corner
+    // is (origin[2b], origin[2b+1]) = (x0, y0), pixels outside the map read as 0 (PIL.Image.crop).  The width pass always runs.
+    const int* origin;
+    int map_h, map_w;
 };
 int launch_resize(const ResizeParams& p, hipStream_t s);   // -1: down-scaling factor above 8
+
+// chain of PIL affine transforms (NEAREST / BILINEAR) + crop + ToTensor + Normalize (kernels_warp.hip)
+static constexpr int WARP_MAX_STAGES = 4;
+static constexpr int WARP_MAX_BILINEAR = 2;
+struct WarpParams {
+    const unsigned char* in;   // [B][H][W][3] uint8; every stage maps an H x W canvas onto an H x W canvas
+    const double* mat;         // [B][n][6] PIL affine data (output pixel -> input position), stage 0 reads `in`
+    int B, H, W, n;
+    unsigned bilinear;         // bit s set: stage s resamples BILINEAR, else NEAREST
+    int top, left, out_h, out_w;   // crop window of the last stage's canvas
+    float mean[3], stdv[3];
+    float* out;                // [B][3][out_h][out_w] fp32
+};
+int launch_warp(const WarpParams& p, hipStream_t s);       // -1: stage pattern without a kernel
 
 void launch_scatter_channels(const float* src, int C, long long P, Dst d0, Dst d1, int ndst, hipStream_t s);
 

@@ -9,6 +9,8 @@
 // recomputed per thread in double precision, bit for bit what precompute_coeffs / normalize_coeffs_8bpc produce),
 // so the result equals PIL's byte for byte and the float stage is the same divide / subtract / divide as torchvision.
 // HBM-bound: a 1024 x 2048 panorama is read once (6.3 MB), the 1024 x 640 intermediate is 2 MB, the output 2.5 MB.
+// The Oxford test split resizes an 800 x 800 window of one resident map (datasets.py:306-321): the width pass reads the window
+// through its origin, zero outside the map, and the rest of the path is unchanged.
 #include "kernels.h"
 
 namespace ccvpe {
@@ -51,7 +53,9 @@ __device__ __forceinline__ unsigned char clip8(int v) {
     return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// pass 1: [B, IH, IW, 3] -> [B, IH, OW, 3], one thread per output pixel
+// pass 1: [B, IH, IW, 3] -> [B, IH, OW, 3], one thread per output pixel.  WINDOW: the IH x IW input of sample b is the window
+// at p.origin[b] of one [map_h, map_w, 3] map, zero outside it (Oxford, datasets.py:306-317 full_satellite_map.crop).
+template <bool WINDOW>
 __global__ __launch_bounds__(256) void resize_h_kernel(const ResizeParams p) {
     const long long total = (long long)p.B * p.IH * p.OW;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -59,11 +63,28 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const ResizeParams p) {
         const long long row = i / p.OW;                      // b * IH + y
         int xmin, n, k[RS_MAXK];
         resize_taps(p.IW, p.OW, xo, xmin, n, k);
-        const unsigned char* src = p.in + ((size_t)row * p.IW + xmin) * 3;
         int a0 = 1 << (RS_BITS - 1), a1 = a0, a2 = a0;
+        if constexpr (!WINDOW) {
+            const unsigned char* src = p.in + ((size_t)row * p.IW + xmin) * 3;
 #pragma unroll
-        for (int x = 0; x < RS_MAXK; ++x)
-            if (x < n) { a0 += src[x * 3] * k[x]; a1 += src[x * 3 + 1] * k[x]; a2 += src[x * 3 + 2] * k[x]; }
+            for (int x = 0; x < RS_MAXK; ++x)
+                if (x < n) { a0 += src[x * 3] * k[x]; a1 += src[x * 3 + 1] * k[x]; a2 += src[x * 3 + 2] * k[x]; }
+        } else {
+            const int b = (int)(row / p.IH);
+            const long long gy = (long long)p.origin[2 * b + 1] + (row - (long long)b * p.IH);
+            const long long gx0 = (long long)p.origin[2 * b] + xmin;
+            if (gy >= 0 && gy < p.map_h) {                   // a row outside the map is all zeros: the sums stay at the rounding bias
+                const unsigned char* src = p.in + (size_t)gy * p.map_w * 3;
+#pragma unroll
+                for (int x = 0; x < RS_MAXK; ++x) {
+                    const long long gx = gx0 + x;
+                    if (x < n && gx >= 0 && gx < p.map_w) {
+                        const unsigned char* q = src + (size_t)gx * 3;
+                        a0 += q[0] * k[x]; a1 += q[1] * k[x]; a2 += q[2] * k[x];
+                    }
+                }
+            }
+        }
         unsigned char* dst = p.tmp + (size_t)i * 3;
         dst[0] = clip8(a0); dst[1] = clip8(a1); dst[2] = clip8(a2);
     }
@@ -103,12 +124,14 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const ResizeParams p) {
     }
 }
 
-// width pass skipped (IW == OW): pass 2 reads the input directly
+// width pass skipped (IW == OW): pass 2 reads the input directly.  A window always takes the width pass: at IW == OW its taps
+// are (2^22, 0), the identity Pillow's skip amounts to.
 int launch_resize(const ResizeParams& p_in, hipStream_t s) {
     ResizeParams p = p_in;
     if (p.IW > 8 * p.OW || p.IH > 8 * p.OH) return -1;      // more taps than RS_MAXK
     auto blocks = [](long long total) { long long b = (total + 255) / 256; return (int)(b > 256 * 32 ? 256 * 32 : b); };
-    if (p.IW != p.OW) CCVPE_LAUNCH(resize_h_kernel, dim3(blocks((long long)p.B * p.IH * p.OW)), dim3(256), 0, s, p);
+    if (p.origin) CCVPE_LAUNCH(resize_h_kernel<true>, dim3(blocks((long long)p.B * p.IH * p.OW)), dim3(256), 0, s, p);
+    else if (p.IW != p.OW) CCVPE_LAUNCH(resize_h_kernel<false>, dim3(blocks((long long)p.B * p.IH * p.OW)), dim3(256), 0, s, p);
     else p.tmp = const_cast<unsigned char*>(p.in);
     CCVPE_LAUNCH(resize_v_kernel, dim3(blocks((long long)p.B * p.OH * p.crop_w)), dim3(256), 0, s, p);
     return 0;

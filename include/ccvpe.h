@@ -200,6 +200,36 @@ int ccvpe_preprocess_resize(const uint8_t* hwc, int32_t batch, int32_t in_h, int
                             const int32_t* shift, int32_t crop_w, const float mean[3], const float stdv[3], uint8_t* scratch,
                             float* out_nchw, void* stream);
 
+/* Aerial preparation of the KITTI test loop on device (reference datasets.py:577-598 SatGrdDatasetTest: sat_map.rotate(-heading),
+ * transform(AFFINE, camera-GPS shift, BILINEAR), transform(AFFINE, test-split shift, BILINEAR), rotate(theta * rotation_range),
+ * TF.center_crop(512), then satmap_transform = Resize (a copy at 512^2) + ToTensor + Normalize, train_KITTI.py:60-64).
+ * uint8 HWC tiles [B,H,W,3] -> a chain of n_stages PIL affine resamplings, each output pixel (x, y) of a stage taking the
+ * input position (m0*x' + m1*y' + m2, m3*x' + m4*y' + m5) of PIL's `data` tuple (x' = x + 0.5 for BILINEAR, Pillow's own
+ * pixel-centre conventions for each filter), every stage an H x W canvas with 0 outside, uint8 between stages, byte-identical
+ * to Pillow -> the out_h x out_w window at (top, left) of the last canvas -> ToTensor + Normalize -> float32 NCHW
+ * [B,3,out_h,out_w].  `matrices` is DEVICE memory [B][n_stages][6] (double, stage 0 reads the input); `filters` is a host
+ * array [n_stages] of CCVPE_RESAMPLE_NEAREST / CCVPE_RESAMPLE_BILINEAR (PIL.Image.NEAREST / BILINEAR); mean/std as above.
+ * NEAREST stages are Pillow's 16.16 fixed-point path, which Pillow takes while the canvas corners map inside +-32768:
+ * every rotation about the centre (Image.rotate, including its copy / transpose shortcuts) qualifies.  CCVPE_EINVAL, with
+ * nothing launched: a null pointer, n_stages outside 1..4, more than 2 BILINEAR stages, an unknown filter, a side above
+ * 16384, batch above 65535, a crop window outside the canvas. */
+#define CCVPE_RESAMPLE_NEAREST 0
+#define CCVPE_RESAMPLE_BILINEAR 2
+int ccvpe_preprocess_affine(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const double* matrices, const int32_t* filters,
+                            int32_t n_stages, int32_t top, int32_t left, int32_t out_h, int32_t out_w, const float mean[3],
+                            const float stdv[3], float* out_nchw, void* stream);
+
+/* Aerial preparation of the Oxford test loop on device (reference datasets.py:306-321: full_satellite_map.crop((x0, y0,
+ * x0 + win_w, y0 + win_h)) on the 400-px grid, then transform_sat = Resize([512,512]) + ToTensor + Normalize,
+ * train_OxfordRobotCar.py:56-60): ONE resident uint8 map [map_h,map_w,3] (DEVICE) -> per sample the win_h x win_w window whose
+ * top-left corner is origins[b] = (x0, y0) (DEVICE int32 [B][2], PIL's crop-box order; pixels outside the map are 0, as
+ * PIL's crop fills them) -> the same Pillow-exact bilinear resize as ccvpe_preprocess_resize to out_h x out_w -> ToTensor +
+ * Normalize -> float32 NCHW [B,3,out_h,out_w].  `scratch` is caller-owned DEVICE memory of batch*win_h*out_w*3 bytes, always
+ * required.  CCVPE_EINVAL: a null pointer, a non-positive size, a down-scaling factor above 8. */
+int ccvpe_preprocess_window_resize(const uint8_t* map_hwc, int32_t map_h, int32_t map_w, const int32_t* origins, int32_t batch,
+                                   int32_t win_h, int32_t win_w, int32_t out_h, int32_t out_w, const float mean[3], const float stdv[3],
+                                   uint8_t* scratch, float* out_nchw, void* stream);
+
 /* Debug taps: when enabled, intermediate tensors of the next forward call stay resident and can be
  * copied out by name as NCHW float32 into HOST memory (`capacity` in floats).  Returns the number
  * of floats written via *n_out.  Names: see DESIGN.md (e.g. "sat_block15", "loc_level6"). */
