@@ -55,6 +55,9 @@ SYMBOLS = [
     ("ccvpe_encode_aerial", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("ccvpe_forward_cached", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.POINTER(Outputs), C.c_void_p]),
+    ("ccvpe_localize", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ccvpe_localize_cached", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p]),
     ("ccvpe_preprocess", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                    C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.c_void_p, C.c_void_p]),
     ("ccvpe_preprocess_resize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,

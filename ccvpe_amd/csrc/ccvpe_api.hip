@@ -238,15 +238,20 @@ static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
     return 0;
 }
 
+// rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read)
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
-                       const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr) {
+                       const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr) {
     const int mode = cache ? 2 : 0;
-    if (!h || !grd || (!sat && !cache) || !out) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    const bool pose = rows != nullptr;
+    if (!h || !grd || (!sat && !cache) || (!out && !pose)) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     if (cache && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
     if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
+    if (pose && h->debug) return ccvpe_fail(CCVPE_ESTATE, "pose plans carry no debug taps: ccvpe_set_debug(h, 0) before ccvpe_localize");
     if (batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "batch must be positive");
-    if (!out->logits_flattened || !out->heatmap || !out->ori) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
-    for (int k = 0; k < 6; ++k) if (!out->matching_score[k]) return ccvpe_fail(CCVPE_EINVAL, "null matching_score[%d]", k);
+    if (!pose) {
+        if (!out->logits_flattened || !out->heatmap || !out->ori) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
+        for (int k = 0; k < 6; ++k) if (!out->matching_score[k]) return ccvpe_fail(CCVPE_EINVAL, "null matching_score[%d]", k);
+    }
     HIPCHK(hipSetDevice(h->cfg.device));
     if (profile) h->prof.clear();
     int mbmax = h->cfg.micro_batch;
@@ -263,14 +268,14 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
     // make sure every plan (and the largest arena) exists before the first launch
     for (int done = 0; done < batch;) {
         const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode);
+        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose);
         if (rc) return rc;
         done += mb;
     }
     const size_t npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
     for (int done = 0; done < batch;) {
         const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode);
+        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose);
         if (rc) return rc;
         h->last_plan = pl;
         Ctx c;
@@ -280,12 +285,16 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         pl->set_scratch(c, 0);
         c.grd = grd + (size_t)done * 3 * gh * gw;
         c.sat = sat ? sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
-        c.out.logits_flattened = out->logits_flattened + done * npx;
-        c.out.heatmap = out->heatmap + done * npx;
-        c.out.ori = out->ori + done * 2 * npx;
-        for (int k = 0; k < 6; ++k) {
-            const size_t hw = (size_t)(8 << k) * (8 << k);
-            c.out.matching_score[k] = out->matching_score[k] + (size_t)done * h->rolls[k] * hw;
+        if (pose) {
+            c.rows = rows + (size_t)done * 5;
+        } else {
+            c.out.logits_flattened = out->logits_flattened + done * npx;
+            c.out.heatmap = out->heatmap + done * npx;
+            c.out.ori = out->ori + done * 2 * npx;
+            for (int k = 0; k < 6; ++k) {
+                const size_t hw = (size_t)(8 << k) * (8 << k);
+                c.out.matching_score[k] = out->matching_score[k] + (size_t)done * h->rolls[k] * hw;
+            }
         }
         if (!profile && pl->use_graph && !h->debug) {
             // latency mode: stage inputs, replay the captured launch sequence, copy the outputs out
@@ -386,6 +395,11 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
 int ccvpe_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
                   const ccvpe_outputs* out, void* stream) {
     return run_forward(h, grd, grd_h, grd_w, sat, batch, out, (hipStream_t)stream, false);
+}
+
+int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch, float* rows, void* stream) {
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows);
 }
 
 int ccvpe_profile_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
@@ -539,6 +553,13 @@ int ccvpe_forward_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_
                          const ccvpe_outputs* out, void* stream) {
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
     return run_forward(h, grd, grd_h, grd_w, nullptr, batch, out, (hipStream_t)stream, false, (const float*)cache);
+}
+
+int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t batch, float* rows,
+                          void* stream) {
+    if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows);
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

@@ -237,6 +237,7 @@ struct Ctx {
     unsigned* tickets = nullptr;       // the plan's last-arriver counters (ticket.h); every launch that draws tickets owns a range
     const float* cache_in = nullptr;   // aerial cache consumed by a "cached" plan
     float* cache_out = nullptr;        // aerial cache produced by an "encode" plan
+    float* rows = nullptr;             // pose plans: the [B][5] result rows of this micro-batch (ccvpe_localize)
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -276,6 +277,7 @@ struct TapInfo { Tensor t; int coff; int C; };
 struct Plan {
     int B = 0, gh = 0, gw = 0;
     int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding
+    bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
     bool debug = false;
     std::vector<size_t> size;     // floats per tensor
     std::vector<size_t> off;      // float offset in the arena
@@ -508,9 +510,9 @@ static inline int score_pad(int nscore) { return round_up(nscore, 8); }
 ConvParams conv_params(const PackedConv& pc, const float* in, int in_ld, int B, int H, int W, int OH, int OW,
                        int stride, int pad_t, int pad_l, int act);
 size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]);
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0);
+int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0, bool pose = false);
 
 // ---- ccvpe_tune.hip ----
 int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known = nullptr);
-int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode = 0);
+int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode = 0, bool pose = false);
 std::string tuning_key(ccvpe_handle_s* h, const Plan& pl, const Op& op);

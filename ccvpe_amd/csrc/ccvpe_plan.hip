@@ -249,10 +249,17 @@ size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]) {
 static int build_aerial_plan(ccvpe_handle_s* h, Plan& pl, int B);
 extern "C" int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t grd_h, int32_t grd_w);
 
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
+// Pose plans (pose = true, ccvpe_localize): the launches of the full (mode 0) or cached (mode 2) plan up to and including the level-2
+// decoders, under the same names - so the same tuning-table entries - and a tail that writes only the [B][5] result rows of
+// ccvpe_postprocess_rows: no matching-score stacks (the match kernels skip the ms store), the logits in the workspace, the first softmax
+// launch alone, pose_argmax_kernel (argmax and prob from recomputed heatmap values) and the orientation field at the argmax pixel only
+// (ori1.pose: the fused level 1 for the one tile that holds it; without the fused level: ori1.tail into the workspace + ori1.gather).
+// Never captured into a hipGraph.
+int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, bool pose) {
     if (mode == 1) return build_aerial_plan(h, pl, B);
     const bool cached = mode == 2;
     pl.mode = mode;
+    pl.pose = pose;
     const VariantSpec& vs = h->vs;
     pl.B = B; pl.gh = gh; pl.gw = gw; pl.debug = h->debug;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
@@ -263,7 +270,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     // host could not keep up.  A batch-1 frame is 137 launches now; issued eagerly (interleaved over the two streams, Plan::schedule) the
     // GPU starts on the first while the host still hands over the rest, and a synchronised frame takes 1.31 ms against 1.44 ms replayed
     // (the replay's set-up precedes its first kernel); back to back both run at the GPU's pace.
-    pl.use_graph = !cached && h->sw.graph_mode == 1;
+    pl.use_graph = !cached && !pose && h->sw.graph_mode == 1;
     if (pl.use_graph) {
         pl.io_grd = pl.alloc(B, 3, gh, gw);
         pl.io_sat = pl.alloc(B, 3, CCVPE_SAT_HW, CCVPE_SAT_HW);
@@ -426,7 +433,8 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
     };
 
     // fused last level: deconv1 + conv1[0] + ReLU + conv1[2] (+ normalize) in one launch
-    auto plan_level1_fused = [&](const DecoderW& dw, Tensor din, int cin_real, int cout, bool is_ori, Tensor raw, const std::string& tag) {
+    // out_ws: the output goes to this workspace tensor instead of the caller's buffer (the logits of a pose plan)
+    auto plan_level1_fused = [&](const DecoderW& dw, Tensor din, int cin_real, int cout, bool is_ori, Tensor raw, const std::string& tag, Tensor out_ws = Tensor{}) {
         Level1Params lp{};
         lp.x_ld = din.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
         lp.wd = dw.l1_wd; lp.bd = dw.l1_bd; lp.wa = dw.l1_wa; lp.ba = dw.l1_ba; lp.wt = dw.l1_wt;
@@ -434,11 +442,12 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         const bool has_raw = raw.id >= 0;
         std::vector<Tensor> uses = {din};
         if (has_raw) uses.push_back(raw);
+        if (out_ws.id >= 0) uses.push_back(out_ws);
         const double px = (double)B * CCVPE_OUT_HW * CCVPE_OUT_HW;
         pl.add(tag + ".fused", uses, [=](const Ctx& c) {
             Level1Params q = lp;
             q.x = c.ptr(din);
-            q.out = is_ori ? c.out.ori : c.out.logits_flattened;
+            q.out = out_ws.id >= 0 ? c.ptr(out_ws) : is_ori ? c.out.ori : c.out.logits_flattened;
             q.raw = has_raw ? c.ptr(raw) : nullptr;
             launch_level1(q, c.stream);
         }, px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * cout, 4.0 * (px / 4 * lp.cx + px * cout));
@@ -446,6 +455,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
 
     Tensor x = dmap;
     Tensor loc_mid;
+    const Tensor logits_ws = pose ? pl.alloc(B, 1, CCVPE_OUT_HW, CCVPE_OUT_HW) : Tensor{};   // pose plans: logits stay in the workspace
     // The preparation launch of every matching level (rolled descriptor / Gm, Mk) depends on the ground descriptor only: the six of them are
     // moved in front of the first matching level, where the localisation stream otherwise waits for the aerial encoder (batch 1: ~40 us off the
     // critical path).  CCVPE_MATCH_PREP_EARLY=0: inside each level's launch as before.
@@ -488,7 +498,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         auto fill = [=](const Ctx& c) {        // the same parameters for the preparation and the main launch: both pick the same form
             MatchParams q = mp;
             q.x = c.ptr(xin); q.g = c.ptr(desc) + goff;
-            q.ms = c.out.matching_score[k];
+            q.ms = pose ? nullptr : c.out.matching_score[k];
             q.cat_max = c.ptr(lin);
             q.cat_all = first ? c.ptr(ori_in6) : nullptr;
             q.gg_scratch = c.ptr(ggs);
@@ -503,7 +513,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         pl.add("match" + std::to_string(k + 1), uses, [=](const Ctx& c) { launch_match(fill(c), c.stream); },
                4.0 * B * hw * (double)R * L[k], 4.0 * B * hw * (2.0 * C + R + 8));
         pl.taps["loc_in" + std::to_string(6 - k)] = {lin, 0, lin.C};
-        if (k == 5 && h->sw.fuse_level1) { plan_level1_fused(h->loc, lin, vs.loc[5].din, 1, false, Tensor{}, "loc1"); break; }
+        if (k == 5 && h->sw.fuse_level1) { plan_level1_fused(h->loc, lin, vs.loc[5].din, 1, false, Tensor{}, "loc1", logits_ws); break; }
         Tensor o = plan_level(h->loc, vs.loc, k, lin, loc_cat[k], "loc" + std::to_string(6 - k));
         if (k < 5) { pl.taps["loc_level" + std::to_string(6 - k)] = {o, 0, o.C}; x = o; }
         else loc_mid = o;
@@ -522,14 +532,34 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         Tensor m = loc_mid;
         const float* tw = h->loc.tail_w;
         const float tb = h->loc.tail_b[0];
-        pl.add("loc1.tail", {m}, [=](const Ctx& c) {
+        std::vector<Tensor> uses = {m};
+        if (pose) uses.push_back(logits_ws);
+        pl.add("loc1.tail", uses, [=](const Ctx& c) {
             TailConvParams p{};
             p.in = c.ptr(m); p.B = B; p.H = CCVPE_OUT_HW; p.W = CCVPE_OUT_HW; p.w = tw; p.bias[0] = tb; p.cout = 1;
-            p.normalize = 0; p.out = c.out.logits_flattened; p.raw = nullptr;
+            p.normalize = 0; p.out = pose ? c.ptr(logits_ws) : c.out.logits_flattened; p.raw = nullptr;
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 144, 4.0 * B * 262144.0 * 17);
     }
-    {
+    Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side
+    if (pose) {
+        static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
+        Tensor part = pl.alloc(B, 1, 64, 2), pairs = pl.alloc(B, 1, 64, 2);
+        pose_index = pl.alloc(B, 1, 1, 1);
+        const Tensor lg = logits_ws, idx = pose_index;
+        pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
+            SoftmaxParams p{};
+            p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
+            launch_softmax_partial(p, c.stream);
+        }, 0, 4.0 * B * 262144.0);
+        const size_t toff = pl.alloc_tickets((size_t)B);
+        pl.add("pose.argmax", {lg, part, pairs, idx}, [=](const Ctx& c) {
+            PoseArgmaxParams p{};
+            p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
+            p.pairs = c.ptr(pairs); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
+            launch_pose_argmax(p, c.stream);
+        }, 0, 4.0 * B * 262144.0);
+    } else {
         Tensor part = pl.alloc(B, 1, 64, 2);
         pl.add("softmax", {part}, [=](const Ctx& c) {
             SoftmaxParams p{};
@@ -543,9 +573,25 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         Tensor xo = ori_in6;
         Tensor ori_mid;
         Tensor raw;
-        if (h->debug) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
+        if (h->debug && !pose) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
         bool fused_done = false;
         for (int j = 0; j < 6; ++j) {
+            if (j == 5 && h->sw.fuse_level1 && pose) {   // the fused level for the tile of each sample's argmax (a wait on pose.argmax)
+                const DecoderW& dw = h->ori;
+                Level1Params lp{};
+                lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
+                lp.wd = dw.l1_wd; lp.bd = dw.l1_bd; lp.wa = dw.l1_wa; lp.ba = dw.l1_ba; lp.wt = dw.l1_wt;
+                lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = 2; lp.normalize = 1;
+                const Tensor din = xo, idx = pose_index;
+                const double px = (double)B * 16 * 16, cin_real = vs.ori[5].din;
+                pl.add("ori1.pose", {din, idx}, [=](const Ctx& c) {
+                    Level1Params q = lp;
+                    q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
+                    launch_level1_pose(q, reinterpret_cast<const int*>(c.ptr(idx)), c.rows, c.stream);
+                }, px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, 4.0 * px / 4 * lp.cx);
+                fused_done = true;
+                break;
+            }
             if (j == 5 && h->sw.fuse_level1) { plan_level1_fused(h->ori, xo, vs.ori[5].din, 2, true, raw, "ori1"); fused_done = true; break; }
             Tensor o = plan_level(h->ori, vs.ori, j, xo, ori_cat[j], "ori" + std::to_string(6 - j));
             if (j < 5) { pl.taps["ori_level" + std::to_string(6 - j)] = {o, 0, o.C}; xo = o; }
@@ -555,15 +601,23 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode) {
         Tensor m = ori_mid;
         const float* tw = h->ori.tail_w;
         const float tb0 = h->ori.tail_b[0], tb1 = h->ori.tail_b[1];
-        const bool dbg = h->debug;
+        const bool dbg = h->debug && !pose;   // (pose plans have no debug taps: ccvpe_localize refuses a debug handle)
         std::vector<Tensor> uses = {m};
         if (dbg) uses.push_back(raw);
+        const Tensor ori_ws = pose ? pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW) : Tensor{};   // pose plans: the whole field, in the workspace
+        if (pose) uses.push_back(ori_ws);
         pl.add("ori1.tail", uses, [=](const Ctx& c) {
             TailConvParams p{};
             p.in = c.ptr(m); p.B = B; p.H = CCVPE_OUT_HW; p.W = CCVPE_OUT_HW; p.w = tw; p.bias[0] = tb0; p.bias[1] = tb1; p.cout = 2;
-            p.normalize = 1; p.out = c.out.ori; p.raw = dbg ? c.ptr(raw) : nullptr;
+            p.normalize = 1; p.out = pose ? c.ptr(ori_ws) : c.out.ori; p.raw = dbg ? c.ptr(raw) : nullptr;
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 288, 4.0 * B * 262144.0 * 18);
+        if (pose) {
+            const Tensor idx = pose_index;
+            pl.add("ori1.gather", {ori_ws, idx}, [=](const Ctx& c) {
+                launch_pose_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+            }, 0, 12.0 * B);
+        }
         }
     }
     // the ground / aerial inputs and the 2 x 512 x 512 orientation output are addressed the same way

@@ -338,6 +338,16 @@ struct Level1Params {
 };
 void launch_level1(const Level1Params& p, hipStream_t s);
 bool level1_supported(int cxp);   // input channel count the fused kernel takes
+// Pose plans (ccvpe_localize): the same fused level for ONE 16 x 16 tile per sample - the tile holding index[b] (pose_argmax_kernel) -
+// one workgroup per sample; the thread that owns the argmax pixel writes rows[b][2..4] = (cos, sin, angle_deg).  cout 2, normalize 1.
+void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hipStream_t s);
+
+// the angle of the test loops (train_VIGOR.py:307-311) in the fp32 form the post-processing kernels write
+__device__ __forceinline__ float pose_angle_deg(float cs, float sn) {
+    float ang = acosf(fminf(fmaxf(cs, -1.f), 1.f)) * 57.29577951308232f;
+    if (sn < 0.f) { ang = fmodf(-ang, 360.f); if (ang < 0.f) ang += 360.f; }
+    return ang;
+}
 
 struct SoftmaxParams {
     const float* logits;       // [B][n]
@@ -347,6 +357,23 @@ struct SoftmaxParams {
     float* out;                // [B][n]
 };
 void launch_softmax(const SoftmaxParams& p, hipStream_t s);
+void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s);   // the first of launch_softmax's two launches alone (pose plans)
+
+// Pose plans: argmax of the softmax WITHOUT the heatmap.  Grid (64 chunks, B): every workgroup re-derives the sample's (max, 1/sum) from
+// the softmax partials as softmax_final_kernel does, recomputes the heatmap values of its chunk in registers with the expression that
+// kernel stores, and keeps the first maximal index; the last arriver of a sample (ticket) writes index[b] and rows[b][0..1].
+struct PoseArgmaxParams {
+    const float* logits;       // [B][n]
+    const float* partial;      // [B][chunks][2] of softmax_partial_kernel
+    int B, n, chunks;          // chunks == 64
+    float* pairs;              // [B][chunks][2] (max, index) hand-off
+    unsigned* tickets;         // [B] counters, zero before and after every launch
+    int* index;                // [B] argmax, always in [0, n)
+    float* rows;               // [B][5]: columns 0 (index) and 1 (prob)
+};
+void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
+// rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
+void launch_pose_gather(const float* ori, const int* index, int B, int n, float* rows, hipStream_t s);
 
 struct PreprocParams {
     const unsigned char* in;   // [B][H][W][3] uint8

@@ -114,13 +114,13 @@ __global__ __launch_bounds__(256) void softmax_partial_kernel(const SoftmaxParam
     }
 }
 
-__global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams p) {
-    __shared__ float gm, gs;
-    const int b = blockIdx.y, ch = blockIdx.x;
+// the sample's (max, 1 / sum) from its chunk partials, into LDS (gm, gs); the caller meets at a barrier before reading them.  Shared by
+// softmax_final_kernel and pose_argmax_kernel: the same order of combines, so the same bits
+__device__ __forceinline__ void softmax_stats(const float* partial, int b, int chunks, float& gm, float& gs) {
     if (threadIdx.x < 64) {
         float m = -INFINITY, s = 0.f;
-        for (int i = threadIdx.x; i < p.chunks; i += 64)
-            combine(m, s, p.partial[((size_t)b * p.chunks + i) * 2], p.partial[((size_t)b * p.chunks + i) * 2 + 1]);
+        for (int i = threadIdx.x; i < chunks; i += 64)
+            combine(m, s, partial[((size_t)b * chunks + i) * 2], partial[((size_t)b * chunks + i) * 2 + 1]);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
@@ -128,6 +128,12 @@ __global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams 
         }
         if (threadIdx.x == 0) { gm = m; gs = 1.f / s; }
     }
+}
+
+__global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams p) {
+    __shared__ float gm, gs;
+    const int b = blockIdx.y, ch = blockIdx.x;
+    softmax_stats(p.partial, b, p.chunks, gm, gs);
     __syncthreads();
     const float m = gm, inv = gs;
     const int per = p.n / p.chunks;
@@ -142,6 +148,10 @@ __global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams 
 void launch_softmax(const SoftmaxParams& p, hipStream_t s) {
     CCVPE_LAUNCH(softmax_partial_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
     CCVPE_LAUNCH(softmax_final_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+}
+
+void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s) {
+    CCVPE_LAUNCH(softmax_partial_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -211,8 +221,7 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* heat, con
         if (threadIdx.x == 0) {
             const float cs = ori[((size_t)b * 2 + 0) * n + bi];
             const float sn = ori[((size_t)b * 2 + 1) * n + bi];
-            float ang = acosf(fminf(fmaxf(cs, -1.f), 1.f)) * 57.29577951308232f;
-            if (sn < 0.f) { ang = fmodf(-ang, 360.f); if (ang < 0.f) ang += 360.f; }
+            const float ang = pose_angle_deg(cs, sn);
             if (rows) {
                 rows[b * 5 + 0] = (float)bi; rows[b * 5 + 1] = best; rows[b * 5 + 2] = cs; rows[b * 5 + 3] = sn; rows[b * 5 + 4] = ang;
             } else {
@@ -234,6 +243,91 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
     unsigned* tickets = reinterpret_cast<unsigned*>(scratch);
     float* part = reinterpret_cast<float*>(scratch) + PP_MAX_BATCH;
     CCVPE_LAUNCH(postprocess_kernel, dim3(PP_CHUNKS, B), dim3(256), 0, s, heat, ori, n, out, rows, part, tickets);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pose plans (ccvpe_localize): postprocess_kernel's argmax over a heatmap that is never stored.  Chunk c of sample b is postprocess_kernel's
+// chunk c (4096 values); its values are recomputed from the logits as __expf(v - m) * inv with softmax_final_kernel's (m, inv), i.e. the
+// bits that kernel would store, so index and prob are those ccvpe_postprocess_rows reads from the heatmap, ties included (strictly greater
+// within a thread, lowest index on ties across threads and chunks).  Every thread's index starts at the first position it scans, so the
+// result is a position of the chunk whatever the values are.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams p) {
+    __shared__ float gm, gs;
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ unsigned flag;
+    const int b = blockIdx.y, c = blockIdx.x;
+    softmax_stats(p.partial, b, p.chunks, gm, gs);
+    const int per = p.n / p.chunks;                   // 4096: a multiple of 4 x 256
+    const int lo = c * per;
+    const float4* src = reinterpret_cast<const float4*>(p.logits + (size_t)b * p.n + lo);
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = src[threadIdx.x + u * 256];   // (per / 4 = 1024 float4 per chunk: four per thread, one trip)
+    __syncthreads();
+    const float m = gm, inv = gs;
+    float best = -INFINITY;
+    int bi = lo + 4 * (int)threadIdx.x;
+    auto take = [&](float x, int i) { const float h = __expf(x - m) * inv; if (h > best) { best = h; bi = i; } };
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int e = lo + (threadIdx.x + u * 256) * 4;
+        take(v[u].x, e); take(v[u].y, e + 1); take(v[u].z, e + 2); take(v[u].w, e + 3);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float v2 = __shfl_xor(best, off);
+        const int i2 = __shfl_xor(bi, off);
+        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+    }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+        st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2, best);
+        st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2 + 1, __int_as_float(bi));
+    }
+    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)p.chunks, &flag)) return;
+    if (threadIdx.x < 64) {
+        best = -INFINITY; bi = 0;
+        for (int k = threadIdx.x; k < p.chunks; k += 64) {
+            const float v2 = ld_sc1(p.pairs + ((size_t)b * p.chunks + k) * 2);
+            const int i2 = __float_as_int(ld_sc1(p.pairs + ((size_t)b * p.chunks + k) * 2 + 1));
+            if (k == threadIdx.x || v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float v2 = __shfl_xor(best, off);
+            const int i2 = __shfl_xor(bi, off);
+            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+        }
+        if (threadIdx.x == 0) {
+            p.index[b] = bi;
+            p.rows[b * 5 + 0] = (float)bi;
+            p.rows[b * 5 + 1] = best;
+        }
+    }
+}
+
+void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s) {
+    CCVPE_LAUNCH(pose_argmax_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+}
+
+__global__ __launch_bounds__(64) void pose_gather_kernel(const float* ori, const int* index, int B, int n, float* rows) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int i = min(max(index[b], 0), n - 1);
+    const float cs = ori[((size_t)b * 2 + 0) * n + i];
+    const float sn = ori[((size_t)b * 2 + 1) * n + i];
+    rows[b * 5 + 2] = cs;
+    rows[b * 5 + 3] = sn;
+    rows[b * 5 + 4] = pose_angle_deg(cs, sn);
+}
+
+void launch_pose_gather(const float* ori, const int* index, int B, int n, float* rows, hipStream_t s) {
+    CCVPE_LAUNCH(pose_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ori, index, B, n, rows);
 }
 
 // ------------------------------------------------------------------------------------------------

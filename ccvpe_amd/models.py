@@ -305,6 +305,41 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return tensors
 
+    # ---- pose-only forward -------------------------------------------------------------------
+    def localize(self, grd: torch.Tensor, sat: torch.Tensor) -> torch.Tensor:
+        """The pose of every query without the nine forward outputs: float32 [B, 5] on the device, the postprocess_rows layout
+        (index, prob, cos, sin, angle_deg).  Bit-identical to postprocess_rows(*forward(grd, sat)[1:3]) (ccvpe_localize)."""
+        grd, sat = self._prepare(grd, sat)
+        B = grd.shape[0]
+        with torch.cuda.device(grd.device):
+            rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
+            stream = torch.cuda.current_stream(grd.device).cuda_stream
+            rc = _lib.load().ccvpe_localize(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                            C.c_void_p(sat.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize")
+        self._tuning_sync()
+        return rows
+
+    def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor) -> torch.Tensor:
+        """localize(grd, sat) with the aerial side taken from encode_aerial(sat): float32 [B, 5] rows (index, prob, cos, sin,
+        angle_deg), the postprocess_rows layout (ccvpe_localize_cached)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        grd = grd.detach().to(torch.float32).contiguous()
+        self._ensure_handle(grd.device)
+        B = grd.shape[0]
+        if getattr(cache, "_ccvpe_batch", B) != B:
+            raise ValueError("cache was encoded for a different batch size")
+        rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
+        stream = torch.cuda.current_stream(grd.device).cuda_stream
+        rc = _lib.load().ccvpe_localize_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                               C.c_void_p(cache.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_cached")
+        self._tuning_sync()
+        return rows
+
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Device-side version of the per-sample loop in train_VIGOR.py:297-316."""

@@ -182,6 +182,17 @@ int ccvpe_encode_aerial(ccvpe_handle h, const float* sat, int32_t batch, void* c
 int ccvpe_forward_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
                          int32_t batch, const ccvpe_outputs* out, void* stream);
 
+/* Pose-only forward: rows[B][5] = (index, prob, cos, sin, angle_deg), DEVICE memory, bit-identical to
+ * ccvpe_forward + ccvpe_postprocess_rows on the same inputs, without writing the nine forward outputs (no heatmap, no
+ * matching-score stacks; the orientation field is computed only around each sample's argmax).  Arguments as ccvpe_forward;
+ * larger batches than the micro-batch loop the same way.  CCVPE_EINVAL for a null `rows`, CCVPE_ESTATE on a handle with debug
+ * taps on (ccvpe_set_debug).  Pose plans run eagerly, never as a captured hipGraph (CCVPE_GRAPH=1 included). */
+int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat,
+                   int32_t batch, float* rows, void* stream);
+/* The same with the aerial side from ccvpe_encode_aerial (batch <= micro_batch, as ccvpe_forward_cached). */
+int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                          int32_t batch, float* rows, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
