@@ -149,6 +149,7 @@ int ccvpe_destroy(ccvpe_handle h) {
     for (void* p : h->dev_allocs) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);
     if (h->post_scratch) (void)hipFree(h->post_scratch);
+    if (h->topk_scratch) (void)hipFree(h->topk_scratch);
     h->plans.clear();
     for (int k = 0; k < 2; ++k) if (h->snap[k]) (void)hipFree(h->snap[k]);
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
@@ -238,11 +239,14 @@ static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
     return 0;
 }
 
-// rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read)
+// rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read);
+// topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller)
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
-                       const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr) {
+                       const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr,
+                       int topk_k = 0, int topk_r = 0) {
     const int mode = cache ? 2 : 0;
     const bool pose = rows != nullptr;
+    const bool topk = pose && topk_k > 0;
     if (!h || !grd || (!sat && !cache) || (!out && !pose)) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     if (cache && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
     if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
@@ -268,14 +272,14 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
     // make sure every plan (and the largest arena) exists before the first launch
     for (int done = 0; done < batch;) {
         const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose);
+        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose, topk);
         if (rc) return rc;
         done += mb;
     }
     const size_t npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
     for (int done = 0; done < batch;) {
         const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose);
+        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose, topk);
         if (rc) return rc;
         h->last_plan = pl;
         Ctx c;
@@ -285,7 +289,10 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         pl->set_scratch(c, 0);
         c.grd = grd + (size_t)done * 3 * gh * gw;
         c.sat = sat ? sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
-        if (pose) {
+        if (topk) {
+            c.rows = rows + (size_t)done * topk_k * 5;
+            c.topk_k = topk_k; c.topk_r = topk_r;
+        } else if (pose) {
             c.rows = rows + (size_t)done * 5;
         } else {
             c.out.logits_flattened = out->logits_flattened + done * npx;
@@ -402,6 +409,20 @@ int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_
     return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows);
 }
 
+// the (k, radius) range of the top-K entry points, checked before the handle is used
+static int check_topk_args(int32_t k, int32_t radius) {
+    if (k < 1 || k > TOPK_MAX_K) return ccvpe_fail(CCVPE_EINVAL, "k must be in 1 .. %d", TOPK_MAX_K);
+    if (radius < 0 || radius > TOPK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d", TOPK_MAX_R);
+    return 0;
+}
+
+int ccvpe_localize_topk(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch, int32_t k,
+                        int32_t radius, float* rows, void* stream) {
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (int rc = check_topk_args(k, radius)) return rc;
+    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, k, radius);
+}
+
 int ccvpe_profile_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
                           const ccvpe_outputs* out, void* stream) {
     int rc = run_forward(h, grd, grd_h, grd_w, sat, batch, out, (hipStream_t)stream, true);
@@ -459,6 +480,42 @@ int ccvpe_postprocess(ccvpe_handle h, const float* heatmap, const float* ori, in
 int ccvpe_postprocess_rows(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, float* rows, void* stream) {
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "bad argument");
     return postprocess_any(h, heatmap, ori, batch, nullptr, rows, stream);
+}
+
+// scratch of the top-K post-processing launch: grows with the largest batch seen, as ensure_post_scratch
+static int ensure_topk_scratch(ccvpe_handle_s* h, int batch) {
+    if (batch <= h->topk_batch) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    if (h->topk_scratch) HIPCHK(hipFree(h->topk_scratch));
+    h->topk_scratch = nullptr; h->topk_batch = 0;
+    const int cap = std::max(batch, 32);
+    void* d = nullptr;
+    if (hipMalloc(&d, topk_scratch_bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "top-K post-processing scratch");
+    HIPCHK(hipMemset(d, 0, topk_scratch_bytes(cap)));
+    HIPCHK(hipDeviceSynchronize());
+    h->topk_scratch = d; h->topk_batch = cap;
+    return 0;
+}
+
+int ccvpe_postprocess_topk(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, int32_t k, int32_t radius, float* rows,
+                           void* stream) {
+    if (!h || !heatmap || !ori || !rows) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (int rc = check_topk_args(k, radius)) return rc;
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "bad argument (batch 1 .. 4096)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_topk_scratch(h, batch)) return rc;
+    // [PP_MAX_BATCH ticket counters][topk_batch x 64 x 64 keys][batch x k indices] (topk_scratch_bytes)
+    unsigned char* base = reinterpret_cast<unsigned char*>(h->topk_scratch);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
+    int* index = reinterpret_cast<int*>(keys + (size_t)h->topk_batch * 64 * TOPK_MAX_K);
+    TopkParams p{};
+    p.heat = heatmap; p.logits = nullptr; p.partial = nullptr; p.B = batch; p.k = k; p.r = radius;
+    p.keys = keys; p.tickets = reinterpret_cast<unsigned*>(base); p.index = index; p.rows = rows;
+    launch_topk_peaks(p, (hipStream_t)stream);
+    launch_topk_gather(ori, index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "postprocess_topk launch failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int ccvpe_eval_metrics(ccvpe_handle h, const ccvpe_pose* poses, const float* heatmap, int32_t batch, const int32_t* gt_index,
@@ -560,6 +617,14 @@ int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows);
+}
+
+int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t batch,
+                               int32_t k, int32_t radius, float* rows, void* stream) {
+    if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (int rc = check_topk_args(k, radius)) return rc;
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius);
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

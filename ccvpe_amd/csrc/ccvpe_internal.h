@@ -237,7 +237,8 @@ struct Ctx {
     unsigned* tickets = nullptr;       // the plan's last-arriver counters (ticket.h); every launch that draws tickets owns a range
     const float* cache_in = nullptr;   // aerial cache consumed by a "cached" plan
     float* cache_out = nullptr;        // aerial cache produced by an "encode" plan
-    float* rows = nullptr;             // pose plans: the [B][5] result rows of this micro-batch (ccvpe_localize)
+    float* rows = nullptr;             // pose plans: the [B][5] result rows of this micro-batch (ccvpe_localize); top-K: [B][topk_k][5]
+    int topk_k = 0, topk_r = 0;        // top-K pose plans: hypotheses per sample (1..64) and suppression radius (0..32) of this call
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -278,6 +279,7 @@ struct Plan {
     int B = 0, gh = 0, gw = 0;
     int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding
     bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
+    bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
     bool debug = false;
     std::vector<size_t> size;     // floats per tensor
     std::vector<size_t> off;      // float offset in the arena
@@ -493,6 +495,8 @@ struct ccvpe_handle_s {
     size_t arena_floats = 0;
     void* post_scratch = nullptr;   // launch_postprocess: partial pairs and ticket counters for post_batch samples
     int post_batch = 0;
+    void* topk_scratch = nullptr;   // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices for topk_batch samples
+    int topk_batch = 0;
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;
@@ -510,9 +514,9 @@ static inline int score_pad(int nscore) { return round_up(nscore, 8); }
 ConvParams conv_params(const PackedConv& pc, const float* in, int in_ld, int B, int H, int W, int OH, int OW,
                        int stride, int pad_t, int pad_l, int act);
 size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]);
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0, bool pose = false);
+int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0, bool pose = false, bool topk = false);
 
 // ---- ccvpe_tune.hip ----
 int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known = nullptr);
-int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode = 0, bool pose = false);
+int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode = 0, bool pose = false, bool topk = false);
 std::string tuning_key(ccvpe_handle_s* h, const Plan& pl, const Op& op);

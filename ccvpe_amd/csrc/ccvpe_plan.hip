@@ -255,11 +255,16 @@ extern "C" int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t g
 // launch alone, pose_argmax_kernel (argmax and prob from recomputed heatmap values) and the orientation field at the argmax pixel only
 // (ori1.pose: the fused level 1 for the one tile that holds it; without the fused level: ori1.tail into the workspace + ori1.gather).
 // Never captured into a hipGraph.
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, bool pose) {
+// Top-K pose plans (topk = true as well, ccvpe_localize_topk): the same launches up to softmax.partial and the level-2 decoders; the
+// tail is topk.peaks (the K best peaks from recomputed heatmap values) and the orientation at those K pixels (ori1.topk:
+// the fused level 1 for each hypothesis' tile; without the fused level: ori1.tail + ori1.topk_gather).  K and r come with each call
+// (Ctx::topk_k / topk_r); the workspace is sized for K = 64.
+int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, bool pose, bool topk) {
     if (mode == 1) return build_aerial_plan(h, pl, B);
     const bool cached = mode == 2;
     pl.mode = mode;
     pl.pose = pose;
+    pl.topk = pose && topk;
     const VariantSpec& vs = h->vs;
     pl.B = B; pl.gh = gh; pl.gw = gw; pl.debug = h->debug;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
@@ -541,8 +546,25 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 144, 4.0 * B * 262144.0 * 17);
     }
-    Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side
-    if (pose) {
+    Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
+    if (pl.topk) {
+        Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, 2 * TOPK_MAX_K);
+        pose_index = pl.alloc(B, 1, 1, TOPK_MAX_K);
+        const Tensor lg = logits_ws, idx = pose_index;
+        pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
+            SoftmaxParams p{};
+            p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
+            launch_softmax_partial(p, c.stream);
+        }, 0, 4.0 * B * 262144.0);
+        const size_t toff = pl.alloc_tickets((size_t)B);
+        pl.add("topk.peaks", {lg, part, keys, idx}, [=](const Ctx& c) {
+            TopkParams p{};
+            p.heat = nullptr; p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.k = c.topk_k; p.r = c.topk_r;
+            p.keys = reinterpret_cast<unsigned long long*>(c.ptr(keys)); p.tickets = c.tickets + toff;
+            p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
+            launch_topk_peaks(p, c.stream);
+        }, 0, 4.0 * B * 262144.0);
+    } else if (pose) {
         static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
         Tensor part = pl.alloc(B, 1, 64, 2), pairs = pl.alloc(B, 1, 64, 2);
         pose_index = pl.alloc(B, 1, 1, 1);
@@ -576,6 +598,22 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         if (h->debug && !pose) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
         bool fused_done = false;
         for (int j = 0; j < 6; ++j) {
+            if (j == 5 && h->sw.fuse_level1 && pl.topk) {   // the fused level for the tile of each hypothesis (a wait on topk.peaks)
+                const DecoderW& dw = h->ori;
+                Level1Params lp{};
+                lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
+                lp.wd = dw.l1_wd; lp.bd = dw.l1_bd; lp.wa = dw.l1_wa; lp.ba = dw.l1_ba; lp.wt = dw.l1_wt;
+                lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = 2; lp.normalize = 1;
+                const Tensor din = xo, idx = pose_index;
+                const double px = (double)B * 8 * 16 * 16, cin_real = vs.ori[5].din;   // (accounted at K = 8)
+                pl.add("ori1.topk", {din, idx}, [=](const Ctx& c) {
+                    Level1Params q = lp;
+                    q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
+                    launch_level1_topk(q, reinterpret_cast<const int*>(c.ptr(idx)), c.topk_k, c.rows, c.stream);
+                }, px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, 4.0 * px / 4 * lp.cx);
+                fused_done = true;
+                break;
+            }
             if (j == 5 && h->sw.fuse_level1 && pose) {   // the fused level for the tile of each sample's argmax (a wait on pose.argmax)
                 const DecoderW& dw = h->ori;
                 Level1Params lp{};
@@ -612,7 +650,12 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             p.normalize = 1; p.out = pose ? c.ptr(ori_ws) : c.out.ori; p.raw = dbg ? c.ptr(raw) : nullptr;
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 288, 4.0 * B * 262144.0 * 18);
-        if (pose) {
+        if (pl.topk) {
+            const Tensor idx = pose_index;
+            pl.add("ori1.topk_gather", {ori_ws, idx}, [=](const Ctx& c) {
+                launch_topk_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, c.topk_k, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+            }, 0, 12.0 * B * 8);
+        } else if (pose) {
             const Tensor idx = pose_index;
             pl.add("ori1.gather", {ori_ws, idx}, [=](const Ctx& c) {
                 launch_pose_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);

@@ -341,6 +341,8 @@ bool level1_supported(int cxp);   // input channel count the fused kernel takes
 // Pose plans (ccvpe_localize): the same fused level for ONE 16 x 16 tile per sample - the tile holding index[b] (pose_argmax_kernel) -
 // one workgroup per sample; the thread that owns the argmax pixel writes rows[b][2..4] = (cos, sin, angle_deg).  cout 2, normalize 1.
 void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hipStream_t s);
+// Top-K pose plans: grid (k, B), workgroup (j, b) runs the tile of index[b][j] and writes rows[b][j][2..4]; index -1 exits at once.
+void launch_level1_topk(const Level1Params& p, const int* index, int k, float* rows, hipStream_t s);
 
 // the angle of the test loops (train_VIGOR.py:307-311) in the fp32 form the post-processing kernels write
 __device__ __forceinline__ float pose_angle_deg(float cs, float sn) {
@@ -374,6 +376,26 @@ struct PoseArgmaxParams {
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
 void launch_pose_gather(const float* ori, const int* index, int B, int n, float* rows, hipStream_t s);
+
+// Top-K peaks (ccvpe_postprocess_topk / ccvpe_localize_topk).  Grid (64 tiles of 64 x 64, B): peaks of the heatmap
+// under a Chebyshev radius r (value descending, index ascending), the best k per tile handed to the sample's last arriver (ticket),
+// which writes index[b][k] (-1: no peak) and rows[b][k][0..1] - the whole row (-1, 0, 0, 0, 0) for a slot without a peak.
+static constexpr int TOPK_MAX_K = 64, TOPK_MAX_R = 32;
+struct TopkParams {
+    const float* heat;          // [B][n] stored heatmap, or null: recompute it from
+    const float* logits;        //   [B][n] logits and
+    const float* partial;       //   [B][64][2] softmax partials (softmax_final_kernel's statistics and expression)
+    int B, k, r;                // k 1..64, r 0..32
+    unsigned long long* keys;   // [B][64][k] hand-off
+    unsigned* tickets;          // [B] counters, zero before and after every launch
+    int* index;                 // [B][k]
+    float* rows;                // [B][k][5]
+};
+void launch_topk_peaks(const TopkParams& p, hipStream_t s);
+// rows[b][k][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b][k] >= 0 (postprocess_topk; pose plans without the fused level 1)
+void launch_topk_gather(const float* ori, const int* index, int B, int K, int n, float* rows, hipStream_t s);
+// ccvpe_postprocess_topk scratch for B samples: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys][B x 64 indices]
+size_t topk_scratch_bytes(int B);
 
 struct PreprocParams {
     const unsigned char* in;   // [B][H][W][3] uint8

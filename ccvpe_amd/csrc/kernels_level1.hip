@@ -59,12 +59,28 @@ __global__ __launch_bounds__(256) void level1_kernel(const Level1Params p) {
     constexpr bool POSE = false;
     const int* pose_index = nullptr;
     float* pose_rows = nullptr;
+    constexpr int pose_slot = 0, pose_sample = 0, pose_ld = 0, pose_r0 = 0;
 #include "kernels_level1_tile.inc"
 }
 
 template <int COUT>
 __global__ __launch_bounds__(256) void level1_pose_kernel(const Level1Params p, const int* pose_index, float* pose_rows) {
     constexpr bool POSE = true;
+    const unsigned pose_slot = blockIdx.x;                 // one workgroup per sample: index[b], rows[b][0..4]
+    const int pose_sample = (int)blockIdx.x;
+    constexpr int pose_ld = 5, pose_r0 = 0;
+#include "kernels_level1_tile.inc"
+}
+
+// Top-K pose plans (ccvpe_localize_topk): grid (K, B), workgroup (k, b) runs the tile of hypothesis index[b][k] and writes
+// rows[b][k][2..4]; a slot without a peak (index -1) exits before it touches anything.  Two hypotheses in one tile each run it.
+template <int COUT>
+__global__ __launch_bounds__(256) void level1_topk_kernel(const Level1Params p, const int* pose_index, float* pose_rows) {
+    constexpr bool POSE = true;
+    const int K = (int)gridDim.x;
+    const int pose_slot = (int)blockIdx.y * K + (int)blockIdx.x, pose_sample = (int)blockIdx.y;
+    const int pose_ld = 5 * K, pose_r0 = 5 * (int)blockIdx.x;
+    if (pose_index[pose_slot] < 0) return;
 #include "kernels_level1_tile.inc"
 }
 
@@ -113,6 +129,13 @@ void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hi
     static LdsAttr attr;
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(level1_pose_kernel<2>), lds);
     CCVPE_LAUNCH(level1_pose_kernel<2>, dim3(p.B), dim3(256), lds, s, p, index, rows);
+}
+
+void launch_level1_topk(const Level1Params& p, const int* index, int k, float* rows, hipStream_t s) {
+    const size_t lds = level1_lds_bytes(p.cxp, 2);
+    static LdsAttr attr;
+    ensure_dynamic_lds(attr, reinterpret_cast<const void*>(level1_topk_kernel<2>), lds);
+    CCVPE_LAUNCH(level1_topk_kernel<2>, dim3(k, p.B), dim3(256), lds, s, p, index, rows);
 }
 
 }  // namespace ccvpe

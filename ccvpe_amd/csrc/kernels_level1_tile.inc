@@ -1,5 +1,6 @@
 // Body of level1_kernel and level1_pose_kernel (kernels_level1.hip), included inside both kernels.  In scope: `p` (Level1Params), COUT,
-// constexpr bool POSE, `pose_index` and `pose_rows` (null unless POSE).
+// constexpr bool POSE, `pose_index` and `pose_rows` (null unless POSE), and the POSE addressing: the workgroup runs the tile of pixel
+// pose_index[pose_slot] of sample pose_sample and writes row pose_rows[b * pose_ld + pose_r0 + 0..4].
 extern __shared__ __attribute__((aligned(16))) float smem[];
 const int CXP = p.cxp;                 // input channels padded to a multiple of 16
 const int XS = CXP + 4;                // row stride of the X tile
@@ -19,10 +20,10 @@ const int stride = ((int)gridDim.x >> 3) + (xcd < ((int)gridDim.x & 7) ? 1 : 0);
 const int t_begin = xcd * (tiles >> 3) + min(xcd, tiles & 7);
 int t_end = t_begin + (tiles >> 3) + (xcd < (tiles & 7) ? 1 : 0);
 int tile = t_begin + ((int)blockIdx.x >> 3);
-int pose_pix = 0;                      // POSE: the argmax pixel (row * W + col) of sample blockIdx.x
+int pose_pix = 0;                      // POSE: the pixel (row * W + col) whose orientation this workgroup writes
 if constexpr (POSE) {
-    pose_pix = min(max(pose_index[blockIdx.x], 0), H * W - 1);
-    tile = (int)blockIdx.x * (tiles_x * tiles_y) + (pose_pix / W / T) * tiles_x + (pose_pix % W) / T;
+    pose_pix = min(max(pose_index[pose_slot], 0), H * W - 1);
+    tile = pose_sample * (tiles_x * tiles_y) + (pose_pix / W / T) * tiles_x + (pose_pix % W) / T;
     t_end = tile + 1;                  // one tile: no next one to prefetch
 }
 if (tile >= t_end) return;
@@ -265,9 +266,9 @@ while (true) {
     if constexpr (POSE) {   // (p.raw is null and p.normalize 1: the values ccvpe_postprocess_rows reads from the orientation output)
         static_assert(COUT == 2, "the pose form serves the orientation decoder");
         if (opix == (size_t)pose_pix) {
-            pose_rows[b * 5 + 2] = o[0];
-            pose_rows[b * 5 + 3] = o[1];
-            pose_rows[b * 5 + 4] = pose_angle_deg(o[0], o[1]);
+            pose_rows[b * pose_ld + pose_r0 + 2] = o[0];
+            pose_rows[b * pose_ld + pose_r0 + 3] = o[1];
+            pose_rows[b * pose_ld + pose_r0 + 4] = pose_angle_deg(o[0], o[1]);
         }
         break;
     }

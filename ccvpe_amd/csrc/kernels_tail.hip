@@ -331,6 +331,179 @@ void launch_pose_gather(const float* ori, const int* index, int B, int n, float*
 }
 
 // ------------------------------------------------------------------------------------------------
+// Top-K peaks (ccvpe_postprocess_topk, ccvpe_localize_topk): pixel q suppresses p when q != p lies in p's (2r+1)^2 window and
+// (H[q], -q) > (H[p], -p); p is a peak when H[p] > 0 and nothing suppresses it.  A pixel's key is u(p) = bits of H[p] when H[p] > 0
+// (positive floats order like their bit patterns), else 0 - so NaN, zeros and pixels outside the image never suppress anything -
+// and p is a peak iff u(p) > 0 and p is the raster-first maximum of u over its window.  That maximum is separable: the first maximum
+// of each row segment (strictly greater keeps the leftmost), then the first of those down the column (strictly greater keeps the
+// topmost row, and a higher row holds the lower index whatever its column).
+//
+// Grid (64 tiles, B): a workgroup owns a 64 x 64 tile, stages the tile plus an r halo as keys in LDS (from the stored heatmap, or
+// recomputed from the logits with softmax_final_kernel's (m, inv) and expression - the same bits), finds its peaks, sorts them as
+// 64-bit keys (value bits << 32 | ~index: value descending, index ascending) with a bitonic sort in LDS and hands its best K to the
+// sample's last arriver (ticket.h), which sorts the 64 K candidates the same way and writes index[b][k] and rows[b][k][0..1].  A slot
+// without a peak gets index -1 and the row (-1, 0, 0, 0, 0); the orientation launches behind skip it.
+// ------------------------------------------------------------------------------------------------
+static constexpr int TK_HW = 512;                  // map side (CCVPE_OUT_HW)
+static constexpr int TK_T = 64;                    // tile side
+static constexpr int TK_TILES = (TK_HW / TK_T) * (TK_HW / TK_T);   // 64 per sample
+static_assert(TK_T * TK_T * (4 + 5) >= TK_TILES * TOPK_MAX_K * 8, "the sort buffer aliases the smallest staging area");
+
+__host__ __device__ constexpr int topk_halo(int r) { return TK_T + 2 * r; }
+// staging: keys [S][S], row maxima [S][64] and their column offsets [S][64] (bytes); the sort buffer (<= 4096 keys) aliases them
+static size_t topk_lds_bytes(int r) { const size_t S = topk_halo(r); return (S * S * 4 + S * TK_T * 5 + 7) & ~(size_t)7; }
+
+// descending bitonic sort of s[0, N), N a power of two >= 2; every thread of the workgroup calls it, and it ends at a barrier
+__device__ __forceinline__ void topk_sort_desc(unsigned long long* s, int N) {
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int q = threadIdx.x; q < N / 2; q += 256) {
+                const int i = 2 * q - (q & (j - 1)), l = i + j;
+                const unsigned long long a = s[i], c = s[l];
+                if ((i & k) == 0 ? a < c : a > c) { s[i] = c; s[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+template <bool LOGITS>
+__global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+    __shared__ float gm, gs;
+    __shared__ unsigned cnt, flag;
+    constexpr int HW = TK_HW, n = HW * HW;
+    const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+    const int r = p.r, S = topk_halo(r);
+    const int Y0 = (t / (HW / TK_T)) * TK_T, X0 = (t % (HW / TK_T)) * TK_T;
+    unsigned* in = reinterpret_cast<unsigned*>(tk_smem);                    // [S][S]
+    unsigned* hv = in + S * S;                                              // [S][64]
+    unsigned char* hc = reinterpret_cast<unsigned char*>(hv + S * TK_T);   // [S][64]
+    unsigned long long* sk = reinterpret_cast<unsigned long long*>(tk_smem);
+    float m = 0.f, inv = 0.f;
+    if (LOGITS) {
+        softmax_stats(p.partial, b, 64, gm, gs);   // (the 64 chunks of the pose plans' softmax.partial launch)
+        __syncthreads();
+        m = gm; inv = gs;
+    }
+    if (tid == 0) cnt = 0u;
+    const float* src = (LOGITS ? p.logits : p.heat) + (size_t)b * n;
+    for (int i = tid; i < S * S; i += 256) {
+        const int ly = i / S, lx = i - ly * S;
+        const int y = Y0 - r + ly, x = X0 - r + lx;
+        unsigned u = 0u;
+        if ((unsigned)y < (unsigned)HW && (unsigned)x < (unsigned)HW) {
+            float h = src[y * HW + x];
+            if (LOGITS) h = __expf(h - m) * inv;
+            u = h > 0.f ? __float_as_uint(h) : 0u;
+        }
+        in[i] = u;
+    }
+    __syncthreads();
+    // first maximum of every row segment [x - r, x + r] of the S staged rows
+    for (int i = tid; i < S * TK_T; i += 256) {
+        const unsigned* row = in + (i >> 6) * S + (i & 63);
+        unsigned best = row[0];
+        int bc = 0;
+#pragma unroll 8
+        for (int d = 1; d <= 2 * r; ++d) { const unsigned v = row[d]; if (v > best) { best = v; bc = d; } }   // (8 LDS reads in flight)
+        hv[i] = best;
+        hc[i] = (unsigned char)bc;
+    }
+    __syncthreads();
+    // the 16 pixels of this thread: peak test, then its key (0: no peak)
+    unsigned long long key[TK_T * TK_T / 256];
+#pragma unroll
+    for (int u = 0; u < TK_T * TK_T / 256; ++u) {
+        const int j = tid + u * 256, py = j >> 6, px = j & 63;
+        const unsigned mine = in[(py + r) * S + px + r];
+        const int own = (py + r) * TK_T + px;
+        bool peak = mine != 0u && hv[own] == mine && hc[own] == r;   // (p is the first maximum of its own row segment)
+        if (peak) {
+            const unsigned* col = hv + py * TK_T + px;
+            unsigned best = col[0];
+            int br = 0;
+#pragma unroll 8
+            for (int d = 1; d <= 2 * r; ++d) { const unsigned v = col[d * TK_T]; if (v > best) { best = v; br = d; } }
+            peak = br == r;
+        }
+        const unsigned idx = (unsigned)((Y0 + py) * HW + X0 + px);
+        key[u] = peak ? ((unsigned long long)mine << 32) | (unsigned long long)(~idx) : 0ull;
+    }
+    __syncthreads();   // the staging area becomes the sort buffer
+#pragma unroll
+    for (int u = 0; u < TK_T * TK_T / 256; ++u)
+        if (key[u]) sk[atomicAdd(&cnt, 1u)] = key[u];
+    __syncthreads();
+    const int np = (int)cnt;
+    int N = TOPK_MAX_K;
+    while (N < np) N <<= 1;
+    for (int i = np + tid; i < N; i += 256) sk[i] = 0ull;
+    __syncthreads();
+    topk_sort_desc(sk, N);
+    const int K = p.k;
+    unsigned long long* hand = p.keys + ((size_t)b * TK_TILES + t) * K;
+    for (int i = tid; i < K; i += 256) __hip_atomic_store(hand + i, sk[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)TK_TILES, &flag)) return;
+    // last arriver of sample b: the best K of the 64 K candidates
+    const int M = TK_TILES * K;
+    N = TOPK_MAX_K;
+    while (N < M) N <<= 1;
+    const unsigned long long* all = p.keys + (size_t)b * TK_TILES * K;
+    for (int i = tid; i < N; i += 256) sk[i] = i < M ? __hip_atomic_load(all + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    __syncthreads();
+    topk_sort_desc(sk, N);
+    for (int i = tid; i < K; i += 256) {
+        const unsigned long long kv = sk[i];
+        float* row = p.rows + ((size_t)b * K + i) * 5;
+        if (kv) {
+            const int idx = (int)~(unsigned)kv;
+            p.index[b * K + i] = idx;
+            row[0] = (float)idx;
+            row[1] = __uint_as_float((unsigned)(kv >> 32));
+        } else {
+            p.index[b * K + i] = -1;
+            row[0] = -1.f; row[1] = 0.f; row[2] = 0.f; row[3] = 0.f; row[4] = 0.f;
+        }
+    }
+}
+
+void launch_topk_peaks(const TopkParams& p, hipStream_t s) {
+    const size_t lds = topk_lds_bytes(p.r);
+    if (p.logits) {
+        static LdsAttr attr;
+        ensure_dynamic_lds(attr, reinterpret_cast<const void*>(topk_peaks_kernel<true>), lds);
+        CCVPE_LAUNCH(topk_peaks_kernel<true>, dim3(TK_TILES, p.B), dim3(256), lds, s, p);
+    } else {
+        static LdsAttr attr;
+        ensure_dynamic_lds(attr, reinterpret_cast<const void*>(topk_peaks_kernel<false>), lds);
+        CCVPE_LAUNCH(topk_peaks_kernel<false>, dim3(TK_TILES, p.B), dim3(256), lds, s, p);
+    }
+}
+
+// pose_gather_kernel for K hypotheses per sample: thread = slot (b, k); slots without a peak (index -1) keep their row
+__global__ __launch_bounds__(64) void topk_gather_kernel(const float* ori, const int* index, int B, int K, int n, float* rows) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= B * K) return;
+    const int i = index[t];
+    if (i < 0 || i >= n) return;
+    const int b = t / K;
+    const float cs = ori[((size_t)b * 2 + 0) * n + i];
+    const float sn = ori[((size_t)b * 2 + 1) * n + i];
+    rows[(size_t)t * 5 + 2] = cs;
+    rows[(size_t)t * 5 + 3] = sn;
+    rows[(size_t)t * 5 + 4] = pose_angle_deg(cs, sn);
+}
+
+void launch_topk_gather(const float* ori, const int* index, int B, int K, int n, float* rows, hipStream_t s) {
+    CCVPE_LAUNCH(topk_gather_kernel, dim3((B * K + 63) / 64), dim3(64), 0, s, ori, index, B, K, n, rows);
+}
+
+size_t topk_scratch_bytes(int B) {
+    return (size_t)PP_MAX_BATCH * sizeof(unsigned) + (size_t)B * TK_TILES * TOPK_MAX_K * sizeof(unsigned long long) +
+           (size_t)B * TOPK_MAX_K * sizeof(int);
+}
+
+// ------------------------------------------------------------------------------------------------
 // GT-side test-loop metrics (second half): train_VIGOR.py:296-326, train_KITTI.py:309-343.  One thread per
 // query, double precision like the reference's numpy / math code.  Inputs: the pose of postprocess_kernel, the heatmap (for
 // the probability at the ground-truth pixel) and per-query ground truth from the dataset side.

@@ -340,6 +340,76 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return rows
 
+    # ---- several pose hypotheses per query ----------------------------------------------------
+    @staticmethod
+    def _topk_args(k: int, radius: int):
+        k, radius = int(k), int(radius)
+        if not 1 <= k <= 64:
+            raise ValueError(f"k must be in 1..64, got {k}")
+        if not 0 <= radius <= 32:
+            raise ValueError(f"radius must be in 0..32, got {radius}")
+        return k, radius
+
+    def localize_topk(self, grd: torch.Tensor, sat: torch.Tensor, k: int, radius: int) -> torch.Tensor:
+        """The k strongest heatmap peaks of every query under a suppression radius, with their orientation: float32 [B, k, 5]
+        on the device, rows (index, prob, cos, sin, angle_deg); (-1, 0, 0, 0, 0) past a query's last peak.  Bit-identical to
+        postprocess_topk(*forward(grd, sat)[1:3], k, radius) (ccvpe_localize_topk)."""
+        grd, sat = self._prepare(grd, sat)
+        k, radius = self._topk_args(k, radius)
+        B = grd.shape[0]
+        with torch.cuda.device(grd.device):
+            rows = torch.empty((B, k, 5), dtype=torch.float32, device=grd.device)
+            stream = torch.cuda.current_stream(grd.device).cuda_stream
+            rc = _lib.load().ccvpe_localize_topk(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                 C.c_void_p(sat.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
+                                                 C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_topk")
+        self._tuning_sync()
+        return rows
+
+    def localize_topk_cached(self, grd: torch.Tensor, cache: torch.Tensor, k: int, radius: int) -> torch.Tensor:
+        """localize_topk(grd, sat, k, radius) with the aerial side taken from encode_aerial(sat): float32 [B, k, 5]
+        (ccvpe_localize_topk_cached)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        k, radius = self._topk_args(k, radius)
+        grd = grd.detach().to(torch.float32).contiguous()
+        self._ensure_handle(grd.device)
+        B = grd.shape[0]
+        if getattr(cache, "_ccvpe_batch", B) != B:
+            raise ValueError("cache was encoded for a different batch size")
+        rows = torch.empty((B, k, 5), dtype=torch.float32, device=grd.device)
+        stream = torch.cuda.current_stream(grd.device).cuda_stream
+        rc = _lib.load().ccvpe_localize_topk_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                    C.c_void_p(cache.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
+                                                    C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_topk_cached")
+        self._tuning_sync()
+        return rows
+
+    def postprocess_topk(self, heatmap: torch.Tensor, ori: torch.Tensor, k: int, radius: int) -> torch.Tensor:
+        """postprocess_rows() generalised to the k strongest peaks under a suppression radius, on forward outputs the caller
+        holds: float32 [B, k, 5] on the device (ccvpe_postprocess_topk, the definition in include/ccvpe.h)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not (heatmap.is_cuda and ori.is_cuda):
+            raise RuntimeError("ccvpe_amd has no CPU path: heatmap and ori must live on an MI355X (cuda) device")
+        k, radius = self._topk_args(k, radius)
+        B = heatmap.shape[0]
+        if heatmap.numel() != B * 512 * 512 or ori.numel() != B * 2 * 512 * 512:
+            raise ValueError(f"expected heatmap [B,1,512,512] and ori [B,2,512,512], got {tuple(heatmap.shape)} / {tuple(ori.shape)}")
+        heatmap = heatmap.detach().to(torch.float32).contiguous()
+        ori = ori.detach().to(torch.float32).contiguous()
+        self._ensure_handle(heatmap.device)
+        rows = torch.empty((B, k, 5), dtype=torch.float32, device=heatmap.device)
+        stream = torch.cuda.current_stream(heatmap.device).cuda_stream
+        rc = _lib.load().ccvpe_postprocess_topk(self._handle, C.c_void_p(heatmap.data_ptr()), C.c_void_p(ori.data_ptr()), B, k,
+                                                radius, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_postprocess_topk")
+        return rows
+
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Device-side version of the per-sample loop in train_VIGOR.py:297-316."""

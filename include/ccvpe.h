@@ -162,6 +162,16 @@ int ccvpe_postprocess(ccvpe_handle h, const float* heatmap, const float* ori, in
  * record a data-parallel evaluation gathers (train_VIGOR.py:297-316 keeps them in Python lists).  batch <= 4096. */
 int ccvpe_postprocess_rows(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch,
                            float* rows, void* stream);
+/* The K strongest pose hypotheses per query instead of the argmax alone: rows[B][k][5] = (index, prob, cos, sin, angle_deg),
+ * DEVICE memory, the row layout of ccvpe_postprocess_rows.  Pixel q suppresses pixel p when q != p, max(|qy-py|, |qx-px|) <=
+ * radius and heatmap[q] > heatmap[p], or the two are equal and q < p (NaN never suppresses); p is a peak when heatmap[p] > 0
+ * and nothing suppresses it.  Peaks are ordered by value (descending), then index (ascending); a query with fewer than k
+ * peaks gets rows (-1, 0, 0, 0, 0) for the rest.  k = 1 on a map without NaN gives the ccvpe_postprocess_rows row.
+ * k 1..64, radius 0..32, batch <= 4096; CCVPE_EINVAL for a null pointer or an argument out of range (checked before the
+ * handle is used).  One call in flight per handle, as ccvpe_postprocess (the launch keeps ticket counters and per-tile
+ * candidates in a scratch buffer of the handle). */
+int ccvpe_postprocess_topk(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, int32_t k,
+                           int32_t radius, float* rows, void* stream);
 
 /* Ground-truth side of the same test loop, on device: `poses` from ccvpe_postprocess, `gt_index[B]` = flat index of
  * argmax(gt map) (y*512 + x), `gt_cos_sin[B][2]` = ground-truth orientation at that pixel (NULL: no orientation error),
@@ -192,6 +202,16 @@ int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_
 /* The same with the aerial side from ccvpe_encode_aerial (batch <= micro_batch, as ccvpe_forward_cached). */
 int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
                           int32_t batch, float* rows, void* stream);
+/* Pose-only forward with the K strongest hypotheses per query: rows[B][k][5], DEVICE memory, bit-identical to ccvpe_forward +
+ * ccvpe_postprocess_topk(k, radius) on the same inputs, without writing the nine forward outputs (the orientation field is
+ * computed only around each hypothesis).  Restrictions as ccvpe_localize (micro-batch loop, CCVPE_ESTATE on a debug handle,
+ * never a captured hipGraph); CCVPE_EINVAL for a null pointer, k outside 1..64 or radius outside 0..32, checked before the
+ * handle is used.  Every (k, radius) runs the same plan. */
+int ccvpe_localize_topk(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat,
+                        int32_t batch, int32_t k, int32_t radius, float* rows, void* stream);
+/* The same with the aerial side from ccvpe_encode_aerial (batch <= micro_batch, as ccvpe_forward_cached). */
+int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                               int32_t batch, int32_t k, int32_t radius, float* rows, void* stream);
 
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
