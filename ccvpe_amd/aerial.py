@@ -193,6 +193,27 @@ def oxford_aerial(map_u8, image_coords, mean=_lib.IMAGENET_MEAN, std=_lib.IMAGEN
     return _lib.preprocess_window_resize(map_u8, win["origin"], (OXFORD_WIN, OXFORD_WIN), (SAT_HW, SAT_HW), mean, std)
 
 
+def oxford_tiles(image_coords) -> Dict[str, np.ndarray]:
+    """The distinct test windows of a batch of ground images at image_coords [B,2]: origin [T,2] int32 = the crop origins of
+    oxford_window in order of first appearance, tile_index [B] int32 with origin[tile_index] == oxford_window(image_coords)["origin"].
+    A sequential drive (the test loader does not shuffle, train_OxfordRobotCar.py:81-83) visits a handful of tiles per batch: encode
+    oxford_tile_aerial(map_u8, origin) once and pass tile_index to the model's cached calls."""
+    win = oxford_window(image_coords)["origin"]
+    seen: Dict[Tuple[int, int], int] = {}
+    index = np.empty(win.shape[0], dtype=np.int32)
+    for b, (x0, y0) in enumerate(win):
+        index[b] = seen.setdefault((int(x0), int(y0)), len(seen))
+    origin = np.array(list(seen), dtype=np.int32).reshape(-1, 2)
+    return {"origin": origin, "tile_index": index}
+
+
+def oxford_tile_aerial(map_u8, origins, mean=_lib.IMAGENET_MEAN, std=_lib.IMAGENET_STD):
+    """The resident satellite map [map_h,map_w,3] (cuda uint8) -> the `sat` tensors [T,3,512,512] of the 800 x 800 windows at crop
+    origins [T,2] = (x0, y0) (oxford_tiles), in two launches: the second half of oxford_aerial, once per distinct tile."""
+    org = np.asarray(origins, dtype=np.int32).reshape(-1, 2)
+    return _lib.preprocess_window_resize(map_u8, org, (OXFORD_WIN, OXFORD_WIN), (SAT_HW, SAT_HW), mean, std)
+
+
 def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
     """Ground-truth side of an Oxford test sample (datasets.py:323-351): gt_index [B] int32 = flat argmax of `gt`, gt_cos_sin [B,2]
     float32 = `orientation` at that pixel, heading_deg [B] float64 = `orientation_angle` (yaw: grdYaw, radians)."""

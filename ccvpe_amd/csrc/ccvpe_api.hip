@@ -243,12 +243,14 @@ static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
 // topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller)
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
                        const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr,
-                       int topk_k = 0, int topk_r = 0) {
+                       int topk_k = 0, int topk_r = 0, const int32_t* tile_index = nullptr, int n_tiles = 0) {
     const int mode = cache ? 2 : 0;
     const bool pose = rows != nullptr;
     const bool topk = pose && topk_k > 0;
     if (!h || !grd || (!sat && !cache) || (!out && !pose)) return ccvpe_fail(CCVPE_EINVAL, "null argument");
-    if (cache && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
+    if (cache && !tile_index && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
+    if (tile_index && n_tiles > h->cfg.micro_batch)
+        return ccvpe_fail(CCVPE_EINVAL, "n_tiles %d exceeds micro_batch (%d), the most ccvpe_encode_aerial writes", n_tiles, h->cfg.micro_batch);
     if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
     if (pose && h->debug) return ccvpe_fail(CCVPE_ESTATE, "pose plans carry no debug taps: ccvpe_set_debug(h, 0) before ccvpe_localize");
     if (batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "batch must be positive");
@@ -284,6 +286,7 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         h->last_plan = pl;
         Ctx c;
         c.cache_in = cache;
+        if (tile_index) { c.tile_index = tile_index + done; c.n_tiles = n_tiles; }   // every slice reads its own indices of the one cache
         c.arena = h->arena; c.off = &pl->off; c.stream = stream;
         c.tickets = pl->tickets;
         pl->set_scratch(c, 0);
@@ -625,6 +628,45 @@ int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, 
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_topk_args(k, radius)) return rc;
     return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius);
+}
+
+// Arguments of the indexed cached forms, checked before the handle is used: tile_index is host memory, so every entry is read
+// here and no launch is issued for a call that names a tile outside the cache.
+static int check_indexed_args(const float* grd, const void* cache, int32_t n_tiles, const int32_t* tile_index, int32_t batch,
+                              const void* result) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+    if (!tile_index) return ccvpe_fail(CCVPE_EINVAL, "null tile_index");
+    if (!result) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
+    if (n_tiles <= 0) return ccvpe_fail(CCVPE_EINVAL, "n_tiles must be positive, got %d", n_tiles);
+    if (batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "batch must be positive");
+    for (int32_t b = 0; b < batch; ++b)
+        if (tile_index[b] < 0 || tile_index[b] >= n_tiles)
+            return ccvpe_fail(CCVPE_EINVAL, "tile_index[%d] = %d is outside 0 .. %d (n_tiles %d)", b, tile_index[b], n_tiles - 1, n_tiles);
+    return 0;
+}
+
+int ccvpe_forward_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                 const int32_t* tile_index, int32_t batch, const ccvpe_outputs* out, void* stream) {
+    if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, out)) return rc;
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, out, (hipStream_t)stream, false, (const float*)cache, nullptr, 0, 0,
+                       tile_index, n_tiles);
+}
+
+int ccvpe_localize_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                  const int32_t* tile_index, int32_t batch, float* rows, void* stream) {
+    if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, 0, 0,
+                       tile_index, n_tiles);
+}
+
+int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                       int32_t n_tiles, const int32_t* tile_index, int32_t batch, int32_t k, int32_t radius, float* rows,
+                                       void* stream) {
+    if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    if (int rc = check_topk_args(k, radius)) return rc;
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius,
+                       tile_index, n_tiles);
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

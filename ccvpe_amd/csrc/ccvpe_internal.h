@@ -239,6 +239,8 @@ struct Ctx {
     float* cache_out = nullptr;        // aerial cache produced by an "encode" plan
     float* rows = nullptr;             // pose plans: the [B][5] result rows of this micro-batch (ccvpe_localize); top-K: [B][topk_k][5]
     int topk_k = 0, topk_r = 0;        // top-K pose plans: hypotheses per sample (1..64) and suppression radius (0..32) of this call
+    const int* tile_index = nullptr;   // indexed cached forms: HOST tile of each sample of this micro-batch (null: sample b reads tile b)
+    int n_tiles = 0;                   // ... and the number of tiles cache_in was encoded for (its section layout)
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)

@@ -328,14 +328,23 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
     if (!cached) {
         plan_encoder(h, pl, h->sat_enc, false, B, CCVPE_SAT_HW, CCVPE_SAT_HW, false, td, senc, "sat");
     } else {
+        // The six launches that read the cache.  Indexed calls (Ctx::tile_index set) run the same plan with a gather in their place:
+        // the cache then holds n_tiles samples, so each section starts at its one-sample offset times n_tiles, and sample b reads
+        // tile tile_index[b].  The indices go by value in the launch arguments - safe because cached plans are never captured
+        // into a hipGraph (use_graph above), so every call issues launches with its own arguments.
+        size_t one[6];
+        cache_layout(vs, 1, one);
         for (int t = 0; t < 5; ++t) {   // cached encoder taps -> skip halves of the decoder concat buffers
             Tensor lc = loc_cat[t], oc = ori_cat[t];
             const int lcoff = deconv_width(vs.loc[t], h->sw.pad_concat), ocoff = deconv_width(vs.ori[t], h->sw.pad_concat);
-            const size_t src_off = coff[t + 1];
-            const int C = TAP_C[t];
+            const size_t src_off = coff[t + 1], src_off1 = one[t + 1];
+            const int C = TAP_C[t], hw = TAP_HW[t];
             const long long P = (long long)B * TAP_HW[t];
             pl.add("sat.cached_tap" + std::to_string(TAP_BLOCK[t]), {lc, oc}, [=](const Ctx& c) {
-                launch_scatter_channels(c.cache_in + src_off, C, P, c.dst(lc, lcoff), c.dst(oc, ocoff), 2, c.stream);
+                if (c.tile_index)
+                    launch_gather_channels(c.cache_in + src_off1 * c.n_tiles, C, hw, c.tile_index, B, c.dst(lc, lcoff), c.dst(oc, ocoff), 2, c.stream);
+                else
+                    launch_scatter_channels(c.cache_in + src_off, C, P, c.dst(lc, lcoff), c.dst(oc, ocoff), 2, c.stream);
             }, 0, 4.0 * P * C * 3);
         }
     }
@@ -371,7 +380,10 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         Tensor dm = dmap;
         const long long P = (long long)B * 64;
         pl.add("sat.cached_descmap", {dm}, [=](const Ctx& c) {
-            launch_scatter_channels(c.cache_in, D, P, c.dst(dm), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
+            if (c.tile_index)   // the descriptor map is the cache's first section: offset 0 whatever n_tiles is
+                launch_gather_channels(c.cache_in, D, 64, c.tile_index, B, c.dst(dm), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
+            else
+                launch_scatter_channels(c.cache_in, D, P, c.dst(dm), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
         }, 0, 8.0 * P * D);
         pl.taps["sat_descriptor_map"] = {dmap, 0, D};
     } else {

@@ -435,6 +435,18 @@ struct WarpParams {
 int launch_warp(const WarpParams& p, hipStream_t s);       // -1: stage pattern without a kernel
 
 void launch_scatter_channels(const float* src, int C, long long P, Dst d0, Dst d1, int ndst, hipStream_t s);
+// the same copy with a per-sample source: destination sample b reads sample tile[b] of a section laid out for n_tiles samples
+// ([n_tiles][hw][C], the indexed cached forms).  The indices travel by value in the launch arguments, GATHER_MAX_SAMPLES per launch.
+static constexpr int GATHER_MAX_SAMPLES = 16;
+struct GatherParams {
+    const float* src;   // section base: [n_tiles][hw][C] fp32
+    Dst d0, d1;
+    int ndst;
+    int C, hw;          // channels (multiple of 4), pixels per sample
+    int b0;             // destination sample of blockIdx.y == 0
+    int tile[GATHER_MAX_SAMPLES];   // source sample of destination sample b0 + blockIdx.y
+};
+void launch_gather_channels(const float* src, int C, int hw, const int* tile, int B, Dst d0, Dst d1, int ndst, hipStream_t s);
 
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call

@@ -619,6 +619,37 @@ void launch_scatter_channels(const float* src, int C, long long P, Dst d0, Dst d
     CCVPE_LAUNCH(scatter_channels_kernel, dim3(blocks), dim3(256), 0, s, src, C, P, d0, d1, ndst);
 }
 
+// [n_tiles][hw][C] -> channel window of an NHWC buffer, destination sample b0 + blockIdx.y reading source sample tile[blockIdx.y]
+// (indexed cached forms: several queries share one cached aerial tile).  The source sample is uniform per block, so its index is
+// one scalar load from the launch arguments.  Samples that share a tile re-read the same lines, which mostly hit L2 / MALL.
+__global__ __launch_bounds__(256) void gather_channels_kernel(const GatherParams p) {
+    const int c4n = p.C >> 2;
+    const unsigned n = (unsigned)p.hw * (unsigned)c4n;   // float4 per sample (<= 2^18)
+    const int b = blockIdx.y;
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(p.src + (size_t)p.tile[b] * p.hw * p.C);
+    const long long pix0 = (long long)(p.b0 + b) * p.hw;
+    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const unsigned q = i / (unsigned)c4n;
+        const int c = (int)(i - q * (unsigned)c4n) * 4;
+        const float4 v = src[i];   // [hw][C] contiguous: float4 i is pixel q, channels c..c+3
+        put4(p.d0, pix0 + q, c, v);
+        if (p.ndst > 1) put4(p.d1, pix0 + q, c, v);
+    }
+}
+
+void launch_gather_channels(const float* src, int C, int hw, const int* tile, int B, Dst d0, Dst d1, int ndst, hipStream_t s) {
+    const unsigned n = (unsigned)hw * (unsigned)(C >> 2);
+    for (int b0 = 0; b0 < B; b0 += GATHER_MAX_SAMPLES) {
+        GatherParams p{};
+        p.src = src; p.d0 = d0; p.d1 = d1; p.ndst = ndst; p.C = C; p.hw = hw; p.b0 = b0;
+        const int nb = std::min(GATHER_MAX_SAMPLES, B - b0);
+        for (int k = 0; k < nb; ++k) p.tile[k] = tile[b0 + k];
+        // about as many blocks in flight as the scatter it replaces (4096 at most)
+        const int per = (int)std::max<unsigned>(1, std::min<unsigned>((n + 255) / 256, 256u * 16 / nb));
+        CCVPE_LAUNCH(gather_channels_kernel, dim3(per, nb), dim3(256), 0, s, p);
+    }
+}
+
 // NHWC view -> NCHW copy (debug taps only).
 __global__ void nhwc_to_nchw_kernel(const float* in, int in_ld, int coff, int C, int B, int HW, float* out) {
     const long long total = (long long)B * C * HW;

@@ -15,6 +15,7 @@ import ctypes as C
 import os
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -286,22 +287,65 @@ class _CVMBase(nn.Module):
         cache._ccvpe_batch = B
         return cache
 
-    def forward_cached(self, grd: torch.Tensor, cache: torch.Tensor):
-        """forward(grd, sat) with the aerial side taken from encode_aerial(sat)."""
+    @staticmethod
+    def _host_tile_index(tile_index, grd: torch.Tensor) -> Optional[np.ndarray]:
+        """tile_index keyword of the cached calls -> contiguous host int32 [B] (None stays None).  Host data only: a device tensor is
+        refused rather than copied back, which would hide a synchronisation.  Range checks are the library's (ccvpe_*_indexed)."""
+        if tile_index is None:
+            return None
+        if isinstance(tile_index, torch.Tensor):
+            if tile_index.device.type != "cpu":
+                raise ValueError(f"tile_index is host data: pass a CPU tensor, a numpy array or a sequence, not a {tile_index.device.type} "
+                                 "tensor (copying it back would synchronise)")
+            tile_index = tile_index.numpy()
+        idx = np.asarray(tile_index)
+        B = grd.shape[0] if grd.dim() > 0 else -1
+        if idx.shape != (B,):
+            raise ValueError(f"tile_index must hold one tile per query: shape ({B},) expected, got {idx.shape}")
+        if B > 0 and not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"tile_index must hold integers, got {idx.dtype}")
+        i32 = np.ascontiguousarray(idx, dtype=np.int32)
+        if not np.array_equal(i32, idx):
+            raise ValueError("tile_index entries must fit in int32")
+        return i32
+
+    @staticmethod
+    def _cache_tiles(cache: torch.Tensor, B: int, idx: Optional[np.ndarray]) -> int:
+        """Tiles a cached call's cache holds: B for the unindexed calls (which need exactly one per query), else the count
+        encode_aerial recorded."""
+        if idx is None:
+            if getattr(cache, "_ccvpe_batch", B) != B:
+                raise ValueError("cache was encoded for a different batch size")
+            return B
+        if not hasattr(cache, "_ccvpe_batch"):
+            raise ValueError("tile_index needs a cache returned by encode_aerial (it records how many tiles the cache holds)")
+        return int(cache._ccvpe_batch)
+
+    def forward_cached(self, grd: torch.Tensor, cache: torch.Tensor, tile_index=None):
+        """forward(grd, sat) with the aerial side taken from encode_aerial(sat).  tile_index (host ints [B], optional): query b
+        reads tile tile_index[b] of a cache encode_aerial wrote for any number of tiles up to the micro-batch, and B may then
+        be any size (ccvpe_forward_cached_indexed)."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        idx = self._host_tile_index(tile_index, grd)
         if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
             raise ValueError("grd must be a cuda tensor [B,3,H,W]")
         grd = grd.detach().to(torch.float32).contiguous()
         self._ensure_handle(grd.device)
         B = grd.shape[0]
-        if getattr(cache, "_ccvpe_batch", B) != B:
-            raise ValueError("cache was encoded for a different batch size")
+        n_tiles = self._cache_tiles(cache, B, idx)
         out, tensors = self._alloc_outputs(B, grd.device)
         stream = torch.cuda.current_stream(grd.device).cuda_stream
-        rc = _lib.load().ccvpe_forward_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                              C.c_void_p(cache.data_ptr()), B, C.byref(out), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_forward_cached")
+        lib = _lib.load()
+        if idx is None:
+            rc = lib.ccvpe_forward_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                          C.c_void_p(cache.data_ptr()), B, C.byref(out), C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_forward_cached")
+        else:
+            rc = lib.ccvpe_forward_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                  C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B,
+                                                  C.byref(out), C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_forward_cached_indexed")
         self._tuning_sync()
         return tensors
 
@@ -320,23 +364,31 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return rows
 
-    def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor) -> torch.Tensor:
+    def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor, tile_index=None) -> torch.Tensor:
         """localize(grd, sat) with the aerial side taken from encode_aerial(sat): float32 [B, 5] rows (index, prob, cos, sin,
-        angle_deg), the postprocess_rows layout (ccvpe_localize_cached)."""
+        angle_deg), the postprocess_rows layout (ccvpe_localize_cached).  tile_index: as forward_cached
+        (ccvpe_localize_cached_indexed)."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        idx = self._host_tile_index(tile_index, grd)
         if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
             raise ValueError("grd must be a cuda tensor [B,3,H,W]")
         grd = grd.detach().to(torch.float32).contiguous()
         self._ensure_handle(grd.device)
         B = grd.shape[0]
-        if getattr(cache, "_ccvpe_batch", B) != B:
-            raise ValueError("cache was encoded for a different batch size")
+        n_tiles = self._cache_tiles(cache, B, idx)
         rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
         stream = torch.cuda.current_stream(grd.device).cuda_stream
-        rc = _lib.load().ccvpe_localize_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                               C.c_void_p(cache.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_cached")
+        lib = _lib.load()
+        if idx is None:
+            rc = lib.ccvpe_localize_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                           C.c_void_p(cache.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_localize_cached")
+        else:
+            rc = lib.ccvpe_localize_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                   C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B,
+                                                   C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_localize_cached_indexed")
         self._tuning_sync()
         return rows
 
@@ -367,25 +419,32 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return rows
 
-    def localize_topk_cached(self, grd: torch.Tensor, cache: torch.Tensor, k: int, radius: int) -> torch.Tensor:
+    def localize_topk_cached(self, grd: torch.Tensor, cache: torch.Tensor, k: int, radius: int, tile_index=None) -> torch.Tensor:
         """localize_topk(grd, sat, k, radius) with the aerial side taken from encode_aerial(sat): float32 [B, k, 5]
-        (ccvpe_localize_topk_cached)."""
+        (ccvpe_localize_topk_cached).  tile_index: as forward_cached (ccvpe_localize_topk_cached_indexed)."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        idx = self._host_tile_index(tile_index, grd)
         if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
             raise ValueError("grd must be a cuda tensor [B,3,H,W]")
         k, radius = self._topk_args(k, radius)
         grd = grd.detach().to(torch.float32).contiguous()
         self._ensure_handle(grd.device)
         B = grd.shape[0]
-        if getattr(cache, "_ccvpe_batch", B) != B:
-            raise ValueError("cache was encoded for a different batch size")
+        n_tiles = self._cache_tiles(cache, B, idx)
         rows = torch.empty((B, k, 5), dtype=torch.float32, device=grd.device)
         stream = torch.cuda.current_stream(grd.device).cuda_stream
-        rc = _lib.load().ccvpe_localize_topk_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                    C.c_void_p(cache.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
-                                                    C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_topk_cached")
+        lib = _lib.load()
+        if idx is None:
+            rc = lib.ccvpe_localize_topk_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                C.c_void_p(cache.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
+                                                C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_localize_topk_cached")
+        else:
+            rc = lib.ccvpe_localize_topk_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                        C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B, k,
+                                                        radius, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, "ccvpe_localize_topk_cached_indexed")
         self._tuning_sync()
         return rows
 

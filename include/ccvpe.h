@@ -213,6 +213,25 @@ int ccvpe_localize_topk(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t
 int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
                                int32_t batch, int32_t k, int32_t radius, float* rows, void* stream);
 
+/* Indexed cached forms: a batch of queries against a few shared tiles (the Oxford test split crops its aerial window on a
+ * 400-px grid, so consecutive frames share tiles).  `cache` was written by ccvpe_encode_aerial(h, sat, n_tiles, cache, ...),
+ * 1 <= n_tiles <= micro_batch; query b is paired with tile tile_index[b].  `tile_index` is HOST memory, int32 [batch], every
+ * entry in 0 .. n_tiles-1.  `batch` is any positive count: larger batches loop over micro-batches as ccvpe_forward does, each
+ * slice reading its own entries of tile_index from the same cache.  Outputs and rows are laid out as in ccvpe_forward_cached,
+ * ccvpe_localize_cached and ccvpe_localize_topk_cached; with n_tiles == batch and tile_index[b] == b the results are
+ * bit-identical to those calls.  CCVPE_EINVAL, with no launch issued, for a null pointer, n_tiles <= 0, an index out of range
+ * (the message names the first bad position and value) or, for the top-K form, k / radius out of range - all checked before
+ * the handle is used - and for n_tiles > micro_batch.  The indices travel in the launch arguments: no copy to the device,
+ * no synchronisation, and the caller may reuse tile_index as soon as the call returns. */
+int ccvpe_forward_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                 int32_t n_tiles, const int32_t* tile_index, int32_t batch, const ccvpe_outputs* out,
+                                 void* stream);
+int ccvpe_localize_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                  int32_t n_tiles, const int32_t* tile_index, int32_t batch, float* rows, void* stream);
+int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                       int32_t n_tiles, const int32_t* tile_index, int32_t batch, int32_t k, int32_t radius,
+                                       float* rows, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
