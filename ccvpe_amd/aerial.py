@@ -214,6 +214,90 @@ def oxford_tile_aerial(map_u8, origins, mean=_lib.IMAGENET_MEAN, std=_lib.IMAGEN
     return _lib.preprocess_window_resize(map_u8, org, (OXFORD_WIN, OXFORD_WIN), (SAT_HW, SAT_HW), mean, std)
 
 
+def _axis_gap(p: float, lo: float, hi: float) -> Tuple[float, bool]:
+    """Distance from p to the half-open interval [lo, hi), and whether it is measured to the excluded end."""
+    if p < lo:
+        return lo - p, False
+    if p >= hi:
+        return p - hi, True
+    return 0.0, False
+
+
+def oxford_region(prior_coords, radius_px: float) -> Dict[str, object]:
+    """The Oxford test windows around position priors: for each prior (col, row) in prior_coords [B,2], the 800 x 800 windows on the
+    400-px grid whose central 400 x 400 cell [x0+200, x0+600) x [y0+200, y0+600) meets the closed disc of radius_px around it - the
+    windows oxford_window picks for the points of that disc.  oxford_window rounds the position to the nearest pixel (half to even),
+    so the cell of window x0 is [x0+199.5, x0+599.5) in map coordinates.  Returns origin [T,2] int32 = the distinct windows in order
+    of first appearance (queries in order, each query's windows row-major), and tiles = one list of tile ids per prior, the form
+    model.localize_region takes.  radius_px = 0 gives oxford_tiles' windows."""
+    pc = np.asarray(prior_coords, dtype=np.float64).reshape(-1, 2)
+    r = float(radius_px)
+    if not r >= 0.0 or not np.isfinite(r):
+        raise ValueError(f"radius_px must be a finite non-negative number, got {radius_px}")
+    if not np.isfinite(pc).all():
+        raise ValueError("prior_coords must be finite")
+    seen: Dict[Tuple[int, int], int] = {}
+    tiles = []
+    for px, py in pc:
+        own = []
+        ys = range(int(np.floor((py - r - 599.5) / OXFORD_GRID)), int(np.floor((py + r - 199.5) / OXFORD_GRID)) + 1)
+        xs = range(int(np.floor((px - r - 599.5) / OXFORD_GRID)), int(np.floor((px + r - 199.5) / OXFORD_GRID)) + 1)
+        for ry in ys:
+            y0 = ry * OXFORD_GRID
+            gy, oy = _axis_gap(py, y0 + 199.5, y0 + 599.5)
+            for rx in xs:
+                x0 = rx * OXFORD_GRID
+                gx, ox = _axis_gap(px, x0 + 199.5, x0 + 599.5)
+                d2 = gx * gx + gy * gy
+                if d2 < r * r or (d2 == r * r and not (ox or oy)):
+                    own.append(seen.setdefault((x0, y0), len(seen)))
+        tiles.append(own)
+    origin = np.array(list(seen), dtype=np.int32).reshape(-1, 2)
+    return {"origin": origin, "tiles": tiles}
+
+
+_OXFORD_CENTRE = None
+
+
+def _oxford_index_centre() -> np.ndarray:
+    """[512] window coordinate of each heatmap column: the centre of the window pixels whose ground-truth column (oxford_window's
+    offset -> gt_argmax) it is.  The construction is many-to-one (an offset step is 800/512 window pixels, and two offsets share the
+    centre column 255); columns no window pixel maps to are interpolated."""
+    global _OXFORD_CENTRE
+    if _OXFORD_CENTRE is None:
+        lo = np.full(SAT_HW, np.inf)
+        hi = np.full(SAT_HW, -np.inf)
+        for cp in range(1, OXFORD_WIN):   # (window pixel 0 puts the peak off the map)
+            col = gt_argmax(int(-(cp / 800 * 512 - 256)), 0) % SAT_HW
+            lo[col] = min(lo[col], cp)
+            hi[col] = max(hi[col], cp)
+        hit = np.isfinite(lo)
+        cols = np.arange(SAT_HW)
+        centre = np.interp(cols, cols[hit], (lo[hit] + hi[hit]) / 2)
+        # beyond the first / last hit column: the linear scale of the grid
+        centre[cols < cols[hit][0]] = cols[cols < cols[hit][0]] * OXFORD_WIN / (SAT_HW - 1)
+        centre[cols > cols[hit][-1]] = cols[cols > cols[hit][-1]] * OXFORD_WIN / (SAT_HW - 1)
+        _OXFORD_CENTRE = centre
+    return _OXFORD_CENTRE
+
+
+def oxford_region_to_map(origin, index) -> np.ndarray:
+    """A flat 512 x 512 heatmap index in the window at origin (x0, y0) -> map pixel coordinates (col, row) float64, the inverse of
+    the test split's ground-truth construction (datasets.py:315-329): the centre of the map pixels whose ground-truth index it is.
+    origin [2] or [B,2], index scalar or [B]; returns [B,2] (or [2] for one scalar index).  The round trip from a position to its
+    ground-truth index and back is within 800/512 px, and within 2.5 px on the window's centre column / row, which two
+    ground-truth offsets share."""
+    idx = np.asarray(index)
+    scalar = idx.ndim == 0
+    idx = idx.reshape(-1).astype(np.int64)
+    if ((idx < 0) | (idx >= SAT_HW * SAT_HW)).any():
+        raise ValueError("heatmap index outside 0 .. 512*512-1")
+    org = np.broadcast_to(np.asarray(origin, dtype=np.float64).reshape(-1, 2), (idx.shape[0], 2))
+    centre = _oxford_index_centre()
+    out = np.stack([org[:, 0] + centre[idx % SAT_HW], org[:, 1] + centre[idx // SAT_HW]], axis=1)
+    return out[0] if scalar else out
+
+
 def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
     """Ground-truth side of an Oxford test sample (datasets.py:323-351): gt_index [B] int32 = flat argmax of `gt`, gt_cos_sin [B,2]
     float32 = `orientation` at that pixel, heading_deg [B] float64 = `orientation_angle` (yaw: grdYaw, radians)."""

@@ -239,6 +239,21 @@ static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
     return 0;
 }
 
+// Samples per plan of a gh x gw ground image: the handle's micro-batch, lowered so that no plan has a tensor of 2 GiB or more (32-bit
+// byte offsets); larger batches loop.
+static int micro_batch_cap(ccvpe_handle h, int gh, int gw) {
+    int mbmax = h->cfg.micro_batch;
+    auto it = h->mb_cap.find({gh, gw});
+    if (it == h->mb_cap.end()) {
+        const std::string keep = ccvpe_err();
+        const int cap = max_micro_batch(h->sw, h->cfg.variant, h->cfg.ori_noise, gh, gw);
+        ccvpe_err() = keep;
+        it = h->mb_cap.emplace(std::make_pair(gh, gw), cap).first;
+    }
+    if (it->second > 0) mbmax = std::min(mbmax, it->second);
+    return mbmax;
+}
+
 // rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read);
 // topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller)
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
@@ -260,17 +275,7 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
     }
     HIPCHK(hipSetDevice(h->cfg.device));
     if (profile) h->prof.clear();
-    int mbmax = h->cfg.micro_batch;
-    {   // never build a plan with a tensor of 2 GiB or more (32-bit byte offsets): larger batches loop
-        auto it = h->mb_cap.find({gh, gw});
-        if (it == h->mb_cap.end()) {
-            const std::string keep = ccvpe_err();
-            const int cap = max_micro_batch(h->sw, h->cfg.variant, h->cfg.ori_noise, gh, gw);
-            ccvpe_err() = keep;
-            it = h->mb_cap.emplace(std::make_pair(gh, gw), cap).first;
-        }
-        if (it->second > 0) mbmax = std::min(mbmax, it->second);
-    }
+    const int mbmax = micro_batch_cap(h, gh, gw);
     // make sure every plan (and the largest arena) exists before the first launch
     for (int done = 0; done < batch;) {
         const int mb = std::min(mbmax, batch - done);
@@ -667,6 +672,101 @@ int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t
     if (int rc = check_topk_args(k, radius)) return rc;
     return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius,
                        tile_index, n_tiles);
+}
+
+size_t ccvpe_ground_cache_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32_t grd_w) {
+    if (!h || batch <= 0) { ccvpe_fail(CCVPE_EINVAL, "bad argument"); return 0; }
+    const int ltot = ground_desc_floats(h, grd_h, grd_w);
+    if (ltot <= 0) return 0;
+    return (size_t)batch * ltot * sizeof(float);
+}
+
+int ccvpe_encode_ground(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, int32_t batch, void* cache, void* stream) {
+    if (!h || !grd || !cache || batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "bad argument");
+    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
+    if (batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "ground encode needs batch <= micro_batch (%d)", h->cfg.micro_batch);
+    HIPCHK(hipSetDevice(h->cfg.device));
+    Plan* pl; int rc = get_plan(h, batch, grd_h, grd_w, &pl, 3);
+    if (rc) return rc;
+    Ctx c;
+    c.arena = h->arena; c.off = &pl->off; c.stream = (hipStream_t)stream;
+    c.tickets = pl->tickets;
+    c.splitk_scratch = c.ptr(pl->scratch); c.splitk_floats = Plan::SPLITK_FLOATS;
+    c.grd = grd; c.cache_out = (float*)cache;
+    for (auto& op : pl->ops) op.fn(c);
+    if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// Arguments of ccvpe_localize_region, checked before the handle is used: offsets and tiles are host memory, read here in full.
+static int check_region_args(const void* grd_cache, int32_t n_queries, const void* sat_cache, int32_t n_tiles, const int32_t* offsets,
+                             const int32_t* tiles, const void* rows, const void* best_pair, const void* pair_rows, const void* pair_stats,
+                             const void* tile_prob) {
+    if (!grd_cache) return ccvpe_fail(CCVPE_EINVAL, "null grd_cache");
+    if (!sat_cache) return ccvpe_fail(CCVPE_EINVAL, "null sat_cache");
+    if (!offsets) return ccvpe_fail(CCVPE_EINVAL, "null offsets");
+    if (!tiles) return ccvpe_fail(CCVPE_EINVAL, "null tiles");
+    if (!rows || !best_pair || !pair_rows || !pair_stats || !tile_prob) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
+    if (n_queries <= 0) return ccvpe_fail(CCVPE_EINVAL, "n_queries must be positive, got %d", n_queries);
+    if (n_tiles <= 0) return ccvpe_fail(CCVPE_EINVAL, "n_tiles must be positive, got %d", n_tiles);
+    if (offsets[0] != 0) return ccvpe_fail(CCVPE_EINVAL, "offsets[0] = %d, must be 0", offsets[0]);
+    for (int32_t g = 0; g < n_queries; ++g)
+        if (offsets[g + 1] <= offsets[g])
+            return ccvpe_fail(CCVPE_EINVAL, "offsets[%d] = %d does not exceed offsets[%d] = %d: every query needs at least one tile", g + 1,
+                              offsets[g + 1], g, offsets[g]);
+    const int32_t P = offsets[n_queries];
+    for (int32_t p = 0; p < P; ++p)
+        if (tiles[p] < 0 || tiles[p] >= n_tiles)
+            return ccvpe_fail(CCVPE_EINVAL, "tiles[%d] = %d is outside 0 .. %d (n_tiles %d)", p, tiles[p], n_tiles - 1, n_tiles);
+    return 0;
+}
+
+int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
+                          int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, float* rows, int32_t* best_pair, float* pair_rows,
+                          float* pair_stats, float* tile_prob, void* stream) {
+    if (int rc = check_region_args(grd_cache, n_queries, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats, tile_prob))
+        return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    if (n_queries > h->cfg.micro_batch)
+        return ccvpe_fail(CCVPE_EINVAL, "n_queries %d exceeds micro_batch (%d), the most ccvpe_encode_ground writes", n_queries, h->cfg.micro_batch);
+    if (n_tiles > h->cfg.micro_batch)
+        return ccvpe_fail(CCVPE_EINVAL, "n_tiles %d exceeds micro_batch (%d), the most ccvpe_encode_aerial writes", n_tiles, h->cfg.micro_batch);
+    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
+    if (h->debug) return ccvpe_fail(CCVPE_ESTATE, "pose plans carry no debug taps: ccvpe_set_debug(h, 0) before ccvpe_localize_region");
+    const int P = offsets[n_queries];
+    std::vector<int32_t> query(P);   // query of each pair; copied into the launch arguments as each slice is issued
+    for (int g = 0; g < n_queries; ++g)
+        for (int p = offsets[g]; p < offsets[g + 1]; ++p) query[p] = g;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int mbmax = micro_batch_cap(h, grd_h, grd_w);
+    for (int done = 0; done < P;) {   // every plan (and the largest arena) exists before the first launch
+        const int mb = std::min(mbmax, P - done);
+        Plan* pl; if (int rc = get_plan(h, mb, grd_h, grd_w, &pl, 4, true)) return rc;
+        done += mb;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    for (int done = 0; done < P;) {
+        const int mb = std::min(mbmax, P - done);
+        Plan* pl; if (int rc = get_plan(h, mb, grd_h, grd_w, &pl, 4, true)) return rc;
+        h->last_plan = pl;
+        Ctx c;
+        c.cache_in = (const float*)sat_cache; c.tile_index = tiles + done; c.n_tiles = n_tiles;
+        c.grd_cache_in = (const float*)grd_cache; c.query_index = query.data() + done; c.n_queries = n_queries;
+        c.arena = h->arena; c.off = &pl->off; c.stream = s;
+        c.tickets = pl->tickets;
+        pl->set_scratch(c, 0);
+        c.rows = pair_rows + (size_t)done * 5;
+        c.stats = pair_stats + (size_t)done * 2;
+        if (int rrc = run_ops(h, *pl, c, s)) return rrc;
+        if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
+        done += mb;
+    }
+    launch_region_reduce(pair_stats, pair_rows, offsets, n_queries, rows, best_pair, tile_prob, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

@@ -241,6 +241,10 @@ struct Ctx {
     int topk_k = 0, topk_r = 0;        // top-K pose plans: hypotheses per sample (1..64) and suppression radius (0..32) of this call
     const int* tile_index = nullptr;   // indexed cached forms: HOST tile of each sample of this micro-batch (null: sample b reads tile b)
     int n_tiles = 0;                   // ... and the number of tiles cache_in was encoded for (its section layout)
+    const float* grd_cache_in = nullptr;   // pair plans (ccvpe_localize_region): ground cache of ccvpe_encode_ground, [n_queries][Ltot]
+    const int* query_index = nullptr;  // ... HOST query of each pair of this micro-batch
+    int n_queries = 0;                 // ... and the number of queries grd_cache_in holds
+    float* stats = nullptr;            // pose plans: optional [B][2] softmax (max, 1/sum) of each sample (pose_argmax_kernel)
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -279,7 +283,8 @@ struct TapInfo { Tensor t; int coff; int C; };
 
 struct Plan {
     int B = 0, gh = 0, gw = 0;
-    int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding
+    int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding, 3 ground encode only,
+                                  // 4 pose plan from both caches (the pairs of ccvpe_localize_region)
     bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
     bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
     bool debug = false;
@@ -516,6 +521,7 @@ static inline int score_pad(int nscore) { return round_up(nscore, 8); }
 ConvParams conv_params(const PackedConv& pc, const float* in, int in_ld, int B, int H, int W, int OH, int OW,
                        int stride, int pad_t, int pad_l, int act);
 size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]);
+int ground_desc_floats(const ccvpe_handle_s* h, int gh, int gw);   // Ltot of a ground image (ground cache row), < 0: bad geometry
 int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0, bool pose = false, bool topk = false);
 
 // ---- ccvpe_tune.hip ----

@@ -247,7 +247,61 @@ size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]) {
 }
 
 static int build_aerial_plan(ccvpe_handle_s* h, Plan& pl, int B);
+static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw);
 extern "C" int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t grd_h, int32_t grd_w);
+
+// Geometry of the ground feature volume (fh x fw) and the per-level descriptor lengths L[k] of a gh x gw ground image.
+static int grd_geometry(const VariantSpec& vs, int gh, int gw, int& fh, int& fw, int L[6]) {
+    fh = conv_out(gh, 3, 2); fw = conv_out(gw, 3, 2);
+    for (int i = 0; i < 16; ++i) { fh = conv_out(fh, B0[i].k, B0[i].s); fw = conv_out(fw, B0[i].k, B0[i].s); }
+    if (fh != vs.feat_h)
+        return ccvpe_fail(CCVPE_EINVAL, "ground image %dx%d gives a %d-row feature volume, the descriptor heads expect %d rows", gh, gw, fh, vs.feat_h);
+    for (int k = 0; k < 6; ++k) {
+        L[k] = fw * vs.head_ch[k];
+        if (L[k] > vs.match_ch[k])
+            return ccvpe_fail(CCVPE_EINVAL, "descriptor length %d exceeds aerial channels %d at level %d", L[k], vs.match_ch[k], k + 1);
+    }
+    return 0;
+}
+
+// Ground cache (ccvpe_encode_ground): the descriptor vector of each query, [B][Ltot] fp32, Ltot = sum of round_up(L_k, 4) - the
+// layout of the plans' `desc` tensor, level k at float offset sum_{j<k} round_up(L_j, 4).
+int ground_desc_floats(const ccvpe_handle_s* h, int gh, int gw) {
+    int fh, fw, L[6];
+    if (int rc = grd_geometry(h->vs, gh, gw, fh, fw, L)) return rc;
+    int ltot = 0;
+    for (int k = 0; k < 6; ++k) ltot += round_up(L[k], 4);
+    return ltot;
+}
+
+// grd.heads + grd.desc: the ground descriptor heads over the encoder volume `vol` into the returned `desc` tensor ([B][ltot]), or -
+// to_cache - into the caller's ground cache (Ctx::cache_out).  The same launches, names and shapes in the full, cached and ground-only plans.
+static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, Tensor vol, bool to_cache) {
+    const VariantSpec& vs = h->vs;
+    int ntot = 0, ltot = 0, hoff[6], loff[6];
+    for (int k = 0; k < 6; ++k) { hoff[k] = ntot; ntot += vs.head_ch[k]; loff[k] = ltot; ltot += round_up(fw * vs.head_ch[k], 4); }
+    Tensor ghead = pl.alloc(B, fh, fw, ntot);
+    Tensor desc = to_cache ? Tensor{} : pl.alloc(B, 1, 1, ltot);
+    const PackedConv* pc = &h->grd_heads;
+    Tensor x = vol;
+    pl.add_conv("grd.heads", {x, ghead}, B * fh * fw, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
+        ConvParams p = conv_params(*pc, c.ptr(x), 1280, B, fh, fw, fh, fw, 1, 0, 0, ACT_NONE);
+        p.dst[0] = {c.ptr(ghead), ntot, 0}; p.ndst = 1;
+        c.launch_conv(p, tile);
+    }, 2.0 * B * fh * fw * 1280 * ntot, 4.0 * B * fh * fw * (1280 + ntot));
+    pl.ops.back().is_pw = true;
+    pl.ops.back().proj_ok = pc->proj != nullptr && h->cfg.reserved[0] == 0;
+    GrdDescParams gp{};
+    gp.B = B; gp.Hf = fh; gp.Wf = fw; gp.Ntot = ntot; gp.nlev = 6; gp.Ltot = ltot;
+    for (int k = 0; k < 6; ++k) { gp.c[k] = vs.head_ch[k]; gp.off[k] = hoff[k]; gp.wh[k] = h->grd_wh[k]; gp.b2[k] = h->grd_b2[k]; gp.loff[k] = loff[k]; }
+    std::vector<Tensor> uses = {ghead};
+    if (!to_cache) uses.push_back(desc);
+    pl.add("grd.desc", uses, [=](const Ctx& c) {
+        GrdDescParams q = gp; q.y = c.ptr(ghead); q.desc = to_cache ? c.cache_out : c.ptr(desc);
+        launch_grd_desc(q, c.stream);
+    }, 2.0 * B * fh * fw * ntot, 4.0 * B * fh * fw * ntot);
+    return desc;
+}
 
 // Pose plans (pose = true, ccvpe_localize): the launches of the full (mode 0) or cached (mode 2) plan up to and including the level-2
 // decoders, under the same names - so the same tuning-table entries - and a tail that writes only the [B][5] result rows of
@@ -259,9 +313,15 @@ extern "C" int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t g
 // tail is topk.peaks (the K best peaks from recomputed heatmap values) and the orientation at those K pixels (ori1.topk:
 // the fused level 1 for each hypothesis' tile; without the fused level: ori1.tail + ori1.topk_gather).  K and r come with each call
 // (Ctx::topk_k / topk_r); the workspace is sized for K = 64.
+// Pair plans (mode 4, pose, ccvpe_localize_region): the cached pose plan with the ground side from a ground cache as well - the ground
+// encoder, grd.heads and grd.desc give way to grd.cached_desc, a gather of each pair's query row (Ctx::query_index); the aerial
+// launches gather each pair's tile (Ctx::tile_index).  Every other launch keeps the cached pose plan's name and tuning entry.
 int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, bool pose, bool topk) {
     if (mode == 1) return build_aerial_plan(h, pl, B);
-    const bool cached = mode == 2;
+    if (mode == 3) return build_ground_plan(h, pl, B, gh, gw);
+    const bool cached = mode == 2 || mode == 4;
+    const bool grd_cached = mode == 4;
+    if (grd_cached && (!pose || topk)) return ccvpe_fail(CCVPE_EINVAL, "pair plans are single-hypothesis pose plans");
     pl.mode = mode;
     pl.pose = pose;
     pl.topk = pose && topk;
@@ -286,16 +346,8 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
     }
 
     // ---- geometry of the ground feature volume ----
-    int fh = conv_out(gh, 3, 2), fw = conv_out(gw, 3, 2);
-    for (int i = 0; i < 16; ++i) { fh = conv_out(fh, B0[i].k, B0[i].s); fw = conv_out(fw, B0[i].k, B0[i].s); }
-    if (fh != vs.feat_h)
-        return ccvpe_fail(CCVPE_EINVAL, "ground image %dx%d gives a %d-row feature volume, the descriptor heads expect %d rows", gh, gw, fh, vs.feat_h);
-    int L[6];
-    for (int k = 0; k < 6; ++k) {
-        L[k] = fw * vs.head_ch[k];
-        if (L[k] > vs.match_ch[k])
-            return ccvpe_fail(CCVPE_EINVAL, "descriptor length %d exceeds aerial channels %d at level %d", L[k], vs.match_ch[k], k + 1);
-    }
+    int fh, fw, L[6];
+    if (int rc = grd_geometry(vs, gh, gw, fh, fw, L)) return rc;
 
     // ---- decoder concat buffers (allocated first: the aerial encoder's tap epilogues write into them) ----
     const int D = vs.sat_desc;
@@ -316,7 +368,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
 
     // ---- encoders ----
     EncOut genc, senc;
-    plan_encoder(h, pl, h->grd_enc, true, B, gh, gw, h->cfg.circular_padding != 0, nullptr, genc, "grd");
+    if (!grd_cached) plan_encoder(h, pl, h->grd_enc, true, B, gh, gw, h->cfg.circular_padding != 0, nullptr, genc, "grd");
     TapDst td[5];
     for (int t = 0; t < 5; ++t) {
         td[t].n = 2;
@@ -350,29 +402,19 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
     }
 
     // ---- ground descriptors ----
-    int ntot = 0, ltot = 0, hoff[6], loff[6];
-    for (int k = 0; k < 6; ++k) { hoff[k] = ntot; ntot += vs.head_ch[k]; loff[k] = ltot; ltot += round_up(L[k], 4); }
-    Tensor ghead = pl.alloc(B, fh, fw, ntot);
-    Tensor desc = pl.alloc(B, 1, 1, ltot);
-    {
-        const PackedConv* pc = &h->grd_heads;
-        Tensor x = genc.vol;
-        pl.add_conv("grd.heads", {x, ghead}, B * fh * fw, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
-            ConvParams p = conv_params(*pc, c.ptr(x), 1280, B, fh, fw, fh, fw, 1, 0, 0, ACT_NONE);
-            p.dst[0] = {c.ptr(ghead), ntot, 0}; p.ndst = 1;
-            c.launch_conv(p, tile);
-        }, 2.0 * B * fh * fw * 1280 * ntot, 4.0 * B * fh * fw * (1280 + ntot));
-        pl.ops.back().is_pw = true;
-        pl.ops.back().proj_ok = pc->proj != nullptr && h->cfg.reserved[0] == 0;
-        GrdDescParams gp{};
-        gp.B = B; gp.Hf = fh; gp.Wf = fw; gp.Ntot = ntot; gp.nlev = 6; gp.Ltot = ltot;
-        for (int k = 0; k < 6; ++k) { gp.c[k] = vs.head_ch[k]; gp.off[k] = hoff[k]; gp.wh[k] = h->grd_wh[k]; gp.b2[k] = h->grd_b2[k]; gp.loff[k] = loff[k]; }
-        pl.add("grd.desc", {ghead, desc}, [=](const Ctx& c) {
-            GrdDescParams q = gp; q.y = c.ptr(ghead); q.desc = c.ptr(desc);
-            launch_grd_desc(q, c.stream);
-        }, 2.0 * B * fh * fw * ntot, 4.0 * B * fh * fw * ntot);
-        for (int k = 0; k < 6; ++k) pl.taps["grd_desc" + std::to_string(k + 1)] = {desc, loff[k], L[k]};
+    int ltot = 0, loff[6];
+    for (int k = 0; k < 6; ++k) { loff[k] = ltot; ltot += round_up(L[k], 4); }
+    Tensor desc;
+    if (grd_cached) {   // each pair's row of the ground cache [n_queries][ltot]: the gather of the aerial side with one "pixel" per sample
+        desc = pl.alloc(B, 1, 1, ltot);
+        Tensor d = desc;
+        pl.add("grd.cached_desc", {d}, [=](const Ctx& c) {
+            launch_gather_channels(c.grd_cache_in, ltot, 1, c.query_index, B, c.dst(d), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
+        }, 0, 8.0 * B * ltot);
+    } else {
+        desc = plan_grd_desc(h, pl, B, fh, fw, genc.vol, false);
     }
+    for (int k = 0; k < 6; ++k) pl.taps["grd_desc" + std::to_string(k + 1)] = {desc, loff[k], L[k]};
 
     // ---- aerial descriptor map: conv k2 s2 over the 1280x16x16 volume ----
     Tensor dmap = pl.alloc(B, 8, 8, D);
@@ -591,6 +633,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
             p.pairs = c.ptr(pairs); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
+            p.stats = c.stats;
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
     } else {
@@ -681,6 +724,24 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         return ccvpe_fail(CCVPE_EINVAL, "micro-batch %d needs a %d x %d x %d x %d tensor of %zu bytes; the kernels address tensors with 32-bit byte offsets (< 2 GiB): "
                     "use a smaller micro_batch (ccvpe_max_micro_batch)", B, pl.max_dims[0], pl.max_dims[1], pl.max_dims[2], pl.max_dims[3], pl.max_tensor_bytes);
     pl.schedule();
+    pl.assign();
+    return 0;
+}
+
+// Ground-only plan (mode 3, ccvpe_encode_ground): the full plan's ground encoder, grd.heads and grd.desc - the same launches, names and
+// shapes (the encoder's latency-plan spread depends on the ground geometry only) - with grd.desc writing into the caller's ground cache.
+static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw) {
+    pl.B = B; pl.gh = gh; pl.gw = gw; pl.mode = 3; pl.debug = false;
+    pl.no_reuse = h->sw.no_reuse;
+    int fh, fw, L[6];
+    if (int rc = grd_geometry(h->vs, gh, gw, fh, fw, L)) return rc;
+    pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
+    EncOut genc;
+    plan_encoder(h, pl, h->grd_enc, true, B, gh, gw, h->cfg.circular_padding != 0, nullptr, genc, "grd");
+    plan_grd_desc(h, pl, B, fh, fw, genc.vol, true);
+    pl.max_tensor_bytes = std::max(pl.max_tensor_bytes, (size_t)B * 3 * gh * gw * sizeof(float));
+    if (pl.max_tensor_bytes >= ((size_t)1 << 31))
+        return ccvpe_fail(CCVPE_EINVAL, "ground encode of %d images needs a tensor of %zu bytes (< 2 GiB): use a smaller batch", B, pl.max_tensor_bytes);
     pl.assign();
     return 0;
 }

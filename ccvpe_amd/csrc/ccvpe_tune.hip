@@ -207,7 +207,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
 
 int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode, bool pose, bool topk) {
     for (auto& p : h->plans)
-        if (p->B == B && p->gh == gh && p->gw == gw && p->mode == mode && p->pose == pose && p->topk == topk && (mode == 1 || p->debug == h->debug)) { *out = p.get(); return 0; }
+        if (p->B == B && p->gh == gh && p->gw == gw && p->mode == mode && p->pose == pose && p->topk == topk && (mode == 1 || mode == 3 || p->debug == h->debug)) { *out = p.get(); return 0; }
     auto pl = std::make_unique<Plan>();
     int rc = build_plan(h, *pl, B, gh, gw, mode, pose, topk);
     if (rc) return rc;

@@ -372,6 +372,7 @@ struct PoseArgmaxParams {
     unsigned* tickets;         // [B] counters, zero before and after every launch
     int* index;                // [B] argmax, always in [0, n)
     float* rows;               // [B][5]: columns 0 (index) and 1 (prob)
+    float* stats;              // optional [B][2]: the sample's softmax (max, 1/sum), written by workgroup (0, b) (ccvpe_localize_region)
 };
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
@@ -447,6 +448,21 @@ struct GatherParams {
     int tile[GATHER_MAX_SAMPLES];   // source sample of destination sample b0 + blockIdx.y
 };
 void launch_gather_channels(const float* src, int C, int hw, const int* tile, int B, Dst d0, Dst d1, int ndst, hipStream_t s);
+
+// Cross-tile reduction of ccvpe_localize_region: one 64-lane workgroup per query.  The pair offsets of the queries
+// travel by value in the launch arguments, REGION_MAX_QUERIES queries per launch.  offsets: HOST [G+1], every range non-empty.
+static constexpr int REGION_MAX_QUERIES = 64;
+struct RegionParams {
+    const float* stats;       // [P][2] (max, 1/sum) of each pair (PoseArgmaxParams::stats)
+    const float* pair_rows;   // [P][5] pose rows of each pair
+    float* rows;              // [G][5]
+    int* best_pair;           // [G]
+    float* tile_prob;         // [P]
+    int g0;                   // query of blockIdx.x == 0
+    int off[REGION_MAX_QUERIES + 1];   // pair offsets of queries g0 .. g0 + gridDim.x
+};
+void launch_region_reduce(const float* stats, const float* pair_rows, const int* offsets, int G, float* rows, int* best_pair, float* tile_prob,
+                          hipStream_t s);
 
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call

@@ -267,6 +267,7 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
     for (int u = 0; u < 4; ++u) v[u] = src[threadIdx.x + u * 256];   // (per / 4 = 1024 float4 per chunk: four per thread, one trip)
     __syncthreads();
     const float m = gm, inv = gs;
+    if (p.stats && c == 0 && threadIdx.x == 0) { p.stats[b * 2 + 0] = m; p.stats[b * 2 + 1] = inv; }   // (read by a later launch)
     float best = -INFINITY;
     int bi = lo + 4 * (int)threadIdx.x;
     auto take = [&](float x, int i) { const float h = __expf(x - m) * inv; if (h > best) { best = h; bi = i; } };
@@ -313,6 +314,64 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
 
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s) {
     CCVPE_LAUNCH(pose_argmax_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Cross-tile reduction of ccvpe_localize_region: one wave per query over its pairs offsets[g] .. offsets[g+1]-1, in
+// float64.  S_p = exp(m_p - M) / inv_p is pair p's unnormalised mass (m_p, inv_p: pose_argmax_kernel's statistics, M the query's largest
+// finite m_p; 0 for a pair whose statistics are not finite), Z = sum S_p, tile_prob[p] = S_p / Z, joint_p = prob_p * S_p / Z.  The best
+// pair is the first with the largest joint_p (NaN never wins; none at all: the first pair, whose probability is then NaN).  Indices are
+// only copied from pair_rows, never dereferenced.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void region_reduce_kernel(const RegionParams p) {
+    const int g = blockIdx.x;
+    const int lo = p.off[g], hi = p.off[g + 1];
+    const int t = threadIdx.x;
+    auto finite = [&](int q) { return isfinite(p.stats[q * 2 + 0]) && isfinite(p.stats[q * 2 + 1]); };
+    double M = -INFINITY;
+    for (int q = lo + t; q < hi; q += 64)
+        if (finite(q)) M = fmax(M, (double)p.stats[q * 2 + 0]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
+    auto mass = [&](int q) { return finite(q) ? exp((double)p.stats[q * 2 + 0] - M) / (double)p.stats[q * 2 + 1] : 0.0; };
+    double Z = 0.0;
+    for (int q = lo + t; q < hi; q += 64) Z += mass(q);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) Z += __shfl_xor(Z, o);
+    double bv = 0.0;
+    int bq = -1;   // eligible pair with the largest joint probability, lowest position on ties
+    for (int q = lo + t; q < hi; q += 64) {
+        const double S = mass(q);
+        p.tile_prob[q] = (float)(S / Z);
+        const double j = (double)p.pair_rows[q * 5 + 1] * S / Z;
+        if (finite(q) && j == j && (bq < 0 || j > bv)) { bv = j; bq = q; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v2 = __shfl_xor(bv, o);
+        const int q2 = __shfl_xor(bq, o);
+        if (q2 >= 0 && (bq < 0 || v2 > bv || (v2 == bv && q2 < bq))) { bv = v2; bq = q2; }
+    }
+    if (t == 0) {
+        const int q = bq >= 0 ? bq : lo;
+        const float* r = p.pair_rows + (size_t)q * 5;
+        float* o = p.rows + (size_t)(p.g0 + g) * 5;
+        o[0] = r[0];
+        o[1] = bq >= 0 ? (float)bv : NAN;
+        o[2] = r[2]; o[3] = r[3]; o[4] = r[4];
+        p.best_pair[p.g0 + g] = q;
+    }
+}
+
+void launch_region_reduce(const float* stats, const float* pair_rows, const int* offsets, int G, float* rows, int* best_pair, float* tile_prob,
+                          hipStream_t s) {
+    for (int g0 = 0; g0 < G; g0 += REGION_MAX_QUERIES) {
+        RegionParams p{};
+        p.stats = stats; p.pair_rows = pair_rows; p.rows = rows; p.best_pair = best_pair; p.tile_prob = tile_prob; p.g0 = g0;
+        const int n = std::min(REGION_MAX_QUERIES, G - g0);
+        for (int k = 0; k <= n; ++k) p.off[k] = offsets[g0 + k];
+        CCVPE_LAUNCH(region_reduce_kernel, dim3(n), dim3(64), 0, s, p);
+    }
 }
 
 __global__ __launch_bounds__(64) void pose_gather_kernel(const float* ori, const int* index, int B, int n, float* rows) {

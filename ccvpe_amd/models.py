@@ -349,6 +349,108 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return tensors
 
+    # ---- one ground encoding against several aerial tiles ---------------------------------------
+    def encode_ground(self, grd: torch.Tensor) -> torch.Tensor:
+        """Encode ground images once: the returned device buffer (float32 [B * Ltot], the descriptor vector of each image, layout in
+        include/ccvpe.h) feeds localize_region, which pairs each image with several aerial tiles (ccvpe_encode_ground)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        grd = grd.detach().to(torch.float32).contiguous()
+        self._ensure_handle(grd.device)
+        lib = _lib.load()
+        B, H, W = grd.shape[0], grd.shape[2], grd.shape[3]
+        nbytes = lib.ccvpe_ground_cache_bytes(self._handle, B, H, W)
+        if nbytes == 0:
+            _lib.check(-1, "ccvpe_ground_cache_bytes")
+        cache = torch.empty(nbytes // 4, dtype=torch.float32, device=grd.device)
+        stream = torch.cuda.current_stream(grd.device).cuda_stream
+        _lib.check(lib.ccvpe_encode_ground(self._handle, C.c_void_p(grd.data_ptr()), H, W, B, C.c_void_p(cache.data_ptr()),
+                                           C.c_void_p(stream)), "ccvpe_encode_ground")
+        self._tuning_sync()
+        cache._ccvpe_batch = B
+        cache._ccvpe_grd_hw = (H, W)
+        return cache
+
+    @staticmethod
+    def _host_region_tiles(tiles):
+        """tiles argument of localize_region -> (offsets int32 [G+1], flat int32 [P]) on the host.  Host data only, as tile_index of
+        the cached calls: device tensors are refused.  Range checks against the cache are the library's (ccvpe_localize_region)."""
+        def host(v, what):
+            if isinstance(v, torch.Tensor):
+                if v.device.type != "cpu":
+                    raise ValueError(f"{what} is host data: pass CPU tensors, numpy arrays or sequences, not a {v.device.type} tensor "
+                                     "(copying it back would synchronise)")
+                return v.numpy()
+            return v
+        tiles = host(tiles, "tiles")
+        if isinstance(tiles, (str, bytes)) or not hasattr(tiles, "__len__"):
+            raise ValueError("tiles must be a sequence of per-query tile-id sequences")
+        if len(tiles) == 0:
+            raise ValueError("tiles must name at least one query")
+        offsets = [0]
+        flat = []
+        for g, t in enumerate(tiles):
+            a = np.asarray(host(t, "tiles"))
+            if a.ndim != 1:
+                raise ValueError(f"tiles[{g}] must be a 1-D sequence of tile ids, got shape {a.shape}")
+            if a.shape[0] == 0:
+                raise ValueError(f"tiles[{g}] is empty: every query needs at least one tile")
+            if not np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_:
+                raise ValueError(f"tiles[{g}] must hold integers, got {a.dtype}")
+            if (a < 0).any():
+                raise ValueError(f"tiles[{g}] holds a negative tile id {int(a[a < 0][0])}")
+            i32 = a.astype(np.int32)
+            if not np.array_equal(i32, a):
+                raise ValueError(f"tiles[{g}] entries must fit in int32")
+            flat.append(i32)
+            offsets.append(offsets[-1] + a.shape[0])
+        if offsets[-1] > np.iinfo(np.int32).max:
+            raise ValueError("too many (query, tile) pairs for int32 offsets")
+        return np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(np.concatenate(flat), dtype=np.int32)
+
+    def localize_region(self, ground_cache: torch.Tensor, sat_cache: torch.Tensor, tiles) -> Dict[str, object]:
+        """Every query of encode_ground(grd) against its own list of tiles of encode_aerial(sat): tiles[g] = the tile ids of query g
+        (host ints, a ragged sequence of G sequences; ids may repeat).  Returns, on the device unless noted:
+            rows [G,5]       (index, prob, cos, sin, angle_deg) of the query's best pair, prob = the softmax over the union of its
+                             tiles at that pair's argmax;
+            pair [G] int32   the position of that pair in the flattened pair list;
+            pair_tile        host int32 [P], the tile of each pair (pair_tile[pair[g]] is query g's chosen tile);
+            pair_rows [P,5]  localize rows of each pair, the probability inside its tile;
+            pair_stats [P,2] (max logit, 1 / sum exp) of each pair's softmax;
+            tile_prob [P]    each pair's share of its query's summed softmax mass (ccvpe_localize_region)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        offsets, flat = self._host_region_tiles(tiles)
+        G, P = offsets.shape[0] - 1, flat.shape[0]
+        for what, c in (("ground_cache", ground_cache), ("sat_cache", sat_cache)):
+            if not isinstance(c, torch.Tensor) or not c.is_cuda:
+                raise ValueError(f"{what} must be the cuda tensor encode_{'ground' if what == 'ground_cache' else 'aerial'} returned")
+        if not hasattr(ground_cache, "_ccvpe_grd_hw"):
+            raise ValueError("ground_cache must come from encode_ground (it records the image count and size)")
+        if not hasattr(sat_cache, "_ccvpe_batch"):
+            raise ValueError("sat_cache must come from encode_aerial (it records how many tiles the cache holds)")
+        if int(ground_cache._ccvpe_batch) != G:
+            raise ValueError(f"tiles names {G} queries, ground_cache holds {ground_cache._ccvpe_batch}")
+        self._ensure_handle(ground_cache.device)
+        dev = ground_cache.device
+        H, W = ground_cache._ccvpe_grd_hw
+        rows = torch.empty((G, 5), dtype=torch.float32, device=dev)
+        pair = torch.empty((G,), dtype=torch.int32, device=dev)
+        pair_rows = torch.empty((P, 5), dtype=torch.float32, device=dev)
+        pair_stats = torch.empty((P, 2), dtype=torch.float32, device=dev)
+        tile_prob = torch.empty((P,), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = _lib.load().ccvpe_localize_region(self._handle, C.c_void_p(ground_cache.data_ptr()), G, H, W, C.c_void_p(sat_cache.data_ptr()),
+                                               int(sat_cache._ccvpe_batch), offsets.ctypes.data_as(C.c_void_p),
+                                               flat.ctypes.data_as(C.c_void_p), C.c_void_p(rows.data_ptr()), C.c_void_p(pair.data_ptr()),
+                                               C.c_void_p(pair_rows.data_ptr()), C.c_void_p(pair_stats.data_ptr()),
+                                               C.c_void_p(tile_prob.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_region")
+        self._tuning_sync()
+        return {"rows": rows, "pair": pair, "pair_tile": flat, "pair_rows": pair_rows, "pair_stats": pair_stats, "tile_prob": tile_prob}
+
     # ---- pose-only forward -------------------------------------------------------------------
     def localize(self, grd: torch.Tensor, sat: torch.Tensor) -> torch.Tensor:
         """The pose of every query without the nine forward outputs: float32 [B, 5] on the device, the postprocess_rows layout

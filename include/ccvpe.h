@@ -232,6 +232,40 @@ int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t
                                        int32_t n_tiles, const int32_t* tile_index, int32_t batch, int32_t k, int32_t radius,
                                        float* rows, void* stream);
 
+/* Ground-side cache: the descriptor vector of each ground image, the ground encoder's only output.  Layout: float32
+ * [batch][Ltot], DEVICE memory of ccvpe_ground_cache_bytes(h, batch, grd_h, grd_w) = batch * Ltot * 4 bytes, where
+ * Ltot = sum over the six matching levels k of round_up(L_k, 4), L_k = (feature width) * (head channels of level k), and level
+ * k's descriptor starts at float sum_{j<k} round_up(L_j, 4) of its row (padding floats unspecified).  batch <= micro_batch.
+ * The launches are the full forward's ground encoder, heads and descriptor launch: at the same batch the cache holds the bits
+ * the full forward computes.  ccvpe_ground_cache_bytes returns 0 for a bad argument or ground geometry (ccvpe_last_error). */
+size_t ccvpe_ground_cache_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32_t grd_w);
+int ccvpe_encode_ground(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, int32_t batch, void* cache,
+                        void* stream);
+
+/* One ground encoding per query against several aerial tiles (VIGOR's positive and semi-positive tiles, Oxford's overlapping
+ * 400-px windows, a coarse position prior).  `grd_cache` is ccvpe_encode_ground's cache of n_queries images of grd_h x grd_w,
+ * `sat_cache` ccvpe_encode_aerial's cache of n_tiles tiles.  The pairs form a CSR list in HOST memory: query g owns pairs
+ * offsets[g] .. offsets[g+1]-1 (offsets: int32 [n_queries+1]), pair p uses tile tiles[p] (int32 [P], P = offsets[n_queries]);
+ * a tile may appear several times, each a pair of its own.  P is any count: the pairs run as micro-batches of the cached pose
+ * plan, every pair reading its query's row and its tile from the two caches.  DEVICE outputs, all required:
+ *   pair_rows[P][5]   ccvpe_localize rows of each pair, the probability normalised inside that pair's tile;
+ *   pair_stats[P][2]  (m_p, inv_p) = (max logit, 1 / sum exp(logit - m_p)) of that tile's softmax;
+ *   tile_prob[P]      S_p / Z with S_p = exp(m_p - M) / inv_p, M the query's largest m_p, Z the sum of its S_p: the pair's share of
+ *                     the query's summed softmax mass (tiles overlap: not a posterior over disjoint areas);
+ *   rows[n_queries][5] the row of the query's best pair with prob = joint_p = prob_p * S_p / Z, the softmax over the union of the
+ *                     query's tiles at that pair's argmax; the best pair has the largest joint_p, the first on ties;
+ *   best_pair[n_queries] that pair's position p.
+ * The cross-tile step is float64.  A pair whose m_p or inv_p is not finite has S_p = 0 and never wins; a query without a finite
+ * pair reports its first pair with prob NaN (and NaN tile_prob).  CCVPE_EINVAL, with no launch issued and every output
+ * untouched, checked before the handle is used: a null pointer, n_queries <= 0, n_tiles <= 0, offsets[0] != 0, offsets that do
+ * not strictly increase (a query without a tile), a tile outside 0 .. n_tiles-1 (the message names the first bad position and
+ * value); then n_queries or n_tiles > micro_batch.  CCVPE_ESTATE on a debug handle.  The CSR arrays travel in the launch
+ * arguments: no copy to the device, no synchronisation, and the caller may reuse them as soon as the call returns. */
+int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w,
+                          const void* sat_cache, int32_t n_tiles, const int32_t* offsets, const int32_t* tiles,
+                          float* rows, int32_t* best_pair, float* pair_rows, float* pair_stats, float* tile_prob,
+                          void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
