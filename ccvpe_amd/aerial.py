@@ -298,6 +298,51 @@ def oxford_region_to_map(origin, index) -> np.ndarray:
     return out[0] if scalar else out
 
 
+def _sigma(sigma_px, n: int) -> np.ndarray:
+    sig = np.broadcast_to(np.asarray(sigma_px, dtype=np.float64).reshape(-1), (n,)).copy()
+    if not (np.isfinite(sig).all() and (sig > 0).all()):
+        raise ValueError(f"sigma_px must be finite and positive, got {sigma_px}")
+    return sig
+
+
+def gaussian_log_prior(center_px, sigma_px, device):
+    """Isotropic Gaussian log-priors in the output-map frame (the localize_prior / postprocess_prior input): float32 [B,512,512] with
+    -0.5 * ((x - cx)^2 + (y - cy)^2) / sigma^2 at column x, row y, for centres center_px [B,2] = (cx, cy) in output pixels (a GNSS fix,
+    the previous pose plus odometry) and sigma_px a scalar or [B].  Evaluated in float64, rounded once to float32."""
+    import torch
+    c = np.asarray(center_px, dtype=np.float64).reshape(-1, 2)
+    if not np.isfinite(c).all():
+        raise ValueError("center_px must be finite")
+    sig = _sigma(sigma_px, c.shape[0])
+    t = torch.arange(SAT_HW, dtype=torch.float64, device=device)
+    cx = torch.as_tensor(c[:, 0], device=device)[:, None, None]
+    cy = torch.as_tensor(c[:, 1], device=device)[:, None, None]
+    s2 = torch.as_tensor(sig * sig, device=device)[:, None, None]
+    return (-0.5 * ((t[None, None, :] - cx) ** 2 + (t[None, :, None] - cy) ** 2) / s2).to(torch.float32).contiguous()
+
+
+def oxford_log_prior(origin, prior_coords, sigma_px, device):
+    """Per-pair log-priors for localize_region_prior on the Oxford windows: float32 [P,512,512], for window origins origin [P,2] = (x0, y0)
+    and map positions prior_coords [P,2] = (col, row) (either may be one row for all pairs), the Gaussian
+    -0.5 * ((X - px)^2 + (Y - py)^2) / sigma^2 in MAP pixels at each heatmap pixel's map position (X, Y) = oxford_region_to_map(origin,
+    index).  One scale across windows: pairs of one query compare through it (ccvpe_localize_region_prior)."""
+    import torch
+    org = np.asarray(origin, dtype=np.float64).reshape(-1, 2)
+    pc = np.asarray(prior_coords, dtype=np.float64).reshape(-1, 2)
+    P = max(org.shape[0], pc.shape[0])
+    org, pc = np.broadcast_to(org, (P, 2)).copy(), np.broadcast_to(pc, (P, 2)).copy()
+    if not (np.isfinite(org).all() and np.isfinite(pc).all()):
+        raise ValueError("origin and prior_coords must be finite")
+    sig = _sigma(sigma_px, P)
+    centre = torch.as_tensor(_oxford_index_centre(), dtype=torch.float64, device=device)
+    col = torch.as_tensor(org[:, 0], device=device)[:, None] + centre[None, :]   # [P, 512] map column of each heatmap column
+    row = torch.as_tensor(org[:, 1], device=device)[:, None] + centre[None, :]   # [P, 512] map row of each heatmap row
+    dx = col - torch.as_tensor(pc[:, 0], device=device)[:, None]
+    dy = row - torch.as_tensor(pc[:, 1], device=device)[:, None]
+    s2 = torch.as_tensor(sig * sig, device=device)[:, None, None]
+    return (-0.5 * (dx[:, None, :] ** 2 + dy[:, :, None] ** 2) / s2).to(torch.float32).contiguous()
+
+
 def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
     """Ground-truth side of an Oxford test sample (datasets.py:323-351): gt_index [B] int32 = flat argmax of `gt`, gt_cos_sin [B,2]
     float32 = `orientation` at that pixel, heading_deg [B] float64 = `orientation_angle` (yaw: grdYaw, radians)."""

@@ -150,6 +150,7 @@ int ccvpe_destroy(ccvpe_handle h) {
     if (h->arena) (void)hipFree(h->arena);
     if (h->post_scratch) (void)hipFree(h->post_scratch);
     if (h->topk_scratch) (void)hipFree(h->topk_scratch);
+    if (h->prior_scratch) (void)hipFree(h->prior_scratch);
     h->plans.clear();
     for (int k = 0; k < 2; ++k) if (h->snap[k]) (void)hipFree(h->snap[k]);
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
@@ -255,10 +256,12 @@ static int micro_batch_cap(ccvpe_handle h, int gh, int gw) {
 }
 
 // rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read);
-// topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller)
+// topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller);
+// log_prior != null: the pose plans of ccvpe_localize_prior* - every slice reads its own maps (prior_stride checked by the caller)
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
                        const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr,
-                       int topk_k = 0, int topk_r = 0, const int32_t* tile_index = nullptr, int n_tiles = 0) {
+                       int topk_k = 0, int topk_r = 0, const int32_t* tile_index = nullptr, int n_tiles = 0,
+                       const float* log_prior = nullptr, long long prior_stride = 0) {
     const int mode = cache ? 2 : 0;
     const bool pose = rows != nullptr;
     const bool topk = pose && topk_k > 0;
@@ -297,6 +300,7 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         pl->set_scratch(c, 0);
         c.grd = grd + (size_t)done * 3 * gh * gw;
         c.sat = sat ? sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
+        if (log_prior) { c.log_prior = log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
         if (topk) {
             c.rows = rows + (size_t)done * topk_k * 5;
             c.topk_k = topk_k; c.topk_r = topk_r;
@@ -723,11 +727,10 @@ static int check_region_args(const void* grd_cache, int32_t n_queries, const voi
     return 0;
 }
 
-int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
-                          int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, float* rows, int32_t* best_pair, float* pair_rows,
-                          float* pair_stats, float* tile_prob, void* stream) {
-    if (int rc = check_region_args(grd_cache, n_queries, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats, tile_prob))
-        return rc;
+// ccvpe_localize_region and, with pair_log_prior set, ccvpe_localize_region_prior (the arguments checked by the caller)
+static int run_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
+                      int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, float* rows, int32_t* best_pair, float* pair_rows,
+                      float* pair_stats, float* tile_prob, void* stream, const float* pair_log_prior, long long prior_stride) {
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     if (n_queries > h->cfg.micro_batch)
         return ccvpe_fail(CCVPE_EINVAL, "n_queries %d exceeds micro_batch (%d), the most ccvpe_encode_ground writes", n_queries, h->cfg.micro_batch);
@@ -759,6 +762,7 @@ int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queri
         pl->set_scratch(c, 0);
         c.rows = pair_rows + (size_t)done * 5;
         c.stats = pair_stats + (size_t)done * 2;
+        if (pair_log_prior) { c.log_prior = pair_log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
         if (int rrc = run_ops(h, *pl, c, s)) return rrc;
         if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
         done += mb;
@@ -767,6 +771,133 @@ int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queri
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
+}
+
+int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
+                          int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, float* rows, int32_t* best_pair, float* pair_rows,
+                          float* pair_stats, float* tile_prob, void* stream) {
+    if (int rc = check_region_args(grd_cache, n_queries, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats, tile_prob))
+        return rc;
+    return run_region(h, grd_cache, n_queries, grd_h, grd_w, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats,
+                      tile_prob, stream, nullptr, 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Localize with a per-query position prior: the pose plans with log_prior added to the logits where softmax.partial,
+// pose.argmax and topk.peaks read them - no launch of their own.
+// ------------------------------------------------------------------------------------------------
+// the prior arguments, checked before the handle is used; k == 0 is the argmax form, which takes no radius
+static int check_prior_args(const float* log_prior, int64_t prior_stride, int32_t k, int32_t radius) {
+    const int64_t n = (int64_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
+    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
+    if (prior_stride != 0 && prior_stride != n)
+        return ccvpe_fail(CCVPE_EINVAL, "prior_stride must be 0 (one shared map) or %lld (one map per query), got %lld", (long long)n,
+                          (long long)prior_stride);
+    if (k < 0 || k > TOPK_MAX_K) return ccvpe_fail(CCVPE_EINVAL, "k must be in 0 .. %d, got %d", TOPK_MAX_K, k);
+    if (radius < 0 || radius > TOPK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TOPK_MAX_R, radius);
+    if (k == 0 && radius != 0) return ccvpe_fail(CCVPE_EINVAL, "radius %d needs k >= 1: the argmax form (k = 0) takes radius 0", radius);
+    return 0;
+}
+
+int ccvpe_localize_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                         const float* log_prior, int64_t prior_stride, int32_t k, int32_t radius, float* rows, void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, k, radius, nullptr, 0,
+                       log_prior, prior_stride);
+}
+
+int ccvpe_localize_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                        const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride, int32_t k,
+                                        int32_t radius, float* rows, void* stream) {
+    if (tile_index) {
+        if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    } else {   // query b reads tile b: the unindexed cached plan, whose cache holds exactly one tile per query
+        if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+        if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+        if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+        if (n_tiles != batch)
+            return ccvpe_fail(CCVPE_EINVAL, "without tile_index the cache holds one tile per query: n_tiles %d != batch %d", n_tiles, batch);
+    }
+    if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius,
+                       tile_index, tile_index ? n_tiles : 0, log_prior, prior_stride);
+}
+
+// scratch of ccvpe_postprocess_prior: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys][B x 64 indices][B x 64 x 2 softmax partials];
+// the argmax form's (max, index) hand-off pairs use the start of the key area.  Grows with the largest batch seen, as
+// ensure_topk_scratch.
+static size_t prior_scratch_bytes(int B) { return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float); }
+
+static int ensure_prior_scratch(ccvpe_handle_s* h, int batch) {
+    if (batch <= h->prior_batch) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    if (h->prior_scratch) HIPCHK(hipFree(h->prior_scratch));
+    h->prior_scratch = nullptr; h->prior_batch = 0;
+    const int cap = std::max(batch, 32);
+    void* d = nullptr;
+    if (hipMalloc(&d, prior_scratch_bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "prior post-processing scratch");
+    HIPCHK(hipMemset(d, 0, prior_scratch_bytes(cap)));
+    HIPCHK(hipDeviceSynchronize());
+    h->prior_scratch = d; h->prior_batch = cap;
+    return 0;
+}
+
+int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                            int64_t prior_stride, int32_t k, int32_t radius, float* rows, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_prior_scratch(h, batch)) return rc;
+    const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
+    const int cap = h->prior_batch;
+    unsigned char* base = reinterpret_cast<unsigned char*>(h->prior_scratch);
+    unsigned* tickets = reinterpret_cast<unsigned*>(base);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
+    int* index = reinterpret_cast<int*>(keys + (size_t)cap * 64 * TOPK_MAX_K);
+    float* partial = reinterpret_cast<float*>(index + (size_t)cap * TOPK_MAX_K);
+    hipStream_t s = (hipStream_t)stream;
+    SoftmaxParams sp{};
+    sp.logits = logits; sp.B = batch; sp.n = n; sp.partial = partial; sp.chunks = 64; sp.out = nullptr;
+    sp.prior = log_prior; sp.prior_stride = prior_stride;
+    launch_softmax_partial(sp, s);
+    if (k == 0) {
+        PoseArgmaxParams p{};
+        p.logits = logits; p.partial = partial; p.B = batch; p.n = n; p.chunks = 64;
+        p.pairs = reinterpret_cast<float*>(keys); p.tickets = tickets; p.index = index; p.rows = rows; p.stats = nullptr;
+        p.prior = log_prior; p.prior_stride = prior_stride;
+        launch_pose_argmax(p, s);
+        launch_pose_gather(ori, index, batch, n, rows, s);
+    } else {
+        TopkParams p{};
+        p.heat = nullptr; p.logits = logits; p.partial = partial; p.B = batch; p.k = k; p.r = radius;
+        p.keys = keys; p.tickets = tickets; p.index = index; p.rows = rows;
+        p.prior = log_prior; p.prior_stride = prior_stride;
+        launch_topk_peaks(p, s);
+        launch_topk_gather(ori, index, batch, k, n, rows, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "postprocess_prior launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
+                                int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, const float* pair_log_prior,
+                                int64_t prior_stride, float* rows, int32_t* best_pair, float* pair_rows, float* pair_stats, float* tile_prob,
+                                void* stream) {
+    if (int rc = check_region_args(grd_cache, n_queries, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats, tile_prob))
+        return rc;
+    if (int rc = check_prior_args(pair_log_prior, prior_stride, 0, 0)) return rc;
+    return run_region(h, grd_cache, n_queries, grd_h, grd_w, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats,
+                      tile_prob, stream, pair_log_prior, prior_stride);
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

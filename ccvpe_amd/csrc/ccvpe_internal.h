@@ -245,6 +245,8 @@ struct Ctx {
     const int* query_index = nullptr;  // ... HOST query of each pair of this micro-batch
     int n_queries = 0;                 // ... and the number of queries grd_cache_in holds
     float* stats = nullptr;            // pose plans: optional [B][2] softmax (max, 1/sum) of each sample (pose_argmax_kernel)
+    const float* log_prior = nullptr;  // pose plans: optional log-prior of this micro-batch's first sample ...
+    long long prior_stride = 0;        // ... and the floats between two samples' maps (0: one map for all)
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -504,6 +506,8 @@ struct ccvpe_handle_s {
     int post_batch = 0;
     void* topk_scratch = nullptr;   // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices for topk_batch samples
     int topk_batch = 0;
+    void* prior_scratch = nullptr;   // ccvpe_postprocess_prior: the top-K scratch plus softmax partials for prior_batch samples
+    int prior_batch = 0;
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;

@@ -309,6 +309,8 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
 // launch alone, pose_argmax_kernel (argmax and prob from recomputed heatmap values) and the orientation field at the argmax pixel only
 // (ori1.pose: the fused level 1 for the one tile that holds it; without the fused level: ori1.tail into the workspace + ori1.gather).
 // Never captured into a hipGraph.
+// A position prior (Ctx::log_prior, ccvpe_*_prior) changes no launch: softmax.partial, pose.argmax and topk.peaks read
+// it beside the logits, each call with its own pointer and stride.
 // Top-K pose plans (topk = true as well, ccvpe_localize_topk): the same launches up to softmax.partial and the level-2 decoders; the
 // tail is topk.peaks (the K best peaks from recomputed heatmap values) and the orientation at those K pixels (ori1.topk:
 // the fused level 1 for each hypothesis' tile; without the fused level: ori1.tail + ori1.topk_gather).  K and r come with each call
@@ -608,6 +610,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
             SoftmaxParams p{};
             p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
+            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_softmax_partial(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
         const size_t toff = pl.alloc_tickets((size_t)B);
@@ -616,6 +619,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             p.heat = nullptr; p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.k = c.topk_k; p.r = c.topk_r;
             p.keys = reinterpret_cast<unsigned long long*>(c.ptr(keys)); p.tickets = c.tickets + toff;
             p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
+            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_topk_peaks(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
     } else if (pose) {
@@ -626,6 +630,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
             SoftmaxParams p{};
             p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
+            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_softmax_partial(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
         const size_t toff = pl.alloc_tickets((size_t)B);
@@ -633,7 +638,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
             p.pairs = c.ptr(pairs); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
-            p.stats = c.stats;
+            p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
     } else {

@@ -357,6 +357,8 @@ struct SoftmaxParams {
     float* partial;            // [B][chunks][2]
     int chunks;
     float* out;                // [B][n]
+    const float* prior;        // optional [B][n] log-prior: partials of fl32(logit + prior); launch_softmax_partial only
+    long long prior_stride;    //   floats between two samples' maps: 0 (one shared map) or n
 };
 void launch_softmax(const SoftmaxParams& p, hipStream_t s);
 void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s);   // the first of launch_softmax's two launches alone (pose plans)
@@ -373,6 +375,8 @@ struct PoseArgmaxParams {
     int* index;                // [B] argmax, always in [0, n)
     float* rows;               // [B][5]: columns 0 (index) and 1 (prob)
     float* stats;              // optional [B][2]: the sample's softmax (max, 1/sum), written by workgroup (0, b) (ccvpe_localize_region)
+    const float* prior;        // optional log-prior as SoftmaxParams::prior (the partials must be of the same sums).  A sample whose
+    long long prior_stride;    //   (max, 1/sum) is not finite gets index 0 and rows (-1, NaN)
 };
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
@@ -391,6 +395,8 @@ struct TopkParams {
     unsigned* tickets;          // [B] counters, zero before and after every launch
     int* index;                 // [B][k]
     float* rows;                // [B][k][5]
+    const float* prior;         // optional log-prior of the logits path (SoftmaxParams::prior): values __expf((l + prior) - m) * inv;
+    long long prior_stride;     //   a sample whose (m, inv) is not finite has no peak
 };
 void launch_topk_peaks(const TopkParams& p, hipStream_t s);
 // rows[b][k][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b][k] >= 0 (postprocess_topk; pose plans without the fused level 1)

@@ -87,16 +87,23 @@ __device__ __forceinline__ void combine(float& m, float& s, float m2, float s2) 
     m = mn;
 }
 
+// PRIOR: the partials of l' = fl32(l + prior), the prior read as float4 beside the logits; everything else - and so
+// every bit for a zero prior - as without it.  A prior excludes pixels with -inf, often whole stretches: a thread that has seen
+// nothing else keeps (-inf, 0) instead of exp(-inf - -inf) = NaN, as combine() does.
+template <bool PRIOR>
 __global__ __launch_bounds__(256) void softmax_partial_kernel(const SoftmaxParams p) {
     __shared__ float sm[4], ss[4];
     const int b = blockIdx.y, ch = blockIdx.x;
     const int per = p.n / p.chunks;
     const float4* src = reinterpret_cast<const float4*>(p.logits + (size_t)b * p.n + (size_t)ch * per);
+    const float4* lp = PRIOR ? reinterpret_cast<const float4*>(p.prior + (size_t)b * p.prior_stride + (size_t)ch * per) : nullptr;
     float m = -INFINITY, s = 0.f;
     for (int i = threadIdx.x; i < per / 4; i += 256) {
-        const float4 v = src[i];
+        float4 v = src[i];
+        if constexpr (PRIOR) { const float4 q = lp[i]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
         const float lm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
         const float mn = fmaxf(m, lm);
+        if constexpr (PRIOR) { if (mn == -INFINITY) continue; }
         s = s * __expf(m - mn) + __expf(v.x - mn) + __expf(v.y - mn) + __expf(v.z - mn) + __expf(v.w - mn);
         m = mn;
     }
@@ -146,12 +153,13 @@ __global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams 
 }
 
 void launch_softmax(const SoftmaxParams& p, hipStream_t s) {
-    CCVPE_LAUNCH(softmax_partial_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    CCVPE_LAUNCH(softmax_partial_kernel<false>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
     CCVPE_LAUNCH(softmax_final_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
 }
 
 void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s) {
-    CCVPE_LAUNCH(softmax_partial_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    if (p.prior) CCVPE_LAUNCH(softmax_partial_kernel<true>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    else CCVPE_LAUNCH(softmax_partial_kernel<false>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -251,7 +259,11 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
 // bits that kernel would store, so index and prob are those ccvpe_postprocess_rows reads from the heatmap, ties included (strictly greater
 // within a thread, lowest index on ties across threads and chunks).  Every thread's index starts at the first position it scans, so the
 // result is a position of the chunk whatever the values are.
+// PRIOR: the values are those of l' = fl32(l + prior), with softmax_partial_kernel<true>'s statistics.  A sample whose
+// (m, inv) is not finite (a prior of -inf everywhere, a +inf, a NaN) has no posterior: rows (-1, NaN) and index 0, so that the
+// orientation launches behind still read inside the map.
 // ------------------------------------------------------------------------------------------------
+template <bool PRIOR>
 __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams p) {
     __shared__ float gm, gs;
     __shared__ float sv[4];
@@ -265,6 +277,14 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
     float4 v[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = src[threadIdx.x + u * 256];   // (per / 4 = 1024 float4 per chunk: four per thread, one trip)
+    if constexpr (PRIOR) {
+        const float4* lp = reinterpret_cast<const float4*>(p.prior + (size_t)b * p.prior_stride + lo);
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = lp[threadIdx.x + u * 256];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { v[u].x += q[u].x; v[u].y += q[u].y; v[u].z += q[u].z; v[u].w += q[u].w; }
+    }
     __syncthreads();
     const float m = gm, inv = gs;
     if (p.stats && c == 0 && threadIdx.x == 0) { p.stats[b * 2 + 0] = m; p.stats[b * 2 + 1] = inv; }   // (read by a later launch)
@@ -305,6 +325,9 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
         }
         if (threadIdx.x == 0) {
+            if constexpr (PRIOR) {
+                if (!(isfinite(m) && isfinite(inv))) { p.index[b] = 0; p.rows[b * 5 + 0] = -1.f; p.rows[b * 5 + 1] = NAN; return; }
+            }
             p.index[b] = bi;
             p.rows[b * 5 + 0] = (float)bi;
             p.rows[b * 5 + 1] = best;
@@ -313,7 +336,8 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
 }
 
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s) {
-    CCVPE_LAUNCH(pose_argmax_kernel, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    if (p.prior) CCVPE_LAUNCH(pose_argmax_kernel<true>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    else CCVPE_LAUNCH(pose_argmax_kernel<false>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -402,6 +426,8 @@ void launch_pose_gather(const float* ori, const int* index, int B, int n, float*
 // 64-bit keys (value bits << 32 | ~index: value descending, index ascending) with a bitonic sort in LDS and hands its best K to the
 // sample's last arriver (ticket.h), which sorts the 64 K candidates the same way and writes index[b][k] and rows[b][k][0..1].  A slot
 // without a peak gets index -1 and the row (-1, 0, 0, 0, 0); the orientation launches behind skip it.
+// PRIOR (logits path only): the values are __expf((l + prior) - m) * inv with softmax_partial_kernel<true>'s statistics;
+// a sample whose (m, inv) is not finite has no peak at all.
 // ------------------------------------------------------------------------------------------------
 static constexpr int TK_HW = 512;                  // map side (CCVPE_OUT_HW)
 static constexpr int TK_T = 64;                    // tile side
@@ -425,8 +451,9 @@ __device__ __forceinline__ void topk_sort_desc(unsigned long long* s, int N) {
         }
 }
 
-template <bool LOGITS>
+template <bool LOGITS, bool PRIOR = false>
 __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
+    static_assert(LOGITS || !PRIOR, "the prior applies to recomputed values");
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     __shared__ float gm, gs;
     __shared__ unsigned cnt, flag;
@@ -446,14 +473,17 @@ __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
     }
     if (tid == 0) cnt = 0u;
     const float* src = (LOGITS ? p.logits : p.heat) + (size_t)b * n;
+    const float* lpb = PRIOR ? p.prior + (size_t)b * p.prior_stride : nullptr;
+    const bool finite_stats = !PRIOR || (isfinite(m) && isfinite(inv));
     for (int i = tid; i < S * S; i += 256) {
         const int ly = i / S, lx = i - ly * S;
         const int y = Y0 - r + ly, x = X0 - r + lx;
         unsigned u = 0u;
         if ((unsigned)y < (unsigned)HW && (unsigned)x < (unsigned)HW) {
             float h = src[y * HW + x];
-            if (LOGITS) h = __expf(h - m) * inv;
-            u = h > 0.f ? __float_as_uint(h) : 0u;
+            if constexpr (PRIOR) h = __expf((h + lpb[y * HW + x]) - m) * inv;
+            else if (LOGITS) h = __expf(h - m) * inv;
+            u = h > 0.f && finite_stats ? __float_as_uint(h) : 0u;
         }
         in[i] = u;
     }
@@ -528,7 +558,11 @@ __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
 
 void launch_topk_peaks(const TopkParams& p, hipStream_t s) {
     const size_t lds = topk_lds_bytes(p.r);
-    if (p.logits) {
+    if (p.logits && p.prior) {
+        static LdsAttr attr;
+        ensure_dynamic_lds(attr, reinterpret_cast<const void*>(topk_peaks_kernel<true, true>), lds);
+        CCVPE_LAUNCH((topk_peaks_kernel<true, true>), dim3(TK_TILES, p.B), dim3(256), lds, s, p);
+    } else if (p.logits) {
         static LdsAttr attr;
         ensure_dynamic_lds(attr, reinterpret_cast<const void*>(topk_peaks_kernel<true>), lds);
         CCVPE_LAUNCH(topk_peaks_kernel<true>, dim3(TK_TILES, p.B), dim3(256), lds, s, p);

@@ -571,6 +571,151 @@ class _CVMBase(nn.Module):
         _lib.check(rc, "ccvpe_postprocess_topk")
         return rows
 
+    # ---- pose with a position prior -------------------------------------------
+    PRIOR_MAP = 512 * 512
+
+    @classmethod
+    def _prior_args(cls, log_prior, B: int, k: int, radius: int):
+        """(log_prior, k, radius) of the prior forms -> (contiguous float32 cuda tensor, prior_stride in floats, k, radius).  log_prior is
+        one map for every query ([512,512], [1,512,512], [1,1,512,512]: stride 0) or one per query ([B,512,512], [B,1,512,512]: stride
+        512*512), log-weights in the pixel order of logits_flattened; k = 0 is the argmax form and takes radius 0."""
+        k, radius = int(k), int(radius)
+        if not 0 <= k <= 64:
+            raise ValueError(f"k must be in 0..64 (0: the argmax row), got {k}")
+        if not 0 <= radius <= 32:
+            raise ValueError(f"radius must be in 0..32, got {radius}")
+        if k == 0 and radius != 0:
+            raise ValueError(f"radius {radius} needs k >= 1: the argmax form (k = 0) takes radius 0")
+        if not isinstance(log_prior, torch.Tensor):
+            raise ValueError("log_prior must be a float32 cuda tensor")
+        shape = tuple(log_prior.shape)
+        ok = shape[-2:] == spec.OUT_HW and (len(shape) in (2, 3) or (len(shape) == 4 and shape[1] == 1))
+        n = 1 if len(shape) == 2 else (shape[0] if ok else -1)
+        if not ok or n not in (1, B):
+            raise ValueError(f"log_prior must be [512,512], [1,512,512], [{B},512,512] or the [.,1,512,512] forms, got {shape}")
+        if log_prior.dtype != torch.float32:
+            raise ValueError(f"log_prior must be float32, got {log_prior.dtype}")
+        if not log_prior.is_contiguous():
+            raise ValueError("log_prior must be contiguous")
+        if not log_prior.is_cuda:
+            raise ValueError(f"log_prior must be a cuda tensor on the inputs' device, not a {log_prior.device.type} tensor")
+        return log_prior.detach(), (cls.PRIOR_MAP if n > 1 else 0), k, radius
+
+    def localize_prior(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0) -> torch.Tensor:
+        """localize (k = 0: rows [B, 5]) or localize_topk (k in 1..64: rows [B, k, 5]) on the posterior softmax(logits + log_prior):
+        the semantics in include/ccvpe.h (ccvpe_localize_prior).  An all-zero prior gives the rows of the forms without one; a query
+        without a finite posterior (a prior of -inf everywhere) has index -1."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        lp, stride, k, radius = self._prior_args(log_prior, grd.shape[0], k, radius)
+        grd, sat = self._prepare(grd, sat)
+        if lp.device != grd.device:
+            raise ValueError("log_prior must be on the inputs' device")
+        B = grd.shape[0]
+        with torch.cuda.device(grd.device):
+            rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=grd.device)
+            stream = torch.cuda.current_stream(grd.device).cuda_stream
+            rc = _lib.load().ccvpe_localize_prior(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                  C.c_void_p(sat.data_ptr()), B, C.c_void_p(lp.data_ptr()), stride, k, radius,
+                                                  C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_prior")
+        self._tuning_sync()
+        return rows
+
+    def localize_prior_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0,
+                              tile_index=None) -> torch.Tensor:
+        """localize_prior(grd, sat, log_prior, k, radius) with the aerial side taken from encode_aerial(sat); tile_index as
+        forward_cached (ccvpe_localize_prior_cached_indexed)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        idx = self._host_tile_index(tile_index, grd)
+        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        lp, stride, k, radius = self._prior_args(log_prior, grd.shape[0], k, radius)
+        if lp.device != grd.device:
+            raise ValueError("log_prior must be on the inputs' device")
+        grd = grd.detach().to(torch.float32).contiguous()
+        self._ensure_handle(grd.device)
+        B = grd.shape[0]
+        n_tiles = self._cache_tiles(cache, B, idx)
+        rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=grd.device)
+        stream = torch.cuda.current_stream(grd.device).cuda_stream
+        rc = _lib.load().ccvpe_localize_prior_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                             C.c_void_p(cache.data_ptr()), n_tiles,
+                                                             idx.ctypes.data_as(C.c_void_p) if idx is not None else None, B,
+                                                             C.c_void_p(lp.data_ptr()), stride, k, radius, C.c_void_p(rows.data_ptr()),
+                                                             C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_prior_cached_indexed")
+        self._tuning_sync()
+        return rows
+
+    def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
+                          ) -> torch.Tensor:
+        """The rows of localize_prior from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori =
+        forward(...)[2] ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_prior)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        B = logits.shape[0] if logits.dim() > 0 else 0
+        if logits.numel() != B * self.PRIOR_MAP or ori.numel() != B * 2 * self.PRIOR_MAP or B == 0:
+            raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
+        lp, stride, k, radius = self._prior_args(log_prior, B, k, radius)
+        if not (logits.is_cuda and ori.is_cuda):
+            raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
+        if not (lp.device == logits.device == ori.device):
+            raise ValueError("logits, ori and log_prior must be on one device")
+        logits = logits.detach().to(torch.float32).contiguous()
+        ori = ori.detach().to(torch.float32).contiguous()
+        self._ensure_handle(logits.device)
+        rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=logits.device)
+        stream = torch.cuda.current_stream(logits.device).cuda_stream
+        rc = _lib.load().ccvpe_postprocess_prior(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B,
+                                                 C.c_void_p(lp.data_ptr()), stride, k, radius, C.c_void_p(rows.data_ptr()),
+                                                 C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_postprocess_prior")
+        return rows
+
+    def localize_region_prior(self, ground_cache: torch.Tensor, sat_cache: torch.Tensor, tiles, pair_log_prior: torch.Tensor
+                              ) -> Dict[str, object]:
+        """localize_region with a log-prior per (query, tile) pair: pair_log_prior is one map for every pair or [P,512,512] in the
+        flattened pair order (query by query, each query's tiles in order), each map on one scale across a query's tiles - a
+        log-density at every heatmap pixel's map position, such as aerial.oxford_log_prior.  Returns localize_region's dict, every
+        value of the posterior (ccvpe_localize_region_prior)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        offsets, flat = self._host_region_tiles(tiles)
+        G, P = offsets.shape[0] - 1, flat.shape[0]
+        lp, stride, _, _ = self._prior_args(pair_log_prior, P, 0, 0)
+        for what, c in (("ground_cache", ground_cache), ("sat_cache", sat_cache)):
+            if not isinstance(c, torch.Tensor) or not c.is_cuda:
+                raise ValueError(f"{what} must be the cuda tensor encode_{'ground' if what == 'ground_cache' else 'aerial'} returned")
+        if not hasattr(ground_cache, "_ccvpe_grd_hw"):
+            raise ValueError("ground_cache must come from encode_ground (it records the image count and size)")
+        if not hasattr(sat_cache, "_ccvpe_batch"):
+            raise ValueError("sat_cache must come from encode_aerial (it records how many tiles the cache holds)")
+        if int(ground_cache._ccvpe_batch) != G:
+            raise ValueError(f"tiles names {G} queries, ground_cache holds {ground_cache._ccvpe_batch}")
+        if lp.device != ground_cache.device:
+            raise ValueError("pair_log_prior must be on the caches' device")
+        self._ensure_handle(ground_cache.device)
+        dev = ground_cache.device
+        H, W = ground_cache._ccvpe_grd_hw
+        rows = torch.empty((G, 5), dtype=torch.float32, device=dev)
+        pair = torch.empty((G,), dtype=torch.int32, device=dev)
+        pair_rows = torch.empty((P, 5), dtype=torch.float32, device=dev)
+        pair_stats = torch.empty((P, 2), dtype=torch.float32, device=dev)
+        tile_prob = torch.empty((P,), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = _lib.load().ccvpe_localize_region_prior(self._handle, C.c_void_p(ground_cache.data_ptr()), G, H, W,
+                                                     C.c_void_p(sat_cache.data_ptr()), int(sat_cache._ccvpe_batch),
+                                                     offsets.ctypes.data_as(C.c_void_p), flat.ctypes.data_as(C.c_void_p),
+                                                     C.c_void_p(lp.data_ptr()), stride, C.c_void_p(rows.data_ptr()),
+                                                     C.c_void_p(pair.data_ptr()), C.c_void_p(pair_rows.data_ptr()),
+                                                     C.c_void_p(pair_stats.data_ptr()), C.c_void_p(tile_prob.data_ptr()),
+                                                     C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_localize_region_prior")
+        self._tuning_sync()
+        return {"rows": rows, "pair": pair, "pair_tile": flat, "pair_rows": pair_rows, "pair_stats": pair_stats, "tile_prob": tile_prob}
+
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Device-side version of the per-sample loop in train_VIGOR.py:297-316."""

@@ -266,6 +266,45 @@ int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queri
                           float* rows, int32_t* best_pair, float* pair_rows, float* pair_stats, float* tile_prob,
                           void* stream);
 
+/* Localize with a per-query position prior (a GNSS fix, the previous pose plus odometry, a road mask).  `log_prior` is float32
+ * DEVICE memory in the output-map frame, 512 x 512 values per map in the pixel order of logits_flattened: log-weights, not
+ * necessarily normalised, -inf excluding a pixel.  prior_stride (in floats) is 0 (one map for every query) or 512*512 (one map
+ * per query); larger batches than micro_batch read each slice's own maps.  With l the logits the plan computes, per query:
+ *     l' = fl32(l + log_prior)                  one IEEE float add per pixel
+ *     (m', inv') = max of l' and 1 / sum exp(l' - m'), the library's softmax statistics (the same order of combines)
+ *     h' = __expf(l' - m') * inv'               the heatmap expression of ccvpe_forward
+ * k == 0 (radius 0): rows[B][5] = (index, prob, cos, sin, angle_deg) at the first maximal h', prob = h' there, the orientation
+ * field at that pixel, as ccvpe_localize.  k in 1..64, radius in 0..32: rows[B][k][5] with ccvpe_postprocess_topk's peaks,
+ * order and (-1, 0, 0, 0, 0) padding applied to h'.  A query without a finite posterior (m' or inv' not finite: a prior of -inf
+ * over the whole map, a +inf or a NaN anywhere) has the argmax row (-1, NaN, unspecified cos / sin / angle) and top-K rows all
+ * (-1, 0, 0, 0, 0); no launch reads outside its tensors whatever the prior holds.  An all-zero prior gives the bits of the
+ * forms without a prior (logits without NaN or inf).  No launch is added: the prior is read where the logits are.
+ * CCVPE_EINVAL, with nothing launched and checked before the handle is used: a null pointer, prior_stride other than 0 or
+ * 512*512, k outside 0..64, radius outside 0..32, radius != 0 with k == 0 (the message names the argument); then the checks of
+ * the forms without a prior.  CCVPE_ESTATE on a debug handle (the three localize forms). */
+int ccvpe_localize_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                         const float* log_prior, int64_t prior_stride, int32_t k, int32_t radius, float* rows, void* stream);
+/* The cached form: tile_index (HOST int32 [batch], as ccvpe_localize_cached_indexed) or NULL, query b then reading tile b of a
+ * cache of n_tiles == batch tiles (the plan of ccvpe_localize_cached). */
+int ccvpe_localize_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                        int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                        int64_t prior_stride, int32_t k, int32_t radius, float* rows, void* stream);
+/* The same rows from forward outputs the caller holds: `logits` is ccvpe_forward's logits_flattened [batch][512*512], `ori` its
+ * orientation field [batch][2][512][512].  Bit-identical to the pose-only forms on the same inputs.  batch <= 4096; any
+ * handle (debug included); one call in flight per handle (ticket counters and partials in a scratch buffer of the handle). */
+int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                            int64_t prior_stride, int32_t k, int32_t radius, float* rows, void* stream);
+/* ccvpe_localize_region with a prior per pair: pair p reads the map at pair_log_prior + p * prior_stride (stride 0: one map for
+ * every pair).  pair_rows are the k == 0 rows of each pair's posterior and pair_stats its (m', inv'); the cross-tile step is
+ * ccvpe_localize_region's on them, so a pair without a finite posterior never wins.  The maps of one query's tiles must share
+ * one scale - a log-density evaluated at each heatmap pixel's map position, not a map normalised inside each tile - or tile_prob
+ * and the joint probability compare nothing.  Argument checks: ccvpe_localize_region's, then a null pair_log_prior or a bad
+ * prior_stride. */
+int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w,
+                                const void* sat_cache, int32_t n_tiles, const int32_t* offsets, const int32_t* tiles,
+                                const float* pair_log_prior, int64_t prior_stride, float* rows, int32_t* best_pair,
+                                float* pair_rows, float* pair_stats, float* tile_prob, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
