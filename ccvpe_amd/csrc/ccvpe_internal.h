@@ -215,8 +215,8 @@ struct DecoderW {
     float* l1_wt = nullptr;       // the same weights as [9][cout][16] for the fused level-1 kernel (channel pairs contiguous)
     float tail_b[2] = {0.f, 0.f};
     // fused last level (kernels_level1.hip)
-    float *l1_wd = nullptr, *l1_bd = nullptr, *l1_wa = nullptr, *l1_ba = nullptr;
-    int l1_cx = 0, l1_cxp = 0;
+    float *l1_wc = nullptr, *l1_ws = nullptr, *l1_bc = nullptr;   // composed deconv + conv_a weights, score k-step, bias table (Level1Params)
+    int l1_cx = 0, l1_cxp = 0, l1_c0 = 0, l1_ng = 0, l1_score = 0;
 };
 
 struct Tensor {

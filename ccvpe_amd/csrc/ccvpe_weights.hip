@@ -240,29 +240,65 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
                                 [&](int nn, int, int c) { int qd = nn / cw, o = nn % cw; return o < cout ? w[((size_t)c * cout + o) * 4 + qd] : 0.f; },
                                 bias, 1, 1))) return rc;
         }
-        if (j == 5) {   // dedicated layouts for the fused last level
-            const auto& w = h->host["deconv" + n + sfx + ".weight"];
+        if (j == 5) {   // the fused last level (kernels_level1.hip): the transposed conv composed with conv_a, per output parity
+            // conv_a pixel (2I + py, 2J + px), tap (ky, kx) reads transposed-conv pixel (2I + py + ky - 1, ...) = input pixel
+            // (I - 1 + py + a, J - 1 + px + b) at parity (ty & 1, tx & 1), ty = py + ky + 1, a = (ty >> 1) - py (likewise for x): so
+            // Wc[py][px][a][b][c][o] = sum over the taps landing in window (a, b) of sum_m Wa[o][m][ky][kx] Wd[c][m][ty & 1][tx & 1],
+            // in double, rounded once.  An input pixel outside the 256x256 input holds exactly the transposed-conv pixels outside the
+            // 512x512 image, so zero input there reproduces the zero padding for the weight terms; the transposed conv's bias, which
+            // zero padding also removes at the borders, enters as bc[case][o] = ba[o] + sum over in-image taps of Wa[o][.][tap] . bd.
+            const auto& w = h->host["deconv" + n + sfx + ".weight"];   // [cin][16][2][2]
             const auto& b = h->host["deconv" + n + sfx + ".bias"];
+            const auto& wa = h->host["conv" + n + sfx + ".0.weight"];  // [16][16][3][3]
+            const auto& ba = h->host["conv" + n + sfx + ".0.bias"];
             const int cin = lv[j].din, cout = lv[j].dout;   // cout == 16
             const int nscore = every_level_scored ? 1 : 0;
             const int spad = score_pad(nscore);
-            d.l1_cx = spad + (cin - nscore);
+            const int cd = cin - nscore;   // descriptor channels
+            d.l1_cx = spad + cd;
             d.l1_cxp = round_up(d.l1_cx, 16);
-            std::vector<float> wd((size_t)64 * d.l1_cxp, 0.f);
-            for (int c = 0; c < cin; ++c) {
-                const int cm = c < nscore ? c : c - nscore + spad;
-                for (int o = 0; o < cout; ++o)
-                    for (int qd = 0; qd < 4; ++qd) wd[(size_t)(qd * 16 + o) * d.l1_cxp + cm] = w[((size_t)c * cout + o) * 4 + qd];
-            }
-            if ((rc = upload(h, wd, &d.l1_wd))) return rc;
-            if ((rc = upload(h, b, &d.l1_bd))) return rc;
-            const auto& wa = h->host["conv" + n + sfx + ".0.weight"];   // [16][16][3][3] -> [16][144], k = tap*16 + c
-            std::vector<float> pk(16 * 144);
-            for (int o = 0; o < 16; ++o)
-                for (int c = 0; c < 16; ++c)
-                    for (int t = 0; t < 9; ++t) pk[o * 144 + t * 16 + c] = wa[((size_t)o * 16 + c) * 9 + t];
-            if ((rc = upload(h, pk, &d.l1_wa))) return rc;
-            if ((rc = upload(h, h->host["conv" + n + sfx + ".0.bias"], &d.l1_ba))) return rc;
+            d.l1_c0 = spad; d.l1_ng = (cd + 3) / 4; d.l1_score = nscore;
+            std::vector<double> wc((size_t)16 * cin * 16, 0.0);   // [py][px][a][b][c][o]
+            for (int py = 0; py < 2; ++py)
+                for (int px = 0; px < 2; ++px)
+                    for (int ky = 0; ky < 3; ++ky)
+                        for (int kx = 0; kx < 3; ++kx) {
+                            const int ty = py + ky + 1, tx = px + kx + 1, a = (ty >> 1) - py, bb = (tx >> 1) - px;
+                            const int qd = (ty & 1) * 2 + (tx & 1);
+                            double* dst = &wc[(size_t)(((py * 2 + px) * 2 + a) * 2 + bb) * cin * 16];
+                            for (int c = 0; c < cin; ++c)
+                                for (int o = 0; o < 16; ++o) {
+                                    double acc = 0.0;
+                                    for (int m = 0; m < cout; ++m)
+                                        acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)w[((size_t)c * cout + m) * 4 + qd];
+                                    dst[(size_t)c * 16 + o] += acc;
+                                }
+                        }
+            // lane l of parity class par holds window q = l >> 4, output channel l & 15
+            std::vector<float> pk((size_t)4 * d.l1_ng * 64 * 4, 0.f), sc(4 * 64, 0.f);
+            for (int par = 0; par < 4; ++par)
+                for (int l = 0; l < 64; ++l) {
+                    const double* src = &wc[(size_t)(par * 4 + (l >> 4)) * cin * 16];
+                    const int o = l & 15;
+                    for (int k = 0; k < 4 * d.l1_ng; ++k)
+                        if (k < cd) pk[((size_t)(par * d.l1_ng + k / 4) * 64 + l) * 4 + k % 4] = (float)src[(size_t)(nscore + k) * 16 + o];
+                    if (nscore) sc[par * 64 + l] = (float)src[o];
+                }
+            if ((rc = upload(h, pk, &d.l1_wc))) return rc;
+            if (nscore && (rc = upload(h, sc, &d.l1_ws))) return rc;
+            std::vector<float> bc(9 * 16);
+            for (int rcase = 0; rcase < 3; ++rcase)
+                for (int ccase = 0; ccase < 3; ++ccase)
+                    for (int o = 0; o < 16; ++o) {
+                        double acc = ba[o];
+                        for (int ky = 0; ky < 3; ++ky)
+                            for (int kx = 0; kx < 3; ++kx) {
+                                if ((rcase == 1 && ky == 0) || (rcase == 2 && ky == 2) || (ccase == 1 && kx == 0) || (ccase == 2 && kx == 2)) continue;
+                                for (int m = 0; m < cout; ++m) acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)b[m];
+                            }
+                        bc[(rcase * 3 + ccase) * 16 + o] = (float)acc;
+                    }
+            if ((rc = upload(h, bc, &d.l1_bc))) return rc;
         }
         {
             const auto& w = h->host["conv" + n + sfx + ".0.weight"];
@@ -308,7 +344,7 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
 // ingestion and the packing entirely.  The caller keys the file (ccvpe_amd/models.py: sha256 of the state_dict bytes,
 // variant, precision, library build digest); the header carries variant / precision / struct sizes and is checked.
 struct PackedHeader {
-    char magic[8];                 // "CCVPEPK4"
+    char magic[8];                 // "CCVPEPK5"
     int32_t variant, precision, circular, fuse_level1;
     char pack_group[128];          // Switches::pack_group() of the handle that packed the weights
     uint64_t n_allocs, sz_encoder, sz_decoder, sz_conv;
@@ -429,7 +465,7 @@ int ccvpe_save_packed(ccvpe_handle h, const char* path) {
         word0 += n / 8;
     });
     PackedHeader hd{};
-    std::memcpy(hd.magic, "CCVPEPK4", 8);
+    std::memcpy(hd.magic, "CCVPEPK5", 8);
     std::snprintf(hd.pack_group, sizeof(hd.pack_group), "%s", h->sw.pack_group().c_str());   // (at most ~100 characters)
     hd.variant = h->cfg.variant; hd.precision = h->cfg.reserved[0]; hd.circular = h->cfg.circular_padding; hd.fuse_level1 = h->sw.fuse_level1 ? 1 : 0;
     hd.n_allocs = h->dev_allocs.size(); hd.sz_encoder = sizeof(EncoderW); hd.sz_decoder = sizeof(DecoderW); hd.sz_conv = sizeof(PackedConv);
@@ -456,7 +492,7 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
     if (!f) return ccvpe_fail(CCVPE_EINVAL, "cannot open %s", path);
     PackedHeader hd{};
     auto bad = [&](const char* why) { std::fclose(f); return ccvpe_fail(CCVPE_EINVAL, "%s: %s", path, why); };
-    if (std::fread(&hd, sizeof(hd), 1, f) != 1 || std::memcmp(hd.magic, "CCVPEPK4", 8) != 0) return bad("not a packed-weight file of this library version");
+    if (std::fread(&hd, sizeof(hd), 1, f) != 1 || std::memcmp(hd.magic, "CCVPEPK5", 8) != 0) return bad("not a packed-weight file of this library version");
     if (hd.variant != h->cfg.variant || hd.precision != h->cfg.reserved[0] || hd.circular != h->cfg.circular_padding) return bad("packed for a different variant / precision / padding mode");
     hd.pack_group[sizeof(hd.pack_group) - 1] = 0;
     if (h->sw.pack_group() != hd.pack_group) return bad("packed under other packer switches (CCVPE_NO_PROJ, CCVPE_WINO4_MIN_N, CCVPE_NO_WINO4, CCVPE_NO_WINO4X, CCVPE_PAD_CONCAT)");
@@ -506,6 +542,16 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
         h->dev_allocs.clear(); h->dev_alloc_bytes.clear();
         packed_state_io(h, [&](void* p, size_t n) { std::memset(p, 0, n); });
         return ccvpe_fail(CCVPE_EINVAL, "%s: layer sizes do not match this variant", path);
+    }
+    // the fused last level's composed weights (a file packed before them has no such buffers and is refused, then re-packed)
+    const auto l1_ok = [&](const DecoderW& d) {
+        return d.l1_wc && d.l1_bc && (d.l1_score == 0 || d.l1_ws) && d.l1_ng > 0 && d.l1_c0 + 4 * d.l1_ng <= d.l1_cxp && level1_supported(d.l1_cxp);
+    };
+    if (hd.fuse_level1 != 0 && !(l1_ok(h->loc) && l1_ok(h->ori))) {
+        for (void* p : h->dev_allocs) (void)hipFree(p);
+        h->dev_allocs.clear(); h->dev_alloc_bytes.clear();
+        packed_state_io(h, [&](void* p, size_t n) { std::memset(p, 0, n); });
+        return ccvpe_fail(CCVPE_EINVAL, "%s: no composed level-1 weights", path);
     }
     h->host.clear();
     h->sw.fuse_level1 = hd.fuse_level1 != 0 && h->sw.fuse_level1;

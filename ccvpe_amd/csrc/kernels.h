@@ -320,16 +320,18 @@ struct TailConvParams {
 };
 void launch_tail_conv(const TailConvParams& p, hipStream_t s);
 
-// Fused last decoder level (kernels_level1.hip): deconv k2s2 (cx -> 16) + conv3x3 (16 -> 16) + ReLU +
+// Fused last decoder level (kernels_level1.hip): deconv k2s2 (cx -> 16) + conv3x3 (16 -> 16) (composed into one conv) + ReLU +
 // conv3x3 (16 -> cout) [+ L2 normalise], NHWC input at H/2 x W/2, NCHW output at H x W.
 struct Level1Params {
     const float* x;            // NHWC [B, H/2, W/2, x_ld], first cx channels used
-    int x_ld, cx, cxp;         // cxp = cx rounded up to 16 (weights zero padded)
+    int x_ld, cx, cxp;         // cxp = cx rounded up to 16 (the X tile's channel count)
     int B, H, W;               // output geometry (512 x 512)
-    const float* wd;           // [64][cxp]  n = (dy*2+dx)*16 + o
-    const float* bd;           // [16]
-    const float* wa;           // [16][144]  k = (ky*3+kx)*16 + c
-    const float* ba;           // [16]
+    // transposed conv composed with the first 3x3 conv (ccvpe_weights.hip): K = the score channel at the 4 window positions (if
+    // score) + ng groups of 4 descriptor channels (input channels c0 + 4g .. + 3) at the 4 window positions
+    int c0, ng, score;
+    const float* wc;           // [4 parity][ng][64 lane][4]: lane = window (lane >> 4) x output channel (lane & 15)
+    const float* ws;           // [4 parity][64 lane] the score channel's k-step (null without a score channel)
+    const float* bc;           // [9][16] conv_a bias by border case (3 * row case + column case; 0 interior, 1 first, 2 last)
     const float* wt;           // [9][cout][16]
     float bt[2];
     int cout, normalize;

@@ -1,14 +1,12 @@
 // Body of level1_kernel and level1_pose_kernel (kernels_level1.hip), included inside both kernels.  In scope: `p` (Level1Params), COUT,
-// constexpr bool POSE, `pose_index` and `pose_rows` (null unless POSE), and the POSE addressing: the workgroup runs the tile of pixel
-// pose_index[pose_slot] of sample pose_sample and writes row pose_rows[b * pose_ld + pose_r0 + 0..4].
+// NG and SCORE (the composed weights' shape; NG == 0: p.ng and p.score at run time), constexpr bool POSE, `pose_index` and `pose_rows` (null unless POSE),
+// and the POSE addressing: the workgroup runs the tile of pixel pose_index[pose_slot] of sample pose_sample and writes row
+// pose_rows[b * pose_ld + pose_r0 + 0..4].
 extern __shared__ __attribute__((aligned(16))) float smem[];
 const int CXP = p.cxp;                 // input channels padded to a multiple of 16
 const int XS = CXP + 4;                // row stride of the X tile
-const int r0f = max(XT * XT * XS, AROWS * PS);   // region 0 holds the X tile, later the aliased A tile
 float* Xs = smem;                      // [XT*XT][XS]
-float* As = smem;                      // [AROWS][PS]  (aliases Xs, dead after the deconv stage; rows >= 324 are a sink)
-float* Ds = smem + r0f;                // [DT*DT + DSINK][PS]  (tail rows: sink for the 12 padding rows of the last m-tile)
-int* dtab = reinterpret_cast<int*>(Ds + (DT * DT + DSINK) * PS);   // [112] X pixel -> float offset of its (dy,dx) = (0,0) D pixel
+float* Ps = smem + XT * XT * XS;      // [AT*AT][PS]  the tail conv's per-tap products (its own region: two barriers per tile)
 
 const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 const int H = p.H, W = p.W;            // output size (512); input is H/2 x W/2
@@ -29,16 +27,10 @@ if constexpr (POSE) {
 if (tile >= t_end) return;
 
 // ---- once per workgroup ----
-// Index arithmetic on the vector ALU costs matrix-pipe issue slots on gfx950, so the pixel -> LDS offset maps of
-// the two epilogues are tabulated (stage 1) or affine (stage 2); tiles whose halo lies fully inside the image
-// (88 % of them) also skip every bounds test.
-if (tid < 112) dtab[tid] = tid < XT * XT ? ((2 * (tid / XT)) * DT + 2 * (tid % XT)) * PS : DT * DT * PS;
 // Last conv (16 -> COUT, 3x3) in two steps (round 3): P[pixel][tap, co] = sum_c A[pixel][c] wt[tap][co][c] for every pixel of the 18 x 18
 // conv_a tile - a [324 x 16] x [16 x 9 COUT] GEMM whose B operand is the conv_a accumulator AS IT STANDS in registers (lane = pixel,
 // 4 channels: exactly the operand layout), 4 MFMAs per 16 pixels and 16 (tap, co) columns - and out[y][x][co] = bt + sum_tap P[(y + dy,
-// x + dx)][tap, co]: nine LDS reads and adds per output.  The P tile takes the A tile's place in LDS (18 of its 20 floats per pixel).
-// Before: 72 COUT packed FMAs, 36 16-byte A reads and 36 COUT weight reads per output pixel on the vector pipe - a quarter of the
-// kernel's time (in-kernel stamps, CCVPE_L1_CLOCK).
+// x + dx)][tap, co]: nine LDS reads and adds per output.
 constexpr int NPT = (9 * COUT + 15) / 16;                     // 16-column tiles of P
 f32x4 wtf[NPT];                                               // A fragments: wt[n = 16 nt + (lane & 15)][4 (lane >> 4) + e], n = tap * COUT + co
 #pragma unroll
@@ -46,20 +38,30 @@ for (int nt = 0; nt < NPT; ++nt) {
     const int n = nt * 16 + (lane & 15);
     wtf[nt] = n < 9 * COUT ? *reinterpret_cast<const f32x4*>(p.wt + (size_t)n * 16 + 4 * (lane >> 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
-const int kch = CXP >> 4;
-// deconv weights: wave w owns output parity (dy,dx) = (w>>1, w&1); B operand of k-chunk kc, MFMA j is
-// Wd[n = w*16 + (lane&15)][16*kc + 4*(lane>>4) + j]
-f32x4 wd[KCH_MAX];
+// Composed transposed conv + conv_a (DESIGN.md 4.3): wave w computes the conv_a pixels of parity (py, px) = (w >> 1, w & 1); position
+// (i, j) of that class (9 x 9 per tile) is conv_a pixel (2i + 1 - py, 2j + 1 - px) of the 18 x 18 tile and reads the 2 x 2 window of X
+// tile pixels (i + a, j + b).  K order: the score k-step (if any), then descriptor group g = 0 .. ng-1, channel 4g + e, e = 0..3; in every
+// k-step the lanes of quarter q = lane >> 4 read window (a, b) = (q >> 1, q & 1).  The weights are the A operand: lane = output channel
+// lane & 15 of window q; the accumulator of a lane holds channels 4 (lane >> 4) .. + 3 of ONE position.
+constexpr bool NG_RT = NG == 0;        // generic form: up to 16 groups, guarded (the width classes of the real variants are exact)
+constexpr int NGR = NG_RT ? 16 : NG;   // register slots for the descriptor groups
+const int ng = NG_RT ? p.ng : NG;
+const bool score = NG_RT ? p.score != 0 : SCORE != 0;
+const float wsc = score ? p.ws[wave * 64 + lane] : 0.f;
+f32x4 wg[NGR];
 #pragma unroll
-for (int kc = 0; kc < KCH_MAX; ++kc)
-    wd[kc] = kc < kch ? *reinterpret_cast<const f32x4*>(p.wd + (size_t)(wave * 16 + (lane & 15)) * CXP + kc * 16 + 4 * (lane >> 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
-// conv_a weights for this lane: B operand of MFMA j at tap t is Wa[n = lane&15][t*16 + 4*(lane>>4) + j]
-f32x4 wa[9];
+for (int g = 0; g < NGR; ++g)
+    wg[g] = g < ng ? *reinterpret_cast<const f32x4*>(p.wc + ((size_t)(wave * ng + g) * 64 + lane) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+const f32x4 bint = *reinterpret_cast<const f32x4*>(p.bc + 4 * (lane >> 4));   // interior bias (table row 0)
+const int py = wave >> 1, px = wave & 1;
+int xoff[NMT1], pq[NMT1];   // per m-tile: this lane's X read offset (window q) and the P tile pixel of its accumulator column
 #pragma unroll
-for (int t = 0; t < 9; ++t) wa[t] = *reinterpret_cast<const f32x4*>(p.wa + (size_t)(lane & 15) * 144 + t * 16 + 4 * (lane >> 4));
-// channel-major accumulators (weights are the A operand of the MFMAs): a lane holds channels 4 (lane >> 4) .. + 3 of ONE pixel
-const f32x4 bd = *reinterpret_cast<const f32x4*>(p.bd + 4 * (lane >> 4));
-const f32x4 ba = *reinterpret_cast<const f32x4*>(p.ba + 4 * (lane >> 4));
+for (int mt = 0; mt < NMT1; ++mt) {
+    const int pos = min(mt * 16 + (lane & 15), NPOS - 1);     // padding lanes of the last m-tile read a real position
+    const int i = pos / 9, j = pos % 9;
+    xoff[mt] = ((i + ((lane >> 4) >> 1)) * XT + j + ((lane >> 4) & 1)) * XS + p.c0;
+    pq[mt] = mt * 16 + (lane & 15) < NPOS ? (2 * i + 1 - py) * AT + 2 * j + 1 - px : -1;   // -1: padding lane, nothing stored
+}
 
 // X tile staging: float4 item i = tid + it*256 -> pixel i / c4n, channels 4*(i % c4n)
 const int c4n = CXP >> 2;
@@ -68,10 +70,10 @@ int x_lds[XI_MAX], x_rc[XI_MAX];   // LDS float offset (-1: no item), (row << 8 
 #pragma unroll
 for (int it = 0; it < XI_MAX; ++it) {
     const int i = tid + it * 256;
-    const int px = i / c4n, c4 = i - px * c4n;
+    const int px_ = i / c4n, c4 = i - px_ * c4n;
     const bool live = i < XT * XT * c4n;
-    x_lds[it] = live ? px * XS + c4 * 4 : -1;
-    x_rc[it] = ((px / XT) << 8) | (px % XT) | ((c4 * 4 < p.cx ? c4 * 4 : 0x7fff) << 16);
+    x_lds[it] = live ? px_ * XS + c4 * 4 : -1;
+    x_rc[it] = ((px_ / XT) << 8) | (px_ % XT) | ((c4 * 4 < p.cx ? c4 * 4 : 0x7fff) << 16);
 }
 f32x4 xv[XI_MAX];
 #define CCVPE_L1_LOAD_X(tl)                                                                              \
@@ -91,7 +93,6 @@ CCVPE_L1_LOAD_X(tile);
 
 const int oy = tid >> 4, ox = tid & 15;      // stage 3: one output pixel per thread
 const size_t hw = (size_t)H * W;
-constexpr int NMT = (AT * AT + 15) / 16;   // 21
 
 #if CCVPE_L1_CLOCK
 unsigned long long clk[7] = {0, 0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
@@ -116,129 +117,59 @@ while (true) {
     const bool have_n = tile_n < t_end;
     if (have_n) { CCVPE_L1_LOAD_X(tile_n); }
 
-    // ---- stage 1: transposed conv as GEMM [100 x CXP] x [CXP x 64]; unit = (m-tile, (dy,dx)) ----
-    // two independent accumulator chains per wave (m-tiles mt and mt+1) hide the dependent-MFMA latency
-    {
-        const int dy = wave >> 1, dx = wave & 1;
-        float* dsub = Ds + (dy * DT + dx) * PS + 4 * (lane >> 4);
-        for (int mt0 = 0; mt0 < 7; mt0 += 2) {
-            const int mt1 = mt0 + 1;               // may be 7 (invalid): computed on clamped rows, never stored
-            const float* ap0 = Xs + min(mt0 * 16 + (lane & 15), XT * XT - 1) * XS + 4 * (lane >> 4);
-            const float* ap1 = Xs + min(mt1 * 16 + (lane & 15), XT * XT - 1) * XS + 4 * (lane >> 4);
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-            if (mt1 < 7) {
+    // ---- stage 1: conv_a of this wave's parity class as one GEMM [81 x K] x [K x 16], K = 4 (score + 4 ng): six independent chains ----
+    f32x4 acc[NMT1];
 #pragma unroll
-                for (int kc = 0; kc < KCH_MAX; ++kc) {
-                    if (kc >= kch) break;
-                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap0 + kc * 16);
-                    const f32x4 a1 = *reinterpret_cast<const f32x4*>(ap1 + kc * 16);
-                    const f32x4 w = wd[kc];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a0.x, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a1.x, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a0.y, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a1.y, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a0.z, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a1.z, acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a0.w, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a1.w, acc1, 0, 0, 0);
-                }
-            } else {   // the seventh m-tile has no partner: one chain
+    for (int mt = 0; mt < NMT1; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (score) {
 #pragma unroll
-                for (int kc = 0; kc < KCH_MAX; ++kc) {
-                    if (kc >= kch) break;
-                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(ap0 + kc * 16);
-                    const f32x4 w = wd[kc];
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a0.x, acc0, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a0.y, acc0, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a0.z, acc0, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a0.w, acc0, 0, 0, 0);
-                }
-            }
+        for (int mt = 0; mt < NMT1; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wsc, Xs[xoff[mt] - p.c0], acc[mt], 0, 0, 0);
+    }
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                const int mt = h2 ? mt1 : mt0;
-                if (mt >= 7) continue;
-                const f32x4 acc = h2 ? acc1 : acc0;
-                const int px = mt * 16 + (lane & 15);           // X pixel of this lane's accumulator (>= 100: sink row)
-                const int dto = dtab[px];
-                if (interior) {
-                    *reinterpret_cast<f32x4*>(dsub + dto) = acc + bd;
-                } else if (px < XT * XT) {
-                    const int dr = 2 * (px / XT) + dy, dc = 2 * (px % XT) + dx;          // position in the D tile
-                    const int gy = Y0 - 2 + dr, gx = X0 - 2 + dc;                        // position in the image
-                    const bool in = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-                    *reinterpret_cast<f32x4*>(dsub + dto) = in ? acc + bd : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            }
+    for (int g = 0; g < NGR; ++g) {
+        if (!NG_RT || g < ng) {   // (a guard, not a break: the loop must unroll fully so that wg stays in registers)
+            f32x4 a[NMT1];
+#pragma unroll
+            for (int mt = 0; mt < NMT1; ++mt) a[mt] = *reinterpret_cast<const f32x4*>(Xs + xoff[mt] + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int mt = 0; mt < NMT1; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wg[g][e], a[mt][e], acc[mt], 0, 0, 0);
         }
     }
     CCVPE_L1_STAMP(1);
-    __syncthreads();
-    CCVPE_L1_STAMP(2);
 
-    // ---- stage 2: conv3x3 16->16 + ReLU on the 18x18 halo tile: 21 m-tiles of 16 pixels, 36 MFMAs each ----
-    for (int mt0 = wave; mt0 < NMT; mt0 += 8) {
-        const int mt1 = mt0 + 4;                   // second chain (may be >= NMT: clamped reads, no stores)
-        const int pa0 = min(mt0 * 16 + (lane & 15), AT * AT - 1);
-        const int pa1 = min(mt1 * 16 + (lane & 15), AT * AT - 1);
-        const float* dp0 = Ds + ((pa0 / AT) * DT + pa0 % AT) * PS + 4 * (lane >> 4);
-        const float* dp1 = Ds + ((pa1 / AT) * DT + pa1 % AT) * PS + 4 * (lane >> 4);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        if (mt1 < NMT) {
+    // ---- stage 2: bias (by border case) + ReLU + zero outside the image, then the tail conv's per-tap products into the P tile ----
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int toff = ((t / 3) * DT + (t % 3)) * PS;
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(dp0 + toff);
-                const f32x4 a1 = *reinterpret_cast<const f32x4*>(dp1 + toff);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].x, a0.x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].x, a1.x, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].y, a0.y, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].y, a1.y, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].z, a0.z, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].z, a1.z, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].w, a0.w, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].w, a1.w, acc1, 0, 0, 0);
-            }
-        } else {   // the last m-tile of a wave has no partner (21 m-tiles over 4 waves x 2 chains): one chain, no padding MFMAs
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int toff = ((t / 3) * DT + (t % 3)) * PS;
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(dp0 + toff);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].x, a0.x, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].y, a0.y, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].z, a0.z, acc0, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t].w, a0.w, acc0, 0, 0, 0);
-            }
+    for (int mt = 0; mt < NMT1; ++mt) {
+        const int q = max(pq[mt], 0);                               // P pixel of this lane's accumulator column
+        f32x4 v;
+        if (interior) {
+            v = acc[mt] + bint;
+        } else {
+            const int gy = Y0 - 1 + q / AT, gx = X0 - 1 + q % AT;
+            const int bcase = (gy == 0 ? 3 : gy == H - 1 ? 6 : 0) + (gx == 0 ? 1 : gx == W - 1 ? 2 : 0);
+            v = acc[mt] + *reinterpret_cast<const f32x4*>(p.bc + bcase * 16 + 4 * (lane >> 4));
+            if (!((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W)) v = f32x4{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int mt = h2 ? mt1 : mt0;
-            if (mt >= NMT) continue;
-            const f32x4 acc = h2 ? acc1 : acc0;
-            const int q = mt * 16 + (lane & 15);                // A pixel of this lane's accumulator (>= 324: sink row)
-            f32x4 v = acc + ba;
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+        // the last conv's per-tap dot products of this pixel: v is the B operand as it stands
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-            if (!interior) {
-                const int gy = Y0 - 1 + q / AT, gx = X0 - 1 + q % AT;
-                const bool in = q < AT * AT && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-                if (!in) v = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            // the last conv's per-tap dot products of this pixel: v is the B operand as it stands
+        for (int nt = 0; nt < NPT; ++nt) {
+            f32x4 pa = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int nt = 0; nt < NPT; ++nt) {
-                f32x4 pa = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pa = __builtin_amdgcn_mfma_f32_16x16x4f32(wtf[nt][e], v[e], pa, 0, 0, 0);
-                // columns 16 nt + 4 (lane >> 4) .. + 3 of pixel q; 9 COUT <= 18 columns are real: the second tile keeps two
-                if (nt == 0) *reinterpret_cast<f32x4*>(As + q * PS + 4 * (lane >> 4)) = pa;
-                else if ((lane >> 4) == 0) *reinterpret_cast<f32x2*>(As + q * PS + 16) = f32x2{pa[0], pa[1]};
+            for (int e = 0; e < 4; ++e) pa = __builtin_amdgcn_mfma_f32_16x16x4f32(wtf[nt][e], v[e], pa, 0, 0, 0);
+            // columns 16 nt + 4 (lane >> 4) .. + 3 of pixel q; 9 COUT <= 18 columns are real: the second tile keeps two
+            if (pq[mt] >= 0) {
+                if (nt == 0) *reinterpret_cast<f32x4*>(Ps + q * PS + 4 * (lane >> 4)) = pa;
+                else if ((lane >> 4) == 0) *reinterpret_cast<f32x2*>(Ps + q * PS + 16) = f32x2{pa[0], pa[1]};
             }
         }
     }
-    CCVPE_L1_STAMP(3);
+    CCVPE_L1_STAMP(2);
     __syncthreads();
-    CCVPE_L1_STAMP(4);
+    CCVPE_L1_STAMP(3);
 
     // ---- stage 3: out = bias + the nine taps' dot products of the shifted pixels, one output pixel per thread, NCHW store ----
     float o[COUT];
@@ -246,7 +177,7 @@ while (true) {
     for (int c = 0; c < COUT; ++c) o[c] = p.bt[c];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        const float* pp = As + ((oy + t / 3) * AT + ox + t % 3) * PS + t * COUT;
+        const float* pp = Ps + ((oy + t / 3) * AT + ox + t % 3) * PS + t * COUT;
         if (COUT == 2) { const f32x2 v = *reinterpret_cast<const f32x2*>(pp); o[0] += v.x; o[COUT - 1] += v.y; }
         else o[0] += pp[0];
     }
@@ -275,10 +206,10 @@ while (true) {
 #pragma unroll
     for (int c = 0; c < COUT; ++c) p.out[((size_t)b * COUT + c) * hw + opix] = o[c];
 
-    CCVPE_L1_STAMP(5);
+    CCVPE_L1_STAMP(4);
     if (!have_n) break;
-    __syncthreads();   // the A tile (aliasing Xs) is fully consumed before the next X tile lands
-    CCVPE_L1_STAMP(6);
+    // (no barrier: the next tile's X stores follow every wave's stage-1 reads of this tile across the barrier above, and its P stores
+    // follow the stage-3 reads of this tile across the barrier behind stage 0)
     tile = tile_n;
 }
 #if CCVPE_L1_CLOCK
