@@ -359,3 +359,70 @@ def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
             orientation_angle = orientation_angle + 360
         heading[b] = orientation_angle
     return {"gt_index": idx, "gt_cos_sin": _cos_sin_f32(heading), "heading_deg": heading}
+
+
+# ---- tracking a frame stream ------------------------------------------------------------------------------------
+
+def gaussian_taps(sigma_px, radius: int) -> np.ndarray:
+    """One-sided blur weights for model.track_predict: float32 [radius+1] (sigma_px a number) or [B, radius+1] (sigma_px [B]),
+    t[i] = exp(-0.5 i^2 / sigma^2) / Z with Z the sum over i = -radius..radius, so the two-sided filter sums to 1 (evaluated in
+    float64, rounded once to float32)."""
+    r = int(radius)
+    if not 0 <= r <= 32:
+        raise ValueError(f"radius must be in 0..32, got {radius}")
+    scalar = np.ndim(sigma_px) == 0
+    sig = _sigma(sigma_px, 1 if scalar else np.asarray(sigma_px).reshape(-1).shape[0])
+    i = np.arange(r + 1, dtype=np.float64)
+    w = np.exp(-0.5 * i[None, :] ** 2 / sig[:, None] ** 2)
+    w /= w[:, :1] + 2.0 * w[:, 1:].sum(axis=1, keepdims=True)
+    w = w.astype(np.float32)
+    return w[0] if scalar else w
+
+
+def oxford_track_shift(origin_prev, origin_next, motion_map_px) -> np.ndarray:
+    """The shift (dx, dy) in OUTPUT pixels, float64 [B,2], that carries a belief over the window at origin_prev = (x0, y0) into the
+    window at origin_next after the vehicle moved by motion_map_px = (d col, d row) MAP pixels (each [2] or [B,2]).  Both 800-px
+    windows are resized to 512, so one scale serves: (origin_prev - origin_next + motion) * 512 / 800 - the inverse convention of
+    oxford_region_to_map, so a map point keeps its map position when the window changes."""
+    a = np.asarray(origin_prev, dtype=np.float64).reshape(-1, 2)
+    b = np.asarray(origin_next, dtype=np.float64).reshape(-1, 2)
+    m = np.asarray(motion_map_px, dtype=np.float64).reshape(-1, 2)
+    B = max(a.shape[0], b.shape[0], m.shape[0])
+    for what, v in (("origin_prev", a), ("origin_next", b), ("motion_map_px", m)):
+        if v.shape[0] not in (1, B):
+            raise ValueError(f"{what} must hold 1 or {B} rows, got {v.shape[0]}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"{what} must be finite")
+    return (a - b + m) * (SAT_HW / OXFORD_WIN) + np.zeros((B, 2))
+
+
+class Tracker:
+    """A histogram filter over the Oxford windows, host side: holds the posterior map of the last frame (a device tensor
+    [B,512,512]) and the window origin it lives in.  step() = model.track_predict (the last posterior moved into this frame's
+    window by the odometry, blurred, floored) + model.track_update_cached (this frame's posterior); the first step has no prior."""
+
+    def __init__(self):
+        self.belief = None    # posterior of the last frame, or None before the first step
+        self.origin = None    # [B,2] int64 window origin (x0, y0) of each query's belief
+
+    def reset(self) -> None:
+        self.belief = None
+        self.origin = None
+
+    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor):
+        """One frame of B parallel streams.  cache / tile_index: as model.localize_cached; origins [T,2]: the crop origin of every
+        cached tile (oxford_tiles' "origin"; one per query when tile_index is None); motion_map_px [B,2] or [2]: the motion since
+        the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5]."""
+        org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+        B = grd.shape[0]
+        now = org if tile_index is None else org[np.asarray(tile_index, dtype=np.int64)]
+        if now.shape[0] != B:
+            raise ValueError(f"origins must name one window per query: {B} expected, got {now.shape[0]}")
+        prior = None
+        if self.belief is not None:
+            if self.belief.shape[0] != B:
+                raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
+            prior = model.track_predict(self.belief, oxford_track_shift(self.origin, now, motion_map_px), taps, floor)
+        rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
+        self.origin = now.copy()
+        return rows

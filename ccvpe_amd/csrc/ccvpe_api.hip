@@ -257,11 +257,12 @@ static int micro_batch_cap(ccvpe_handle h, int gh, int gw) {
 
 // rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read);
 // topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller);
-// log_prior != null: the pose plans of ccvpe_localize_prior* - every slice reads its own maps (prior_stride checked by the caller)
+// log_prior != null: the pose plans of ccvpe_localize_prior* - every slice reads its own maps (prior_stride checked by the caller);
+// posterior != null (argmax pose plans): ccvpe_track_update* - every slice also writes its own posterior maps
 static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
                        const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr,
                        int topk_k = 0, int topk_r = 0, const int32_t* tile_index = nullptr, int n_tiles = 0,
-                       const float* log_prior = nullptr, long long prior_stride = 0) {
+                       const float* log_prior = nullptr, long long prior_stride = 0, float* posterior = nullptr) {
     const int mode = cache ? 2 : 0;
     const bool pose = rows != nullptr;
     const bool topk = pose && topk_k > 0;
@@ -301,6 +302,7 @@ static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const f
         c.grd = grd + (size_t)done * 3 * gh * gw;
         c.sat = sat ? sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
         if (log_prior) { c.log_prior = log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
+        if (posterior) c.posterior = posterior + (size_t)done * npx;
         if (topk) {
             c.rows = rows + (size_t)done * topk_k * 5;
             c.topk_k = topk_k; c.topk_r = topk_r;
@@ -898,6 +900,107 @@ int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n
     if (int rc = check_prior_args(pair_log_prior, prior_stride, 0, 0)) return rc;
     return run_region(h, grd_cache, n_queries, grd_h, grd_w, sat_cache, n_tiles, offsets, tiles, rows, best_pair, pair_rows, pair_stats,
                       tile_prob, stream, pair_log_prior, prior_stride);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tracking a frame stream.  Update: the argmax pose plans of ccvpe_localize_prior* with the posterior map as a second
+// output of pose.argmax - no launch of their own.  Predict: one launch of track_predict_kernel, no plan and no tuning entry.
+// ------------------------------------------------------------------------------------------------
+// log_prior may be null (the map is then the forward's heatmap); the stride is checked only beside a prior
+static int check_track_update_args(const float* log_prior, int64_t prior_stride, const float* rows, const float* posterior) {
+    const int64_t n = (int64_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!posterior) return ccvpe_fail(CCVPE_EINVAL, "null posterior");
+    if (log_prior && prior_stride != 0 && prior_stride != n)
+        return ccvpe_fail(CCVPE_EINVAL, "prior_stride must be 0 (one shared map) or %lld (one map per query), got %lld", (long long)n,
+                          (long long)prior_stride);
+    if (log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    return 0;
+}
+
+int ccvpe_track_update(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                       const float* log_prior, int64_t prior_stride, float* rows, float* posterior, void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, 0, 0, nullptr, 0, log_prior,
+                       log_prior ? prior_stride : 0, posterior);
+}
+
+int ccvpe_track_update_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                      const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride, float* rows,
+                                      float* posterior, void* stream) {
+    if (tile_index) {
+        if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    } else {   // query b reads tile b, as ccvpe_localize_prior_cached_indexed
+        if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+        if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+        if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+        if (n_tiles != batch)
+            return ccvpe_fail(CCVPE_EINVAL, "without tile_index the cache holds one tile per query: n_tiles %d != batch %d", n_tiles, batch);
+    }
+    if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, 0, 0,
+                       tile_index, tile_index ? n_tiles : 0, log_prior, log_prior ? prior_stride : 0, posterior);
+}
+
+int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, float* rows, float* posterior, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
+    if (posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_prior_scratch(h, batch)) return rc;
+    const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
+    const int cap = h->prior_batch;   // the layout of ccvpe_postprocess_prior's scratch
+    unsigned char* base = reinterpret_cast<unsigned char*>(h->prior_scratch);
+    unsigned* tickets = reinterpret_cast<unsigned*>(base);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
+    int* index = reinterpret_cast<int*>(keys + (size_t)cap * 64 * TOPK_MAX_K);
+    float* partial = reinterpret_cast<float*>(index + (size_t)cap * TOPK_MAX_K);
+    hipStream_t s = (hipStream_t)stream;
+    SoftmaxParams sp{};
+    sp.logits = logits; sp.B = batch; sp.n = n; sp.partial = partial; sp.chunks = 64; sp.out = nullptr;
+    sp.prior = log_prior; sp.prior_stride = log_prior ? prior_stride : 0;
+    launch_softmax_partial(sp, s);
+    PoseArgmaxParams p{};
+    p.logits = logits; p.partial = partial; p.B = batch; p.n = n; p.chunks = 64;
+    p.pairs = reinterpret_cast<float*>(keys); p.tickets = tickets; p.index = index; p.rows = rows; p.stats = nullptr;
+    p.prior = log_prior; p.prior_stride = sp.prior_stride; p.posterior = posterior;
+    launch_pose_argmax(p, s);
+    launch_pose_gather(ori, index, batch, n, rows, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "track_update_logits launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps, int32_t taps_stride,
+                        int32_t radius, const float* floor, float* log_prior, void* stream) {
+    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
+    if (!shift) return ccvpe_fail(CCVPE_EINVAL, "null shift");
+    if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
+    if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
+    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
+    if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
+    if (taps_stride != 0 && taps_stride != radius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
+                          taps_stride);
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (log_prior == belief) return ccvpe_fail(CCVPE_EINVAL, "log_prior must not alias belief");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackPredictParams p{};
+    p.belief = belief; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
+    p.log_prior = log_prior; p.B = batch;
+    launch_track_predict(p, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "track_predict launch failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

@@ -247,6 +247,7 @@ struct Ctx {
     float* stats = nullptr;            // pose plans: optional [B][2] softmax (max, 1/sum) of each sample (pose_argmax_kernel)
     const float* log_prior = nullptr;  // pose plans: optional log-prior of this micro-batch's first sample ...
     long long prior_stride = 0;        // ... and the floats between two samples' maps (0: one map for all)
+    float* posterior = nullptr;        // pose plans: optional posterior map [mb][512*512] of this micro-batch (ccvpe_track_update*)
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)

@@ -638,7 +638,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
             p.pairs = c.ptr(pairs); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
-            p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride;
+            p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.posterior = c.posterior;
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
     } else {

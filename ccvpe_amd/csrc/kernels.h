@@ -379,6 +379,8 @@ struct PoseArgmaxParams {
     float* stats;              // optional [B][2]: the sample's softmax (max, 1/sum), written by workgroup (0, b) (ccvpe_localize_region)
     const float* prior;        // optional log-prior as SoftmaxParams::prior (the partials must be of the same sums).  A sample whose
     long long prior_stride;    //   (max, 1/sum) is not finite gets index 0 and rows (-1, NaN)
+    float* posterior;          // optional [B][n] (ccvpe_track_update*): the heatmap of l' the chunks recompute, stored as
+                               //   float4; all zeros (and the row (-1, NaN)) for a sample whose (max, 1/sum) is not finite
 };
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
@@ -471,6 +473,22 @@ struct RegionParams {
 };
 void launch_region_reduce(const float* stats, const float* pair_rows, const int* offsets, int G, float* rows, int* best_pair, float* tile_prob,
                           hipStream_t s);
+
+// Motion update of a position belief (ccvpe_track_predict, DESIGN.md 4.11, kernels_track.hip): per query the belief [512][512], zero
+// outside, moved by (dx, dy) with bilinear weights, blurred along x then y with the symmetric taps t[|i|], i = -radius..radius, and
+// log_prior = logf(that + floor[b]).  One launch, grid (256 tiles of 32 x 32, B).
+static constexpr int TRACK_MAX_R = 32;
+struct TrackPredictParams {
+    const float* belief;       // [B][512*512]
+    const float* shift;        // [B][2] = (dx, dy) in output pixels
+    const float* taps;         // [radius + 1] one-sided weights, one set (taps_stride 0) or one per query (taps_stride radius + 1)
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0, added before the logarithm
+    float* log_prior;          // [B][512*512], not aliasing belief
+    int B;
+};
+void launch_track_predict(const TrackPredictParams& p, hipStream_t s);
 
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call

@@ -262,8 +262,11 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
 // PRIOR: the values are those of l' = fl32(l + prior), with softmax_partial_kernel<true>'s statistics.  A sample whose
 // (m, inv) is not finite (a prior of -inf everywhere, a +inf, a NaN) has no posterior: rows (-1, NaN) and index 0, so that the
 // orientation launches behind still read inside the map.
+// POST (ccvpe_track_update*): the values the chunk has just recomputed are also stored, as float4, to posterior[b] - the
+// map softmax_final_kernel would store for l'.  Every workgroup knows (m, inv), so each applies the rule for a sample without a finite
+// posterior to its own chunk: all zeros.
 // ------------------------------------------------------------------------------------------------
-template <bool PRIOR>
+template <bool PRIOR, bool POST = false>
 __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams p) {
     __shared__ float gm, gs;
     __shared__ float sv[4];
@@ -296,6 +299,15 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
         const int e = lo + (threadIdx.x + u * 256) * 4;
         take(v[u].x, e); take(v[u].y, e + 1); take(v[u].z, e + 2); take(v[u].w, e + 3);
     }
+    if constexpr (POST) {
+        float4* dst = reinterpret_cast<float4*>(p.posterior + (size_t)b * p.n + lo);
+        const bool fin = isfinite(m) && isfinite(inv);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {   // take()'s expression: the bits rows[b][1] carries at the argmax
+            const float4 h = make_float4(__expf(v[u].x - m) * inv, __expf(v[u].y - m) * inv, __expf(v[u].z - m) * inv, __expf(v[u].w - m) * inv);
+            dst[threadIdx.x + u * 256] = fin ? h : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const float v2 = __shfl_xor(best, off);
@@ -325,7 +337,7 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
         }
         if (threadIdx.x == 0) {
-            if constexpr (PRIOR) {
+            if constexpr (PRIOR || POST) {
                 if (!(isfinite(m) && isfinite(inv))) { p.index[b] = 0; p.rows[b * 5 + 0] = -1.f; p.rows[b * 5 + 1] = NAN; return; }
             }
             p.index[b] = bi;
@@ -336,7 +348,9 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
 }
 
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s) {
-    if (p.prior) CCVPE_LAUNCH(pose_argmax_kernel<true>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    if (p.posterior && p.prior) CCVPE_LAUNCH((pose_argmax_kernel<true, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    else if (p.posterior) CCVPE_LAUNCH((pose_argmax_kernel<false, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+    else if (p.prior) CCVPE_LAUNCH(pose_argmax_kernel<true>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
     else CCVPE_LAUNCH(pose_argmax_kernel<false>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
 }
 

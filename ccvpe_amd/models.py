@@ -716,6 +716,157 @@ class _CVMBase(nn.Module):
         self._tuning_sync()
         return {"rows": rows, "pair": pair, "pair_tile": flat, "pair_rows": pair_rows, "pair_stats": pair_stats, "tile_prob": tile_prob}
 
+    # ---- tracking a frame stream ----------------------------------------------
+    @classmethod
+    def _track_prior(cls, log_prior, B: int):
+        """log_prior of the update forms -> (tensor or None, prior_stride): None means no prior, anything else is checked as
+        localize_prior checks it."""
+        if log_prior is None:
+            return None, 0
+        lp, stride, _, _ = cls._prior_args(log_prior, B, 0, 0)
+        return lp, stride
+
+    def track_update(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None):
+        """The update half of a filter step: (rows [B, 5], posterior [B, 512, 512]).  rows are localize_prior(grd, sat, log_prior)'s,
+        posterior is the map they are the argmax of - softmax(logits + log_prior) in the pixel order of the logits, with the bits of
+        rows[b, 1] at rows[b, 0]; log_prior=None: the forward's heatmap.  A query without a finite posterior gets the row (-1, NaN, ..)
+        and an all-zero map (ccvpe_track_update)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        lp, stride = self._track_prior(log_prior, grd.shape[0])
+        grd, sat = self._prepare(grd, sat)
+        if lp is not None and lp.device != grd.device:
+            raise ValueError("log_prior must be on the inputs' device")
+        B = grd.shape[0]
+        with torch.cuda.device(grd.device):
+            rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
+            post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=grd.device)
+            stream = torch.cuda.current_stream(grd.device).cuda_stream
+            rc = _lib.load().ccvpe_track_update(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                C.c_void_p(sat.data_ptr()), B, C.c_void_p(lp.data_ptr()) if lp is not None else None,
+                                                stride, C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_track_update")
+        self._tuning_sync()
+        return rows, post
+
+    def track_update_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, tile_index=None):
+        """track_update(grd, sat, log_prior) with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
+        (ccvpe_track_update_cached_indexed)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        idx = self._host_tile_index(tile_index, grd)
+        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        lp, stride = self._track_prior(log_prior, grd.shape[0])
+        if lp is not None and lp.device != grd.device:
+            raise ValueError("log_prior must be on the inputs' device")
+        grd = grd.detach().to(torch.float32).contiguous()
+        self._ensure_handle(grd.device)
+        B = grd.shape[0]
+        n_tiles = self._cache_tiles(cache, B, idx)
+        rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
+        post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=grd.device)
+        stream = torch.cuda.current_stream(grd.device).cuda_stream
+        rc = _lib.load().ccvpe_track_update_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
+                                                           C.c_void_p(cache.data_ptr()), n_tiles,
+                                                           idx.ctypes.data_as(C.c_void_p) if idx is not None else None, B,
+                                                           C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
+                                                           C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_track_update_cached_indexed")
+        self._tuning_sync()
+        return rows, post
+
+    def track_update_logits(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None):
+        """track_update from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
+        ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_track_update_logits)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        B = logits.shape[0] if logits.dim() > 0 else 0
+        if logits.numel() != B * self.PRIOR_MAP or ori.numel() != B * 2 * self.PRIOR_MAP or B == 0:
+            raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
+        lp, stride = self._track_prior(log_prior, B)
+        if not (logits.is_cuda and ori.is_cuda):
+            raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
+        if not (logits.device == ori.device and (lp is None or lp.device == logits.device)):
+            raise ValueError("logits, ori and log_prior must be on one device")
+        logits = logits.detach().to(torch.float32).contiguous()
+        ori = ori.detach().to(torch.float32).contiguous()
+        self._ensure_handle(logits.device)
+        rows = torch.empty((B, 5), dtype=torch.float32, device=logits.device)
+        post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=logits.device)
+        stream = torch.cuda.current_stream(logits.device).cuda_stream
+        rc = _lib.load().ccvpe_track_update_logits(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B,
+                                                   C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
+                                                   C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_track_update_logits")
+        return rows, post
+
+    @staticmethod
+    def _track_vec(value, what: str, shape, dev):
+        """A small per-query argument of track_predict -> contiguous float32 tensor of `shape` on dev.  Host data (numbers, sequences,
+        numpy arrays, CPU tensors) is copied up; a tensor already on the device is used as it is (no synchronisation either way)."""
+        if isinstance(value, torch.Tensor):
+            t = value.detach()
+            if t.dtype != torch.float32:
+                if t.is_floating_point() or t.device.type == "cpu":
+                    t = t.to(torch.float32)
+                else:
+                    raise ValueError(f"{what} must hold floats, got {t.dtype}")
+        else:
+            t = torch.as_tensor(np.asarray(value, dtype=np.float32))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t.to(dev).contiguous()
+
+    def track_predict(self, belief: torch.Tensor, shift_px, taps, floor) -> torch.Tensor:
+        """The predict half of a filter step: the log-prior [B, 512, 512] of the next frame from a posterior map.  belief [B,512,512]
+        (track_update's map) is extended by zero, moved by shift_px [B,2] = (dx, dy) output pixels with bilinear weights, blurred
+        along x and y with the one-sided taps t[0..radius] ([radius+1] for every query or [B, radius+1]; aerial.gaussian_taps), and
+        the result is log(. + floor), floor a number or [B], >= 0: the definition in include/ccvpe.h (ccvpe_track_predict).  One
+        launch.  shift_px, taps and floor may be host data or tensors on the belief's device."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(belief, torch.Tensor):
+            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
+        shape = tuple(belief.shape)
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
+                                                                                       and shape[2:] == spec.OUT_HW):
+            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
+        if belief.dtype != torch.float32:
+            raise ValueError(f"belief must be float32, got {belief.dtype}")
+        if not belief.is_contiguous():
+            raise ValueError("belief must be contiguous")
+        B = shape[0]
+        if B > 4096:
+            raise ValueError(f"belief holds {B} maps, at most 4096 per call")
+        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
+        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
+            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
+        radius = int(tshape[-1]) - 1
+        if radius > 32:
+            raise ValueError(f"taps give radius {radius}, must be in 0..32")
+        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
+        if fshape == () and not float(floor) >= 0.0:
+            raise ValueError(f"floor must be >= 0, got {floor}")
+        dev = belief.device
+        host = torch.device("cpu")
+        # shapes and values first (so that they are refused without a device), then the copies
+        sh = self._track_vec(shift_px, "shift_px", (B, 2), host if not belief.is_cuda else dev)
+        tp = self._track_vec(taps, "taps", tshape, host if not belief.is_cuda else dev)
+        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
+              else self._track_vec(floor, "floor", (B,), dev))
+        if not belief.is_cuda:
+            raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+        self._ensure_handle(dev)
+        out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = _lib.load().ccvpe_track_predict(self._handle, C.c_void_p(belief.data_ptr()), B, C.c_void_p(sh.data_ptr()),
+                                                 C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
+                                                 C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_track_predict")
+        return out
+
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Device-side version of the per-sample loop in train_VIGOR.py:297-316."""

@@ -305,6 +305,41 @@ int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n
                                 const float* pair_log_prior, int64_t prior_stride, float* rows, int32_t* best_pair,
                                 float* pair_rows, float* pair_stats, float* tile_prob, void* stream);
 
+/* Tracking a frame stream: a recursive Bayes (histogram) filter over the 512 x 512 position grid, one step per frame =
+ * ccvpe_track_predict (the previous posterior -> this frame's log-prior) + ccvpe_track_update* (this frame's posterior).
+ *
+ * Update.  rows [batch][5] are exactly the k == 0 rows of ccvpe_localize_prior / ccvpe_localize_prior_cached_indexed /
+ * ccvpe_postprocess_prior for the same arguments.  `posterior` is float32 DEVICE memory [batch][512*512] in the pixel order of
+ * logits_flattened and receives h' = __expf(l' - m') * inv' of the definition above - the bits rows[b][1] carries at
+ * rows[b][0].  log_prior may be NULL (prior_stride is then ignored): l' = l and the map is ccvpe_forward's heatmap.  A query
+ * without a finite posterior keeps the row (-1, NaN, ...) and gets an all-zero map, so that with a positive floor the next
+ * predicted prior is flat and the filter starts over instead of spreading NaN.  No launch is added to the pose plans: the map
+ * is stored by the launch that finds the argmax.  CCVPE_EINVAL, nothing launched, checked before the handle is used: the
+ * checks of the matching prior form (a null log_prior excepted), a null posterior, a posterior that is log_prior or logits. */
+int ccvpe_track_update(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                       const float* log_prior, int64_t prior_stride, float* rows, float* posterior, void* stream);
+int ccvpe_track_update_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                      int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                      int64_t prior_stride, float* rows, float* posterior, void* stream);
+int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, float* rows, float* posterior, void* stream);
+/* Predict.  All pointers DEVICE float32: belief [batch][512*512] (a posterior map), shift [batch][2] = (dx, dy) in output
+ * pixels, taps the one-sided blur weights t[0..radius] (taps_stride 0: one set for every query; radius + 1: one per query),
+ * radius 0..32, floor [batch] >= 0, log_prior [batch][512*512] out (must not alias belief).  Per query, with the belief extended
+ * by zero outside its grid, on the infinite plane
+ *     s(x, y)   = bilinear sample of the belief at (x - dx, y - dy)             the content moves by (+dx, +dy)
+ *     c         = s convolved with t[|i|], i = -radius..radius, along x, then along y
+ *     out(x, y) = logf(c(x, y) + floor)                                          for the 512 x 512 window only
+ * Mass that leaves the window is lost; floor stands for it (and for a relocalisation probability).  floor = 0 and c = 0 give
+ * -inf, which the prior forms read as "pixel excluded".  A fractional part of exactly 0 weighs the one source pixel with
+ * exactly 1.  The bilinear weights are folded into the two passes (every term is non-negative; a pass is 2 radius + 2 fused
+ * multiply-adds), so c is within a relative (4 radius + 12) * 2^-24 of the exact value.  NaN / inf shifts may give NaN, but no
+ * launch reads outside its tensors whatever the inputs hold.  One launch.  CCVPE_EINVAL, nothing launched, checked before the
+ * handle is used: a null pointer, radius outside 0..32, a taps_stride other than 0 or radius + 1, batch outside 1..4096,
+ * log_prior == belief. */
+int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps,
+                        int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
