@@ -93,7 +93,9 @@ static int max_micro_batch(const Switches& sw, int variant, float ori_noise, int
     while (hi - lo > 1) {
         const int mid = (lo + hi) / 2;
         Plan pl;
-        if (build_plan(&tmp, pl, mid, grd_h, grd_w) == 0) lo = mid; else hi = mid;
+        PlanKey key;
+        key.B = mid; key.gh = grd_h; key.gw = grd_w;
+        if (build_plan(&tmp, pl, key) == 0) lo = mid; else hi = mid;
     }
     if (lo == 0) return ccvpe_fail(CCVPE_EINVAL, "ground size %d x %d is not valid for variant %d: %s", grd_h, grd_w, variant, ccvpe_err().c_str());
     return lo;
@@ -148,9 +150,7 @@ int ccvpe_destroy(ccvpe_handle h) {
     (void)hipSetDevice(h->cfg.device);
     for (void* p : h->dev_allocs) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);
-    if (h->post_scratch) (void)hipFree(h->post_scratch);
-    if (h->topk_scratch) (void)hipFree(h->topk_scratch);
-    if (h->prior_scratch) (void)hipFree(h->prior_scratch);
+    for (auto* buf : {&h->post_scratch, &h->topk_scratch, &h->prior_scratch}) if (buf->ptr) (void)hipFree(buf->ptr);
     h->plans.clear();
     for (int k = 0; k < 2; ++k) if (h->snap[k]) (void)hipFree(h->snap[k]);
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
@@ -167,11 +167,17 @@ int ccvpe_output_channels(ccvpe_handle h, int32_t level) {
 size_t ccvpe_workspace_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32_t grd_w) {
     if (!h || !h->finalized || batch <= 0) { ccvpe_fail(CCVPE_ESTATE, "handle not ready"); return 0; }
     Plan pl;
-    const int mb = std::min(batch, h->cfg.micro_batch);
-    if (build_plan(h, pl, mb, grd_h, grd_w)) return 0;
+    PlanKey key;
+    key.B = std::min(batch, h->cfg.micro_batch); key.gh = grd_h; key.gw = grd_w;
+    if (build_plan(h, pl, key)) return 0;
     return pl.total * sizeof(float);
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// forward orchestration (C++ linkage: the micro-batch loop is a template)
+// ------------------------------------------------------------------------------------------------
 // Issue a plan's ops: in order on one stream, or on two streams with event edges for the cross-stream dependencies.
 // First issue of a plan: every tiled launch must run the (tile, split-K) its plan entry names.  launch_conv_igemm falls back to the shape
 // heuristic when a tile cannot serve a launch (a hand-edited or foreign tuning table): legal, but then "same table -> same launches ->
@@ -181,7 +187,7 @@ static void check_issued_tile(Plan& pl, const Op& op) {
     if (!op.tile || (*op.tile & 0xff) == 0 || got == 0) return;
     const int want = *op.tile, ws = (want >> 8) & 0xff, gs = (got >> 8) & 0xff;
     if ((want & 0xff) != (got & 0xff) || (ws > 1 ? ws : 1) != (gs > 1 ? gs : 1))
-        std::fprintf(stderr, "ccvpe: launch %s (batch %d) runs %s split %d instead of the planned %s split %d\n", op.name.c_str(), pl.B,
+        std::fprintf(stderr, "ccvpe: launch %s (batch %d) runs %s split %d instead of the planned %s split %d\n", op.name.c_str(), pl.key.B,
                      conv_igemm_tile_name(got), gs, conv_igemm_tile_name(want), ws);
 }
 
@@ -255,172 +261,204 @@ static int micro_batch_cap(ccvpe_handle h, int gh, int gw) {
     return mbmax;
 }
 
-// rows != null: the pose plans of ccvpe_localize - [batch][5] result rows instead of the nine outputs (`out` is not read);
-// topk_k > 0: the top-K pose plans of ccvpe_localize_topk - [batch][topk_k][5] rows (topk_k and topk_r checked by the caller);
-// log_prior != null: the pose plans of ccvpe_localize_prior* - every slice reads its own maps (prior_stride checked by the caller);
-// posterior != null (argmax pose plans): ccvpe_track_update* - every slice also writes its own posterior maps
-static int run_forward(ccvpe_handle h, const float* grd, int gh, int gw, const float* sat, int batch,
-                       const ccvpe_outputs* out, hipStream_t stream, bool profile, const float* cache = nullptr, float* rows = nullptr,
-                       int topk_k = 0, int topk_r = 0, const int32_t* tile_index = nullptr, int n_tiles = 0,
-                       const float* log_prior = nullptr, long long prior_stride = 0, float* posterior = nullptr) {
-    const int mode = cache ? 2 : 0;
-    const bool pose = rows != nullptr;
-    const bool topk = pose && topk_k > 0;
-    if (!h || !grd || (!sat && !cache) || (!out && !pose)) return ccvpe_fail(CCVPE_EINVAL, "null argument");
-    if (cache && !tile_index && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
-    if (tile_index && n_tiles > h->cfg.micro_batch)
-        return ccvpe_fail(CCVPE_EINVAL, "n_tiles %d exceeds micro_batch (%d), the most ccvpe_encode_aerial writes", n_tiles, h->cfg.micro_batch);
-    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
-    if (pose && h->debug) return ccvpe_fail(CCVPE_ESTATE, "pose plans carry no debug taps: ccvpe_set_debug(h, 0) before ccvpe_localize");
-    if (batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "batch must be positive");
-    if (!pose) {
-        if (!out->logits_flattened || !out->heatmap || !out->ori) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
-        for (int k = 0; k < 6; ++k) if (!out->matching_score[k]) return ccvpe_fail(CCVPE_EINVAL, "null matching_score[%d]", k);
-    }
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (profile) h->prof.clear();
-    const int mbmax = micro_batch_cap(h, gh, gw);
-    // make sure every plan (and the largest arena) exists before the first launch
-    for (int done = 0; done < batch;) {
-        const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose, topk);
-        if (rc) return rc;
-        done += mb;
-    }
-    const size_t npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
-    for (int done = 0; done < batch;) {
-        const int mb = std::min(mbmax, batch - done);
-        Plan* pl; int rc = get_plan(h, mb, gh, gw, &pl, mode, pose, topk);
-        if (rc) return rc;
-        h->last_plan = pl;
-        Ctx c;
-        c.cache_in = cache;
-        if (tile_index) { c.tile_index = tile_index + done; c.n_tiles = n_tiles; }   // every slice reads its own indices of the one cache
-        c.arena = h->arena; c.off = &pl->off; c.stream = stream;
-        c.tickets = pl->tickets;
-        pl->set_scratch(c, 0);
-        c.grd = grd + (size_t)done * 3 * gh * gw;
-        c.sat = sat ? sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
-        if (log_prior) { c.log_prior = log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
-        if (posterior) c.posterior = posterior + (size_t)done * npx;
-        if (topk) {
-            c.rows = rows + (size_t)done * topk_k * 5;
-            c.topk_k = topk_k; c.topk_r = topk_r;
-        } else if (pose) {
-            c.rows = rows + (size_t)done * 5;
-        } else {
-            c.out.logits_flattened = out->logits_flattened + done * npx;
-            c.out.heatmap = out->heatmap + done * npx;
-            c.out.ori = out->ori + done * 2 * npx;
-            for (int k = 0; k < 6; ++k) {
-                const size_t hw = (size_t)(8 << k) * (8 << k);
-                c.out.matching_score[k] = out->matching_score[k] + (size_t)done * h->rolls[k] * hw;
-            }
-        }
-        if (!profile && pl->use_graph && !h->debug) {
-            // latency mode: stage inputs, replay the captured launch sequence, copy the outputs out
-            const ccvpe_outputs user = c.out;
-            const float* ugrd = c.grd; const float* usat = c.sat;
-            c.grd = c.ptr(pl->io_grd); c.sat = c.ptr(pl->io_sat);
-            c.out.logits_flattened = c.ptr(pl->io_logits); c.out.heatmap = c.ptr(pl->io_heat); c.out.ori = c.ptr(pl->io_ori);
-            for (int k = 0; k < 6; ++k) c.out.matching_score[k] = c.ptr(pl->io_ms[k]);
-            {   // both inputs in one launch (sizes are multiples of 4 floats: 3 x H x W with even H or W - else the runtime copies)
-                const size_t ng = (size_t)mb * 3 * gh * gw, ns = (size_t)mb * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW;
-                if (ng % 4 == 0 && ((uintptr_t)ugrd % 16) == 0 && ((uintptr_t)usat % 16) == 0) {
-                    MultiCopy mc{};
-                    mc.src[0] = ugrd; mc.dst[0] = (float*)c.grd; mc.n[0] = ng;
-                    mc.src[1] = usat; mc.dst[1] = (float*)c.sat; mc.n[1] = ns;
-                    mc.count = 2;
-                    launch_multi_copy(mc, stream);
-                } else {
-                    HIPCHK(hipMemcpyAsync((void*)c.grd, ugrd, ng * sizeof(float), hipMemcpyDeviceToDevice, stream));
-                    HIPCHK(hipMemcpyAsync((void*)c.sat, usat, ns * sizeof(float), hipMemcpyDeviceToDevice, stream));
-                }
-            }
-            if (!pl->exec && pl->runs >= 1) {   // first call ran eagerly (lazy kernel attributes are set): capture now
-                // capture on a private stream (the caller's may be the legacy null stream, which cannot capture)
-                hipGraph_t graph = nullptr;
-                if (!h->capture_stream) HIPCHK(hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking));
-                HIPCHK(hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal));
-                const int rrc = run_ops(h, *pl, c, h->capture_stream);
-                hipError_t ce = hipStreamEndCapture(h->capture_stream, &graph);
-                if (rrc) ce = hipErrorUnknown;
-                if (ce == hipSuccess && graph) {
-                    hipGraphExec_t ex = nullptr;
-                    if (hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess) pl->exec = ex;
-                    (void)hipGraphDestroy(graph);
-                }
-                if (!pl->exec) { (void)hipGetLastError(); pl->use_graph = false; }   // fall back to eager launches for good
-            }
-            if (pl->exec) HIPCHK(hipGraphLaunch(pl->exec, stream));
-            else if (int rrc = run_ops(h, *pl, c, stream)) return rrc;
-            pl->runs++;
-            {   // the nine outputs in one launch
-                MultiCopy mc{};
-                auto add = [&](float* dst, const float* src, size_t n) { mc.src[mc.count] = src; mc.dst[mc.count] = dst; mc.n[mc.count] = n; ++mc.count; };
-                add(user.logits_flattened, c.out.logits_flattened, (size_t)mb * npx);
-                add(user.heatmap, c.out.heatmap, (size_t)mb * npx);
-                add(user.ori, c.out.ori, (size_t)mb * 2 * npx);
-                bool aligned = true;
-                for (int k = 0; k < 6; ++k) add(user.matching_score[k], c.out.matching_score[k], (size_t)mb * h->rolls[k] * ((size_t)(8 << k) * (8 << k)));
-                for (int i = 0; i < mc.count; ++i) aligned = aligned && mc.n[i] % 4 == 0 && ((uintptr_t)mc.dst[i] % 16) == 0 && ((uintptr_t)mc.src[i] % 16) == 0;
-                if (aligned) launch_multi_copy(mc, stream);
-                else
-                    for (int i = 0; i < mc.count; ++i) HIPCHK(hipMemcpyAsync(mc.dst[i], mc.src[i], mc.n[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
-            }
-        } else if (!profile) {
-            if (int rrc = run_ops(h, *pl, c, stream)) return rrc;
-        } else {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0));
-            HIPCHK(hipEventCreate(&e1));
-            for (auto& op : pl->ops) {
-                (void)conv_igemm_last_tile();
-                HIPCHK(hipEventRecord(e0, stream));
-                op.fn(c);
-                HIPCHK(hipEventRecord(e1, stream));
-                HIPCHK(hipEventSynchronize(e1));
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-                const int tile = conv_igemm_last_tile();
-                std::string nm = op.name;
-                double issued = op.flops;   // launches that are not tiled GEMMs: issued == algorithmic
-                if (tile) {
-                    nm += std::string("|") + conv_igemm_tile_name(tile);
-                    if ((tile >> 8) == 255) nm += "_tailsplit";
-                    else if ((tile >> 8) > SPLIT_FUSED) nm += "_splitk" + std::to_string((tile >> 8) - SPLIT_FUSED) + "r";   // r: reduces itself
-                    else if ((tile >> 8) > 1) nm += "_splitk" + std::to_string(tile >> 8);
-                    // FLOPs the launch puts on the matrix pipe: M and N padded to the tile, K to the packed depth;
-                    // Winograd F(2x2,3x3): 16 products per 2x2 output tile and channel pair; bf16x3: three MFMAs per product
-                    ConvParams q{};
-                    q.M = op.gemm_m; q.N = op.gemm_n;
-                    const double util = conv_igemm_tile_util(q, tile & 0xff);
-                    const double mn_pad = util > 0 ? (double)op.gemm_m * op.gemm_n / util : 0.0;
-                    if (conv_igemm_tile_is_wino4(tile)) issued = 2.0 * mn_pad * 2.25 * ((op.conv_cin + 3) / 4 * 4);   // 36 products per 4x4 tile; k-steps of 4 channels, all-zero ones skipped
-                    else if (conv_igemm_tile_is_wino(tile)) issued = 2.0 * mn_pad * 4.0 * op.conv_cin;
-                    else issued = 2.0 * mn_pad * op.gemm_kpad * (conv_igemm_tile_is_bf16x3(tile) ? 3.0 : 1.0);
-                }
-                h->prof.push_back({nm, ms, op.flops, op.bytes, issued});
-            }
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-        }
-        if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
-        done += mb;
-    }
+// the launches just issued, as "<what> failed: ..." when one of them was refused
+static int launch_status(const char* what) {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "%s failed: %s", what, hipGetErrorString(e));
     return 0;
 }
 
+// launch context of a plan on the caller's stream: the workspace side; the caller adds what the call reads and writes
+static Ctx plan_ctx(ccvpe_handle h, const Plan& pl, hipStream_t stream) {
+    Ctx c;
+    c.arena = h->arena; c.off = &pl.off; c.stream = stream;
+    c.tickets = pl.tickets;
+    pl.set_scratch(c, 0);
+    return c;
+}
+
+// The micro-batch loop of the forward family and of ccvpe_localize_region: `total` samples (pairs) in slices of at most micro_batch_cap.
+// Two passes: every plan (and the largest arena) exists before the first launch; then slice(pl, c, done, mb) adds the slice's own pointers
+// to the plan's launch context and issues it.
+template <class Slice>
+static int for_each_micro_batch(ccvpe_handle h, PlanKey key, int total, hipStream_t stream, Slice slice) {
+    const int mbmax = micro_batch_cap(h, key.gh, key.gw);
+    for (int pass = 0; pass < 2; ++pass)
+        for (int done = 0; done < total; done += key.B) {
+            key.B = std::min(mbmax, total - done);
+            Plan* pl;
+            if (int rc = get_plan(h, key, &pl)) return rc;
+            if (pass == 0) continue;
+            h->last_plan = pl;
+            Ctx c = plan_ctx(h, *pl, stream);
+            if (int rc = slice(pl, c, done, key.B)) return rc;
+            if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
+        }
+    return 0;
+}
+
+// One slice of a forward call: a replayed hipGraph (latency mode), eager launches, or launch by launch between events (profile)
+static int issue_forward(ccvpe_handle h, Plan* pl, Ctx& c, const ForwardCall& fc, int mb) {
+    const int gh = fc.gh, gw = fc.gw;
+    const bool profile = fc.profile;
+    hipStream_t stream = fc.stream;
+    const size_t npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
+    if (!profile && pl->use_graph && !h->debug) {
+        // latency mode: stage inputs, replay the captured launch sequence, copy the outputs out
+        const ccvpe_outputs user = c.out;
+        const float* ugrd = c.grd; const float* usat = c.sat;
+        c.grd = c.ptr(pl->io_grd); c.sat = c.ptr(pl->io_sat);
+        c.out.logits_flattened = c.ptr(pl->io_logits); c.out.heatmap = c.ptr(pl->io_heat); c.out.ori = c.ptr(pl->io_ori);
+        for (int k = 0; k < 6; ++k) c.out.matching_score[k] = c.ptr(pl->io_ms[k]);
+        {   // both inputs in one launch (sizes are multiples of 4 floats: 3 x H x W with even H or W - else the runtime copies)
+            const size_t ng = (size_t)mb * 3 * gh * gw, ns = (size_t)mb * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW;
+            if (ng % 4 == 0 && ((uintptr_t)ugrd % 16) == 0 && ((uintptr_t)usat % 16) == 0) {
+                MultiCopy mc{};
+                mc.src[0] = ugrd; mc.dst[0] = (float*)c.grd; mc.n[0] = ng;
+                mc.src[1] = usat; mc.dst[1] = (float*)c.sat; mc.n[1] = ns;
+                mc.count = 2;
+                launch_multi_copy(mc, stream);
+            } else {
+                HIPCHK(hipMemcpyAsync((void*)c.grd, ugrd, ng * sizeof(float), hipMemcpyDeviceToDevice, stream));
+                HIPCHK(hipMemcpyAsync((void*)c.sat, usat, ns * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            }
+        }
+        if (!pl->exec && pl->runs >= 1) {   // first call ran eagerly (lazy kernel attributes are set): capture now
+            // capture on a private stream (the caller's may be the legacy null stream, which cannot capture)
+            hipGraph_t graph = nullptr;
+            if (!h->capture_stream) HIPCHK(hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking));
+            HIPCHK(hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal));
+            const int rrc = run_ops(h, *pl, c, h->capture_stream);
+            hipError_t ce = hipStreamEndCapture(h->capture_stream, &graph);
+            if (rrc) ce = hipErrorUnknown;
+            if (ce == hipSuccess && graph) {
+                hipGraphExec_t ex = nullptr;
+                if (hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) == hipSuccess) pl->exec = ex;
+                (void)hipGraphDestroy(graph);
+            }
+            if (!pl->exec) { (void)hipGetLastError(); pl->use_graph = false; }   // fall back to eager launches for good
+        }
+        if (pl->exec) HIPCHK(hipGraphLaunch(pl->exec, stream));
+        else if (int rrc = run_ops(h, *pl, c, stream)) return rrc;
+        pl->runs++;
+        {   // the nine outputs in one launch
+            MultiCopy mc{};
+            auto add = [&](float* dst, const float* src, size_t n) { mc.src[mc.count] = src; mc.dst[mc.count] = dst; mc.n[mc.count] = n; ++mc.count; };
+            add(user.logits_flattened, c.out.logits_flattened, (size_t)mb * npx);
+            add(user.heatmap, c.out.heatmap, (size_t)mb * npx);
+            add(user.ori, c.out.ori, (size_t)mb * 2 * npx);
+            bool aligned = true;
+            for (int k = 0; k < 6; ++k) add(user.matching_score[k], c.out.matching_score[k], (size_t)mb * h->rolls[k] * ((size_t)(8 << k) * (8 << k)));
+            for (int i = 0; i < mc.count; ++i) aligned = aligned && mc.n[i] % 4 == 0 && ((uintptr_t)mc.dst[i] % 16) == 0 && ((uintptr_t)mc.src[i] % 16) == 0;
+            if (aligned) launch_multi_copy(mc, stream);
+            else
+                for (int i = 0; i < mc.count; ++i) HIPCHK(hipMemcpyAsync(mc.dst[i], mc.src[i], mc.n[i] * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        }
+    } else if (!profile) {
+        if (int rrc = run_ops(h, *pl, c, stream)) return rrc;
+    } else {
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        for (auto& op : pl->ops) {
+            (void)conv_igemm_last_tile();
+            HIPCHK(hipEventRecord(e0, stream));
+            op.fn(c);
+            HIPCHK(hipEventRecord(e1, stream));
+            HIPCHK(hipEventSynchronize(e1));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            const int tile = conv_igemm_last_tile();
+            std::string nm = op.name;
+            double issued = op.flops;   // launches that are not tiled GEMMs: issued == algorithmic
+            if (tile) {
+                nm += std::string("|") + conv_igemm_tile_name(tile);
+                if ((tile >> 8) == 255) nm += "_tailsplit";
+                else if ((tile >> 8) > SPLIT_FUSED) nm += "_splitk" + std::to_string((tile >> 8) - SPLIT_FUSED) + "r";   // r: reduces itself
+                else if ((tile >> 8) > 1) nm += "_splitk" + std::to_string(tile >> 8);
+                // FLOPs the launch puts on the matrix pipe: M and N padded to the tile, K to the packed depth;
+                // Winograd F(2x2,3x3): 16 products per 2x2 output tile and channel pair; bf16x3: three MFMAs per product
+                ConvParams q{};
+                q.M = op.gemm_m; q.N = op.gemm_n;
+                const double util = conv_igemm_tile_util(q, tile & 0xff);
+                const double mn_pad = util > 0 ? (double)op.gemm_m * op.gemm_n / util : 0.0;
+                if (conv_igemm_tile_is_wino4(tile)) issued = 2.0 * mn_pad * 2.25 * ((op.conv_cin + 3) / 4 * 4);   // 36 products per 4x4 tile; k-steps of 4 channels, all-zero ones skipped
+                else if (conv_igemm_tile_is_wino(tile)) issued = 2.0 * mn_pad * 4.0 * op.conv_cin;
+                else issued = 2.0 * mn_pad * op.gemm_kpad * (conv_igemm_tile_is_bf16x3(tile) ? 3.0 : 1.0);
+            }
+            h->prof.push_back({nm, ms, op.flops, op.bytes, issued});
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    return 0;
+}
+
+static int run_forward(ccvpe_handle h, const ForwardCall& fc) {
+    const PlanKey key = fc.plan_key();
+    const int batch = fc.batch;
+    if (!h || !fc.grd || (!fc.sat && !fc.cache) || (!fc.out && !key.pose)) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (fc.cache && !fc.tile_index && batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "cached forward needs batch <= micro_batch (%d)", h->cfg.micro_batch);
+    if (fc.tile_index && fc.n_tiles > h->cfg.micro_batch)
+        return ccvpe_fail(CCVPE_EINVAL, "n_tiles %d exceeds micro_batch (%d), the most ccvpe_encode_aerial writes", fc.n_tiles, h->cfg.micro_batch);
+    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
+    if (key.pose && h->debug) return ccvpe_fail(CCVPE_ESTATE, "pose plans carry no debug taps: ccvpe_set_debug(h, 0) before ccvpe_localize");
+    if (batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "batch must be positive");
+    if (!key.pose) {
+        if (!fc.out->logits_flattened || !fc.out->heatmap || !fc.out->ori) return ccvpe_fail(CCVPE_EINVAL, "null output buffer");
+        for (int k = 0; k < 6; ++k) if (!fc.out->matching_score[k]) return ccvpe_fail(CCVPE_EINVAL, "null matching_score[%d]", k);
+    }
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (fc.profile) h->prof.clear();
+    const size_t npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
+    auto slice = [&](Plan* pl, Ctx& c, int done, int mb) {
+        c.cache_in = fc.cache;
+        if (fc.tile_index) { c.tile_index = fc.tile_index + done; c.n_tiles = fc.n_tiles; }   // every slice reads its own indices of the one cache
+        c.grd = fc.grd + (size_t)done * 3 * fc.gh * fc.gw;
+        c.sat = fc.sat ? fc.sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
+        if (fc.log_prior) { c.log_prior = fc.log_prior + (size_t)done * fc.prior_stride; c.prior_stride = fc.prior_stride; }
+        if (fc.posterior) c.posterior = fc.posterior + (size_t)done * npx;
+        if (key.topk) {
+            c.rows = fc.rows + (size_t)done * fc.topk_k * 5;
+            c.topk_k = fc.topk_k; c.topk_r = fc.topk_r;
+        } else if (key.pose) {
+            c.rows = fc.rows + (size_t)done * 5;
+        } else {
+            c.out.logits_flattened = fc.out->logits_flattened + done * npx;
+            c.out.heatmap = fc.out->heatmap + done * npx;
+            c.out.ori = fc.out->ori + done * 2 * npx;
+            for (int k = 0; k < 6; ++k) {
+                const size_t hw = (size_t)(8 << k) * (8 << k);
+                c.out.matching_score[k] = fc.out->matching_score[k] + (size_t)done * h->rolls[k] * hw;
+            }
+        }
+        return issue_forward(h, pl, c, fc, mb);
+    };
+    if (int rc = for_each_micro_batch(h, key, batch, fc.stream, slice)) return rc;
+    return launch_status("kernel launch");
+}
+
+// the fields every form of the forward family has; the entry point names the rest
+static ForwardCall forward_call(const float* grd, int32_t grd_h, int32_t grd_w, int32_t batch, void* stream) {
+    ForwardCall fc;
+    fc.grd = grd; fc.gh = grd_h; fc.gw = grd_w; fc.batch = batch; fc.stream = (hipStream_t)stream;
+    return fc;
+}
+
+extern "C" {
+
 int ccvpe_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
                   const ccvpe_outputs* out, void* stream) {
-    return run_forward(h, grd, grd_h, grd_w, sat, batch, out, (hipStream_t)stream, false);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.out = out;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch, float* rows, void* stream) {
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
-    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.rows = rows;
+    return run_forward(h, fc);
 }
 
 // the (k, radius) range of the top-K entry points, checked before the handle is used
@@ -434,13 +472,16 @@ int ccvpe_localize_topk(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t
                         int32_t radius, float* rows, void* stream) {
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_topk_args(k, radius)) return rc;
-    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, k, radius);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    return run_forward(h, fc);
 }
 
 int ccvpe_profile_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
                           const ccvpe_outputs* out, void* stream) {
-    int rc = run_forward(h, grd, grd_h, grd_w, sat, batch, out, (hipStream_t)stream, true);
-    if (rc) return rc;
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.out = out; fc.profile = true;
+    if (int rc = run_forward(h, fc)) return rc;
     return (int)h->prof.size();
 }
 
@@ -460,30 +501,43 @@ int ccvpe_profile_row_issued(ccvpe_handle h, int32_t i, double* issued_flops) {
     return 0;
 }
 
-// scratch of the post-processing launch: grows with the largest batch seen (the only synchronising step, once per size)
-static int ensure_post_scratch(ccvpe_handle_s* h, int batch) {
-    if (batch <= h->post_batch) return 0;
+// Scratch of a post-processing family: grows with the largest batch seen (the only synchronising step, once per size); bytes(cap) is
+// its size for cap samples, `what` names it in the out-of-memory message
+static int ensure_scratch(ccvpe_handle_s::Scratch& buf, int batch, size_t (*bytes)(int), const char* what) {
+    if (batch <= buf.batch) return 0;
     HIPCHK(hipDeviceSynchronize());   // a launch in flight may still use the old buffer
-    if (h->post_scratch) HIPCHK(hipFree(h->post_scratch));
-    h->post_scratch = nullptr; h->post_batch = 0;
+    if (buf.ptr) HIPCHK(hipFree(buf.ptr));
+    buf = {};
     const int cap = std::max(batch, 32);
     void* d = nullptr;
-    if (hipMalloc(&d, postprocess_scratch_bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "post-processing scratch");
-    HIPCHK(hipMemset(d, 0, postprocess_scratch_bytes(cap)));
+    if (hipMalloc(&d, bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "%s", what);
+    HIPCHK(hipMemset(d, 0, bytes(cap)));
     HIPCHK(hipDeviceSynchronize());
-    h->post_scratch = d; h->post_batch = cap;
+    buf = {d, cap};
     return 0;
+}
+
+// The top-K scratch (topk_scratch_bytes) and the prior scratch for buf.batch samples: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys]
+// [B x 64 indices] and, in the prior scratch only, [B x 64 x 2 softmax partials]; the argmax form's (max, index) hand-off pairs use the
+// start of the key area.
+static size_t prior_scratch_bytes(int B) { return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float); }
+struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; };
+static TopkScratch topk_scratch_layout(const ccvpe_handle_s::Scratch& buf) {
+    TopkScratch w;
+    w.tickets = reinterpret_cast<unsigned*>(buf.ptr);
+    w.keys = reinterpret_cast<unsigned long long*>(w.tickets + PP_MAX_BATCH);
+    w.index = reinterpret_cast<int*>(w.keys + (size_t)buf.batch * 64 * TOPK_MAX_K);
+    w.partial = reinterpret_cast<float*>(w.index + (size_t)buf.batch * TOPK_MAX_K);
+    return w;
 }
 
 static int postprocess_any(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, ccvpe_pose* poses, float* rows, void* stream) {
     if (!h || !heatmap || !ori || (!poses && !rows) || batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "bad argument (batch 1 .. 4096)");
     HIPCHK(hipSetDevice(h->cfg.device));
     static_assert(sizeof(ccvpe_pose) == sizeof(PoseOut), "pose layout");
-    if (int rc = ensure_post_scratch(h, batch)) return rc;
-    launch_postprocess(heatmap, ori, batch, CCVPE_OUT_HW * CCVPE_OUT_HW, reinterpret_cast<PoseOut*>(poses), rows, h->post_scratch, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "postprocess launch failed: %s", hipGetErrorString(e));
-    return 0;
+    if (int rc = ensure_scratch(h->post_scratch, batch, postprocess_scratch_bytes, "post-processing scratch")) return rc;
+    launch_postprocess(heatmap, ori, batch, CCVPE_OUT_HW * CCVPE_OUT_HW, reinterpret_cast<PoseOut*>(poses), rows, h->post_scratch.ptr, (hipStream_t)stream);
+    return launch_status("postprocess launch");
 }
 
 int ccvpe_postprocess(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, ccvpe_pose* poses, void* stream) {
@@ -496,40 +550,20 @@ int ccvpe_postprocess_rows(ccvpe_handle h, const float* heatmap, const float* or
     return postprocess_any(h, heatmap, ori, batch, nullptr, rows, stream);
 }
 
-// scratch of the top-K post-processing launch: grows with the largest batch seen, as ensure_post_scratch
-static int ensure_topk_scratch(ccvpe_handle_s* h, int batch) {
-    if (batch <= h->topk_batch) return 0;
-    HIPCHK(hipDeviceSynchronize());
-    if (h->topk_scratch) HIPCHK(hipFree(h->topk_scratch));
-    h->topk_scratch = nullptr; h->topk_batch = 0;
-    const int cap = std::max(batch, 32);
-    void* d = nullptr;
-    if (hipMalloc(&d, topk_scratch_bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "top-K post-processing scratch");
-    HIPCHK(hipMemset(d, 0, topk_scratch_bytes(cap)));
-    HIPCHK(hipDeviceSynchronize());
-    h->topk_scratch = d; h->topk_batch = cap;
-    return 0;
-}
-
 int ccvpe_postprocess_topk(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch, int32_t k, int32_t radius, float* rows,
                            void* stream) {
     if (!h || !heatmap || !ori || !rows) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     if (int rc = check_topk_args(k, radius)) return rc;
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "bad argument (batch 1 .. 4096)");
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_topk_scratch(h, batch)) return rc;
-    // [PP_MAX_BATCH ticket counters][topk_batch x 64 x 64 keys][batch x k indices] (topk_scratch_bytes)
-    unsigned char* base = reinterpret_cast<unsigned char*>(h->topk_scratch);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
-    int* index = reinterpret_cast<int*>(keys + (size_t)h->topk_batch * 64 * TOPK_MAX_K);
+    if (int rc = ensure_scratch(h->topk_scratch, batch, topk_scratch_bytes, "top-K post-processing scratch")) return rc;
+    const TopkScratch w = topk_scratch_layout(h->topk_scratch);   // (no partials: the peaks come from the heatmap)
     TopkParams p{};
     p.heat = heatmap; p.logits = nullptr; p.partial = nullptr; p.B = batch; p.k = k; p.r = radius;
-    p.keys = keys; p.tickets = reinterpret_cast<unsigned*>(base); p.index = index; p.rows = rows;
+    p.keys = w.keys; p.tickets = w.tickets; p.index = w.index; p.rows = rows;
     launch_topk_peaks(p, (hipStream_t)stream);
-    launch_topk_gather(ori, index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "postprocess_topk launch failed: %s", hipGetErrorString(e));
-    return 0;
+    launch_topk_gather(ori, w.index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, (hipStream_t)stream);
+    return launch_status("postprocess_topk launch");
 }
 
 int ccvpe_eval_metrics(ccvpe_handle h, const ccvpe_pose* poses, const float* heatmap, int32_t batch, const int32_t* gt_index,
@@ -539,9 +573,7 @@ int ccvpe_eval_metrics(ccvpe_handle h, const ccvpe_pose* poses, const float* hea
     static_assert(sizeof(ccvpe_metrics) == sizeof(MetricsOut), "metrics layout");
     launch_metrics(reinterpret_cast<const PoseOut*>(poses), heatmap, batch, CCVPE_OUT_HW, CCVPE_OUT_HW * CCVPE_OUT_HW, gt_index, gt_cos_sin,
                    meter_per_pixel, heading_deg, reinterpret_cast<MetricsOut*>(out), (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "metrics launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("metrics launch");
 }
 
 int ccvpe_set_streams(ccvpe_handle h, int32_t n_streams) {
@@ -602,35 +634,44 @@ size_t ccvpe_aerial_cache_bytes(ccvpe_handle h, int32_t batch) {
     return cache_layout(h->vs, batch, off) * sizeof(float);
 }
 
-int ccvpe_encode_aerial(ccvpe_handle h, const float* sat, int32_t batch, void* cache, void* stream) {
-    if (!h || !sat || !cache || batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "bad argument");
+// ccvpe_encode_aerial and ccvpe_encode_ground: one plan (key) for the whole batch, reading the images through the Ctx field `input`
+// names, its last launches writing the caller's cache
+static int run_encode(ccvpe_handle h, const PlanKey& key, const char* side, const float* Ctx::*input, const float* img, void* cache,
+                      void* stream) {
+    if (!h || !img || !cache || key.B <= 0) return ccvpe_fail(CCVPE_EINVAL, "bad argument");
     if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
-    if (batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "aerial encode needs batch <= micro_batch (%d)", h->cfg.micro_batch);
+    if (key.B > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "%s encode needs batch <= micro_batch (%d)", side, h->cfg.micro_batch);
     HIPCHK(hipSetDevice(h->cfg.device));
-    Plan* pl; int rc = get_plan(h, batch, 0, 0, &pl, 1);
-    if (rc) return rc;
-    Ctx c;
-    c.arena = h->arena; c.off = &pl->off; c.stream = (hipStream_t)stream;
-    c.tickets = pl->tickets;
-    c.splitk_scratch = c.ptr(pl->scratch); c.splitk_floats = Plan::SPLITK_FLOATS;
-    c.sat = sat; c.cache_out = (float*)cache;
+    Plan* pl;
+    if (int rc = get_plan(h, key, &pl)) return rc;
+    Ctx c = plan_ctx(h, *pl, (hipStream_t)stream);
+    c.*input = img; c.cache_out = (float*)cache;
     for (auto& op : pl->ops) op.fn(c);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
+    return launch_status("kernel launch");
+}
+
+int ccvpe_encode_aerial(ccvpe_handle h, const float* sat, int32_t batch, void* cache, void* stream) {
+    PlanKey key;
+    key.B = batch; key.mode = 1;
+    return run_encode(h, key, "aerial", &Ctx::sat, sat, cache, stream);
 }
 
 int ccvpe_forward_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t batch,
                          const ccvpe_outputs* out, void* stream) {
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, out, (hipStream_t)stream, false, (const float*)cache);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.out = out;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t batch, float* rows,
                           void* stream) {
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.rows = rows;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t batch,
@@ -638,7 +679,9 @@ int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, 
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_topk_args(k, radius)) return rc;
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    return run_forward(h, fc);
 }
 
 // Arguments of the indexed cached forms, checked before the handle is used: tile_index is host memory, so every entry is read
@@ -657,18 +700,32 @@ static int check_indexed_args(const float* grd, const void* cache, int32_t n_til
     return 0;
 }
 
+// ... and of the cached forms whose tile_index may be null: then query b reads tile b - the unindexed cached plan, whose cache holds
+// exactly one tile per query
+static int check_cached_args(const float* grd, const void* cache, int32_t n_tiles, const int32_t* tile_index, int32_t batch, const void* rows) {
+    if (tile_index) return check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows);
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (n_tiles != batch)
+        return ccvpe_fail(CCVPE_EINVAL, "without tile_index the cache holds one tile per query: n_tiles %d != batch %d", n_tiles, batch);
+    return 0;
+}
+
 int ccvpe_forward_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
                                  const int32_t* tile_index, int32_t batch, const ccvpe_outputs* out, void* stream) {
     if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, out)) return rc;
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, out, (hipStream_t)stream, false, (const float*)cache, nullptr, 0, 0,
-                       tile_index, n_tiles);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.out = out;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
                                   const int32_t* tile_index, int32_t batch, float* rows, void* stream) {
     if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, 0, 0,
-                       tile_index, n_tiles);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.rows = rows;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
@@ -676,8 +733,9 @@ int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t
                                        void* stream) {
     if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
     if (int rc = check_topk_args(k, radius)) return rc;
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius,
-                       tile_index, n_tiles);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    return run_forward(h, fc);
 }
 
 size_t ccvpe_ground_cache_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32_t grd_w) {
@@ -688,22 +746,9 @@ size_t ccvpe_ground_cache_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, in
 }
 
 int ccvpe_encode_ground(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, int32_t batch, void* cache, void* stream) {
-    if (!h || !grd || !cache || batch <= 0) return ccvpe_fail(CCVPE_EINVAL, "bad argument");
-    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
-    if (batch > h->cfg.micro_batch) return ccvpe_fail(CCVPE_EINVAL, "ground encode needs batch <= micro_batch (%d)", h->cfg.micro_batch);
-    HIPCHK(hipSetDevice(h->cfg.device));
-    Plan* pl; int rc = get_plan(h, batch, grd_h, grd_w, &pl, 3);
-    if (rc) return rc;
-    Ctx c;
-    c.arena = h->arena; c.off = &pl->off; c.stream = (hipStream_t)stream;
-    c.tickets = pl->tickets;
-    c.splitk_scratch = c.ptr(pl->scratch); c.splitk_floats = Plan::SPLITK_FLOATS;
-    c.grd = grd; c.cache_out = (float*)cache;
-    for (auto& op : pl->ops) op.fn(c);
-    if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    PlanKey key;
+    key.B = batch; key.gh = grd_h; key.gw = grd_w; key.mode = 3;
+    return run_encode(h, key, "ground", &Ctx::grd, grd, cache, stream);
 }
 
 // Arguments of ccvpe_localize_region, checked before the handle is used: offsets and tiles are host memory, read here in full.
@@ -745,34 +790,20 @@ static int run_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, 
     for (int g = 0; g < n_queries; ++g)
         for (int p = offsets[g]; p < offsets[g + 1]; ++p) query[p] = g;
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int mbmax = micro_batch_cap(h, grd_h, grd_w);
-    for (int done = 0; done < P;) {   // every plan (and the largest arena) exists before the first launch
-        const int mb = std::min(mbmax, P - done);
-        Plan* pl; if (int rc = get_plan(h, mb, grd_h, grd_w, &pl, 4, true)) return rc;
-        done += mb;
-    }
     hipStream_t s = (hipStream_t)stream;
-    for (int done = 0; done < P;) {
-        const int mb = std::min(mbmax, P - done);
-        Plan* pl; if (int rc = get_plan(h, mb, grd_h, grd_w, &pl, 4, true)) return rc;
-        h->last_plan = pl;
-        Ctx c;
+    auto slice = [&](Plan* pl, Ctx& c, int done, int) {
         c.cache_in = (const float*)sat_cache; c.tile_index = tiles + done; c.n_tiles = n_tiles;
         c.grd_cache_in = (const float*)grd_cache; c.query_index = query.data() + done; c.n_queries = n_queries;
-        c.arena = h->arena; c.off = &pl->off; c.stream = s;
-        c.tickets = pl->tickets;
-        pl->set_scratch(c, 0);
         c.rows = pair_rows + (size_t)done * 5;
         c.stats = pair_stats + (size_t)done * 2;
         if (pair_log_prior) { c.log_prior = pair_log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
-        if (int rrc = run_ops(h, *pl, c, s)) return rrc;
-        if (c.conv_errors) return ccvpe_fail(CCVPE_EINVAL, "%d convolution launches were refused (unsupported geometry)", c.conv_errors);
-        done += mb;
-    }
+        return run_ops(h, *pl, c, s);
+    };
+    PlanKey key;   // (B: set per slice by the micro-batch loop)
+    key.gh = grd_h; key.gw = grd_w; key.mode = 4; key.pose = true;
+    if (int rc = for_each_micro_batch(h, key, P, s, slice)) return rc;
     launch_region_reduce(pair_stats, pair_rows, offsets, n_queries, rows, best_pair, tile_prob, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("kernel launch");
 }
 
 int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
@@ -788,13 +819,19 @@ int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queri
 // Localize with a per-query position prior: the pose plans with log_prior added to the logits where softmax.partial,
 // pose.argmax and topk.peaks read them - no launch of their own.
 // ------------------------------------------------------------------------------------------------
-// the prior arguments, checked before the handle is used; k == 0 is the argmax form, which takes no radius
-static int check_prior_args(const float* log_prior, int64_t prior_stride, int32_t k, int32_t radius) {
+// the stride between two queries' prior maps: one shared map or one map each
+static int check_prior_stride(int64_t prior_stride) {
     const int64_t n = (int64_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
-    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
     if (prior_stride != 0 && prior_stride != n)
         return ccvpe_fail(CCVPE_EINVAL, "prior_stride must be 0 (one shared map) or %lld (one map per query), got %lld", (long long)n,
                           (long long)prior_stride);
+    return 0;
+}
+
+// the prior arguments, checked before the handle is used; k == 0 is the argmax form, which takes no radius
+static int check_prior_args(const float* log_prior, int64_t prior_stride, int32_t k, int32_t radius) {
+    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
+    if (int rc = check_prior_stride(prior_stride)) return rc;
     if (k < 0 || k > TOPK_MAX_K) return ccvpe_fail(CCVPE_EINVAL, "k must be in 0 .. %d, got %d", TOPK_MAX_K, k);
     if (radius < 0 || radius > TOPK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TOPK_MAX_R, radius);
     if (k == 0 && radius != 0) return ccvpe_fail(CCVPE_EINVAL, "radius %d needs k >= 1: the argmax form (k = 0) takes radius 0", radius);
@@ -808,45 +845,43 @@ int ccvpe_localize_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, k, radius, nullptr, 0,
-                       log_prior, prior_stride);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius; fc.log_prior = log_prior; fc.prior_stride = prior_stride;
+    return run_forward(h, fc);
 }
 
 int ccvpe_localize_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
                                         const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride, int32_t k,
                                         int32_t radius, float* rows, void* stream) {
-    if (tile_index) {
-        if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
-    } else {   // query b reads tile b: the unindexed cached plan, whose cache holds exactly one tile per query
-        if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
-        if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
-        if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
-        if (n_tiles != batch)
-            return ccvpe_fail(CCVPE_EINVAL, "without tile_index the cache holds one tile per query: n_tiles %d != batch %d", n_tiles, batch);
-    }
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
     if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, k, radius,
-                       tile_index, tile_index ? n_tiles : 0, log_prior, prior_stride);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    fc.rows = rows; fc.topk_k = k; fc.topk_r = radius; fc.log_prior = log_prior; fc.prior_stride = prior_stride;
+    return run_forward(h, fc);
 }
 
-// scratch of ccvpe_postprocess_prior: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys][B x 64 indices][B x 64 x 2 softmax partials];
-// the argmax form's (max, index) hand-off pairs use the start of the key area.  Grows with the largest batch seen, as
-// ensure_topk_scratch.
-static size_t prior_scratch_bytes(int B) { return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float); }
+// The logits-based tails over forward outputs the caller holds, in the prior scratch `w`.  softmax.partial (logits + prior): the first
+// launch of both ...
+static void launch_logits_softmax(const TopkScratch& w, const float* logits, int batch, const float* prior, long long stride, hipStream_t s) {
+    SoftmaxParams sp{};
+    sp.logits = logits; sp.B = batch; sp.n = CCVPE_OUT_HW * CCVPE_OUT_HW; sp.partial = w.partial; sp.chunks = 64; sp.out = nullptr;
+    sp.prior = prior; sp.prior_stride = stride;
+    launch_softmax_partial(sp, s);
+}
 
-static int ensure_prior_scratch(ccvpe_handle_s* h, int batch) {
-    if (batch <= h->prior_batch) return 0;
-    HIPCHK(hipDeviceSynchronize());
-    if (h->prior_scratch) HIPCHK(hipFree(h->prior_scratch));
-    h->prior_scratch = nullptr; h->prior_batch = 0;
-    const int cap = std::max(batch, 32);
-    void* d = nullptr;
-    if (hipMalloc(&d, prior_scratch_bytes(cap)) != hipSuccess) return ccvpe_fail(CCVPE_ENOMEM, "prior post-processing scratch");
-    HIPCHK(hipMemset(d, 0, prior_scratch_bytes(cap)));
-    HIPCHK(hipDeviceSynchronize());
-    h->prior_scratch = d; h->prior_batch = cap;
-    return 0;
+// ... and softmax.partial -> pose.argmax -> pose.gather, the tail of an argmax pose plan (build_plan): prior and posterior are optional
+static void launch_logits_argmax(const TopkScratch& w, const float* logits, const float* ori, int batch, const float* prior, long long stride,
+                                 float* posterior, float* rows, hipStream_t s) {
+    const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
+    launch_logits_softmax(w, logits, batch, prior, stride, s);
+    PoseArgmaxParams p{};
+    p.logits = logits; p.partial = w.partial; p.B = batch; p.n = n; p.chunks = 64;
+    p.pairs = reinterpret_cast<float*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = rows; p.stats = nullptr;
+    p.prior = prior; p.prior_stride = stride; p.posterior = posterior;
+    launch_pose_argmax(p, s);
+    launch_pose_gather(ori, w.index, batch, n, rows, s);
 }
 
 int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
@@ -858,37 +893,21 @@ int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* or
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_prior_scratch(h, batch)) return rc;
-    const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
-    const int cap = h->prior_batch;
-    unsigned char* base = reinterpret_cast<unsigned char*>(h->prior_scratch);
-    unsigned* tickets = reinterpret_cast<unsigned*>(base);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
-    int* index = reinterpret_cast<int*>(keys + (size_t)cap * 64 * TOPK_MAX_K);
-    float* partial = reinterpret_cast<float*>(index + (size_t)cap * TOPK_MAX_K);
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
     hipStream_t s = (hipStream_t)stream;
-    SoftmaxParams sp{};
-    sp.logits = logits; sp.B = batch; sp.n = n; sp.partial = partial; sp.chunks = 64; sp.out = nullptr;
-    sp.prior = log_prior; sp.prior_stride = prior_stride;
-    launch_softmax_partial(sp, s);
     if (k == 0) {
-        PoseArgmaxParams p{};
-        p.logits = logits; p.partial = partial; p.B = batch; p.n = n; p.chunks = 64;
-        p.pairs = reinterpret_cast<float*>(keys); p.tickets = tickets; p.index = index; p.rows = rows; p.stats = nullptr;
-        p.prior = log_prior; p.prior_stride = prior_stride;
-        launch_pose_argmax(p, s);
-        launch_pose_gather(ori, index, batch, n, rows, s);
+        launch_logits_argmax(w, logits, ori, batch, log_prior, prior_stride, nullptr, rows, s);
     } else {
+        launch_logits_softmax(w, logits, batch, log_prior, prior_stride, s);
         TopkParams p{};
-        p.heat = nullptr; p.logits = logits; p.partial = partial; p.B = batch; p.k = k; p.r = radius;
-        p.keys = keys; p.tickets = tickets; p.index = index; p.rows = rows;
+        p.heat = nullptr; p.logits = logits; p.partial = w.partial; p.B = batch; p.k = k; p.r = radius;
+        p.keys = w.keys; p.tickets = w.tickets; p.index = w.index; p.rows = rows;
         p.prior = log_prior; p.prior_stride = prior_stride;
         launch_topk_peaks(p, s);
-        launch_topk_gather(ori, index, batch, k, n, rows, s);
+        launch_topk_gather(ori, w.index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, s);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "postprocess_prior launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("postprocess_prior launch");
 }
 
 int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
@@ -908,12 +927,9 @@ int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n
 // ------------------------------------------------------------------------------------------------
 // log_prior may be null (the map is then the forward's heatmap); the stride is checked only beside a prior
 static int check_track_update_args(const float* log_prior, int64_t prior_stride, const float* rows, const float* posterior) {
-    const int64_t n = (int64_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (!posterior) return ccvpe_fail(CCVPE_EINVAL, "null posterior");
-    if (log_prior && prior_stride != 0 && prior_stride != n)
-        return ccvpe_fail(CCVPE_EINVAL, "prior_stride must be 0 (one shared map) or %lld (one map per query), got %lld", (long long)n,
-                          (long long)prior_stride);
+    if (log_prior) if (int rc = check_prior_stride(prior_stride)) return rc;
     if (log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
     return 0;
 }
@@ -924,26 +940,21 @@ int ccvpe_track_update(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t 
     if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
     if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    return run_forward(h, grd, grd_h, grd_w, sat, batch, nullptr, (hipStream_t)stream, false, nullptr, rows, 0, 0, nullptr, 0, log_prior,
-                       log_prior ? prior_stride : 0, posterior);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    return run_forward(h, fc);
 }
 
 int ccvpe_track_update_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
                                       const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride, float* rows,
                                       float* posterior, void* stream) {
-    if (tile_index) {
-        if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
-    } else {   // query b reads tile b, as ccvpe_localize_prior_cached_indexed
-        if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
-        if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
-        if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
-        if (n_tiles != batch)
-            return ccvpe_fail(CCVPE_EINVAL, "without tile_index the cache holds one tile per query: n_tiles %d != batch %d", n_tiles, batch);
-    }
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
     if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    return run_forward(h, grd, grd_h, grd_w, nullptr, batch, nullptr, (hipStream_t)stream, false, (const float*)cache, rows, 0, 0,
-                       tile_index, tile_index ? n_tiles : 0, log_prior, log_prior ? prior_stride : 0, posterior);
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    return run_forward(h, fc);
 }
 
 int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
@@ -955,28 +966,10 @@ int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* 
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_prior_scratch(h, batch)) return rc;
-    const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
-    const int cap = h->prior_batch;   // the layout of ccvpe_postprocess_prior's scratch
-    unsigned char* base = reinterpret_cast<unsigned char*>(h->prior_scratch);
-    unsigned* tickets = reinterpret_cast<unsigned*>(base);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + (size_t)PP_MAX_BATCH * sizeof(unsigned));
-    int* index = reinterpret_cast<int*>(keys + (size_t)cap * 64 * TOPK_MAX_K);
-    float* partial = reinterpret_cast<float*>(index + (size_t)cap * TOPK_MAX_K);
-    hipStream_t s = (hipStream_t)stream;
-    SoftmaxParams sp{};
-    sp.logits = logits; sp.B = batch; sp.n = n; sp.partial = partial; sp.chunks = 64; sp.out = nullptr;
-    sp.prior = log_prior; sp.prior_stride = log_prior ? prior_stride : 0;
-    launch_softmax_partial(sp, s);
-    PoseArgmaxParams p{};
-    p.logits = logits; p.partial = partial; p.B = batch; p.n = n; p.chunks = 64;
-    p.pairs = reinterpret_cast<float*>(keys); p.tickets = tickets; p.index = index; p.rows = rows; p.stats = nullptr;
-    p.prior = log_prior; p.prior_stride = sp.prior_stride; p.posterior = posterior;
-    launch_pose_argmax(p, s);
-    launch_pose_gather(ori, index, batch, n, rows, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "track_update_logits launch failed: %s", hipGetErrorString(e));
-    return 0;
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, log_prior, log_prior ? prior_stride : 0, posterior, rows,
+                         (hipStream_t)stream);
+    return launch_status("track_update_logits launch");
 }
 
 int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps, int32_t taps_stride,
@@ -998,9 +991,7 @@ int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, cons
     p.belief = belief; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
     p.log_prior = log_prior; p.B = batch;
     launch_track_predict(p, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "track_predict launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("track_predict launch");
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,
@@ -1011,9 +1002,7 @@ int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, co
     p.in = hwc; p.B = batch; p.H = H; p.W = W; p.crop_w = crop_w; p.shift = shift; p.out = out_nchw;
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
     launch_preprocess(p, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "preprocess launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("preprocess launch");
 }
 
 
@@ -1028,9 +1017,7 @@ int ccvpe_preprocess_resize(const uint8_t* hwc, int32_t batch, int32_t in_h, int
     p.in = hwc; p.B = batch; p.IH = in_h; p.IW = in_w; p.OH = out_h; p.OW = out_w; p.crop_w = crop_w; p.tmp = scratch; p.shift = shift; p.out = out_nchw;
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
     if (launch_resize(p, (hipStream_t)stream) != 0) return ccvpe_fail(CCVPE_EINVAL, "down-scaling factors above 8 are not supported (%dx%d -> %dx%d)", in_h, in_w, out_h, out_w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "resize launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("resize launch");
 }
 
 int ccvpe_preprocess_affine(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const double* matrices, const int32_t* filters,
@@ -1054,9 +1041,7 @@ int ccvpe_preprocess_affine(const uint8_t* hwc, int32_t batch, int32_t H, int32_
     p.top = top; p.left = left; p.out_h = out_h; p.out_w = out_w; p.out = out_nchw;
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
     if (launch_warp(p, (hipStream_t)stream) != 0) return ccvpe_fail(CCVPE_EINVAL, "no kernel for this stage pattern");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "affine launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("affine launch");
 }
 
 int ccvpe_preprocess_window_resize(const uint8_t* map_hwc, int32_t map_h, int32_t map_w, const int32_t* origins, int32_t batch,
@@ -1073,9 +1058,7 @@ int ccvpe_preprocess_window_resize(const uint8_t* map_hwc, int32_t map_h, int32_
     p.origin = origins; p.map_h = map_h; p.map_w = map_w;
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.stdv[c] = stdv[c]; }
     if (launch_resize(p, (hipStream_t)stream) != 0) return ccvpe_fail(CCVPE_EINVAL, "down-scaling factors above 8 are not supported");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "window resize launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status("window resize launch");
 }
 
 int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
@@ -1099,7 +1082,7 @@ int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
     if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "checksum copy failed: %s", hipGetErrorString(e));
     FILE* f = std::fopen(path, "w");
     if (!f) return ccvpe_fail(CCVPE_EINVAL, "cannot open %s", path);
-    std::fprintf(f, "# plan B=%d grd=%dx%d mode=%d two_streams=%d tensors=%zu arena_floats=%zu\n", pl->B, pl->gh, pl->gw, pl->mode, (int)pl->two_streams, n, pl->total);
+    std::fprintf(f, "# plan B=%d grd=%dx%d mode=%d two_streams=%d tensors=%zu arena_floats=%zu\n", pl->key.B, pl->key.gh, pl->key.gw, pl->key.mode, (int)pl->two_streams, n, pl->total);
     for (size_t i = 0; i < pl->ops.size(); ++i) {
         const Op& op = pl->ops[i];
         std::fprintf(f, "op %zu %s stream=%d wait=%d signal=%d tile=%s", i, op.name.c_str(), op.stream, op.wait_on.empty() ? -1 : op.wait_on[0], (int)op.signal,

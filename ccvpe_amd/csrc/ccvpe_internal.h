@@ -260,6 +260,41 @@ struct Ctx {
     }
 };
 
+// What selects a plan: one key from the call descriptor (ForwardCall) through get_plan's lookup to build_plan
+struct PlanKey {
+    int B = 0, gh = 0, gw = 0;
+    int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding, 3 ground encode only,
+                                  // 4 pose plan from both caches (the pairs of ccvpe_localize_region)
+    bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
+    bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
+    bool operator==(const PlanKey& o) const { return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk; }
+};
+
+// One call of the forward family (run_forward, ccvpe_api.hip): every extern "C" entry point checks its own arguments, fills the fields
+// it has by name and leaves the rest at their defaults.  The fields that are set select the plan (plan_key) and what each slice's Ctx gets.
+struct ForwardCall {
+    const float* grd = nullptr;        // ground images [batch][3][gh][gw]
+    int gh = 0, gw = 0;
+    const float* sat = nullptr;        // full forms: aerial images [batch][3][512][512] (mode 0 plans) ...
+    const float* cache = nullptr;      // ... cached forms: the aerial cache of ccvpe_encode_aerial instead (mode 2 plans)
+    const int32_t* tile_index = nullptr;   // indexed cached forms: HOST tile of each sample (null: sample b reads tile b, batch <= micro_batch) ...
+    int n_tiles = 0;                   // ... and the tiles the cache holds (range of tile_index checked by the entry point)
+    int batch = 0;
+    const ccvpe_outputs* out = nullptr;   // the nine outputs, or ...
+    float* rows = nullptr;             // ... pose plans (ccvpe_localize*): [batch][5] result rows, `out` is not read
+    int topk_k = 0, topk_r = 0;        // topk_k > 0: top-K pose plans (ccvpe_localize_topk*), rows [batch][topk_k][5]; range checked by the entry point
+    const float* log_prior = nullptr;  // pose plans, optional (ccvpe_localize_prior*, ccvpe_track_update*): every slice reads its own maps ...
+    long long prior_stride = 0;        // ... this many floats apart (0: one map for all; checked by the entry point)
+    float* posterior = nullptr;        // argmax pose plans, optional (ccvpe_track_update*): every slice also writes its own posterior maps
+    hipStream_t stream = nullptr;
+    bool profile = false;              // ccvpe_profile_forward: a hipEvent pair around every launch
+    PlanKey plan_key() const {         // (B: set per slice by the micro-batch loop)
+        PlanKey key;
+        key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = rows != nullptr; key.topk = rows && topk_k > 0;
+        return key;
+    }
+};
+
 struct Op {
     std::string name;
     std::function<void(const Ctx&)> fn;
@@ -285,11 +320,7 @@ struct Op {
 struct TapInfo { Tensor t; int coff; int C; };
 
 struct Plan {
-    int B = 0, gh = 0, gw = 0;
-    int mode = 0;                 // 0 full forward, 1 aerial encode only, 2 forward from a cached aerial encoding, 3 ground encode only,
-                                  // 4 pose plan from both caches (the pairs of ccvpe_localize_region)
-    bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
-    bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
+    PlanKey key;
     bool debug = false;
     std::vector<size_t> size;     // floats per tensor
     std::vector<size_t> off;      // float offset in the arena
@@ -503,12 +534,12 @@ struct ccvpe_handle_s {
     int tuned_plans = 0;          // plans this handle has (partly) tuned by measurement (ccvpe_tuning_generation)
     float* arena = nullptr;
     size_t arena_floats = 0;
-    void* post_scratch = nullptr;   // launch_postprocess: partial pairs and ticket counters for post_batch samples
-    int post_batch = 0;
-    void* topk_scratch = nullptr;   // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices for topk_batch samples
-    int topk_batch = 0;
-    void* prior_scratch = nullptr;   // ccvpe_postprocess_prior: the top-K scratch plus softmax partials for prior_batch samples
-    int prior_batch = 0;
+    // Growable scratch of the three post-processing families (ensure_scratch, ccvpe_api.hip).  One buffer each: the families may be in
+    // flight on different streams of one handle at once, and every buffer carries its own ticket counters.
+    struct Scratch { void* ptr = nullptr; int batch = 0; };
+    Scratch post_scratch;         // launch_postprocess: partial pairs and ticket counters
+    Scratch topk_scratch;         // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices
+    Scratch prior_scratch;        // ccvpe_postprocess_prior, ccvpe_track_update_logits: the top-K scratch plus softmax partials
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;
@@ -527,9 +558,9 @@ ConvParams conv_params(const PackedConv& pc, const float* in, int in_ld, int B, 
                        int stride, int pad_t, int pad_l, int act);
 size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]);
 int ground_desc_floats(const ccvpe_handle_s* h, int gh, int gw);   // Ltot of a ground image (ground cache row), < 0: bad geometry
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode = 0, bool pose = false, bool topk = false);
+int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key);
 
 // ---- ccvpe_tune.hip ----
 int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known = nullptr);
-int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode = 0, bool pose = false, bool topk = false);
+int get_plan(ccvpe_handle_s* h, const PlanKey& key, Plan** out);
 std::string tuning_key(ccvpe_handle_s* h, const Plan& pl, const Op& op);

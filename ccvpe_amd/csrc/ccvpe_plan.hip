@@ -318,17 +318,18 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
 // Pair plans (mode 4, pose, ccvpe_localize_region): the cached pose plan with the ground side from a ground cache as well - the ground
 // encoder, grd.heads and grd.desc give way to grd.cached_desc, a gather of each pair's query row (Ctx::query_index); the aerial
 // launches gather each pair's tile (Ctx::tile_index).  Every other launch keeps the cached pose plan's name and tuning entry.
-int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, bool pose, bool topk) {
+int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
+    const int B = key.B, gh = key.gh, gw = key.gw, mode = key.mode;
+    const bool pose = key.pose;
+    pl.key = key;
+    pl.key.topk = pose && key.topk;
     if (mode == 1) return build_aerial_plan(h, pl, B);
     if (mode == 3) return build_ground_plan(h, pl, B, gh, gw);
     const bool cached = mode == 2 || mode == 4;
     const bool grd_cached = mode == 4;
-    if (grd_cached && (!pose || topk)) return ccvpe_fail(CCVPE_EINVAL, "pair plans are single-hypothesis pose plans");
-    pl.mode = mode;
-    pl.pose = pose;
-    pl.topk = pose && topk;
+    if (grd_cached && (!pose || key.topk)) return ccvpe_fail(CCVPE_EINVAL, "pair plans are single-hypothesis pose plans");
     const VariantSpec& vs = h->vs;
-    pl.B = B; pl.gh = gh; pl.gw = gw; pl.debug = h->debug;
+    pl.debug = h->debug;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
     pl.two_streams = h->sw.two_streams && !h->debug;
     pl.issue_interleaved = h->sw.issue_interleaved; pl.log_schedule = h->sw.log_schedule; pl.no_reuse = h->sw.no_reuse;
@@ -603,9 +604,11 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         }, 2.0 * B * 262144.0 * 144, 4.0 * B * 262144.0 * 17);
     }
     Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
-    if (pl.topk) {
-        Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, 2 * TOPK_MAX_K);
-        pose_index = pl.alloc(B, 1, 1, TOPK_MAX_K);
+    if (pose) {
+        static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
+        const bool topk = pl.key.topk;
+        Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, topk ? 2 * TOPK_MAX_K : 2);   // (argmax: the (max, index) hand-off pairs)
+        pose_index = pl.alloc(B, 1, 1, topk ? TOPK_MAX_K : 1);
         const Tensor lg = logits_ws, idx = pose_index;
         pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
             SoftmaxParams p{};
@@ -614,7 +617,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             launch_softmax_partial(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
         const size_t toff = pl.alloc_tickets((size_t)B);
-        pl.add("topk.peaks", {lg, part, keys, idx}, [=](const Ctx& c) {
+        if (topk) pl.add("topk.peaks", {lg, part, keys, idx}, [=](const Ctx& c) {
             TopkParams p{};
             p.heat = nullptr; p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.k = c.topk_k; p.r = c.topk_r;
             p.keys = reinterpret_cast<unsigned long long*>(c.ptr(keys)); p.tickets = c.tickets + toff;
@@ -622,22 +625,10 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_topk_peaks(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
-    } else if (pose) {
-        static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
-        Tensor part = pl.alloc(B, 1, 64, 2), pairs = pl.alloc(B, 1, 64, 2);
-        pose_index = pl.alloc(B, 1, 1, 1);
-        const Tensor lg = logits_ws, idx = pose_index;
-        pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
-            SoftmaxParams p{};
-            p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
-            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
-            launch_softmax_partial(p, c.stream);
-        }, 0, 4.0 * B * 262144.0);
-        const size_t toff = pl.alloc_tickets((size_t)B);
-        pl.add("pose.argmax", {lg, part, pairs, idx}, [=](const Ctx& c) {
+        else pl.add("pose.argmax", {lg, part, keys, idx}, [=](const Ctx& c) {
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
-            p.pairs = c.ptr(pairs); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
+            p.pairs = c.ptr(keys); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
             p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.posterior = c.posterior;
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
@@ -658,35 +649,26 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
         if (h->debug && !pose) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
         bool fused_done = false;
         for (int j = 0; j < 6; ++j) {
-            if (j == 5 && h->sw.fuse_level1 && pl.topk) {   // the fused level for the tile of each hypothesis (a wait on topk.peaks)
+            if (j == 5 && h->sw.fuse_level1 && pose) {   // the fused level for the tile of each sample's argmax / of each hypothesis (a wait on pose.argmax / topk.peaks)
                 const DecoderW& dw = h->ori;
                 Level1Params lp{};
                 lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
                 lp.c0 = dw.l1_c0; lp.ng = dw.l1_ng; lp.score = dw.l1_score; lp.wc = dw.l1_wc; lp.ws = dw.l1_ws; lp.bc = dw.l1_bc; lp.wt = dw.l1_wt;
                 lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = 2; lp.normalize = 1;
                 const Tensor din = xo, idx = pose_index;
-                const double px = (double)B * 8 * 16 * 16, cin_real = vs.ori[5].din;   // (accounted at K = 8)
-                pl.add("ori1.topk", {din, idx}, [=](const Ctx& c) {
+                const bool topk = pl.key.topk;
+                const double px = (double)B * (topk ? 8 : 1) * 16 * 16, cin_real = vs.ori[5].din;   // (top-K: accounted at K = 8)
+                const double flops = px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, bytes = 4.0 * px / 4 * lp.cx;
+                if (topk) pl.add("ori1.topk", {din, idx}, [=](const Ctx& c) {
                     Level1Params q = lp;
                     q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
                     launch_level1_topk(q, reinterpret_cast<const int*>(c.ptr(idx)), c.topk_k, c.rows, c.stream);
-                }, px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, 4.0 * px / 4 * lp.cx);
-                fused_done = true;
-                break;
-            }
-            if (j == 5 && h->sw.fuse_level1 && pose) {   // the fused level for the tile of each sample's argmax (a wait on pose.argmax)
-                const DecoderW& dw = h->ori;
-                Level1Params lp{};
-                lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
-                lp.c0 = dw.l1_c0; lp.ng = dw.l1_ng; lp.score = dw.l1_score; lp.wc = dw.l1_wc; lp.ws = dw.l1_ws; lp.bc = dw.l1_bc; lp.wt = dw.l1_wt;
-                lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = 2; lp.normalize = 1;
-                const Tensor din = xo, idx = pose_index;
-                const double px = (double)B * 16 * 16, cin_real = vs.ori[5].din;
-                pl.add("ori1.pose", {din, idx}, [=](const Ctx& c) {
+                }, flops, bytes);
+                else pl.add("ori1.pose", {din, idx}, [=](const Ctx& c) {
                     Level1Params q = lp;
                     q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
                     launch_level1_pose(q, reinterpret_cast<const int*>(c.ptr(idx)), c.rows, c.stream);
-                }, px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, 4.0 * px / 4 * lp.cx);
+                }, flops, bytes);
                 fused_done = true;
                 break;
             }
@@ -710,7 +692,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
             p.normalize = 1; p.out = pose ? c.ptr(ori_ws) : c.out.ori; p.raw = dbg ? c.ptr(raw) : nullptr;
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 288, 4.0 * B * 262144.0 * 18);
-        if (pl.topk) {
+        if (pl.key.topk) {
             const Tensor idx = pose_index;
             pl.add("ori1.topk_gather", {ori_ws, idx}, [=](const Ctx& c) {
                 launch_topk_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, c.topk_k, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
@@ -736,7 +718,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw, int mode, boo
 // Ground-only plan (mode 3, ccvpe_encode_ground): the full plan's ground encoder, grd.heads and grd.desc - the same launches, names and
 // shapes (the encoder's latency-plan spread depends on the ground geometry only) - with grd.desc writing into the caller's ground cache.
 static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw) {
-    pl.B = B; pl.gh = gh; pl.gw = gw; pl.mode = 3; pl.debug = false;
+    pl.debug = false;
     pl.no_reuse = h->sw.no_reuse;
     int fh, fw, L[6];
     if (int rc = grd_geometry(h->vs, gh, gw, fh, fw, L)) return rc;
@@ -753,7 +735,7 @@ static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw)
 
 static int build_aerial_plan(ccvpe_handle_s* h, Plan& pl, int B) {
     const VariantSpec& vs = h->vs;
-    pl.B = B; pl.gh = 0; pl.gw = 0; pl.mode = 1; pl.debug = false;
+    pl.debug = false;
     pl.no_reuse = h->sw.no_reuse;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
     EncOut senc;

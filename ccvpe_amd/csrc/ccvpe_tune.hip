@@ -14,7 +14,7 @@
 static constexpr size_t TUNING_KEY_MAX = 255;
 std::string tuning_key(ccvpe_handle_s* h, const Plan& pl, const Op& op) {
     char head[64], tail[64];
-    std::snprintf(head, sizeof(head), "v%d_r%d_c%d_p%d_b%d|", h->cfg.variant, h->rolls[1], h->cfg.circular_padding, h->cfg.reserved[0], pl.B);
+    std::snprintf(head, sizeof(head), "v%d_r%d_c%d_p%d_b%d|", h->cfg.variant, h->rolls[1], h->cfg.circular_padding, h->cfg.reserved[0], pl.key.B);
     std::snprintf(tail, sizeof(tail), "|%dx%dx%d|%d%d%d%d%s%s", op.gemm_m, op.gemm_n, op.gemm_kpad, op.wino_ok ? 1 : 0, op.wino4_ok ? 1 : 0,
                   op.is_pw ? 1 : 0, op.bf16x3_only ? 1 : 0, op.wino4x_ok ? "x" : "", op.proj_ok ? "p" : "");
     std::string key = std::string(head) + op.name + tail;
@@ -205,11 +205,11 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
     return 0;
 }
 
-int get_plan(ccvpe_handle_s* h, int B, int gh, int gw, Plan** out, int mode, bool pose, bool topk) {
+int get_plan(ccvpe_handle_s* h, const PlanKey& key, Plan** out) {
     for (auto& p : h->plans)
-        if (p->B == B && p->gh == gh && p->gw == gw && p->mode == mode && p->pose == pose && p->topk == topk && (mode == 1 || mode == 3 || p->debug == h->debug)) { *out = p.get(); return 0; }
+        if (p->key == key && (key.mode == 1 || key.mode == 3 || p->debug == h->debug)) { *out = p.get(); return 0; }
     auto pl = std::make_unique<Plan>();
-    int rc = build_plan(h, *pl, B, gh, gw, mode, pose, topk);
+    int rc = build_plan(h, *pl, key);
     if (rc) return rc;
     if (pl->total > h->arena_floats) {
         // growing the arena is the only synchronising step; it happens on the first call per shape

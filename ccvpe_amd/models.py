@@ -254,17 +254,56 @@ class _CVMBase(nn.Module):
             out.matching_score[k] = ms[k].data_ptr()
         return out, (logits, heat, ori, *ms)
 
-    def forward(self, grd: torch.Tensor, sat: torch.Tensor):
-        grd, sat = self._prepare(grd, sat)
-        B = grd.shape[0]
-        with torch.cuda.device(grd.device):
-            out, tensors = self._alloc_outputs(B, grd.device)
-            stream = torch.cuda.current_stream(grd.device).cuda_stream
-            rc = _lib.load().ccvpe_forward(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                           C.c_void_p(sat.data_ptr()), B, C.byref(out), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_forward")
+    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False):
+        """The skeleton forward and the pose forms share: validate and normalise grd and sat - or, sat=None, the cache and tile_index of a
+        cached form -, ensure the handle, allocate the results, call ccvpe_<name> under the inputs' device on its current stream, check
+        the return code, sync the tuning table.  args(B) holds the method's own argument checks, run after those of the inputs, and
+        returns the C arguments between batch and the results; a tensor among them, the log_prior, must be on the inputs' device and is
+        passed by pointer, None as a null pointer.  Returns the nine outputs (outputs=True) or rows [B, 5] (k = 0, the argmax forms) /
+        [B, k, 5] (k as the method received it: args has checked it), with the posterior [B, 512, 512] behind them if asked.
+        Cached forms: ccvpe_<name> takes a nullable tile_index if the name ends in _indexed; the older forms have two entry points each,
+        ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it."""
+        if sat is not None:
+            grd, sat = self._prepare(grd, sat)
+        else:
+            if self.training:
+                raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+            idx = self._host_tile_index(tile_index, grd)
+            if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
+                raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        extra, k = args(grd.shape[0]), int(k)
+        if any(isinstance(a, torch.Tensor) and a.device != grd.device for a in extra):
+            raise ValueError("log_prior must be on the inputs' device")
+        if sat is not None:
+            src = (C.c_void_p(sat.data_ptr()),)
+        else:
+            grd = grd.detach().to(torch.float32).contiguous()
+            self._ensure_handle(grd.device)
+            n_tiles = self._cache_tiles(cache, grd.shape[0], idx)
+            src = (C.c_void_p(cache.data_ptr()),)
+            if name.endswith("_indexed") or idx is not None:
+                name = name if name.endswith("_indexed") else name + "_indexed"
+                src += (n_tiles, idx.ctypes.data_as(C.c_void_p) if idx is not None else None)
+        B, dev = grd.shape[0], grd.device
+        with torch.cuda.device(dev):
+            if outputs:
+                out, res = self._alloc_outputs(B, dev)
+                ptrs = (C.byref(out),)
+            else:
+                res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
+                if posterior:
+                    res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
+                ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
+            extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3], *src, B,
+                                                       *extra, *ptrs, C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_" + name)
         self._tuning_sync()
-        return tensors
+        return res if outputs or posterior else res[0]
+
+    def forward(self, grd: torch.Tensor, sat: torch.Tensor):
+        return self._call("forward", grd, sat, outputs=True)
 
     # ---- aerial-side caching for streaming (SURVEY 8f row 4) -------------------------------
     def encode_aerial(self, sat: torch.Tensor) -> torch.Tensor:
@@ -274,15 +313,20 @@ class _CVMBase(nn.Module):
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
         if not sat.is_cuda or sat.dim() != 4 or tuple(sat.shape[1:]) != (3,) + spec.SAT_HW:
             raise ValueError("sat must be a cuda tensor [B,3,512,512]")
-        sat = sat.detach().to(torch.float32).contiguous()
-        self._ensure_handle(sat.device)
+        return self._encode("aerial", sat)
+
+    def _encode(self, side: str, img: torch.Tensor, hw=()) -> torch.Tensor:
+        """encode_aerial / encode_ground behind their input checks: the cache of ccvpe_<side>_cache_bytes, written by ccvpe_encode_<side>
+        (hw: the image size, an argument of the ground side only), with the image count recorded on it."""
+        img = img.detach().to(torch.float32).contiguous()
+        self._ensure_handle(img.device)
         lib = _lib.load()
-        B = sat.shape[0]
-        nbytes = lib.ccvpe_aerial_cache_bytes(self._handle, B)
-        cache = torch.empty(nbytes // 4, dtype=torch.float32, device=sat.device)
-        stream = torch.cuda.current_stream(sat.device).cuda_stream
-        _lib.check(lib.ccvpe_encode_aerial(self._handle, C.c_void_p(sat.data_ptr()), B, C.c_void_p(cache.data_ptr()),
-                                           C.c_void_p(stream)), "ccvpe_encode_aerial")
+        B = img.shape[0]
+        nbytes = getattr(lib, f"ccvpe_{side}_cache_bytes")(self._handle, B, *hw)
+        cache = torch.empty(nbytes // 4, dtype=torch.float32, device=img.device)
+        stream = torch.cuda.current_stream(img.device).cuda_stream
+        _lib.check(getattr(lib, f"ccvpe_encode_{side}")(self._handle, C.c_void_p(img.data_ptr()), *hw, B, C.c_void_p(cache.data_ptr()),
+                                                         C.c_void_p(stream)), f"ccvpe_encode_{side}")
         self._tuning_sync()
         cache._ccvpe_batch = B
         return cache
@@ -325,29 +369,7 @@ class _CVMBase(nn.Module):
         """forward(grd, sat) with the aerial side taken from encode_aerial(sat).  tile_index (host ints [B], optional): query b
         reads tile tile_index[b] of a cache encode_aerial wrote for any number of tiles up to the micro-batch, and B may then
         be any size (ccvpe_forward_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        idx = self._host_tile_index(tile_index, grd)
-        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        grd = grd.detach().to(torch.float32).contiguous()
-        self._ensure_handle(grd.device)
-        B = grd.shape[0]
-        n_tiles = self._cache_tiles(cache, B, idx)
-        out, tensors = self._alloc_outputs(B, grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        lib = _lib.load()
-        if idx is None:
-            rc = lib.ccvpe_forward_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                          C.c_void_p(cache.data_ptr()), B, C.byref(out), C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_forward_cached")
-        else:
-            rc = lib.ccvpe_forward_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                  C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B,
-                                                  C.byref(out), C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_forward_cached_indexed")
-        self._tuning_sync()
-        return tensors
+        return self._call("forward_cached", grd, cache=cache, tile_index=tile_index, outputs=True)
 
     # ---- one ground encoding against several aerial tiles ---------------------------------------
     def encode_ground(self, grd: torch.Tensor) -> torch.Tensor:
@@ -357,19 +379,11 @@ class _CVMBase(nn.Module):
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
         if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
             raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        grd = grd.detach().to(torch.float32).contiguous()
         self._ensure_handle(grd.device)
-        lib = _lib.load()
         B, H, W = grd.shape[0], grd.shape[2], grd.shape[3]
-        nbytes = lib.ccvpe_ground_cache_bytes(self._handle, B, H, W)
-        if nbytes == 0:
+        if _lib.load().ccvpe_ground_cache_bytes(self._handle, B, H, W) == 0:   # (a size the variant does not take)
             _lib.check(-1, "ccvpe_ground_cache_bytes")
-        cache = torch.empty(nbytes // 4, dtype=torch.float32, device=grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        _lib.check(lib.ccvpe_encode_ground(self._handle, C.c_void_p(grd.data_ptr()), H, W, B, C.c_void_p(cache.data_ptr()),
-                                           C.c_void_p(stream)), "ccvpe_encode_ground")
-        self._tuning_sync()
-        cache._ccvpe_batch = B
+        cache = self._encode("ground", grd, (H, W))
         cache._ccvpe_grd_hw = (H, W)
         return cache
 
@@ -420,10 +434,19 @@ class _CVMBase(nn.Module):
             pair_rows [P,5]  localize rows of each pair, the probability inside its tile;
             pair_stats [P,2] (max logit, 1 / sum exp) of each pair's softmax;
             tile_prob [P]    each pair's share of its query's summed softmax mass (ccvpe_localize_region)."""
+        return self._region(ground_cache, sat_cache, tiles)
+
+    _NO_PRIOR = object()   # (not None: localize_region_prior refuses a None prior as it refuses any other non-tensor)
+
+    def _region(self, ground_cache, sat_cache, tiles, pair_log_prior=_NO_PRIOR) -> Dict[str, object]:
+        """localize_region and, with a pair_log_prior, localize_region_prior."""
+        prior = pair_log_prior is not self._NO_PRIOR
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
         offsets, flat = self._host_region_tiles(tiles)
         G, P = offsets.shape[0] - 1, flat.shape[0]
+        if prior:
+            lp, stride, _, _ = self._prior_args(pair_log_prior, P, 0, 0)
         for what, c in (("ground_cache", ground_cache), ("sat_cache", sat_cache)):
             if not isinstance(c, torch.Tensor) or not c.is_cuda:
                 raise ValueError(f"{what} must be the cuda tensor encode_{'ground' if what == 'ground_cache' else 'aerial'} returned")
@@ -433,6 +456,8 @@ class _CVMBase(nn.Module):
             raise ValueError("sat_cache must come from encode_aerial (it records how many tiles the cache holds)")
         if int(ground_cache._ccvpe_batch) != G:
             raise ValueError(f"tiles names {G} queries, ground_cache holds {ground_cache._ccvpe_batch}")
+        if prior and lp.device != ground_cache.device:
+            raise ValueError("pair_log_prior must be on the caches' device")
         self._ensure_handle(ground_cache.device)
         dev = ground_cache.device
         H, W = ground_cache._ccvpe_grd_hw
@@ -442,12 +467,13 @@ class _CVMBase(nn.Module):
         pair_stats = torch.empty((P, 2), dtype=torch.float32, device=dev)
         tile_prob = torch.empty((P,), dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.load().ccvpe_localize_region(self._handle, C.c_void_p(ground_cache.data_ptr()), G, H, W, C.c_void_p(sat_cache.data_ptr()),
-                                               int(sat_cache._ccvpe_batch), offsets.ctypes.data_as(C.c_void_p),
-                                               flat.ctypes.data_as(C.c_void_p), C.c_void_p(rows.data_ptr()), C.c_void_p(pair.data_ptr()),
-                                               C.c_void_p(pair_rows.data_ptr()), C.c_void_p(pair_stats.data_ptr()),
-                                               C.c_void_p(tile_prob.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_region")
+        name = "ccvpe_localize_region_prior" if prior else "ccvpe_localize_region"
+        rc = getattr(_lib.load(), name)(self._handle, C.c_void_p(ground_cache.data_ptr()), G, H, W, C.c_void_p(sat_cache.data_ptr()),
+                                        int(sat_cache._ccvpe_batch), offsets.ctypes.data_as(C.c_void_p), flat.ctypes.data_as(C.c_void_p),
+                                        *((C.c_void_p(lp.data_ptr()), stride) if prior else ()), C.c_void_p(rows.data_ptr()),
+                                        C.c_void_p(pair.data_ptr()), C.c_void_p(pair_rows.data_ptr()), C.c_void_p(pair_stats.data_ptr()),
+                                        C.c_void_p(tile_prob.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, name)
         self._tuning_sync()
         return {"rows": rows, "pair": pair, "pair_tile": flat, "pair_rows": pair_rows, "pair_stats": pair_stats, "tile_prob": tile_prob}
 
@@ -455,44 +481,13 @@ class _CVMBase(nn.Module):
     def localize(self, grd: torch.Tensor, sat: torch.Tensor) -> torch.Tensor:
         """The pose of every query without the nine forward outputs: float32 [B, 5] on the device, the postprocess_rows layout
         (index, prob, cos, sin, angle_deg).  Bit-identical to postprocess_rows(*forward(grd, sat)[1:3]) (ccvpe_localize)."""
-        grd, sat = self._prepare(grd, sat)
-        B = grd.shape[0]
-        with torch.cuda.device(grd.device):
-            rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
-            stream = torch.cuda.current_stream(grd.device).cuda_stream
-            rc = _lib.load().ccvpe_localize(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                            C.c_void_p(sat.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize")
-        self._tuning_sync()
-        return rows
+        return self._call("localize", grd, sat)
 
     def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor, tile_index=None) -> torch.Tensor:
         """localize(grd, sat) with the aerial side taken from encode_aerial(sat): float32 [B, 5] rows (index, prob, cos, sin,
         angle_deg), the postprocess_rows layout (ccvpe_localize_cached).  tile_index: as forward_cached
         (ccvpe_localize_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        idx = self._host_tile_index(tile_index, grd)
-        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        grd = grd.detach().to(torch.float32).contiguous()
-        self._ensure_handle(grd.device)
-        B = grd.shape[0]
-        n_tiles = self._cache_tiles(cache, B, idx)
-        rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        lib = _lib.load()
-        if idx is None:
-            rc = lib.ccvpe_localize_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                           C.c_void_p(cache.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_localize_cached")
-        else:
-            rc = lib.ccvpe_localize_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                   C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B,
-                                                   C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_localize_cached_indexed")
-        self._tuning_sync()
-        return rows
+        return self._call("localize_cached", grd, cache=cache, tile_index=tile_index)
 
     # ---- several pose hypotheses per query ----------------------------------------------------
     @staticmethod
@@ -508,47 +503,13 @@ class _CVMBase(nn.Module):
         """The k strongest heatmap peaks of every query under a suppression radius, with their orientation: float32 [B, k, 5]
         on the device, rows (index, prob, cos, sin, angle_deg); (-1, 0, 0, 0, 0) past a query's last peak.  Bit-identical to
         postprocess_topk(*forward(grd, sat)[1:3], k, radius) (ccvpe_localize_topk)."""
-        grd, sat = self._prepare(grd, sat)
-        k, radius = self._topk_args(k, radius)
-        B = grd.shape[0]
-        with torch.cuda.device(grd.device):
-            rows = torch.empty((B, k, 5), dtype=torch.float32, device=grd.device)
-            stream = torch.cuda.current_stream(grd.device).cuda_stream
-            rc = _lib.load().ccvpe_localize_topk(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                 C.c_void_p(sat.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
-                                                 C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_topk")
-        self._tuning_sync()
-        return rows
+        return self._call("localize_topk", grd, sat, args=lambda B: self._topk_args(k, radius), k=k)
 
     def localize_topk_cached(self, grd: torch.Tensor, cache: torch.Tensor, k: int, radius: int, tile_index=None) -> torch.Tensor:
         """localize_topk(grd, sat, k, radius) with the aerial side taken from encode_aerial(sat): float32 [B, k, 5]
         (ccvpe_localize_topk_cached).  tile_index: as forward_cached (ccvpe_localize_topk_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        idx = self._host_tile_index(tile_index, grd)
-        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        k, radius = self._topk_args(k, radius)
-        grd = grd.detach().to(torch.float32).contiguous()
-        self._ensure_handle(grd.device)
-        B = grd.shape[0]
-        n_tiles = self._cache_tiles(cache, B, idx)
-        rows = torch.empty((B, k, 5), dtype=torch.float32, device=grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        lib = _lib.load()
-        if idx is None:
-            rc = lib.ccvpe_localize_topk_cached(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                C.c_void_p(cache.data_ptr()), B, k, radius, C.c_void_p(rows.data_ptr()),
-                                                C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_localize_topk_cached")
-        else:
-            rc = lib.ccvpe_localize_topk_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                        C.c_void_p(cache.data_ptr()), n_tiles, idx.ctypes.data_as(C.c_void_p), B, k,
-                                                        radius, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-            _lib.check(rc, "ccvpe_localize_topk_cached_indexed")
-        self._tuning_sync()
-        return rows
+        return self._call("localize_topk_cached", grd, cache=cache, tile_index=tile_index, args=lambda B: self._topk_args(k, radius),
+                          k=k)
 
     def postprocess_topk(self, heatmap: torch.Tensor, ori: torch.Tensor, k: int, radius: int) -> torch.Tensor:
         """postprocess_rows() generalised to the k strongest peaks under a suppression radius, on forward outputs the caller
@@ -607,72 +568,49 @@ class _CVMBase(nn.Module):
         without a finite posterior (a prior of -inf everywhere) has index -1."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        lp, stride, k, radius = self._prior_args(log_prior, grd.shape[0], k, radius)
-        grd, sat = self._prepare(grd, sat)
-        if lp.device != grd.device:
-            raise ValueError("log_prior must be on the inputs' device")
-        B = grd.shape[0]
-        with torch.cuda.device(grd.device):
-            rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=grd.device)
-            stream = torch.cuda.current_stream(grd.device).cuda_stream
-            rc = _lib.load().ccvpe_localize_prior(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                  C.c_void_p(sat.data_ptr()), B, C.c_void_p(lp.data_ptr()), stride, k, radius,
-                                                  C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_prior")
-        self._tuning_sync()
-        return rows
+        own = self._prior_args(log_prior, grd.shape[0], k, radius)   # (before the inputs' checks)
+        return self._call("localize_prior", grd, sat, args=lambda B: own, k=k)
 
     def localize_prior_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0,
                               tile_index=None) -> torch.Tensor:
         """localize_prior(grd, sat, log_prior, k, radius) with the aerial side taken from encode_aerial(sat); tile_index as
         forward_cached (ccvpe_localize_prior_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        idx = self._host_tile_index(tile_index, grd)
-        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        lp, stride, k, radius = self._prior_args(log_prior, grd.shape[0], k, radius)
-        if lp.device != grd.device:
-            raise ValueError("log_prior must be on the inputs' device")
-        grd = grd.detach().to(torch.float32).contiguous()
-        self._ensure_handle(grd.device)
-        B = grd.shape[0]
-        n_tiles = self._cache_tiles(cache, B, idx)
-        rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        rc = _lib.load().ccvpe_localize_prior_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                             C.c_void_p(cache.data_ptr()), n_tiles,
-                                                             idx.ctypes.data_as(C.c_void_p) if idx is not None else None, B,
-                                                             C.c_void_p(lp.data_ptr()), stride, k, radius, C.c_void_p(rows.data_ptr()),
-                                                             C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_prior_cached_indexed")
-        self._tuning_sync()
-        return rows
+        return self._call("localize_prior_cached_indexed", grd, cache=cache, tile_index=tile_index,
+                          args=lambda B: self._prior_args(log_prior, B, k, radius), k=k)
 
-    def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
-                          ) -> torch.Tensor:
-        """The rows of localize_prior from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori =
-        forward(...)[2] ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_prior)."""
+    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False):
+        """postprocess_prior and track_update_logits: validate and normalise the forward outputs the caller holds, check the prior with
+        args(B) and take k (both as _call's), allocate rows (and the posterior) and call ccvpe_<name>."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
         B = logits.shape[0] if logits.dim() > 0 else 0
         if logits.numel() != B * self.PRIOR_MAP or ori.numel() != B * 2 * self.PRIOR_MAP or B == 0:
             raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
-        lp, stride, k, radius = self._prior_args(log_prior, B, k, radius)
+        extra, k = args(B), int(k)
         if not (logits.is_cuda and ori.is_cuda):
             raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
-        if not (lp.device == logits.device == ori.device):
+        if logits.device != ori.device or any(isinstance(a, torch.Tensor) and a.device != logits.device for a in extra):
             raise ValueError("logits, ori and log_prior must be on one device")
         logits = logits.detach().to(torch.float32).contiguous()
         ori = ori.detach().to(torch.float32).contiguous()
-        self._ensure_handle(logits.device)
-        rows = torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=logits.device)
-        stream = torch.cuda.current_stream(logits.device).cuda_stream
-        rc = _lib.load().ccvpe_postprocess_prior(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B,
-                                                 C.c_void_p(lp.data_ptr()), stride, k, radius, C.c_void_p(rows.data_ptr()),
-                                                 C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_postprocess_prior")
-        return rows
+        dev = logits.device
+        self._ensure_handle(dev)
+        with torch.cuda.device(dev):
+            res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
+            if posterior:
+                res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
+            extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, *extra,
+                                                       *(C.c_void_p(t.data_ptr()) for t in res), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_" + name)
+        return res if posterior else res[0]
+
+    def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
+                          ) -> torch.Tensor:
+        """The rows of localize_prior from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori =
+        forward(...)[2] ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_prior)."""
+        return self._logits_call("postprocess_prior", logits, ori, lambda B: self._prior_args(log_prior, B, k, radius), k=k)
 
     def localize_region_prior(self, ground_cache: torch.Tensor, sat_cache: torch.Tensor, tiles, pair_log_prior: torch.Tensor
                               ) -> Dict[str, object]:
@@ -680,41 +618,7 @@ class _CVMBase(nn.Module):
         flattened pair order (query by query, each query's tiles in order), each map on one scale across a query's tiles - a
         log-density at every heatmap pixel's map position, such as aerial.oxford_log_prior.  Returns localize_region's dict, every
         value of the posterior (ccvpe_localize_region_prior)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        offsets, flat = self._host_region_tiles(tiles)
-        G, P = offsets.shape[0] - 1, flat.shape[0]
-        lp, stride, _, _ = self._prior_args(pair_log_prior, P, 0, 0)
-        for what, c in (("ground_cache", ground_cache), ("sat_cache", sat_cache)):
-            if not isinstance(c, torch.Tensor) or not c.is_cuda:
-                raise ValueError(f"{what} must be the cuda tensor encode_{'ground' if what == 'ground_cache' else 'aerial'} returned")
-        if not hasattr(ground_cache, "_ccvpe_grd_hw"):
-            raise ValueError("ground_cache must come from encode_ground (it records the image count and size)")
-        if not hasattr(sat_cache, "_ccvpe_batch"):
-            raise ValueError("sat_cache must come from encode_aerial (it records how many tiles the cache holds)")
-        if int(ground_cache._ccvpe_batch) != G:
-            raise ValueError(f"tiles names {G} queries, ground_cache holds {ground_cache._ccvpe_batch}")
-        if lp.device != ground_cache.device:
-            raise ValueError("pair_log_prior must be on the caches' device")
-        self._ensure_handle(ground_cache.device)
-        dev = ground_cache.device
-        H, W = ground_cache._ccvpe_grd_hw
-        rows = torch.empty((G, 5), dtype=torch.float32, device=dev)
-        pair = torch.empty((G,), dtype=torch.int32, device=dev)
-        pair_rows = torch.empty((P, 5), dtype=torch.float32, device=dev)
-        pair_stats = torch.empty((P, 2), dtype=torch.float32, device=dev)
-        tile_prob = torch.empty((P,), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = _lib.load().ccvpe_localize_region_prior(self._handle, C.c_void_p(ground_cache.data_ptr()), G, H, W,
-                                                     C.c_void_p(sat_cache.data_ptr()), int(sat_cache._ccvpe_batch),
-                                                     offsets.ctypes.data_as(C.c_void_p), flat.ctypes.data_as(C.c_void_p),
-                                                     C.c_void_p(lp.data_ptr()), stride, C.c_void_p(rows.data_ptr()),
-                                                     C.c_void_p(pair.data_ptr()), C.c_void_p(pair_rows.data_ptr()),
-                                                     C.c_void_p(pair_stats.data_ptr()), C.c_void_p(tile_prob.data_ptr()),
-                                                     C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_localize_region_prior")
-        self._tuning_sync()
-        return {"rows": rows, "pair": pair, "pair_tile": flat, "pair_rows": pair_rows, "pair_stats": pair_stats, "tile_prob": tile_prob}
+        return self._region(ground_cache, sat_cache, tiles, pair_log_prior)
 
     # ---- tracking a frame stream (DESIGN.md 4.11) ----------------------------------------------
     @classmethod
@@ -733,73 +637,19 @@ class _CVMBase(nn.Module):
         and an all-zero map (ccvpe_track_update)."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        lp, stride = self._track_prior(log_prior, grd.shape[0])
-        grd, sat = self._prepare(grd, sat)
-        if lp is not None and lp.device != grd.device:
-            raise ValueError("log_prior must be on the inputs' device")
-        B = grd.shape[0]
-        with torch.cuda.device(grd.device):
-            rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
-            post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=grd.device)
-            stream = torch.cuda.current_stream(grd.device).cuda_stream
-            rc = _lib.load().ccvpe_track_update(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                C.c_void_p(sat.data_ptr()), B, C.c_void_p(lp.data_ptr()) if lp is not None else None,
-                                                stride, C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_track_update")
-        self._tuning_sync()
-        return rows, post
+        own = self._track_prior(log_prior, grd.shape[0])   # (before the inputs' checks)
+        return self._call("track_update", grd, sat, args=lambda B: own, posterior=True)
 
     def track_update_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, tile_index=None):
         """track_update(grd, sat, log_prior) with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
         (ccvpe_track_update_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        idx = self._host_tile_index(tile_index, grd)
-        if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        lp, stride = self._track_prior(log_prior, grd.shape[0])
-        if lp is not None and lp.device != grd.device:
-            raise ValueError("log_prior must be on the inputs' device")
-        grd = grd.detach().to(torch.float32).contiguous()
-        self._ensure_handle(grd.device)
-        B = grd.shape[0]
-        n_tiles = self._cache_tiles(cache, B, idx)
-        rows = torch.empty((B, 5), dtype=torch.float32, device=grd.device)
-        post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=grd.device)
-        stream = torch.cuda.current_stream(grd.device).cuda_stream
-        rc = _lib.load().ccvpe_track_update_cached_indexed(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3],
-                                                           C.c_void_p(cache.data_ptr()), n_tiles,
-                                                           idx.ctypes.data_as(C.c_void_p) if idx is not None else None, B,
-                                                           C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
-                                                           C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_track_update_cached_indexed")
-        self._tuning_sync()
-        return rows, post
+        return self._call("track_update_cached_indexed", grd, cache=cache, tile_index=tile_index,
+                          args=lambda B: self._track_prior(log_prior, B), posterior=True)
 
     def track_update_logits(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None):
         """track_update from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
         ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_track_update_logits)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        B = logits.shape[0] if logits.dim() > 0 else 0
-        if logits.numel() != B * self.PRIOR_MAP or ori.numel() != B * 2 * self.PRIOR_MAP or B == 0:
-            raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
-        lp, stride = self._track_prior(log_prior, B)
-        if not (logits.is_cuda and ori.is_cuda):
-            raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
-        if not (logits.device == ori.device and (lp is None or lp.device == logits.device)):
-            raise ValueError("logits, ori and log_prior must be on one device")
-        logits = logits.detach().to(torch.float32).contiguous()
-        ori = ori.detach().to(torch.float32).contiguous()
-        self._ensure_handle(logits.device)
-        rows = torch.empty((B, 5), dtype=torch.float32, device=logits.device)
-        post = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=logits.device)
-        stream = torch.cuda.current_stream(logits.device).cuda_stream
-        rc = _lib.load().ccvpe_track_update_logits(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B,
-                                                   C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
-                                                   C.c_void_p(rows.data_ptr()), C.c_void_p(post.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_track_update_logits")
-        return rows, post
+        return self._logits_call("track_update_logits", logits, ori, lambda B: self._track_prior(log_prior, B), posterior=True)
 
     @staticmethod
     def _track_vec(value, what: str, shape, dev):
