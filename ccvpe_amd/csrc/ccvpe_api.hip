@@ -183,18 +183,18 @@ size_t ccvpe_workspace_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32
 // heuristic when a tile cannot serve a launch (a hand-edited or foreign tuning table): legal, but then "same table -> same launches ->
 // same bits" no longer holds, so it is said out loud once per plan.
 static void check_issued_tile(Plan& pl, const Op& op) {
-    const int got = conv_igemm_last_tile();
+    const int got = conv_tile_last();
     if (!op.tile || (*op.tile & 0xff) == 0 || got == 0) return;
     const int want = *op.tile, ws = (want >> 8) & 0xff, gs = (got >> 8) & 0xff;
     if ((want & 0xff) != (got & 0xff) || (ws > 1 ? ws : 1) != (gs > 1 ? gs : 1))
         std::fprintf(stderr, "ccvpe: launch %s (batch %d) runs %s split %d instead of the planned %s split %d\n", op.name.c_str(), pl.key.B,
-                     conv_igemm_tile_name(got), gs, conv_igemm_tile_name(want), ws);
+                     conv_tile_name(got), gs, conv_tile_name(want), ws);
 }
 
 static int run_ops(ccvpe_handle h, Plan& pl, const Ctx& base, hipStream_t s0) {
     const bool check = !pl.tiles_checked;
     pl.tiles_checked = true;
-    if (check) (void)conv_igemm_last_tile();
+    if (check) (void)conv_tile_last();
     if (!pl.two_streams || h->serial_issue) {
         Ctx c = base;
         c.stream = s0;
@@ -361,18 +361,18 @@ static int issue_forward(ccvpe_handle h, Plan* pl, Ctx& c, const ForwardCall& fc
         HIPCHK(hipEventCreate(&e0));
         HIPCHK(hipEventCreate(&e1));
         for (auto& op : pl->ops) {
-            (void)conv_igemm_last_tile();
+            (void)conv_tile_last();
             HIPCHK(hipEventRecord(e0, stream));
             op.fn(c);
             HIPCHK(hipEventRecord(e1, stream));
             HIPCHK(hipEventSynchronize(e1));
             float ms = 0.f;
             HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-            const int tile = conv_igemm_last_tile();
+            const int tile = conv_tile_last();
             std::string nm = op.name;
             double issued = op.flops;   // launches that are not tiled GEMMs: issued == algorithmic
-            if (tile) {
-                nm += std::string("|") + conv_igemm_tile_name(tile);
+            if (const ConvTile* t = conv_tile(tile)) {
+                nm += std::string("|") + t->name;
                 if ((tile >> 8) == 255) nm += "_tailsplit";
                 else if ((tile >> 8) > SPLIT_FUSED) nm += "_splitk" + std::to_string((tile >> 8) - SPLIT_FUSED) + "r";   // r: reduces itself
                 else if ((tile >> 8) > 1) nm += "_splitk" + std::to_string(tile >> 8);
@@ -380,11 +380,11 @@ static int issue_forward(ccvpe_handle h, Plan* pl, Ctx& c, const ForwardCall& fc
                 // Winograd F(2x2,3x3): 16 products per 2x2 output tile and channel pair; bf16x3: three MFMAs per product
                 ConvParams q{};
                 q.M = op.gemm_m; q.N = op.gemm_n;
-                const double util = conv_igemm_tile_util(q, tile & 0xff);
+                const double util = conv_tile_util(q, *t);
                 const double mn_pad = util > 0 ? (double)op.gemm_m * op.gemm_n / util : 0.0;
-                if (conv_igemm_tile_is_wino4(tile)) issued = 2.0 * mn_pad * 2.25 * ((op.conv_cin + 3) / 4 * 4);   // 36 products per 4x4 tile; k-steps of 4 channels, all-zero ones skipped
-                else if (conv_igemm_tile_is_wino(tile)) issued = 2.0 * mn_pad * 4.0 * op.conv_cin;
-                else issued = 2.0 * mn_pad * op.gemm_kpad * (conv_igemm_tile_is_bf16x3(tile) ? 3.0 : 1.0);
+                if (t->wino_f == 4) issued = 2.0 * mn_pad * 2.25 * ((op.conv_cin + 3) / 4 * 4);   // 36 products per 4x4 tile; k-steps of 4 channels, all-zero ones skipped
+                else if (t->wino_f == 2) issued = 2.0 * mn_pad * 4.0 * op.conv_cin;
+                else issued = 2.0 * mn_pad * op.gemm_kpad * (t->family == TILE_BF16X3 ? 3.0 : 1.0);
             }
             h->prof.push_back({nm, ms, op.flops, op.bytes, issued});
         }
@@ -1086,7 +1086,7 @@ int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
     for (size_t i = 0; i < pl->ops.size(); ++i) {
         const Op& op = pl->ops[i];
         std::fprintf(f, "op %zu %s stream=%d wait=%d signal=%d tile=%s", i, op.name.c_str(), op.stream, op.wait_on.empty() ? -1 : op.wait_on[0], (int)op.signal,
-                     op.tile ? conv_igemm_tile_name(*op.tile & 0xff) : "-");
+                     op.tile ? conv_tile_name(*op.tile) : "-");
         if (op.tile && (*op.tile >> 8) == 255) std::fprintf(f, "_tailsplit");
         else if (op.tile && (*op.tile >> 8) > SPLIT_FUSED) std::fprintf(f, "_splitk%dr", (*op.tile >> 8) - SPLIT_FUSED);
         else if (op.tile && (*op.tile >> 8) > 1) std::fprintf(f, "_splitk%d", *op.tile >> 8);
@@ -1115,8 +1115,8 @@ int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
     return 0;
 }
 
-int ccvpe_op_num_tiles(void) { return conv_igemm_num_tiles(); }
-const char* ccvpe_op_tile_name(int32_t tile) { return conv_igemm_tile_name(tile); }
+int ccvpe_op_num_tiles(void) { return conv_num_tiles(); }
+const char* ccvpe_op_tile_name(int32_t tile) { return conv_tile_name(tile); }
 
 int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
                     int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, int32_t tile,
@@ -1161,7 +1161,7 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
         tmp.dev_alloc_bytes.push_back(fl * sizeof(float));
         p.partial = (float*)d; p.partial_floats = fl;
     }
-    if (conv_igemm_tile_is_wino(tile) && !conv_wino_tile_supported(p, tile)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "layer is not Winograd-shaped (3x3, stride 1, pad 1, W %% 16 == 0, H %% 16 == 0, output channels a multiple of 4; F(4x4): >= 40 of them)"); }
+    if (const ConvTile* t = conv_tile(tile); t && t->family == TILE_WINO && !conv_tile_runs(*t, p)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "layer is not Winograd-shaped (3x3, stride 1, pad 1, W %% 16 == 0, H %% 16 == 0, output channels a multiple of 4; F(4x4): >= 40 of them)"); }
     if (launch_conv_igemm(p, tile, st) != 0) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "unsupported conv geometry (KH*KW <= 16, Cin %% 8 == 0)"); }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && iters > 0 && ms) {

@@ -252,10 +252,12 @@ struct Ctx {
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
     mutable size_t conv_tick_off = 0;   // ticket range of the convolution launch being issued (set by Plan::add_conv's wrapper)
+    mutable ConvParams* probe = nullptr;   // autotune_plan: the launch is not issued, its parameters are copied here
     void launch_conv(ConvParams& p, int cfg) const {
         p.tickets = tickets ? tickets + conv_tick_off : nullptr;
         p.partial = splitk_scratch;
         p.partial_floats = splitk_floats;
+        if (probe) { *probe = p; return; }
         if (launch_conv_igemm(p, cfg, stream) != 0) ++conv_errors;
     }
 };

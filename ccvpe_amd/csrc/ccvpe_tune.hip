@@ -24,8 +24,8 @@ std::string tuning_key(ccvpe_handle_s* h, const Plan& pl, const Op& op) {
 
 static int tile_by_name(const std::string& name) {
     if (name == "auto") return 0;
-    for (int t = 1; t <= conv_igemm_num_tiles(); ++t)
-        if (name == conv_igemm_tile_name(t)) return t;
+    for (int t = 1; t <= conv_num_tiles(); ++t)
+        if (name == conv_tile_name(t)) return t;
     return -1;
 }
 
@@ -54,7 +54,7 @@ static void record_tuning(ccvpe_handle_s* h, const Plan& pl) {
         if (!op.tile) continue;
         const int cfg = *op.tile;
         const std::string key = tuning_key(h, pl, op);
-        if (!key.empty()) h->tuning[key] = {(cfg & 0xff) ? conv_igemm_tile_name(cfg & 0xff) : "auto", (cfg >> 8) & 0xff};
+        if (!key.empty()) h->tuning[key] = {(cfg & 0xff) ? conv_tile_name(cfg) : "auto", (cfg >> 8) & 0xff};
     }
 }
 
@@ -114,40 +114,35 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     launch_fill_random(h->arena, pl.total, 0x9e3779b9u, nullptr);
-    const int nt = conv_igemm_num_tiles();
+    const int nt = conv_num_tiles();
     const Switches& sw = h->sw;
     for (size_t oi = 0; oi < pl.ops.size(); ++oi) {
         Op& op = pl.ops[oi];
         if (!op.tile || (known && (*known)[oi])) continue;   // launches the tuning table covers are not measured
-        ConvParams q{};
-        q.M = op.gemm_m; q.N = op.gemm_n;
+        ConvParams q{};   // the launch's own parameters: what conv_tile_runs asks about
+        c.probe = &q;
+        op.fn(c);
+        c.probe = nullptr;
         int best = 0;
         float best_ms = 1e30f;
         const int nkt = op.gemm_kpad / 32;
         for (int t = 1; t <= nt; ++t) {
-            if (conv_igemm_tile_util(q, t) < 0.45) continue;
-            if (conv_igemm_tile_is_bf16x3(t) && (h->cfg.reserved[0] != 1 || sw.tune_no_bf16x3)) continue;
-            if (op.bf16x3_only && !conv_igemm_tile_is_bf16x3(t)) continue;
-            if (conv_igemm_tile_is_wino(t) && !op.wino_ok) continue;
-            if (conv_igemm_tile_is_wino4x(t)) { if (!op.wino4x_ok || conv_igemm_tile_wino4x_cfg(t) != conv_wino4x_config(op.gemm_n)) continue; }
-            else if (conv_igemm_tile_is_wino4(t) && !op.wino4_ok) continue;
-            if (sw.tune_prefer_pw && op.is_pw && !op.bf16x3_only && !conv_igemm_tile_is_pw(t) && op.gemm_kpad <= 512) continue;
-            if (sw.tune_prefer_proj && op.proj_ok && !conv_igemm_tile_is_proj(t)) continue;
-            if (sw.tune_prefer_lat && op.proj_ok && op.gemm_m <= 4096 && conv_igemm_tile_proj_rt(t) < 100) continue;
-            if (conv_igemm_tile_is_proj(t)) {
-                const int rt = conv_igemm_tile_proj_rt(t);   // row tiles per workgroup; >= 100: the latency form (small M only)
-                if (!op.proj_ok || !conv_proj_has(rt, op.gemm_n) || sw.no_pw) continue;
-                if (rt >= 100 && (op.gemm_m > 4096 || op.gemm_kpad > 10240)) continue;   // (conv_proj_supported has the exact rule)
-                // the multi-row forms (conv_projl_r2 / r4) win the level-6 transposed convs by 1 us when timed alone (17.7 against 18.8 us) and lose
-                // in the frame, where the two decoders run that layer at the same time: 2 x 256 sixteen-wave workgroups, one per CU - 31.7 us
-                // each in the traced frame against ~24 for the four-wave implicit GEMM.  CCVPE_TUNE_LAT_ROWS=1 times them all the same.
-                if (rt > 104 && (!sw.tune_lat_rows || op.gemm_m > 1024)) continue;
-            } else if (conv_igemm_tile_is_pw(t)) {
-                ConvParams qq{}; qq.M = 16; qq.N = 1 << 20;
-                const int bn = (int)(((long long)qq.N) / conv_igemm_tile_blocks(qq, t));   // the tile's column width
-                if (!op.is_pw || op.bf16x3_only || !conv_pw_fits(bn, op.gemm_kpad) || sw.no_pw) continue;
-            }
-            const long long blocks = conv_igemm_tile_blocks(q, t);
+            const ConvTile& ct = *conv_tile(t);
+            const int splits = conv_tile_splits(ct);
+            const bool wino = ct.family == TILE_WINO, pw = ct.family == TILE_PW;
+            if (conv_tile_util(q, ct) < 0.45 || !conv_tile_runs(ct, q)) continue;   // (the latency forms' row and depth limits among the rest: conv_proj_supported has the exact rule)
+            // what the plan allows the op (precision, switches), beyond what the kernels can run
+            if (ct.family == TILE_BF16X3 ? h->cfg.reserved[0] != 1 || sw.tune_no_bf16x3 : op.bf16x3_only) continue;
+            if (wino && !(ct.xcfg >= 0 ? op.wino4x_ok : ct.wino_f == 4 ? op.wino4_ok : op.wino_ok)) continue;
+            if (pw && (sw.no_pw || !(ct.proj_rt > 0 ? op.proj_ok : op.is_pw))) continue;
+            if (sw.tune_prefer_pw && op.is_pw && !op.bf16x3_only && !pw && op.gemm_kpad <= 512) continue;
+            if (sw.tune_prefer_proj && op.proj_ok && ct.proj_rt == 0) continue;
+            if (sw.tune_prefer_lat && op.proj_ok && op.gemm_m <= 4096 && ct.proj_rt < 100) continue;
+            // the multi-row forms (conv_projl_r2 / r4) win the level-6 transposed convs by 1 us when timed alone (17.7 against 18.8 us) and lose
+            // in the frame, where the two decoders run that layer at the same time: 2 x 256 sixteen-wave workgroups, one per CU - 31.7 us
+            // each in the traced frame against ~24 for the four-wave implicit GEMM.  CCVPE_TUNE_LAT_ROWS=1 times them all the same.
+            if (ct.proj_rt > 104 && (!sw.tune_lat_rows || op.gemm_m > 1024)) continue;
+            const long long blocks = conv_tile_blocks(q, ct);
             const bool no_split = sw.tune_splitk == 0;
             // the persistent Winograd grids also try odd split factors: 160 work items on 256 resident workgroups (conv6.0) are
             // 3 rounds of quarter items with split 4 but 2 rounds of thirds with split 3
@@ -155,29 +150,28 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
             // (20 / 24 / 32 slices were timed for the batch-1 decoder layers in round 4 - two workgroups per CU instead of one: never picked)
             for (int split : SPLITS) {
                 if (split > 1 && no_split) break;
-                if (split == 255 && (!conv_igemm_tile_is_wino4(t) || conv_igemm_tile_is_wino4x(t))) continue;
-                if (split > 1 && (split & (split - 1)) && !conv_igemm_tile_is_wino(t)) continue;
+                if (split == 255 && !(splits & SPLIT_TAIL)) continue;
+                if (split > 1 && (split & (split - 1)) && !wino) continue;
                 // the latency form can split K (self-reducing, layers without a gate) but never wins: a sixteen-wave workgroup is alone on its CU
                 // and lives ~6 us whatever its share of K, so S times as many workgroups are S times as many rounds (tools/time_lat_gemm.py:
                 // level-6 transposed conv 18 / 25 / 41 / 73 us at S = 1 / 2 / 4 / 8).  CCVPE_TUNE_LAT_SPLIT=1 times them all the same.
-                const bool lat_split = sw.tune_lat_split && conv_igemm_tile_proj_rt(t) >= 100 && op.gemm_m <= 256;
-                if (split > 1 && conv_igemm_tile_is_pw(t) && !lat_split) break;   // the pointwise persistent tiles keep K whole
+                const bool lat_split = sw.tune_lat_split && ct.proj_rt >= 100 && op.gemm_m <= 256;
+                if (split > 1 && pw && !lat_split) break;   // the pointwise persistent tiles keep K whole
                 if (split > 1 && split != 255) {   // split-K only where the grid underfills the chip and K is deep enough
                     // (the persistent Winograd grid also splits when the tile count is an awkward multiple of the
                     // 512 resident workgroups: 640 tiles = 1.25 per workgroup, 4 x 640 quarter-tiles = 5 each)
-                    const bool wino = conv_igemm_tile_is_wino(t);
                     if (blocks >= (wino ? 2048 : 512) || blocks * split > (wino ? 8192 : 2048) || nkt < 4 * split) break;
                     if ((size_t)split * op.gemm_m * op.gemm_n > Plan::SPLITK_FLOATS) break;
                 }
-                for (int fuse = (split > 1 && conv_igemm_tile_is_pw(t)) ? 1 : 0; fuse < 2; ++fuse) {   // a split launch: with the reduce launch, and reducing itself (ticket.h) where the kernel can
-                if (fuse && (split <= 1 || split == 255 || !conv_igemm_tile_can_fuse_split(t) || pl.tickets == nullptr || sw.tune_no_fused_split)) break;
+                for (int fuse = (split > 1 && pw) ? 1 : 0; fuse < 2; ++fuse) {   // a split launch: with the reduce launch, and reducing itself (ticket.h) where the kernel can
+                if (fuse && (split <= 1 || split == 255 || !(splits & SPLIT_SELF) || pl.tickets == nullptr || sw.tune_no_fused_split)) break;
                 const int cfg = t | ((fuse ? split + SPLIT_FUSED : split) << 8);
                 *op.tile = cfg;
                 op.fn(c);   // warm-up (also sets the dynamic-LDS attribute on first use)
-                const int ran = conv_igemm_last_tile();   // (tile | split code << 8 of the launch just issued; reading it clears it)
-                if ((ran & 0xff) != t) break;   // the launch did not take this tile (launch_conv_igemm fell back to its own pick): nothing to time under this name
+                const int ran = conv_tile_last();   // (tile | split code << 8 of the launch just issued; reading it clears it)
+                if ((ran & 0xff) != t) break;   // the launch did not take this tile (an op that names its own: the squeeze-excite project conv): nothing to time under this name
                 if (split == 255 && (ran >> 8) != 255) break;   // tail split not applicable to this grid
-                if (split > 1 && conv_igemm_tile_is_pw(t) && ((ran >> 8) & 0xff) <= 1) break;   // (a gated layer: the launch kept K whole)
+                if (split > 1 && pw && ((ran >> 8) & 0xff) <= 1) break;   // (a gated layer: the launch kept K whole)
                 float ms = 1e30f;
                 for (int trial = 0; trial < 3; ++trial) {   // min of three timed pairs: one noisy sample must not pick the tile
                     HIPCHK(hipEventRecord(e0, nullptr));
@@ -190,7 +184,7 @@ int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known) {
                     ms = std::min(ms, t);
                 }
                 if (!sw.tune_verbose.empty() && op.name.find(sw.tune_verbose) != std::string::npos)
-                    std::fprintf(stderr, "tune %-28s %-28s split %3d%s: %8.1f us\n", op.name.c_str(), conv_igemm_tile_name(t), split, fuse ? " self-reducing" : "", 500.0 * ms);
+                    std::fprintf(stderr, "tune %-28s %-28s split %3d%s: %8.1f us\n", op.name.c_str(), ct.name, split, fuse ? " self-reducing" : "", 500.0 * ms);
                 if (ms < best_ms) { best_ms = ms; best = cfg; }
                 }
             }

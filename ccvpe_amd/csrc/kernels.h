@@ -117,63 +117,69 @@ struct ConvParams {
     const float* se_b2;        // [Cin]
 };
 
-// tile = 0 picks automatically from (M, N); otherwise one of the TILE_* ids.
+// One descriptor per tiled convolution kernel.  Every family file keeps its array beside its launchers (conv_*_tiles) and
+// kernels_igemm.hip concatenates them once, in the order igemm, bf16x3, wino, pw: tile id = index + 1, 0 picks from (M, N).
+// A launch cfg word is tile | (split code << 8).
 enum { TILE_AUTO = 0 };
+enum TileFamily { TILE_IGEMM, TILE_BF16X3, TILE_WINO, TILE_PW };
+using ConvLaunch = void (*)(const ConvParams&, hipStream_t);
+struct ConvTile {
+    int bm, bn;                // output pixels / channels per workgroup (padding of M and N)
+    const char* name;
+    ConvLaunch launch;
+    TileFamily family;
+    double intrinsic = 0.0;    // prior of the shape heuristic (pick_tile); 0: only a tuning table or the autotuner names the tile
+    int wino_f = 0;            // Winograd output tile edge, 2 or 4
+    int xcfg = -1;             // >= 0: xi-split F(4x4) configuration (kernels_wino4x.hip)
+    int proj_rt = 0;           // > 0: a kernels_proj.hip tile of that many row tiles; >= 100: its latency form
+};
+// one constructor per family: a table row names only what its family has
+constexpr ConvTile igemm_tile(int bm, int bn, const char* name, ConvLaunch l, double intrinsic) { return {bm, bn, name, l, TILE_IGEMM, intrinsic}; }
+constexpr ConvTile bf16x3_tile(int bm, int bn, const char* name, ConvLaunch l) { return {bm, bn, name, l, TILE_BF16X3}; }
+constexpr ConvTile wino_tile(int bm, int bn, const char* name, ConvLaunch l, int f, int xcfg = -1) { return {bm, bn, name, l, TILE_WINO, 0.0, f, xcfg}; }
+constexpr ConvTile pw_tile(int bm, int bn, const char* name, ConvLaunch l, int proj_rt = 0) { return {bm, bn, name, l, TILE_PW, 0.0, 0, -1, proj_rt}; }
 static constexpr int CONV_TICKETS = 8192;   // ticket counters a convolution launch may use (output regions of a split-K launch)
-static constexpr int SPLIT_FUSED = 64;       // split code 64 + S: S slices, reduced by the last arriver (S <= 32)      // tile ids are 1..conv_igemm_num_tiles(); a launch cfg word is tile | (splitk << 8)
-int conv_igemm_num_tiles();
-double conv_igemm_tile_util(const ConvParams& p, int tile);
-long long conv_igemm_tile_blocks(const ConvParams& p, int tile);
+static constexpr int SPLIT_FUSED = 64;       // split code 64 + S: S slices, reduced by the last arriver (S <= 32)
+int conv_num_tiles();
+const ConvTile* conv_tile(int id);           // by tile id or cfg word (masks & 0xff); null for 0 and ids past the last
+const char* conv_tile_name(int id);          // "" where conv_tile is null
+int conv_proj_lat_tile();                    // id of conv_projl_1: the one kernel that computes squeeze-excite gates itself
+bool conv_tile_runs(const ConvTile& t, const ConvParams& p);   // the form the tile needs is packed and the layer is shaped for it
+// the split codes a tile takes beyond a plain K split with the reduce launch: self-reducing (SPLIT_FUSED + S), the F(4x4) tail split (255).
+// The pointwise family (TILE_PW) keeps K whole; its latency form splits it only self-reducing.
+enum { SPLIT_SELF = 1, SPLIT_TAIL = 2 };
+int conv_tile_splits(const ConvTile& t);
+double conv_tile_util(const ConvParams& p, const ConvTile& t);
+long long conv_tile_blocks(const ConvParams& p, const ConvTile& t);
+int conv_tile_last();        // cfg word of the most recent launch on this thread (then reset to 0)
 int conv_igemm_prepare(ConvParams& p);
 int conv_igemm_k_index(int cin, int taps, int tap, int c);   // packed-weight column of (tap, channel)
 int launch_conv_igemm(const ConvParams& p, int tile, hipStream_t s);   // 0, or -1 for unsupported geometry
 int conv_igemm_npad();       // row padding of packed weights (multiple every tile divides)
-bool conv_igemm_tile_is_bf16x3(int tile);
-bool conv_igemm_tile_can_fuse_split(int tile);   // the kernel reduces its own split-K when given the split code SPLIT_FUSED + S
 void launch_splitk_reduce(const ConvParams& p, hipStream_t s);
-struct Bf16x3Tile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); };
-int bf16x3_num_tiles();
-const Bf16x3Tile* bf16x3_tile(int i);
-struct WinoTile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); int f; int xcfg; };   // f: output tile edge, 2 or 4; xcfg >= 0: xi-split configuration
-int wino_num_tiles();
-const WinoTile* wino_tile(int i);
+const ConvTile* conv_bf16x3_tiles(int* n);
+const ConvTile* conv_wino_tiles(int* n);
 bool conv_wino_supported(const ConvParams& p);
 bool conv_wino4_supported(const ConvParams& p);
-bool conv_wino_tile_supported(const ConvParams& p, int tile);   // the form tile id `tile` needs is packed and the layer is shaped for it
-bool conv_igemm_tile_is_wino4(int tile);
 void launch_wino4_64(const ConvParams& p, hipStream_t s);
 void launch_wino4_128(const ConvParams& p, hipStream_t s);
 bool conv_wino4_tail_applied();
-bool conv_igemm_tile_is_wino4x(int tile);
-int conv_igemm_tile_wino4x_cfg(int tile);   // xi-split configuration of the tile, -1 for other tiles
 void launch_wino4x(const ConvParams& p, hipStream_t s);       // xi-split form (kernels_wino4x.hip)
 bool conv_wino4x_supported(const ConvParams& p);
 int conv_wino4x_config(int N);
 size_t conv_wino4x_pack(int N, int cin, const std::function<float(int, int, int)>& get, std::vector<float>& out, int* cfg_out);
 size_t conv_wino4_pack(int N, int cin, const std::function<float(int, int, int)>& get, std::vector<float>& out);
-bool conv_igemm_tile_is_wino(int tile);
 size_t conv_wino_pack(int N, int cin, const std::function<float(int, int, int)>& get, std::vector<float>& out, int* n16_out);
 // pointwise persistent kernel (kernels_pw.hip): 1x1 convs / k2s2 transposed convs with K <= 512
-struct PwTile { int bm, bn; const char* name; void (*launch)(const ConvParams&, hipStream_t); int proj_rt; };   // proj_rt > 0: a kernels_proj.hip tile of that many row tiles
-int pw_num_tiles();
-const PwTile* pw_tile(int i);
+const ConvTile* conv_pw_tiles(int* n);
 bool conv_pw_supported(const ConvParams& p);
 bool conv_pw_fits(int bn, int kpad);
-bool conv_pw_tile_ok(int i, const ConvParams& p);   // tile i of the family can run this launch
-int conv_pw_tile_proj_rt(int i);                    // row-tile code of a kernels_proj.hip tile (>= 100: its latency form), 0 for the others
-int conv_igemm_tile_proj_rt(int tile);              // the same by tile id
-int conv_proj_lat_tile();                           // tile id of conv_projl_1 (the latency form with one column tile per workgroup)
 // deep-K project GEMM (kernels_proj.hip)
 bool conv_proj_supported(const ConvParams& p, int rt);
 void launch_proj(const ConvParams& p, int rt, hipStream_t s);
 bool conv_proj_wanted(int N, int cin);
-bool conv_proj_has(int rt, int N);
 size_t conv_proj_pack(int N, int cin, const std::function<float(int, int)>& get, std::vector<float>& out, int taps = 1);
 bool conv_proj_lat_wanted(int taps, int KH, int KW, int cinp);   // deep-K 1x1 / k2s2 layers the latency form may serve
-bool conv_igemm_tile_is_pw(int tile);
-bool conv_igemm_tile_is_proj(int tile);   // a kernels_proj.hip tile (member of the pointwise family)
-int conv_igemm_last_tile();  // tile id of the most recent launch on this thread (then reset to 0)
-const char* conv_igemm_tile_name(int tile);
 
 // ---------------------------------------------------------------------------------------------
 // Encoder pieces

@@ -19,6 +19,9 @@
 #include "igemm_common.h"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 namespace ccvpe {
 
@@ -334,117 +337,111 @@ static void launch_cfg(const ConvParams& p, hipStream_t s) {
     else launch_cfg2<BM, BN, WGM, WGN, MT, false, NS>(p, s);
 }
 
-// Tile table.  id = index + 1 (0 is TILE_AUTO).  `intrinsic` is only the prior used when the plan has not been
-// autotuned (ccvpe_api.hip times every candidate per layer on the device and keeps the fastest).
-struct TileCfg { int bm, bn; double intrinsic; const char* name; void (*launch)(const ConvParams&, hipStream_t); };
-static const TileCfg TILES[] = {
-    {128, 128, 0.95, "conv_igemm_128x128_m32", launch_cfg<128, 128, 2, 2, 32>},
-    {128, 64, 0.85, "conv_igemm_128x64_m32", launch_cfg<128, 64, 2, 2, 32>},
-    {64, 64, 0.85, "conv_igemm_64x64_m32", launch_cfg<64, 64, 2, 2, 32>},
-    {128, 32, 0.85, "conv_igemm_128x32_m32", launch_cfg<128, 32, 4, 1, 32>},
-    {256, 16, 0.60, "conv_igemm_256x16_m16", launch_cfg<256, 16, 4, 1, 16>},
-    {128, 48, 0.85, "conv_igemm_128x48_m16", launch_cfg<128, 48, 4, 1, 16>},
-    {128, 80, 1.00, "conv_igemm_128x80_m16", launch_cfg<128, 80, 4, 1, 16>},
-    {256, 32, 0.70, "conv_igemm_256x32_m32", launch_cfg<256, 32, 4, 1, 32>},
-    {128, 128, 1.00, "conv_igemm_128x128_m16", launch_cfg<128, 128, 2, 2, 16>},
-    {128, 64, 0.95, "conv_igemm_128x64_m16", launch_cfg<128, 64, 2, 2, 16>},
-    {128, 32, 0.85, "conv_igemm_128x32_m16", launch_cfg<128, 32, 4, 1, 16>},
-    {128, 16, 0.60, "conv_igemm_128x16_m16", launch_cfg<128, 16, 4, 1, 16>},
-    {128, 96, 1.00, "conv_igemm_128x96_m16", launch_cfg<128, 96, 4, 1, 16>},
-    {128, 112, 1.00, "conv_igemm_128x112_m16", launch_cfg<128, 112, 4, 1, 16>},
-    {64, 64, 0.85, "conv_igemm_64x64_m16", launch_cfg<64, 64, 2, 2, 16>},
-    {64, 32, 0.70, "conv_igemm_64x32_m16", launch_cfg<64, 32, 2, 2, 16>},
-    {256, 48, 0.85, "conv_igemm_256x48_m16", launch_cfg<256, 48, 4, 1, 16>},
-    {64, 128, 0.90, "conv_igemm_64x128_m16", launch_cfg<64, 128, 2, 2, 16>},
+// The fp32 implicit-GEMM tiles.  `intrinsic` is only the prior used when the plan has not been autotuned (ccvpe_tune.hip
+// times every candidate per layer on the device and keeps the fastest).
+static const ConvTile IGEMM_TILES[] = {
+    igemm_tile(128, 128, "conv_igemm_128x128_m32", launch_cfg<128, 128, 2, 2, 32>, 0.95),
+    igemm_tile(128, 64, "conv_igemm_128x64_m32", launch_cfg<128, 64, 2, 2, 32>, 0.85),
+    igemm_tile(64, 64, "conv_igemm_64x64_m32", launch_cfg<64, 64, 2, 2, 32>, 0.85),
+    igemm_tile(128, 32, "conv_igemm_128x32_m32", launch_cfg<128, 32, 4, 1, 32>, 0.85),
+    igemm_tile(256, 16, "conv_igemm_256x16_m16", launch_cfg<256, 16, 4, 1, 16>, 0.60),
+    igemm_tile(128, 48, "conv_igemm_128x48_m16", launch_cfg<128, 48, 4, 1, 16>, 0.85),
+    igemm_tile(128, 80, "conv_igemm_128x80_m16", launch_cfg<128, 80, 4, 1, 16>, 1.00),
+    igemm_tile(256, 32, "conv_igemm_256x32_m32", launch_cfg<256, 32, 4, 1, 32>, 0.70),
+    igemm_tile(128, 128, "conv_igemm_128x128_m16", launch_cfg<128, 128, 2, 2, 16>, 1.00),
+    igemm_tile(128, 64, "conv_igemm_128x64_m16", launch_cfg<128, 64, 2, 2, 16>, 0.95),
+    igemm_tile(128, 32, "conv_igemm_128x32_m16", launch_cfg<128, 32, 4, 1, 16>, 0.85),
+    igemm_tile(128, 16, "conv_igemm_128x16_m16", launch_cfg<128, 16, 4, 1, 16>, 0.60),
+    igemm_tile(128, 96, "conv_igemm_128x96_m16", launch_cfg<128, 96, 4, 1, 16>, 1.00),
+    igemm_tile(128, 112, "conv_igemm_128x112_m16", launch_cfg<128, 112, 4, 1, 16>, 1.00),
+    igemm_tile(64, 64, "conv_igemm_64x64_m16", launch_cfg<64, 64, 2, 2, 16>, 0.85),
+    igemm_tile(64, 32, "conv_igemm_64x32_m16", launch_cfg<64, 32, 2, 2, 16>, 0.70),
+    igemm_tile(256, 48, "conv_igemm_256x48_m16", launch_cfg<256, 48, 4, 1, 16>, 0.85),
+    igemm_tile(64, 128, "conv_igemm_64x128_m16", launch_cfg<64, 128, 2, 2, 16>, 0.90),
     // single-stage forms of the tiles the shallow layers use (prior 0: only the autotuner picks them)
-    {64, 64, 0.0, "conv_igemm_64x64_m16_s1", launch_cfg<64, 64, 2, 2, 16, 1>},
-    {64, 32, 0.0, "conv_igemm_64x32_m16_s1", launch_cfg<64, 32, 2, 2, 16, 1>},
-    {64, 64, 0.0, "conv_igemm_64x64_m32_s1", launch_cfg<64, 64, 2, 2, 32, 1>},
-    {128, 48, 0.0, "conv_igemm_128x48_m16_s1", launch_cfg<128, 48, 4, 1, 16, 1>},
-    {128, 16, 0.0, "conv_igemm_128x16_m16_s1", launch_cfg<128, 16, 4, 1, 16, 1>},
-    {128, 80, 0.0, "conv_igemm_128x80_m16_s1", launch_cfg<128, 80, 4, 1, 16, 1>},
+    igemm_tile(64, 64, "conv_igemm_64x64_m16_s1", launch_cfg<64, 64, 2, 2, 16, 1>, 0.0),
+    igemm_tile(64, 32, "conv_igemm_64x32_m16_s1", launch_cfg<64, 32, 2, 2, 16, 1>, 0.0),
+    igemm_tile(64, 64, "conv_igemm_64x64_m32_s1", launch_cfg<64, 64, 2, 2, 32, 1>, 0.0),
+    igemm_tile(128, 48, "conv_igemm_128x48_m16_s1", launch_cfg<128, 48, 4, 1, 16, 1>, 0.0),
+    igemm_tile(128, 16, "conv_igemm_128x16_m16_s1", launch_cfg<128, 16, 4, 1, 16, 1>, 0.0),
+    igemm_tile(128, 80, "conv_igemm_128x80_m16_s1", launch_cfg<128, 80, 4, 1, 16, 1>, 0.0),
 };
-static constexpr int NTILES = (int)(sizeof(TILES) / sizeof(TILES[0]));
 
 int conv_igemm_npad() { return 128; }
-int conv_igemm_num_tiles() { return NTILES + bf16x3_num_tiles() + wino_num_tiles() + pw_num_tiles(); }
-bool conv_igemm_tile_is_wino(int tile) { tile &= 0xff; return tile > NTILES + bf16x3_num_tiles() && tile <= NTILES + bf16x3_num_tiles() + wino_num_tiles(); }
-static int pw_index(int tile) { return (tile & 0xff) - NTILES - bf16x3_num_tiles() - wino_num_tiles() - 1; }
-bool conv_igemm_tile_is_pw(int tile) { const int i = pw_index(tile); return i >= 0 && i < pw_num_tiles(); }
-bool conv_igemm_tile_is_proj(int tile) { return conv_igemm_tile_is_pw(tile) && pw_tile(pw_index(tile))->proj_rt > 0; }
-int conv_igemm_tile_proj_rt(int tile) { return conv_igemm_tile_is_pw(tile) ? conv_pw_tile_proj_rt(pw_index(tile)) : 0; }
-int conv_proj_lat_tile() {
-    for (int i = 0; i < pw_num_tiles(); ++i)
-        if (pw_tile(i)->proj_rt == 101) return NTILES + bf16x3_num_tiles() + wino_num_tiles() + i + 1;
+
+// The tile registry: the four family tables in one id space (id = index + 1; an id is one byte of the cfg word).  Built once; the two
+// tiles the launcher names itself are looked up here by name, and a missing or duplicated name ends the process - ids may move when a
+// table grows, names may not.
+struct TileRegistry {
+    std::vector<ConvTile> tiles;
+    int bf16x3_any;   // conv_bf16x3_64x64_m32: takes any shape (the fallback of launches that read a pre-split bf16 input)
+    int proj_lat;     // conv_projl_1
+    TileRegistry() : tiles(std::begin(IGEMM_TILES), std::end(IGEMM_TILES)) {
+        for (auto family : {conv_bf16x3_tiles, conv_wino_tiles, conv_pw_tiles}) { int n = 0; const ConvTile* t = family(&n); tiles.insert(tiles.end(), t, t + n); }
+        bf16x3_any = id_of("conv_bf16x3_64x64_m32");
+        proj_lat = id_of("conv_projl_1");
+        bool ok = tiles.size() <= 255 && bf16x3_any && proj_lat;
+        for (size_t i = 0; i < tiles.size(); ++i) ok = ok && id_of(tiles[i].name) == (int)i + 1;   // the first of its name: no duplicates
+        if (!ok) { std::fprintf(stderr, "ccvpe: tile registry: a tile name is duplicated, or conv_bf16x3_64x64_m32 / conv_projl_1 is missing\n"); std::abort(); }
+    }
+    int id_of(const char* name) const {   // first tile of that name; 0: none
+        for (size_t i = 0; i < tiles.size(); ++i)
+            if (!std::strcmp(tiles[i].name, name)) return (int)i + 1;
+        return 0;
+    }
+};
+static const TileRegistry& registry() { static const TileRegistry r; return r; }
+
+int conv_num_tiles() { return (int)registry().tiles.size(); }
+const ConvTile* conv_tile(int id) { id &= 0xff; return id >= 1 && id <= conv_num_tiles() ? &registry().tiles[id - 1] : nullptr; }
+const char* conv_tile_name(int id) { const ConvTile* t = conv_tile(id); return t ? t->name : ""; }
+int conv_proj_lat_tile() { return registry().proj_lat; }
+
+// Each family's rules, once: the launcher, the autotuner and ccvpe_op_conv2d all ask here.
+bool conv_tile_runs(const ConvTile& t, const ConvParams& p) {
+    switch (t.family) {
+    case TILE_IGEMM: return true;
+    case TILE_BF16X3: return p.w_hi != nullptr && p.w_lo != nullptr;   // the bf16 planes are packed
+    case TILE_WINO:
+        if (t.xcfg >= 0) return conv_wino4x_supported(p) && p.wino4x_cfg == t.xcfg;
+        return t.wino_f == 4 ? conv_wino4_supported(p) : conv_wino_supported(p);
+    case TILE_PW: return t.proj_rt > 0 ? conv_proj_supported(p, t.proj_rt) : conv_pw_supported(p) && conv_pw_fits(t.bn, p.Kpad);
+    }
+    return false;
+}
+int conv_tile_splits(const ConvTile& t) {
+    switch (t.family) {
+    case TILE_IGEMM: return SPLIT_SELF;
+    case TILE_BF16X3: return 0;
+    case TILE_WINO: return t.xcfg >= 0 ? 0 : SPLIT_SELF | (t.wino_f == 4 ? SPLIT_TAIL : 0);   // the tail split is sized by the F(4x4) launcher
+    case TILE_PW: return t.proj_rt >= 100 ? SPLIT_SELF : 0;   // (the latency form of the deep-K GEMM, layers without a gate)
+    }
     return 0;
 }
-bool conv_igemm_tile_is_wino4(int tile) { return conv_igemm_tile_is_wino(tile) && wino_tile((tile & 0xff) - NTILES - bf16x3_num_tiles() - 1)->f == 4; }
-static int wino4x_cfg_of(int tile) { return conv_igemm_tile_is_wino(tile) ? wino_tile((tile & 0xff) - NTILES - bf16x3_num_tiles() - 1)->xcfg : -1; }
-bool conv_igemm_tile_is_wino4x(int tile) { return wino4x_cfg_of(tile) >= 0; }
-int conv_igemm_tile_wino4x_cfg(int tile) { return wino4x_cfg_of(tile); }
-bool conv_wino_tile_supported(const ConvParams& p, int tile) {
-    if (!conv_igemm_tile_is_wino(tile)) return false;
-    if (conv_igemm_tile_is_wino4x(tile)) return conv_wino4x_supported(p) && p.wino4x_cfg == wino4x_cfg_of(tile);
-    return conv_igemm_tile_is_wino4(tile) ? conv_wino4_supported(p) : conv_wino_supported(p);
-}
-bool conv_igemm_tile_is_bf16x3(int tile) { tile &= 0xff; return tile > NTILES && tile <= NTILES + bf16x3_num_tiles(); }
-// kernels that can reduce their own split-K (split code SPLIT_FUSED + S): the fp32 implicit GEMM and the fused F(4x4) / F(2x2) Winograd kernels
-bool conv_igemm_tile_can_fuse_split(int tile) {
-    tile &= 0xff;
-    return (tile >= 1 && tile <= NTILES) || (conv_igemm_tile_is_wino(tile) && !conv_igemm_tile_is_wino4x(tile)) ||
-           conv_igemm_tile_proj_rt(tile) >= 100;   // (the latency form of the deep-K GEMM: layers without a gate)
-}
-static void tile_dims(int tile, int& bm, int& bn) {
-    if (tile >= 1 && tile <= NTILES) { bm = TILES[tile - 1].bm; bn = TILES[tile - 1].bn; }
-    else if (conv_igemm_tile_is_bf16x3(tile)) { bm = (*bf16x3_tile(tile - NTILES - 1)).bm; bn = (*bf16x3_tile(tile - NTILES - 1)).bn; }
-    else if (conv_igemm_tile_is_wino(tile)) { bm = wino_tile(tile - NTILES - bf16x3_num_tiles() - 1)->bm; bn = wino_tile(tile - NTILES - bf16x3_num_tiles() - 1)->bn; }
-    else if (conv_igemm_tile_is_pw(tile)) { bm = pw_tile(pw_index(tile))->bm; bn = pw_tile(pw_index(tile))->bn; }
-    else { bm = bn = 0; }
-}
 
+long long conv_tile_blocks(const ConvParams& p, const ConvTile& t) { return (long long)((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn); }
 // fraction of the launched MFMA work that is useful (padding of M and N to the tile)
-double conv_igemm_tile_util(const ConvParams& p, int tile) {
-    int bm, bn;
-    tile_dims(tile, bm, bn);
-    if (!bm) return 0.0;
-    double gm = (p.M + bm - 1) / bm, gn = (p.N + bn - 1) / bn;
-    return ((double)p.M * p.N) / (gm * bm * gn * bn);
-}
-
-long long conv_igemm_tile_blocks(const ConvParams& p, int tile) {
-    int bm, bn;
-    tile_dims(tile, bm, bn);
-    if (!bm) return 0;
-    return (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
-}
+double conv_tile_util(const ConvParams& p, const ConvTile& t) { return ((double)p.M * p.N) / ((double)conv_tile_blocks(p, t) * t.bm * t.bn); }
 
 static int pick_tile(const ConvParams& p) {
     const double cus = 256.0;
     int best = 3;
     double best_score = -1.0;
-    for (int t = 1; t <= NTILES; ++t) {
-        const TileCfg& c = TILES[t - 1];
-        double gm = (p.M + c.bm - 1) / c.bm, gn = (p.N + c.bn - 1) / c.bn;
-        double blocks = gm * gn;
-        double util = conv_igemm_tile_util(p, t);
+    const auto& tiles = registry().tiles;
+    for (size_t i = 0; i < tiles.size(); ++i) {
+        const ConvTile& c = tiles[i];
+        if (c.intrinsic <= 0.0) continue;
+        double blocks = (double)conv_tile_blocks(p, c);
         double rounds = (double)(long long)((blocks + cus - 1) / cus);
         double quant = blocks / (rounds * cus);
-        double score = util * quant * c.intrinsic;
-        if (score > best_score) { best_score = score; best = t; }
+        double score = conv_tile_util(p, c) * quant * c.intrinsic;
+        if (score > best_score) { best_score = score; best = (int)i + 1; }
     }
     return best;
 }
 
 static thread_local int g_last_tile = 0;
-int conv_igemm_last_tile() { int t = g_last_tile; g_last_tile = 0; return t; }
-const char* conv_igemm_tile_name(int tile) {
-    tile &= 0xff;
-    if (tile >= 1 && tile <= NTILES) return TILES[tile - 1].name;
-    if (conv_igemm_tile_is_bf16x3(tile)) return (*bf16x3_tile(tile - NTILES - 1)).name;
-    if (conv_igemm_tile_is_wino(tile)) return wino_tile(tile - NTILES - bf16x3_num_tiles() - 1)->name;
-    if (conv_igemm_tile_is_pw(tile)) return pw_tile(pw_index(tile))->name;
-    return "";
-}
+int conv_tile_last() { int t = g_last_tile; g_last_tile = 0; return t; }
 
 // exact small-range division by multiplication: q = (g * mul) >> 20 for 0 <= g < limit
 static int find_div_mul(int d, int limit) {
@@ -518,31 +515,28 @@ int launch_conv_igemm(const ConvParams& p_in, int tile, hipStream_t s) {
     tile &= 0xff;
     bool fused = false;
     if (splitk > SPLIT_FUSED && splitk <= SPLIT_FUSED + 32) { fused = p.tickets != nullptr; splitk -= SPLIT_FUSED; }   // (no counters: the reduce launch)
-    if (conv_igemm_tile_is_bf16x3(tile) && (p.w_hi == nullptr || p.w_lo == nullptr)) tile = 0;   // planes not packed: fp32 path
-    if (conv_igemm_tile_is_wino(tile) && !conv_wino_tile_supported(p, tile)) tile = 0;
-    if (conv_igemm_tile_is_pw(tile) && !conv_pw_tile_ok(pw_index(tile), p)) tile = 0;   // not a layer this pointwise tile takes
-    if (conv_igemm_tile_is_pw(tile)) {   // the pointwise persistent tiles keep K whole; the latency form of the deep-K GEMM splits it only self-reducing, without a gate
-        const bool lat = conv_igemm_tile_proj_rt(tile) >= 100;
-        const int ct = lat ? std::max(1, (conv_igemm_tile_proj_rt(tile) - 100) % 10) : 1, rt = lat ? std::max(1, (conv_igemm_tile_proj_rt(tile) - 100) / 10) : 1;
+    const ConvTile* t = conv_tile(tile);
+    if (t && !conv_tile_runs(*t, p)) t = nullptr;   // not a layer this tile takes (form not packed, shape): the heuristic's pick
+    if (t && t->family == TILE_PW) {   // the pointwise family: K whole, or (latency form) split self-reducing, without a gate
+        const bool lat = t->proj_rt >= 100;
+        const int ct = lat ? std::max(1, (t->proj_rt - 100) % 10) : 1, rt = lat ? std::max(1, (t->proj_rt - 100) / 10) : 1;
         const long long regions = (long long)((p.M + 16 * rt - 1) / (16 * rt)) * (((p.N + 15) / 16 + ct - 1) / ct);
         if (!(lat && fused && p.gate == nullptr && p.se_rows == nullptr && p.partial != nullptr && regions <= CONV_TICKETS)) splitk = 1;
     }
-    if (tile < 1 || tile > conv_igemm_num_tiles()) tile = pick_tile(p);
+    tile = t ? tile : pick_tile(p);
     if (p.in_split) {   // pre-split bf16 input: only the bf16x3 kernels can read it
         if (p.w_hi == nullptr) return -1;
-        if (!conv_igemm_tile_is_bf16x3(tile)) tile = NTILES + 3;   // conv_bf16x3_64x64_m32: valid for any shape
+        if (conv_tile(tile)->family != TILE_BF16X3) tile = registry().bf16x3_any;
     }
-    if (splitk == 255) { if (!conv_igemm_tile_is_wino4(tile) || conv_igemm_tile_is_wino4x(tile) || p.partial == nullptr) splitk = 1; }   // F(4x4) tail split: sized by its launcher
+    t = conv_tile(tile);
+    const int splits = conv_tile_splits(*t);
+    if (splitk == 255) { if (!(splits & SPLIT_TAIL) || p.partial == nullptr) splitk = 1; }
     else if (splitk < 2 || p.partial == nullptr || (size_t)splitk * p.M * p.N > p.partial_floats) splitk = 1;
     p.splitk = splitk;
-    // which kernels reduce their own split: the fp32 implicit GEMM, the F(4x4) and F(2x2) Winograd kernels
-    fused = fused && splitk > 1 && splitk != 255 && conv_igemm_tile_can_fuse_split(tile);
+    fused = fused && splitk > 1 && splitk != 255 && (splits & SPLIT_SELF);
     p.split_fused = (fused || (splitk == 255 && p.tickets != nullptr)) ? 1 : 0;       // (the tail split's K-split sub-launch reduces itself whenever it can)
     g_last_tile = tile | ((fused ? splitk + SPLIT_FUSED : splitk) << 8);
-    if (tile <= NTILES) TILES[tile - 1].launch(p, s);
-    else if (conv_igemm_tile_is_pw(tile)) pw_tile(pw_index(tile))->launch(p, s);
-    else if (conv_igemm_tile_is_wino(tile)) wino_tile(tile - NTILES - bf16x3_num_tiles() - 1)->launch(p, s);
-    else (*bf16x3_tile(tile - NTILES - 1)).launch(p, s);
+    t->launch(p, s);
     if (splitk == 255 && !conv_wino4_tail_applied()) g_last_tile = tile | (1 << 8);   // the tail split did not apply: a plain launch
     return 0;
 }

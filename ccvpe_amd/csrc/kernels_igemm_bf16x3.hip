@@ -373,21 +373,20 @@ static void launch_b(const ConvParams& p, hipStream_t s) {
     else launch_b2<BM, BN, WGM, WGN, MT, false, false>(p, s);
 }
 
-static const Bf16x3Tile BF16X3_TILES_[] = {
-    {128, 128, "conv_bf16x3_128x128_m32", launch_b<128, 128, 2, 2, 32>},
-    {128, 64, "conv_bf16x3_128x64_m32", launch_b<128, 64, 2, 2, 32>},
-    {64, 64, "conv_bf16x3_64x64_m32", launch_b<64, 64, 2, 2, 32>},
-    {128, 128, "conv_bf16x3_128x128_m16", launch_b<128, 128, 2, 2, 16>},
-    {128, 64, "conv_bf16x3_128x64_m16", launch_b<128, 64, 2, 2, 16>},
-    {128, 80, "conv_bf16x3_128x80_m16", launch_b<128, 80, 4, 1, 16>},
-    {128, 48, "conv_bf16x3_128x48_m16", launch_b<128, 48, 4, 1, 16>},
-    {128, 32, "conv_bf16x3_128x32_m16", launch_b<128, 32, 4, 1, 16>},
-    {128, 16, "conv_bf16x3_128x16_m16", launch_b<128, 16, 4, 1, 16>},
-    {64, 64, "conv_bf16x3_64x64_m16", launch_b<64, 64, 2, 2, 16>},
-    {64, 32, "conv_bf16x3_64x32_m16", launch_b<64, 32, 2, 2, 16>},
-    {256, 64, "conv_bf16x3_256x64_m32", launch_b<256, 64, 4, 1, 32>},
+static const ConvTile BF16X3_TILES[] = {
+    bf16x3_tile(128, 128, "conv_bf16x3_128x128_m32", launch_b<128, 128, 2, 2, 32>),
+    bf16x3_tile(128, 64, "conv_bf16x3_128x64_m32", launch_b<128, 64, 2, 2, 32>),
+    bf16x3_tile(64, 64, "conv_bf16x3_64x64_m32", launch_b<64, 64, 2, 2, 32>),
+    bf16x3_tile(128, 128, "conv_bf16x3_128x128_m16", launch_b<128, 128, 2, 2, 16>),
+    bf16x3_tile(128, 64, "conv_bf16x3_128x64_m16", launch_b<128, 64, 2, 2, 16>),
+    bf16x3_tile(128, 80, "conv_bf16x3_128x80_m16", launch_b<128, 80, 4, 1, 16>),
+    bf16x3_tile(128, 48, "conv_bf16x3_128x48_m16", launch_b<128, 48, 4, 1, 16>),
+    bf16x3_tile(128, 32, "conv_bf16x3_128x32_m16", launch_b<128, 32, 4, 1, 16>),
+    bf16x3_tile(128, 16, "conv_bf16x3_128x16_m16", launch_b<128, 16, 4, 1, 16>),
+    bf16x3_tile(64, 64, "conv_bf16x3_64x64_m16", launch_b<64, 64, 2, 2, 16>),
+    bf16x3_tile(64, 32, "conv_bf16x3_64x32_m16", launch_b<64, 32, 2, 2, 16>),
+    bf16x3_tile(256, 64, "conv_bf16x3_256x64_m32", launch_b<256, 64, 4, 1, 32>),
 };
-int bf16x3_num_tiles() { return (int)(sizeof(BF16X3_TILES_) / sizeof(BF16X3_TILES_[0])); }
-const Bf16x3Tile* bf16x3_tile(int i) { return &BF16X3_TILES_[i]; }
+const ConvTile* conv_bf16x3_tiles(int* n) { *n = (int)(sizeof(BF16X3_TILES) / sizeof(BF16X3_TILES[0])); return BF16X3_TILES; }
 
 }  // namespace ccvpe

@@ -435,13 +435,6 @@ bool conv_proj_supported(const ConvParams& p, int rt) {
     return false;
 }
 
-bool conv_proj_has(int rt, int N) {   // an instantiated (row tiles, column tiles) pair
-    if (rt >= 100) return true;
-    for (int i = 0; i < PROJ_NCFG; ++i)
-        if (PROJ_CFGS[i].rt == rt && PROJ_CFGS[i].ct == (N + 15) / 16) return true;
-    return false;
-}
-
 void launch_proj(const ConvParams& p, int rt, hipStream_t s) {
     if (rt == 101) { launch_proj_lat<1>(p, s); return; }
     if (rt == 102) { launch_proj_lat<2>(p, s); return; }

@@ -404,25 +404,24 @@ static void launch_wino(const ConvParams& p_in, hipStream_t s) {
 }
 
 // bm = output pixels per workgroup (32 tiles x 4 pixels per set), bn = output channels per workgroup
-static const WinoTile WINO_TILES[] = {
-    {256, 32, "conv_wino_64x32", launch_wino<2, 2, 2>, 2, -1},
-    {128, 48, "conv_wino_32x48", launch_wino<3, 1, 2>, 2, -1},
-    {128, 64, "conv_wino_32x64", launch_wino<4, 1, 4>, 2, -1},
-    {128, 80, "conv_wino_32x80", launch_wino<5, 1, 4>, 2, -1},
-    {256, 48, "conv_wino_64x48", launch_wino<3, 2, 2>, 2, -1},
+static const ConvTile WINO_TILES[] = {
+    wino_tile(256, 32, "conv_wino_64x32", launch_wino<2, 2, 2>, 2),
+    wino_tile(128, 48, "conv_wino_32x48", launch_wino<3, 1, 2>, 2),
+    wino_tile(128, 64, "conv_wino_32x64", launch_wino<4, 1, 4>, 2),
+    wino_tile(128, 80, "conv_wino_32x80", launch_wino<5, 1, 4>, 2),
+    wino_tile(256, 48, "conv_wino_64x48", launch_wino<3, 2, 2>, 2),
     // F(4x4,3x3), kernels_wino4.hip: 16 tiles of 4x4 pixels x 64 channels per workgroup
-    {256, 64, "conv_wino4_16x64", launch_wino4_64, 4, -1},
-    {256, 128, "conv_wino4_16x128", launch_wino4_128, 4, -1},
+    wino_tile(256, 64, "conv_wino4_16x64", launch_wino4_64, 4),
+    wino_tile(256, 128, "conv_wino4_16x128", launch_wino4_128, 4),
     // F(4x4,3x3) xi-split form, kernels_wino4x.hip: one n-block = the whole (narrow) layer, nine xi per wave
-    {256, 32, "conv_wino4x_32", launch_wino4x, 4, 0},
-    {256, 48, "conv_wino4x_48", launch_wino4x, 4, 1},
-    {256, 64, "conv_wino4x_64", launch_wino4x, 4, 2},
-    {256, 80, "conv_wino4x_80", launch_wino4x, 4, 3},
-    {256, 96, "conv_wino4x_96", launch_wino4x, 4, 4},
-    {256, 128, "conv_wino4x_128", launch_wino4x, 4, 5},
+    wino_tile(256, 32, "conv_wino4x_32", launch_wino4x, 4, 0),
+    wino_tile(256, 48, "conv_wino4x_48", launch_wino4x, 4, 1),
+    wino_tile(256, 64, "conv_wino4x_64", launch_wino4x, 4, 2),
+    wino_tile(256, 80, "conv_wino4x_80", launch_wino4x, 4, 3),
+    wino_tile(256, 96, "conv_wino4x_96", launch_wino4x, 4, 4),
+    wino_tile(256, 128, "conv_wino4x_128", launch_wino4x, 4, 5),
 };
-int wino_num_tiles() { return (int)(sizeof(WINO_TILES) / sizeof(WINO_TILES[0])); }
-const WinoTile* wino_tile(int i) { return &WINO_TILES[i]; }
+const ConvTile* conv_wino_tiles(int* n) { *n = (int)(sizeof(WINO_TILES) / sizeof(WINO_TILES[0])); return WINO_TILES; }
 
 bool conv_wino_supported(const ConvParams& p) {
     return p.wino_w != nullptr && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.mode == MODE_CONV &&

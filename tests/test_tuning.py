@@ -51,6 +51,19 @@ def test_committed_table_parses_if_present():
         assert tab and all(len(v.split()) == 4 for v in tab.values())
 
 
+def test_tile_names_are_distinct_and_cover_the_committed_table():
+    """The tile registry's invariant: ids 1..n have non-empty, pairwise distinct names, ids 0 and n + 1 have none, and every
+    tile the committed table names is one the built library knows (or auto)."""
+    from ccvpe_amd import _lib
+    lib = _lib.load()
+    n = lib.ccvpe_op_num_tiles()
+    names = [lib.ccvpe_op_tile_name(t).decode() for t in range(1, n + 1)]
+    assert n > 0 and all(names) and len(set(names)) == n
+    assert lib.ccvpe_op_tile_name(0) == b"" and lib.ccvpe_op_tile_name(n + 1) == b""
+    tab = tuning.parse(open(tuning.COMMITTED).read())
+    assert tab and {v.split()[2] for v in tab.values()} <= set(names) | {"auto"}
+
+
 CHILD = r"""
 import json, sys, time, hashlib
 import torch
