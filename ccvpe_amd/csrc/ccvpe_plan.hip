@@ -368,6 +368,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         if (h->cfg.reserved[0] == 1 && j < 5 && h->sw.split_planes) { loc_cat[j].split = true; ori_cat[j].split = true; }
     }
     ori_in6 = pl.alloc(B, 8, 8, rpad + D);
+    pl.taps["ori_in6"] = {ori_in6, 0, ori_in6.C};   // (read by debug handles only, like every tap: [rfull scores | pad to rpad | D])
 
     // ---- encoders ----
     EncOut genc, senc;

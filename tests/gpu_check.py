@@ -1,4 +1,5 @@
-"""Manual parity script (GPU box; lives under tests/ because it uses the oracle): run the HIP forward with debug taps and compare every tap with the oracle."""
+"""Manual parity script (GPU box; lives under tests/ because it uses the oracle): run the HIP forward with debug taps, print the per-stage
+table of tests/stage_ref.py (every stage against the fp64 oracle on the device's own input) and compare the nine outputs with the oracle's forward."""
 import os
 import sys
 import time
@@ -8,6 +9,7 @@ import torch
 
 from ccvpe_amd import models, weights
 from oracle import ccvpe_oracle as orc
+from tests import stage_ref
 
 CASES = {
     "vigor_ori_prior": (models.CVM_VIGOR_ori_prior, dict(ori_noise=180.0, circular_padding=True), 360.0),
@@ -24,9 +26,8 @@ def run(case, B=1, debug=True):
     sd = weights.generate_state_dict(variant, 0)
     grd, sat = weights.generate_inputs(variant, B, 0, fov)
     grd, sat = torch.from_numpy(grd), torch.from_numpy(sat)
-    taps = {}
     t0 = time.time()
-    ref = orc.forward(variant, sd, grd, sat, kw.get("circular_padding", False), kw.get("ori_noise"), taps)
+    ref = orc.forward(variant, sd, grd, sat, kw.get("circular_padding", False), kw.get("ori_noise"))
     print(f"[{case}] oracle {time.time()-t0:.2f}s", flush=True)
     m = cls("cuda", **kw)
     m.load_state_dict(sd)
@@ -38,25 +39,9 @@ def run(case, B=1, debug=True):
     print(f"[{case}] hip first call {time.time()-t0:.2f}s", flush=True)
     names = ["logits", "heatmap", "ori", "ms1", "ms2", "ms3", "ms4", "ms5", "ms6"]
     worst = 0.0
-    if debug:
-        order = ["grd_block0", "grd_block1", "grd_block15", "grd_volume", "grd_desc1", "grd_desc6", "sat_block0", "sat_block2", "sat_block4", "sat_block10",
-                 "sat_block15", "sat_volume", "sat_descriptor_map", "loc_level6", "loc_level5", "loc_level4", "loc_level3", "loc_level2",
-                 "ori_level6", "ori_level5", "ori_level4", "ori_level3", "ori_level2", "ori_level1_nchw"]
-        for k in order:
-            try:
-                t = m.read_tap(k)
-            except Exception as e:
-                print(f"  tap {k}: {e}")
-                continue
-            key = {"ori_level1_nchw": "ori_level1"}.get(k, k)
-            if key.startswith("grd_block"):
-                continue
-            r = taps[key]
-            if r.dim() == 2:
-                r = r[:, :, None, None]
-            d = (t - r).abs().max().item()
-            s = r.abs().max().item()
-            print(f"  tap {k:20s} {tuple(t.shape)} maxdiff {d:.3g} rel {d/s:.3g}")
+    if debug:   # every stage against the fp64 oracle on the device's own input (tests/stage_ref.py; asserted in tests/test_stages_gpu.py)
+        circ, noise = kw.get("circular_padding", False), kw.get("ori_noise")
+        print(stage_ref.format_table(stage_ref.check_stages(m.read_tap, out, variant, sd, grd, sat, circ, noise)))
     for n, a, b in zip(names, ref, out):
         b = b.cpu()
         d = (a - b).abs().max().item()

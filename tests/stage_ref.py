@@ -1,0 +1,227 @@
+"""Stage-by-stage checker of one forward against the oracle, every stage fed the device's own input (teacher forcing).
+
+`check_stages` walks the forward of oracle/ccvpe_oracle.py one stage at a time.  For each stage it
+  1. takes the stage's input from the device (`read_tap`, the images, or one of the nine outputs), never from the previous stage of
+     the oracle, so errors do not compound and a failure names the launch group that produced it;
+  2. computes that one stage with the oracle's functions twice on that input: in fp64 (state dict and input cast up, `ref64`) and
+     in fp32 (`ref32`);
+  3. records e_ref = max|ref32 - ref64| / max|ref64| - what fp32 arithmetic in another order costs on this very input, the yardstick
+     of the tolerance - and e_dev = max|dev - ref64| / max|ref64|, both over the full tensor, with the index of the worst element.
+
+This module imports the oracle and, like the oracle itself, the plain-data tables of `ccvpe_amd.spec` (block schedule, variants, roll
+shifts); nothing of the library's code path.  `read_tap` is any callable tap name -> NCHW CPU tensor of the whole
+batch (models.read_tap on a debug handle, or a dict of oracle taps in tests/test_stages_cpu.py).
+
+Tap layouts the checker relies on (ccvpe_plan.hip):
+  - grd_desc{k}: [B, L, 1, 1], the descriptor d[w*c + ch] along dim 1;
+  - loc_in{n}:   [B, 8 + C, h, w] = [max score | 7 pad channels | normalize(x)]; the pad channels are not compared;
+  - ori_in6:     [B, rpad + D, 8, 8] = [R scores of the full roll set | rpad - R pad channels | normalize(x)], rpad = R rounded up
+                 to 8; the pad channels are not compared.
+"""
+from __future__ import annotations
+
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+import torch.nn.functional as F
+
+from ccvpe_amd import spec
+from oracle import ccvpe_oracle as orc
+
+LOC_IN_PAD = 8          # leading score slot of the loc_in* buffers (1 real channel + 7 pad)
+
+
+class StageResult(NamedTuple):
+    name: str                       # "<stage>" or "<stage>:<tensor>" when a stage writes several tensors
+    shape: Tuple[int, ...]
+    e_dev: float
+    e_ref: float
+    worst_index: Tuple[int, ...]    # of |dev - ref64|, in the compared tensor (batch index = position in `samples`)
+    launches: Tuple[str, ...]       # prefixes of the plan's launch names that compute this stage (() = no launch of its own)
+
+
+def launches_of(r: StageResult, launch_names: Sequence[str]) -> List[str]:
+    """The launches of a plan (names from its profile rows) that belong to a stage."""
+    return [n for n in launch_names if n.startswith(r.launches)]
+
+
+def _f64(sd):
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def _unravel(i: int, shape) -> Tuple[int, ...]:
+    out = []
+    for n in reversed(shape):
+        out.append(i % n)
+        i //= n
+    return tuple(reversed(out))
+
+
+def _max_err(a: torch.Tensor, ref64: torch.Tensor, weight: Optional[torch.Tensor] = None):
+    """max |a - ref64| (* weight) and where."""
+    assert a.shape == ref64.shape, (tuple(a.shape), tuple(ref64.shape))
+    d = (a.double() - ref64).abs()
+    if weight is not None:
+        d = d * weight
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)   # a NaN on the device is the worst element
+    i = int(d.argmax())
+    return d.reshape(-1)[i].item(), _unravel(i, d.shape)
+
+
+def _result(name, dev, ref32, ref64, launches, weight=None) -> StageResult:
+    dev = dev.reshape(ref64.shape)
+    scale = max((weight.max() if weight is not None else ref64.abs().max()).item(), 1e-300)
+    e_dev, where = _max_err(dev, ref64, weight)
+    e_ref, _ = _max_err(ref32, ref64, weight)
+    return StageResult(name, tuple(ref64.shape), e_dev / scale, e_ref / scale, where, launches)
+
+
+def stem_block0(img, sd, p, circular):
+    """Stem (conv + bn0 + swish) and block 0, the first lines of orc.encoder."""
+    x = orc._pad_static(img, 3, 2, circular)
+    x = orc._swish(orc._bn(F.conv2d(x, sd[p + "._conv_stem.weight"], stride=2), sd, p + "._bn0"))
+    return orc.mbconv(x, sd, p + "._blocks.0", spec.B0_BLOCKS[0], circular)
+
+
+def head_conv(x, sd, p):
+    """Head conv + bn1 + swish, the last line of orc.encoder."""
+    return orc._swish(orc._bn(F.conv2d(x, sd[p + "._conv_head.weight"]), sd, p + "._bn1"))
+
+
+def match_cat(score, x):
+    """What a matching level hands to its decoder level: cat(max over the rolls, normalize(x)) (orc.forward)."""
+    return torch.cat([score.max(dim=1, keepdim=True).values, F.normalize(x, p=2, dim=1)], dim=1)
+
+
+def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str, sd, grd: torch.Tensor, sat: torch.Tensor,
+                 circular: bool, ori_noise: Optional[float], samples: Optional[Sequence[int]] = None) -> List[StageResult]:
+    """Every stage of the forward, see the module docstring.  `outputs`: the nine tensors of the forward (logits, heatmap, ori,
+    ms1..ms6) for the whole batch; `grd`, `sat`: the input images of the whole batch; `samples`: batch indices to check (default: all)."""
+    v = spec.VARIANTS[variant]
+    prior = variant == "vigor_ori_prior"
+    idx = torch.arange(grd.shape[0]) if samples is None else torch.tensor(list(samples))
+    sd32 = {k: t.detach().cpu() for k, t in sd.items()}
+    sd64 = _f64(sd32)
+    cache = {}
+
+    def tap(name):                  # the checked samples of a device tap; each tap is read once
+        if name not in cache:
+            cache[name] = read_tap(name).detach().cpu()[idx].float().clone()
+        return cache[name]
+
+    outs = [o.detach().cpu()[idx].float() for o in outputs]
+    out_logits, out_heat, out_ori, out_ms = outs[0], outs[1], outs[2], outs[3:]
+    results: List[StageResult] = []
+
+    def stage(name, fn, inputs, dev, launches):
+        """fn(sd, *inputs) in fp32 and fp64 against the device tensor(s) `dev` ({suffix: tensor} when the stage writes several)."""
+        with torch.no_grad():
+            r32 = fn(sd32, *inputs)
+            r64 = fn(sd64, *[t.double() for t in inputs])
+        if not isinstance(dev, dict):
+            dev, r32, r64 = {"": dev}, {"": r32}, {"": r64}
+        for key, d in dev.items():
+            results.append(_result(name + (":" + key if key else ""), d, r32[key], r64[key], launches))
+
+    # ---- encoders ----
+    for tag, img, circ in (("grd", grd[idx].float(), circular), ("sat", sat[idx].float(), False)):
+        p = tag + "_efficientnet"
+        stage(f"{tag}_block0", lambda s, x: stem_block0(x, s, p, circ), [img], tap(f"{tag}_block0"), (f"{tag}.stem", f"{tag}.b0."))
+        for i in range(1, len(spec.B0_BLOCKS)):
+            stage(f"{tag}_block{i}", lambda s, x: orc.mbconv(x, s, f"{p}._blocks.{i}", spec.B0_BLOCKS[i], circ),
+                  [tap(f"{tag}_block{i - 1}")], tap(f"{tag}_block{i}"), (f"{tag}.b{i}.",))
+        stage(f"{tag}_volume", lambda s, x: head_conv(x, s, p), [tap(f"{tag}_block15")], tap(f"{tag}_volume"), (f"{tag}.head",))
+
+    # ---- descriptors ----
+    for k in range(1, 7):
+        stage(f"grd_desc{k}", lambda s, x: orc.ground_descriptor(x, s, k), [tap("grd_volume")],
+              tap(f"grd_desc{k}").flatten(1), ("grd.heads", "grd.desc"))
+    stage("sat_descriptor_map", lambda s, x: orc.aerial_descriptor_map(x, s), [tap("sat_volume")], tap("sat_descriptor_map"),
+          ("sat.descmap",))
+
+    # ---- matching levels: x and the ground descriptor -> ms{k}, the maximum over the rolls, loc_in{7-k} (and ori_in6 at level 1) ----
+    def real_loc_in(n):
+        t = tap(f"loc_in{n}")
+        return torch.cat([t[:, :1], t[:, LOC_IN_PAD:]], dim=1)
+
+    n_rolls = v.n_rolls
+    D = v.match_ch[0]
+
+    def real_ori_in6():
+        t = tap("ori_in6")
+        rpad = t.shape[1] - D
+        assert rpad >= n_rolls
+        return torch.cat([t[:, :n_rolls], t[:, rpad:]], dim=1)
+
+    for k in range(1, 7):
+        n = 7 - k
+        x = tap("sat_descriptor_map") if k == 1 else tap(f"loc_level{8 - k}")
+        g = tap(f"grd_desc{k}").flatten(1)
+        L = g.shape[1]
+        shifts = spec.roll_shifts(v, k, L, ori_noise)
+        full = spec.full_roll_shifts(v, 1, L) if k == 1 else None
+
+        def match(s, x, g):
+            score = orc.rolling_match(x, g, shifts)
+            # the maximum also as a row of its own: inside loc_in{n} it is scaled by the normalised features (up to 1 against scores of 0.1-0.2)
+            out = {"ms": score, "max": score.max(dim=1, keepdim=True).values, f"loc_in{n}": match_cat(score, x)}
+            if k == 1:   # the full roll set: returned as ms1 and fed to the orientation decoder (the restricted set's maximum enters loc_in6)
+                out["ms"] = orc.rolling_match(x, g, full) if prior else score
+                out["ori_in6"] = torch.cat([out["ms"], F.normalize(x, p=2, dim=1)], dim=1)
+            return out
+
+        dev = {"ms": out_ms[k - 1], "max": tap(f"loc_in{n}")[:, :1], f"loc_in{n}": real_loc_in(n)}
+        if k == 1:
+            dev["ori_in6"] = real_ori_in6()
+        stage(f"match{k}", match, [x, g], dev, (f"match{k}",))
+
+        # ---- localisation decoder level n ----
+        if n >= 2:
+            skip = tap(f"sat_block{spec.TAP_BLOCKS[k - 1]}")
+            stage(f"loc_level{n}", lambda s, x, sk: orc._decoder_level(x, sk, s, n, ""), [real_loc_in(n), skip], tap(f"loc_level{n}"),
+                  (f"loc{n}.",))
+        else:
+            stage("logits", lambda s, x: orc._decoder_level(x, None, s, 1, ""), [real_loc_in(1)], out_logits, ("loc1.",))
+
+    # ---- softmax ----
+    def softmax(s, lg):
+        heat = torch.softmax(lg.flatten(1), dim=-1)
+        return {"": heat, "over_max": heat / heat.max(dim=1, keepdim=True).values}
+
+    hd = out_heat.flatten(1)
+    stage("heatmap", softmax, [out_logits], {"": hd, "over_max": hd / hd.max(dim=1, keepdim=True).values}, ("softmax",))
+
+    # ---- orientation decoder ----
+    for n in range(6, 1, -1):
+        xo = real_ori_in6() if n == 6 else tap(f"ori_level{n + 1}")
+        skip = tap(f"sat_block{spec.TAP_BLOCKS[6 - n]}")
+        stage(f"ori_level{n}", lambda s, x, sk: orc._decoder_level(x, sk, s, n, "_ori"), [xo, skip], tap(f"ori_level{n}"), (f"ori{n}.",))
+    stage("ori_level1", lambda s, x: orc._decoder_level(x, None, s, 1, "_ori"), [tap("ori_level2")], tap("ori_level1_nchw"), ("ori1.",))
+
+    # ---- normalise: weighted by the magnitude of the un-normalised vector (tests/test_parity_gpu.py ori_weighted_error) ----
+    raw = tap("ori_level1_nchw")
+    mag = raw.double().pow(2).sum(dim=1, keepdim=True).sqrt()
+    with torch.no_grad():
+        results.append(_result("ori", out_ori, F.normalize(raw, p=2, dim=1), F.normalize(raw.double(), p=2, dim=1), ("ori1.",), weight=mag))
+    return results
+
+
+# Tolerances.  The yardstick is e_ref, measured on the stage's own input by the reference arithmetic, never by the code under test.
+BOUND_FP32 = 2e-5       # what tests/test_ops_gpu.py holds the implicit-GEMM and F(2x2) tiles to
+BOUND_F4 = 1e-4         # ... and the F(4x4) Winograd tiles and every bf16x3 tile to
+REF_FACTOR = 8.0        # another summation order over K up to 11520, hardware exp and reciprocal
+
+
+def bound(r: StageResult, f4: bool = False, bf16x3: bool = False, factor: float = REF_FACTOR) -> float:
+    """The largest e_dev a stage may show: min(2e-5, factor * e_ref), or 1e-4 where one of its launches ran an F(4x4) Winograd tile
+    or the handle runs in bf16x3 precision."""
+    if f4 or bf16x3:
+        return BOUND_F4
+    return min(BOUND_FP32, factor * r.e_ref)
+
+
+def format_table(results: Sequence[StageResult]) -> str:
+    rows = [f"{'stage':24s} {'shape':22s} {'e_dev':>9s} {'e_ref':>9s}  worst"]
+    for r in results:
+        rows.append(f"{r.name:24s} {'x'.join(map(str, r.shape)):22s} {r.e_dev:9.2e} {r.e_ref:9.2e}  {r.worst_index}")
+    return "\n".join(rows)
