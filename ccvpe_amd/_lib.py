@@ -116,6 +116,8 @@ SYMBOLS = [
     ("ccvpe_op_conv2d", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
+    ("ccvpe_op_level1", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -241,6 +243,28 @@ def op_conv2d(x_nhwc, w, bias=None, stride=1, pad=0, act=0, tile=0, iters=0):
                              C.c_void_p(out.data_ptr()), iters, C.byref(ms), C.c_void_p(stream))
     check(rc, "ccvpe_op_conv2d")
     return out, (ms.value if iters > 0 else None)
+
+
+def op_level1(x_nhwc, wd, bd, wa, ba, wt, bt, score=False, tile=1, max_wg=0):
+    """Kernel-level hook: the fused last decoder level on its own.  x [B,h,w,Cin] cuda fp32 in the reference's channel order (channel 0
+    the score channel when `score`), wd [Cin,16,2,2], bd [16], wa [16,16,3,3], ba [16], wt [Cout,16,3,3], bt [Cout]; tile 0 = 16 x 16
+    output tiles, 1 = 32 x 16 where the width allows; max_wg (>= 8) caps the grid so that workgroups loop over tiles.  Returns (out NCHW [B,Cout,2h,2w], the tile that ran)."""
+    import torch
+    lib = load()
+    B, h, w, Cin = x_nhwc.shape
+    Cout = wt.shape[0]
+    x = x_nhwc.float()
+    if score:   # the plan's layout: [score, 7 unused, descriptors]
+        x = torch.cat([x[..., :1], x.new_zeros((B, h, w, 7)), x[..., 1:]], dim=-1)
+    x = x.contiguous()
+    ws = [t.detach().float().contiguous() for t in (wd, bd, wa, ba, wt, bt)]
+    out = torch.empty((B, Cout, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    rc = lib.ccvpe_op_level1(C.c_void_p(x.data_ptr()), B, 2 * h, 2 * w, Cin, 1 if score else 0, *[C.c_void_p(t.data_ptr()) for t in ws],
+                             Cout, tile | (max_wg << 8), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+    check(rc, "ccvpe_op_level1")
+    return out, rc
+
 
 _lib = None
 

@@ -41,6 +41,7 @@ Switches read_switches() {
     if (const char* e = getenv("CCVPE_AUTOTUNE")) s.autotune = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_FUSE_MBCONV")) s.fuse_mbconv = std::atoi(e);
     if (const char* e = getenv("CCVPE_FUSE_L1")) s.fuse_level1 = std::atoi(e) != 0;
+    if (const char* e = getenv("CCVPE_L1_TILE")) s.l1_tile = std::atoi(e);
     if (const char* e = getenv("CCVPE_WINOGRAD")) s.wino = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_GRAPH")) s.graph_mode = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_STREAMS")) s.two_streams = std::atoi(e) >= 2;
@@ -1181,6 +1182,42 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
     if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "conv launch failed: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "conv execution failed: %s", hipGetErrorString(e2));
     return 0;
+}
+
+int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t score, const float* wd, const float* bd,
+                    const float* wa, const float* ba, const float* wt, const float* bt, int32_t Cout, int32_t tile, float* out, void* stream) {
+    if (!in || !wd || !bd || !wa || !ba || !wt || !bt || !out) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    const int cd = Cin - (score ? 1 : 0);
+    if (B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16 || (Cout != 1 && Cout != 2) || cd <= 0 || cd % 4 || tile < 0 || (tile & 0xff) > 1 || ((tile >> 8) != 0 && (tile >> 8) < 8))
+        return ccvpe_fail(CCVPE_EINVAL, "bad level-1 geometry (H, W multiples of 16, Cout 1 or 2, descriptor channels a multiple of 4, tile 0 or 1, workgroup cap 0 or >= 8)");
+    if ((double)B * H * W * 16 >= 2147483647.0) return ccvpe_fail(CCVPE_EINVAL, "tensor exceeds 2^31 elements");
+    std::vector<float> hwd((size_t)Cin * 64), hbd(16), hwa(16 * 16 * 9), hba(16), hwt((size_t)Cout * 16 * 9), hbt(Cout);
+    HIPCHK(hipMemcpy(hwd.data(), wd, hwd.size() * sizeof(float), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hbd.data(), bd, hbd.size() * sizeof(float), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hwa.data(), wa, hwa.size() * sizeof(float), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hba.data(), ba, hba.size() * sizeof(float), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hwt.data(), wt, hwt.size() * sizeof(float), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hbt.data(), bt, hbt.size() * sizeof(float), hipMemcpyDefault));
+    ccvpe_handle_s tmp;   // only its dev_allocs list is used
+    DecoderW d;
+    auto cleanup = [&]() { for (void* p : tmp.dev_allocs) (void)hipFree(p); };
+    int rc = compose_level1(&tmp, d, hwd, hbd, hwa, hba, Cin, score ? 1 : 0);
+    if (!rc) rc = pack_level1_tail(&tmp, d, hwt, hbt, Cout);
+    if (rc) { cleanup(); return rc; }
+    if (!level1_supported(d.l1_cxp)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "the fused level takes up to 64 input channels"); }
+    Level1Params lp{};
+    lp.x = in; lp.x_ld = d.l1_cx; lp.cx = d.l1_cx; lp.cxp = d.l1_cxp; lp.B = B; lp.H = H; lp.W = W;
+    lp.c0 = d.l1_c0; lp.ng = d.l1_ng; lp.score = d.l1_score; lp.wc = d.l1_wc; lp.ws = d.l1_ws; lp.bc = d.l1_bc; lp.wt = d.l1_wt;
+    lp.bt[0] = d.tail_b[0]; lp.bt[1] = d.tail_b[1]; lp.cout = Cout; lp.normalize = Cout == 2 ? 1 : 0;
+    lp.out = out; lp.raw = nullptr; lp.tile = tile & 0xff; lp.max_wg = tile >> 8;
+    hipStream_t st = (hipStream_t)stream;
+    launch_level1(lp, st);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    cleanup();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "level-1 launch failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "level-1 execution failed: %s", hipGetErrorString(e2));
+    return level1_tile(lp);
 }
 
 }  // extern "C"

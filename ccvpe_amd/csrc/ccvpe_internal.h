@@ -120,6 +120,7 @@ struct Switches {
     bool autotune = true;                 // CCVPE_AUTOTUNE=0: plans the tuning table does not cover run the shape heuristic's tiles
     int fuse_mbconv = 1;                  // CCVPE_FUSE_MBCONV: 0 never, 1 where measured profitable (3x3 blocks), 2 every supported block
     bool fuse_level1 = true;              // CCVPE_FUSE_L1=0 falls back to deconv / conv / tail launches
+    int l1_tile = 1;                      // CCVPE_L1_TILE=0: the fused last level on 16 x 16 output tiles (1: 32 wide x 16 high)
     // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
     // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
     bool wino = true;
@@ -218,6 +219,11 @@ struct DecoderW {
     float *l1_wc = nullptr, *l1_ws = nullptr, *l1_bc = nullptr;   // composed deconv + conv_a weights, score k-step, bias table (Level1Params)
     int l1_cx = 0, l1_cxp = 0, l1_c0 = 0, l1_ng = 0, l1_score = 0;
 };
+struct ccvpe_handle_s;
+// the fused level's weights from the reference's layouts (ccvpe_weights.hip; the plan and ccvpe_op_level1 share them)
+int compose_level1(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& wa,
+                   const std::vector<float>& ba, int cin, int nscore);
+int pack_level1_tail(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w2, const std::vector<float>& b2, int cout);
 
 struct Tensor {
     int id = -1; int B = 0, H = 0, W = 0, C = 0;

@@ -502,6 +502,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         lp.x_ld = din.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
         lp.c0 = dw.l1_c0; lp.ng = dw.l1_ng; lp.score = dw.l1_score; lp.wc = dw.l1_wc; lp.ws = dw.l1_ws; lp.bc = dw.l1_bc; lp.wt = dw.l1_wt;
         lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = cout; lp.normalize = is_ori ? 1 : 0;
+        lp.tile = h->sw.l1_tile;
         const bool has_raw = raw.id >= 0;
         std::vector<Tensor> uses = {din};
         if (has_raw) uses.push_back(raw);

@@ -219,6 +219,79 @@ static int build_encoder(ccvpe_handle_s* h, EncoderW& e, const std::string& p) {
 }
 
 
+// The fused last level (kernels_level1.hip): the transposed conv composed with conv_a, per output parity.  w [cin][16][2][2], b [16]:
+// the transposed conv; wa [16][16][3][3], ba [16]: conv_a; nscore: 1 when input channel 0 is a score channel (the kernel's input then
+// holds [score, 7 unused, cin - 1 descriptor channels]).  Fills d.l1_wc / l1_ws / l1_bc and the l1_* shape fields.
+int compose_level1(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& wa,
+                   const std::vector<float>& ba, int cin, int nscore) {
+    int rc;
+    // conv_a pixel (2I + py, 2J + px), tap (ky, kx) reads transposed-conv pixel (2I + py + ky - 1, ...) = input pixel
+    // (I - 1 + py + a, J - 1 + px + b) at parity (ty & 1, tx & 1), ty = py + ky + 1, a = (ty >> 1) - py (likewise for x): so
+    // Wc[py][px][a][b][c][o] = sum over the taps landing in window (a, b) of sum_m Wa[o][m][ky][kx] Wd[c][m][ty & 1][tx & 1],
+    // in double, rounded once.  An input pixel outside the 256x256 input holds exactly the transposed-conv pixels outside the
+    // 512x512 image, so zero input there reproduces the zero padding for the weight terms; the transposed conv's bias, which
+    // zero padding also removes at the borders, enters as bc[case][o] = ba[o] + sum over in-image taps of Wa[o][.][tap] . bd.
+    const int cout = 16;
+    const int spad = score_pad(nscore);
+    const int cd = cin - nscore;   // descriptor channels
+    d.l1_cx = spad + cd;
+    d.l1_cxp = round_up(d.l1_cx, 16);
+    d.l1_c0 = spad; d.l1_ng = (cd + 3) / 4; d.l1_score = nscore;
+    std::vector<double> wc((size_t)16 * cin * 16, 0.0);   // [py][px][a][b][c][o]
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px)
+            for (int ky = 0; ky < 3; ++ky)
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int ty = py + ky + 1, tx = px + kx + 1, a = (ty >> 1) - py, bb = (tx >> 1) - px;
+                    const int qd = (ty & 1) * 2 + (tx & 1);
+                    double* dst = &wc[(size_t)(((py * 2 + px) * 2 + a) * 2 + bb) * cin * 16];
+                    for (int c = 0; c < cin; ++c)
+                        for (int o = 0; o < 16; ++o) {
+                            double acc = 0.0;
+                            for (int m = 0; m < cout; ++m)
+                                acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)w[((size_t)c * cout + m) * 4 + qd];
+                            dst[(size_t)c * 16 + o] += acc;
+                        }
+                }
+    // lane l of parity class par holds window q = l >> 4, output channel l & 15
+    std::vector<float> pk((size_t)4 * d.l1_ng * 64 * 4, 0.f), sc(4 * 64, 0.f);
+    for (int par = 0; par < 4; ++par)
+        for (int l = 0; l < 64; ++l) {
+            const double* src = &wc[(size_t)(par * 4 + (l >> 4)) * cin * 16];
+            const int o = l & 15;
+            for (int k = 0; k < 4 * d.l1_ng; ++k)
+                if (k < cd) pk[((size_t)(par * d.l1_ng + k / 4) * 64 + l) * 4 + k % 4] = (float)src[(size_t)(nscore + k) * 16 + o];
+            if (nscore) sc[par * 64 + l] = (float)src[o];
+        }
+    if ((rc = upload(h, pk, &d.l1_wc))) return rc;
+    if (nscore && (rc = upload(h, sc, &d.l1_ws))) return rc;
+    std::vector<float> bc(9 * 16);
+    for (int rcase = 0; rcase < 3; ++rcase)
+        for (int ccase = 0; ccase < 3; ++ccase)
+            for (int o = 0; o < 16; ++o) {
+                double acc = ba[o];
+                for (int ky = 0; ky < 3; ++ky)
+                    for (int kx = 0; kx < 3; ++kx) {
+                        if ((rcase == 1 && ky == 0) || (rcase == 2 && ky == 2) || (ccase == 1 && kx == 0) || (ccase == 2 && kx == 2)) continue;
+                        for (int m = 0; m < cout; ++m) acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)b[m];
+                    }
+                bc[(rcase * 3 + ccase) * 16 + o] = (float)acc;
+            }
+    if ((rc = upload(h, bc, &d.l1_bc))) return rc;
+    return 0;
+}
+
+// The last conv for the fused level: w2 [cout][16][3][3] -> d.l1_wt [9][cout][16], b2 -> d.tail_b
+int pack_level1_tail(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w2, const std::vector<float>& b2, int cout) {
+    std::vector<float> pk1(9 * 16 * cout);
+    for (int o = 0; o < cout; ++o)
+        for (int c = 0; c < 16; ++c)
+            for (int t = 0; t < 9; ++t) pk1[(t * cout + o) * 16 + c] = w2[((size_t)o * 16 + c) * 9 + t];
+    if (int rc = upload(h, pk1, &d.l1_wt)) return rc;
+    for (int o = 0; o < cout; ++o) d.tail_b[o] = b2[o];
+    return 0;
+}
+
 static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, const std::string& sfx, int nscore_l6, bool every_level_scored) {
     int rc;
     for (int j = 0; j < 6; ++j) {
@@ -240,65 +313,9 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
                                 [&](int nn, int, int c) { int qd = nn / cw, o = nn % cw; return o < cout ? w[((size_t)c * cout + o) * 4 + qd] : 0.f; },
                                 bias, 1, 1))) return rc;
         }
-        if (j == 5) {   // the fused last level (kernels_level1.hip): the transposed conv composed with conv_a, per output parity
-            // conv_a pixel (2I + py, 2J + px), tap (ky, kx) reads transposed-conv pixel (2I + py + ky - 1, ...) = input pixel
-            // (I - 1 + py + a, J - 1 + px + b) at parity (ty & 1, tx & 1), ty = py + ky + 1, a = (ty >> 1) - py (likewise for x): so
-            // Wc[py][px][a][b][c][o] = sum over the taps landing in window (a, b) of sum_m Wa[o][m][ky][kx] Wd[c][m][ty & 1][tx & 1],
-            // in double, rounded once.  An input pixel outside the 256x256 input holds exactly the transposed-conv pixels outside the
-            // 512x512 image, so zero input there reproduces the zero padding for the weight terms; the transposed conv's bias, which
-            // zero padding also removes at the borders, enters as bc[case][o] = ba[o] + sum over in-image taps of Wa[o][.][tap] . bd.
-            const auto& w = h->host["deconv" + n + sfx + ".weight"];   // [cin][16][2][2]
-            const auto& b = h->host["deconv" + n + sfx + ".bias"];
-            const auto& wa = h->host["conv" + n + sfx + ".0.weight"];  // [16][16][3][3]
-            const auto& ba = h->host["conv" + n + sfx + ".0.bias"];
-            const int cin = lv[j].din, cout = lv[j].dout;   // cout == 16
-            const int nscore = every_level_scored ? 1 : 0;
-            const int spad = score_pad(nscore);
-            const int cd = cin - nscore;   // descriptor channels
-            d.l1_cx = spad + cd;
-            d.l1_cxp = round_up(d.l1_cx, 16);
-            d.l1_c0 = spad; d.l1_ng = (cd + 3) / 4; d.l1_score = nscore;
-            std::vector<double> wc((size_t)16 * cin * 16, 0.0);   // [py][px][a][b][c][o]
-            for (int py = 0; py < 2; ++py)
-                for (int px = 0; px < 2; ++px)
-                    for (int ky = 0; ky < 3; ++ky)
-                        for (int kx = 0; kx < 3; ++kx) {
-                            const int ty = py + ky + 1, tx = px + kx + 1, a = (ty >> 1) - py, bb = (tx >> 1) - px;
-                            const int qd = (ty & 1) * 2 + (tx & 1);
-                            double* dst = &wc[(size_t)(((py * 2 + px) * 2 + a) * 2 + bb) * cin * 16];
-                            for (int c = 0; c < cin; ++c)
-                                for (int o = 0; o < 16; ++o) {
-                                    double acc = 0.0;
-                                    for (int m = 0; m < cout; ++m)
-                                        acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)w[((size_t)c * cout + m) * 4 + qd];
-                                    dst[(size_t)c * 16 + o] += acc;
-                                }
-                        }
-            // lane l of parity class par holds window q = l >> 4, output channel l & 15
-            std::vector<float> pk((size_t)4 * d.l1_ng * 64 * 4, 0.f), sc(4 * 64, 0.f);
-            for (int par = 0; par < 4; ++par)
-                for (int l = 0; l < 64; ++l) {
-                    const double* src = &wc[(size_t)(par * 4 + (l >> 4)) * cin * 16];
-                    const int o = l & 15;
-                    for (int k = 0; k < 4 * d.l1_ng; ++k)
-                        if (k < cd) pk[((size_t)(par * d.l1_ng + k / 4) * 64 + l) * 4 + k % 4] = (float)src[(size_t)(nscore + k) * 16 + o];
-                    if (nscore) sc[par * 64 + l] = (float)src[o];
-                }
-            if ((rc = upload(h, pk, &d.l1_wc))) return rc;
-            if (nscore && (rc = upload(h, sc, &d.l1_ws))) return rc;
-            std::vector<float> bc(9 * 16);
-            for (int rcase = 0; rcase < 3; ++rcase)
-                for (int ccase = 0; ccase < 3; ++ccase)
-                    for (int o = 0; o < 16; ++o) {
-                        double acc = ba[o];
-                        for (int ky = 0; ky < 3; ++ky)
-                            for (int kx = 0; kx < 3; ++kx) {
-                                if ((rcase == 1 && ky == 0) || (rcase == 2 && ky == 2) || (ccase == 1 && kx == 0) || (ccase == 2 && kx == 2)) continue;
-                                for (int m = 0; m < cout; ++m) acc += (double)wa[((size_t)o * 16 + m) * 9 + ky * 3 + kx] * (double)b[m];
-                            }
-                        bc[(rcase * 3 + ccase) * 16 + o] = (float)acc;
-                    }
-            if ((rc = upload(h, bc, &d.l1_bc))) return rc;
+        if (j == 5) {   // the fused last level (kernels_level1.hip)
+            if ((rc = compose_level1(h, d, h->host["deconv" + n + sfx + ".weight"], h->host["deconv" + n + sfx + ".bias"], h->host["conv" + n + sfx + ".0.weight"],
+                                     h->host["conv" + n + sfx + ".0.bias"], lv[j].din, every_level_scored ? 1 : 0))) return rc;
         }
         {
             const auto& w = h->host["conv" + n + sfx + ".0.weight"];
@@ -325,12 +342,7 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
                 for (int c = 0; c < 16; ++c)
                     for (int t = 0; t < 9; ++t) pk[(t * 16 + c) * cout + o] = w2[((size_t)o * 16 + c) * 9 + t];
             if ((rc = upload(h, pk, &d.tail_w))) return rc;
-            std::vector<float> pk1(9 * 16 * cout);
-            for (int o = 0; o < cout; ++o)
-                for (int c = 0; c < 16; ++c)
-                    for (int t = 0; t < 9; ++t) pk1[(t * cout + o) * 16 + c] = w2[((size_t)o * 16 + c) * 9 + t];
-            if ((rc = upload(h, pk1, &d.l1_wt))) return rc;
-            for (int o = 0; o < cout; ++o) d.tail_b[o] = b2[o];
+            if ((rc = pack_level1_tail(h, d, w2, b2, cout))) return rc;
         }
     }
     return 0;

@@ -343,8 +343,12 @@ struct Level1Params {
     int cout, normalize;
     float* out;                // NCHW [B, cout, H, W]
     float* raw;                // optional un-normalised copy (debug tap)
+    int tile;                  // output tile of launch_level1: 0 = 16 x 16, 1 = 32 wide x 16 high (where W % 32 == 0; else 16 x 16)
+    int max_wg;                // 0: the persistent grid; else at most this many workgroups (>= 8: one per XCD), so that a small
+                               // problem still loops over tiles (ccvpe_op_level1)
 };
 void launch_level1(const Level1Params& p, hipStream_t s);
+int level1_tile(const Level1Params& p);   // the tile launch_level1 runs for p
 bool level1_supported(int cxp);   // input channel count the fused kernel takes
 // Pose plans (ccvpe_localize): the same fused level for ONE 16 x 16 tile per sample - the tile holding index[b] (pose_argmax_kernel) -
 // one workgroup per sample; the thread that owns the argmax pixel writes rows[b][2..4] = (cos, sin, angle_deg).  cout 2, normalize 1.

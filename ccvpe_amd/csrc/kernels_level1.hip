@@ -6,7 +6,7 @@
 //
 // Unfused, this level moves three 512x512x16 fp32 tensors per sample through HBM and runs its 3x3 conv as
 // an N=16 GEMM with 5 K tiles (prologue/epilogue dominated).  Here one workgroup owns a 16x16 output
-// tile: the 10x10 input pixels it depends on are staged in LDS once.  Nothing lies between the transposed conv
+// tile (below; a 32x16 tile - L1Shape - has the same stages on larger extents): the 10x10 input pixels it depends on are staged in LDS once.  Nothing lies between the transposed conv
 // and the first 3x3 conv, so the two are composed into one convolution: a conv_a pixel of parity
 // (py, px) reads a 2x2 window of input pixels with weights of its parity, so each of the four parity classes of
 // the 18x18 conv_a tile is one [81 x 4 CX] x [4 CX x 16] GEMM whose A operand is gathered from the LDS tile at the
@@ -23,13 +23,18 @@ namespace ccvpe {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-static constexpr int T = 16;          // output tile
-static constexpr int AT = T + 2;      // conv_a-output tile (halo 1)
-static constexpr int XT = T / 2 + 2;  // input tile (10 x 10)
-static constexpr int PS = 20;         // floats per pixel in the P tile (18 + 2 pad)
-static constexpr int NPOS = (AT / 2) * (AT / 2);    // conv_a pixels of one parity class: 9 x 9
-static constexpr int NMT1 = (NPOS + 15) / 16;       // their m-tiles: 6
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Output tile (TY rows x TX columns) and workgroup size of the shared body (kernels_level1_tile.inc), by Level1Params::tile.
+// 16 x 16: an 18 x 18 conv_a tile for 256 outputs and 4 x 6 m-tiles for 4 x 81 positions - 384 GEMM rows per 256 outputs.
+// 32 x 16: 18 x 34 for 512 and 4 x 10 m-tiles for 4 x 153 positions - 640 rows per 512 outputs, 1/6 fewer MFMAs per output.
+template <int TILE> struct L1Shape;
+template <> struct L1Shape<0> { static constexpr int TY = 16, TX = 16, NTHR = 256; };
+template <> struct L1Shape<1> { static constexpr int TY = 16, TX = 32, NTHR = 512; };   // wave = (parity class, half of its m-tiles)
+static constexpr int L1_TILES = 2;
+// Floats per pixel of the P tile.  16 wide: 18 + 2 pad.  32 wide: the 9 COUT real columns and no more - two loc workgroups fit a CU's LDS,
+// and stage 3's reads (32 consecutive pixels per LDS lane group) are conflict-free: dword reads at stride 9, 8-byte reads at stride 18.
+static constexpr int l1_ps(int cout, int tx) { return tx == 16 ? 20 : 9 * cout; }
 
 
 #ifndef CCVPE_L1_CLOCK
@@ -43,11 +48,10 @@ __device__ unsigned long long g_l1_clk[10];
 #endif
 
 static constexpr int KCH_MAX = 4;     // input channels <= 64 (16 per chunk); the host falls back to the unfused path beyond
-static constexpr int XI_MAX = (XT * XT * KCH_MAX * 4 + 255) / 256;   // float4 items per thread of one X tile
 
-static constexpr int L1_WG_PER_CU = 2;   // persistent grid: workgroups per CU
+static constexpr int L1_WAVES_PER_CU = 8;   // persistent grid: two 256-thread workgroups or one 512-thread workgroup per CU
 
-// Persistent: L1_WG_PER_CU workgroups per CU loop over the 16x16 output tiles (XCD x owns a contiguous run, so neighbouring
+// Persistent: L1_WAVES_PER_CU waves per CU loop over the output tiles (XCD x owns a contiguous run, so neighbouring
 // tiles - which share their input halo - meet in one L2).  Per-workgroup constants (the composed weights and the tail conv's
 // weights as MFMA fragments, the interior bias, the per-lane LDS offsets) are set up once, and the next tile's input pixels are
 // loaded into registers while the current tile runs its stages.  Measured before this: with one tile per workgroup 0.36 of the
@@ -63,8 +67,8 @@ static constexpr int L1_WG_PER_CU = 2;   // persistent grid: workgroups per CU
 // form computes for it - and the thread that owns the argmax pixel writes (cos, sin, angle_deg) to pose_rows[b][2..4] instead of storing the
 // tile.  The fragment is included into both kernels rather than called as a force-inlined function: inlining reorders level1_kernel's
 // kernarg loads and register assignment.
-template <int COUT, int NG, int SCORE>
-__global__ __launch_bounds__(256) void level1_kernel(const Level1Params p) {
+template <int COUT, int NG, int SCORE, int TILE>
+__global__ __launch_bounds__(L1Shape<TILE>::NTHR) void level1_kernel(const Level1Params p) {
     constexpr bool POSE = false;
     const int* pose_index = nullptr;
     float* pose_rows = nullptr;
@@ -72,9 +76,11 @@ __global__ __launch_bounds__(256) void level1_kernel(const Level1Params p) {
 #include "kernels_level1_tile.inc"
 }
 
+// (the pose and top-K forms run one tile per workgroup and stay on 16 x 16: fewer pixels computed around the one that is kept)
 template <int COUT, int NG, int SCORE>
 __global__ __launch_bounds__(256) void level1_pose_kernel(const Level1Params p, const int* pose_index, float* pose_rows) {
     constexpr bool POSE = true;
+    constexpr int TILE = 0;
     const unsigned pose_slot = blockIdx.x;                 // one workgroup per sample: index[b], rows[b][0..4]
     const int pose_sample = (int)blockIdx.x;
     constexpr int pose_ld = 5, pose_r0 = 0;
@@ -86,6 +92,7 @@ __global__ __launch_bounds__(256) void level1_pose_kernel(const Level1Params p, 
 template <int COUT, int NG, int SCORE>
 __global__ __launch_bounds__(256) void level1_topk_kernel(const Level1Params p, const int* pose_index, float* pose_rows) {
     constexpr bool POSE = true;
+    constexpr int TILE = 0;
     const int K = (int)gridDim.x;
     const int pose_slot = (int)blockIdx.y * K + (int)blockIdx.x, pose_sample = (int)blockIdx.y;
     const int pose_ld = 5 * K, pose_r0 = 5 * (int)blockIdx.x;
@@ -95,8 +102,15 @@ __global__ __launch_bounds__(256) void level1_topk_kernel(const Level1Params p, 
 
 bool level1_supported(int cxp) { return cxp >= 16 && cxp <= 16 * KCH_MAX && cxp % 16 == 0; }
 
-size_t level1_lds_bytes(int cxp) {
-    return ((size_t)XT * XT * (cxp + 4) + (size_t)AT * AT * PS) * sizeof(float);   // X tile, P tile
+template <int TILE>
+static size_t lds_bytes(int cxp, int cout) {
+    using S = L1Shape<TILE>;
+    return ((size_t)(S::TY / 2 + 2) * (S::TX / 2 + 2) * (cxp + 4) + (size_t)(S::TY + 2) * (S::TX + 2) * l1_ps(cout, S::TX)) * sizeof(float);   // X tile, P tile
+}
+
+int level1_tile(const Level1Params& p) {
+    const int t = p.tile < 0 || p.tile >= L1_TILES ? 0 : p.tile;
+    return t == 1 && (p.H % L1Shape<1>::TY || p.W % L1Shape<1>::TX) ? 0 : t;
 }
 
 // shape class of the composed weights: f(NG, SCORE)
@@ -109,24 +123,34 @@ static void with_shape(const Level1Params& p, F&& f) {
     else f(integral_constant<int, 0>{}, integral_constant<int, 0>{});
 }
 
-template <int COUT, int NG, int SCORE>
-static void launch_level1_t(const Level1Params& p, dim3 grid, size_t lds, hipStream_t s) {
+template <int COUT, int NG, int SCORE, int TILE>
+static void launch_level1_t(const Level1Params& p, hipStream_t s) {
+    using S = L1Shape<TILE>;
+    const size_t lds = lds_bytes<TILE>(p.cxp, COUT);
+    const int tiles = (p.W / S::TX) * (p.H / S::TY) * p.B;
+    dim3 grid(std::min(tiles, p.max_wg >= 8 ? p.max_wg : L1_WAVES_PER_CU * 64 / S::NTHR * 256));   // persistent
     static LdsAttr attr;
-    ensure_dynamic_lds(attr, reinterpret_cast<const void*>(level1_kernel<COUT, NG, SCORE>), lds);
-    CCVPE_LAUNCH((level1_kernel<COUT, NG, SCORE>), grid, dim3(256), lds, s, p);
+    ensure_dynamic_lds(attr, reinterpret_cast<const void*>(level1_kernel<COUT, NG, SCORE, TILE>), lds);
+    CCVPE_LAUNCH((level1_kernel<COUT, NG, SCORE, TILE>), grid, dim3(S::NTHR), lds, s, p);
+}
+
+template <int COUT>
+static void launch_level1_c(const Level1Params& p, hipStream_t s) {
+    with_shape(p, [&](auto ng, auto sc) {
+        constexpr int NG = decltype(ng)::value, SCORE = decltype(sc)::value;
+        if (level1_tile(p) == 1) launch_level1_t<COUT, NG, SCORE, 1>(p, s);
+        else launch_level1_t<COUT, NG, SCORE, 0>(p, s);
+    });
 }
 
 void launch_level1(const Level1Params& p, hipStream_t s) {
-    const size_t lds = level1_lds_bytes(p.cxp);
-    const int tiles = (p.W / T) * (p.H / T) * p.B;
-    dim3 grid(std::min(tiles, L1_WG_PER_CU * 256));   // persistent
 #if CCVPE_L1_CLOCK
     static int calls = 0;
     const bool stamp = ++calls % 4 == 0;
     if (stamp) { (void)hipStreamSynchronize(s); unsigned long long z[10] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_l1_clk), z, sizeof z); }
 #endif
-    if (p.cout == 1) with_shape(p, [&](auto ng, auto sc) { launch_level1_t<1, decltype(ng)::value, decltype(sc)::value>(p, grid, lds, s); });
-    else with_shape(p, [&](auto ng, auto sc) { launch_level1_t<2, decltype(ng)::value, decltype(sc)::value>(p, grid, lds, s); });
+    if (p.cout == 1) launch_level1_c<1>(p, s);
+    else launch_level1_c<2>(p, s);
 #if CCVPE_L1_CLOCK
     if (stamp) {
         (void)hipStreamSynchronize(s);
@@ -141,7 +165,7 @@ void launch_level1(const Level1Params& p, hipStream_t s) {
 }
 
 void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hipStream_t s) {
-    const size_t lds = level1_lds_bytes(p.cxp);
+    const size_t lds = lds_bytes<0>(p.cxp, 2);
     with_shape(p, [&](auto ng, auto sc) {
         constexpr int NG = decltype(ng)::value, SCORE = decltype(sc)::value;
         static LdsAttr attr;
@@ -151,7 +175,7 @@ void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hi
 }
 
 void launch_level1_topk(const Level1Params& p, const int* index, int k, float* rows, hipStream_t s) {
-    const size_t lds = level1_lds_bytes(p.cxp);
+    const size_t lds = lds_bytes<0>(p.cxp, 2);
     with_shape(p, [&](auto ng, auto sc) {
         constexpr int NG = decltype(ng)::value, SCORE = decltype(sc)::value;
         static LdsAttr attr;

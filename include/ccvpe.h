@@ -430,6 +430,19 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
                     int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, int32_t tile,
                     float* out, int32_t iters, float* ms, void* stream);
 
+/* Kernel-level hook for parity tests (not on the product path): the fused last decoder level on its own,
+ * ConvTranspose2d(k2, s2, Cin -> 16) -> conv3x3(16 -> 16, pad 1) + ReLU -> conv3x3(16 -> Cout, pad 1), and for Cout == 2 the L2
+ * normalisation over the channel (F.normalize, eps 1e-12).  H x W is the OUTPUT size (multiples of 16).  score != 0: channel 0 of the
+ * Cin reference channels is a score channel, and `in` is the plan's padded layout [B, H/2, W/2, 8 + (Cin - 1)] = [score, 7 unused,
+ * Cin - 1 descriptor channels]; score == 0: in [B, H/2, W/2, Cin].  The descriptor channel count is a multiple of 4, and at most 64
+ * channels reach the kernel.  Weights and biases in the reference's layouts, host or device: wd [Cin,16,2,2], bd [16], wa [16,16,3,3],
+ * ba [16], wt [Cout,16,3,3], bt [Cout]; they are composed by the code that serves ccvpe_create.  tile: 0 = 16 x 16 output tiles, 1 = 32
+ * wide x 16 high where W is a multiple of 32 (16 x 16 otherwise); every tile gives every output the same bits.  tile word = id |
+ * (workgroup cap << 8): a cap (>= 8) makes a small problem run the kernel's loop over tiles; 0 = the persistent grid.  out [B,Cout,H,W]
+ * (device, NCHW).  Returns the tile that ran (0 or 1), or a negative error code. */
+int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t score, const float* wd, const float* bd,
+                    const float* wa, const float* ba, const float* wt, const float* bt, int32_t Cout, int32_t tile, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
