@@ -361,6 +361,36 @@ def oxford_ground_truth(image_coords, yaw) -> Dict[str, np.ndarray]:
     return {"gt_index": idx, "gt_cos_sin": _cos_sin_f32(heading), "heading_deg": heading}
 
 
+# ---- posterior summary ------------------------------------------------------------------------------------------
+
+# the 16 columns of model.localize_summary's / belief_summary's rows, in order (include/ccvpe.h): positions in cells of the 512 grid
+SUMMARY_FIELDS = ("index", "prob", "mass", "entropy", "mean_x", "mean_y", "var_xx", "cov_xy", "var_yy",
+                  "peak_mass", "peak_mean_x", "peak_mean_y", "peak_var_xx", "peak_cov_xy", "peak_var_yy", "peak_cells")
+_SUMMARY_LENGTHS = (4, 5, 10, 11)
+_SUMMARY_AREAS = (6, 7, 8, 12, 13, 14)
+
+
+def summary_to_metres(summary, metres_per_px):
+    """Summary rows [..., 16] (a tensor or an array) with the means in metres and the (co)variances in square metres: metres_per_px
+    is the ground size of one cell of the 512 grid, a number or one per row ([B]; KITTI / Oxford: their map resolution times the
+    resize factor, VIGOR: the tile's).  The four means scale by it, the six (co)variances by its square; index, prob, mass,
+    entropy, peak_mass and peak_cells are unchanged.  The means stay relative to the centre of cell (0, 0)."""
+    import torch
+    if isinstance(summary, torch.Tensor):
+        out = summary.clone()
+        f = torch.as_tensor(metres_per_px, dtype=out.dtype, device=out.device)
+    else:
+        out = np.array(summary, dtype=np.float64 if np.asarray(summary).dtype == np.float64 else np.float32)
+        f = np.asarray(metres_per_px, dtype=out.dtype)
+    if out.shape[-1] != len(SUMMARY_FIELDS):
+        raise ValueError(f"summary must be [..., {len(SUMMARY_FIELDS)}], got {tuple(out.shape)}")
+    if f.ndim > 0:
+        f = f.reshape(tuple(f.shape) + (1,))
+    for cols, g in ((_SUMMARY_LENGTHS, f), (_SUMMARY_AREAS, f * f)):
+        out[..., list(cols)] = out[..., list(cols)] * g
+    return out
+
+
 # ---- tracking a frame stream (DESIGN.md 4.11) ------------------------------------------------------------------------------------
 
 def gaussian_taps(sigma_px, radius: int) -> np.ndarray:
@@ -409,10 +439,12 @@ class Tracker:
         self.belief = None
         self.origin = None
 
-    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor):
+    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None):
         """One frame of B parallel streams.  cache / tile_index: as model.localize_cached; origins [T,2]: the crop origin of every
         cached tile (oxford_tiles' "origin"; one per query when tile_index is None); motion_map_px [B,2] or [2]: the motion since
-        the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5]."""
+        the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5];
+        with summary_radius (0..32) the update is model.localize_summary_cached - the same rows and belief - and the step returns
+        (rows, summary [B,16]): entropy, covariance and peak mass of the new belief (SUMMARY_FIELDS), to gate on."""
         org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
         B = grd.shape[0]
         now = org if tile_index is None else org[np.asarray(tile_index, dtype=np.int64)]
@@ -423,6 +455,11 @@ class Tracker:
             if self.belief.shape[0] != B:
                 raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
             prior = model.track_predict(self.belief, oxford_track_shift(self.origin, now, motion_map_px), taps, floor)
-        rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
+        summary = None
+        if summary_radius is None:
+            rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
+        else:
+            rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
+                                                                       tile_index=tile_index)
         self.origin = now.copy()
-        return rows
+        return rows if summary is None else (rows, summary)

@@ -419,6 +419,7 @@ static int run_forward(ccvpe_handle h, const ForwardCall& fc) {
         c.sat = fc.sat ? fc.sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
         if (fc.log_prior) { c.log_prior = fc.log_prior + (size_t)done * fc.prior_stride; c.prior_stride = fc.prior_stride; }
         if (fc.posterior) c.posterior = fc.posterior + (size_t)done * npx;
+        if (fc.summary) { c.summary = fc.summary + (size_t)done * SUMMARY_COLS; c.summary_r = fc.summary_r; }
         if (key.topk) {
             c.rows = fc.rows + (size_t)done * fc.topk_k * 5;
             c.topk_k = fc.topk_k; c.topk_r = fc.topk_r;
@@ -519,16 +520,19 @@ static int ensure_scratch(ccvpe_handle_s::Scratch& buf, int batch, size_t (*byte
 }
 
 // The top-K scratch (topk_scratch_bytes) and the prior scratch for buf.batch samples: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys]
-// [B x 64 indices] and, in the prior scratch only, [B x 64 x 2 softmax partials]; the argmax form's (max, index) hand-off pairs use the
-// start of the key area.
-static size_t prior_scratch_bytes(int B) { return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float); }
-struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; };
+// [B x 64 indices] and, in the prior scratch only, [B x 64 x 2 softmax partials][B x 64 x 8 float64 sums of the summary forms]; the
+// argmax form's (max, index) hand-off pairs use the start of the key area.  Every area is a multiple of 8 bytes long.
+static size_t prior_scratch_bytes(int B) {
+    return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float) + (size_t)B * 64 * SUMMARY_PART * sizeof(double);
+}
+struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; double* summ; };
 static TopkScratch topk_scratch_layout(const ccvpe_handle_s::Scratch& buf) {
     TopkScratch w;
     w.tickets = reinterpret_cast<unsigned*>(buf.ptr);
     w.keys = reinterpret_cast<unsigned long long*>(w.tickets + PP_MAX_BATCH);
     w.index = reinterpret_cast<int*>(w.keys + (size_t)buf.batch * 64 * TOPK_MAX_K);
     w.partial = reinterpret_cast<float*>(w.index + (size_t)buf.batch * TOPK_MAX_K);
+    w.summ = reinterpret_cast<double*>(w.partial + (size_t)buf.batch * 64 * 2);   // (read by the summary forms alone)
     return w;
 }
 
@@ -872,15 +876,17 @@ static void launch_logits_softmax(const TopkScratch& w, const float* logits, int
     launch_softmax_partial(sp, s);
 }
 
-// ... and softmax.partial -> pose.argmax -> pose.gather, the tail of an argmax pose plan (build_plan): prior and posterior are optional
+// ... and softmax.partial -> pose.argmax -> pose.gather, the tail of an argmax pose plan (build_plan): prior, posterior and summary
+// (with its window radius) are optional
 static void launch_logits_argmax(const TopkScratch& w, const float* logits, const float* ori, int batch, const float* prior, long long stride,
-                                 float* posterior, float* rows, hipStream_t s) {
+                                 float* posterior, float* rows, hipStream_t s, float* summary = nullptr, int summary_r = 0) {
     const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
     launch_logits_softmax(w, logits, batch, prior, stride, s);
     PoseArgmaxParams p{};
     p.logits = logits; p.partial = w.partial; p.B = batch; p.n = n; p.chunks = 64;
     p.pairs = reinterpret_cast<float*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = rows; p.stats = nullptr;
     p.prior = prior; p.prior_stride = stride; p.posterior = posterior;
+    if (summary) { p.summary = summary; p.summ_part = w.summ; p.summary_r = summary_r; }
     launch_pose_argmax(p, s);
     launch_pose_gather(ori, w.index, batch, n, rows, s);
 }
@@ -993,6 +999,83 @@ int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, cons
     p.log_prior = log_prior; p.B = batch;
     launch_track_predict(p, (hipStream_t)stream);
     return launch_status("track_predict launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Posterior summary: the argmax pose plans with the summary row as one more output of pose.argmax (plans of their own,
+// PlanKey::summary, for the float64 hand-off in the workspace; the launches, names and tuning entries of the pose plans), the logits
+// form on the prior scratch, and one launch of belief_summary_kernel for a stored map.
+// ------------------------------------------------------------------------------------------------
+// log_prior and posterior may be null; the posterior's aliasing rules are ccvpe_track_update's
+static int check_summary_args(const float* log_prior, int64_t prior_stride, int32_t radius, const float* rows, const float* summary,
+                              const float* posterior) {
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!summary) return ccvpe_fail(CCVPE_EINVAL, "null summary");
+    if (radius < 0 || radius > SUMMARY_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", SUMMARY_MAX_R, radius);
+    if (log_prior) if (int rc = check_prior_stride(prior_stride)) return rc;
+    if (summary == rows) return ccvpe_fail(CCVPE_EINVAL, "summary must not alias rows");
+    if (posterior && log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    if (posterior && (posterior == summary || posterior == rows)) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias rows or summary");
+    return 0;
+}
+
+int ccvpe_localize_summary(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                           const float* log_prior, int64_t prior_stride, int32_t radius, float* rows, float* summary, float* posterior,
+                           void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (int rc = check_summary_args(log_prior, prior_stride, radius, rows, summary, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    fc.summary = summary; fc.summary_r = radius;
+    return run_forward(h, fc);
+}
+
+int ccvpe_localize_summary_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                          const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride,
+                                          int32_t radius, float* rows, float* summary, float* posterior, void* stream) {
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    if (int rc = check_summary_args(log_prior, prior_stride, radius, rows, summary, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    fc.summary = summary; fc.summary_r = radius;
+    return run_forward(h, fc);
+}
+
+int ccvpe_postprocess_summary(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, int32_t radius, float* rows, float* summary, float* posterior, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (int rc = check_summary_args(log_prior, prior_stride, radius, rows, summary, posterior)) return rc;
+    if (posterior && posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, log_prior, log_prior ? prior_stride : 0, posterior, rows,
+                         (hipStream_t)stream, summary, radius);
+    return launch_status("postprocess_summary launch");
+}
+
+int ccvpe_belief_summary(ccvpe_handle h, const float* belief, int32_t batch, int32_t radius, float* summary, void* stream) {
+    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
+    if (!summary) return ccvpe_fail(CCVPE_EINVAL, "null summary");
+    if (radius < 0 || radius > SUMMARY_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", SUMMARY_MAX_R, radius);
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (summary == belief) return ccvpe_fail(CCVPE_EINVAL, "summary must not alias belief");
+    if (((uintptr_t)belief & 3) != 0) return ccvpe_fail(CCVPE_EINVAL, "belief must be 4-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
+    BeliefSummaryParams p{};
+    p.belief = belief; p.B = batch; p.r = radius; p.pairs = reinterpret_cast<float*>(w.keys); p.summ_part = w.summ; p.tickets = w.tickets;
+    p.summary = summary;
+    launch_belief_summary(p, (hipStream_t)stream);
+    return launch_status("belief_summary launch");
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

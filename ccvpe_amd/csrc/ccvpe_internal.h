@@ -254,6 +254,8 @@ struct Ctx {
     const float* log_prior = nullptr;  // pose plans: optional log-prior of this micro-batch's first sample ...
     long long prior_stride = 0;        // ... and the floats between two samples' maps (0: one map for all)
     float* posterior = nullptr;        // pose plans: optional posterior map [mb][512*512] of this micro-batch (ccvpe_track_update*)
+    float* summary = nullptr;          // summary pose plans: the [mb][16] summary rows of this micro-batch (ccvpe_localize_summary*) ...
+    int summary_r = 0;                 // ... and the window radius 0..32 of this call
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -275,7 +277,11 @@ struct PlanKey {
                                   // 4 pose plan from both caches (the pairs of ccvpe_localize_region)
     bool pose = false;            // modes 0 / 2: the pose plan of ccvpe_localize - result rows instead of the nine outputs (build_plan)
     bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
-    bool operator==(const PlanKey& o) const { return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk; }
+    bool summary = false;         // argmax pose plans: pose.argmax also writes the summary rows (ccvpe_localize_summary*); the only plans whose
+                                  // workspace holds the float64 hand-off of the chunks' sums
+    bool operator==(const PlanKey& o) const {
+        return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk && summary == o.summary;
+    }
 };
 
 // One call of the forward family (run_forward, ccvpe_api.hip): every extern "C" entry point checks its own arguments, fills the fields
@@ -294,11 +300,14 @@ struct ForwardCall {
     const float* log_prior = nullptr;  // pose plans, optional (ccvpe_localize_prior*, ccvpe_track_update*): every slice reads its own maps ...
     long long prior_stride = 0;        // ... this many floats apart (0: one map for all; checked by the entry point)
     float* posterior = nullptr;        // argmax pose plans, optional (ccvpe_track_update*): every slice also writes its own posterior maps
+    float* summary = nullptr;          // argmax pose plans (ccvpe_localize_summary*): [batch][16] summary rows, every slice its own; selects the
+    int summary_r = 0;                 //   summary plans.  The window radius, checked by the entry point
     hipStream_t stream = nullptr;
     bool profile = false;              // ccvpe_profile_forward: a hipEvent pair around every launch
     PlanKey plan_key() const {         // (B: set per slice by the micro-batch loop)
         PlanKey key;
         key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = rows != nullptr; key.topk = rows && topk_k > 0;
+        key.summary = rows && summary;
         return key;
     }
 };
@@ -547,7 +556,8 @@ struct ccvpe_handle_s {
     struct Scratch { void* ptr = nullptr; int batch = 0; };
     Scratch post_scratch;         // launch_postprocess: partial pairs and ticket counters
     Scratch topk_scratch;         // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices
-    Scratch prior_scratch;        // ccvpe_postprocess_prior, ccvpe_track_update_logits: the top-K scratch plus softmax partials
+    Scratch prior_scratch;        // ccvpe_postprocess_prior, ccvpe_track_update_logits, ccvpe_postprocess_summary, ccvpe_belief_summary: the
+                                  // top-K scratch plus softmax partials plus the summary's float64 hand-off
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;

@@ -323,6 +323,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     const bool pose = key.pose;
     pl.key = key;
     pl.key.topk = pose && key.topk;
+    pl.key.summary = pose && !key.topk && key.summary;
     if (mode == 1) return build_aerial_plan(h, pl, B);
     if (mode == 3) return build_ground_plan(h, pl, B, gh, gw);
     const bool cached = mode == 2 || mode == 4;
@@ -611,6 +612,11 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         const bool topk = pl.key.topk;
         Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, topk ? 2 * TOPK_MAX_K : 2);   // (argmax: the (max, index) hand-off pairs)
         pose_index = pl.alloc(B, 1, 1, topk ? TOPK_MAX_K : 1);
+        // summary plans: the chunks' float64 sums, B x 64 x 8 doubles (tensors start on 256-byte granules); no other
+        // plan allocates it, so theirs keep their workspace
+        static_assert(sizeof(double) == 2 * sizeof(float), "the hand-off is allocated in floats");
+        const bool summ = pl.key.summary;
+        const Tensor spart = summ ? pl.alloc(B, 1, 64, 2 * SUMMARY_PART) : Tensor{};
         const Tensor lg = logits_ws, idx = pose_index;
         pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
             SoftmaxParams p{};
@@ -627,11 +633,12 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_topk_peaks(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
-        else pl.add("pose.argmax", {lg, part, keys, idx}, [=](const Ctx& c) {
+        else pl.add("pose.argmax", summ ? std::vector<Tensor>{lg, part, keys, idx, spart} : std::vector<Tensor>{lg, part, keys, idx}, [=](const Ctx& c) {
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
             p.pairs = c.ptr(keys); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
             p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.posterior = c.posterior;
+            if (summ) { p.summary = c.summary; p.summ_part = reinterpret_cast<double*>(c.ptr(spart)); p.summary_r = c.summary_r; }
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
     } else {

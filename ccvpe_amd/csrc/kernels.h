@@ -391,8 +391,29 @@ struct PoseArgmaxParams {
     long long prior_stride;    //   (max, 1/sum) is not finite gets index 0 and rows (-1, NaN)
     float* posterior;          // optional [B][n] (ccvpe_track_update*): the heatmap of l' the chunks recompute, stored as
                                //   float4; all zeros (and the row (-1, NaN)) for a sample whose (max, 1/sum) is not finite
+    float* summary;            // optional [B][SUMMARY_COLS] (ccvpe_*_summary): moments, entropy and peak mass of that heatmap;
+    double* summ_part;         //   with it [B][chunks][SUMMARY_PART] float64 hand-off of the chunks' sums and
+    int summary_r;             //   the half side 0 .. SUMMARY_MAX_R of the window around the argmax
 };
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s);
+
+// Posterior summary: one row of SUMMARY_COLS floats per map h of 512 x 512 values, x = index % 512, y = index / 512 -
+//   0 argmax (first maximal index)   1 h there   2 S0 = sum h   3 entropy -sum (h/S0) ln(h/S0) over h > 0, nats
+//   4, 5 mean x, y   6, 7, 8 var_xx, cov_xy, var_yy about it                            (weights h / S0)
+//   9 sum of h over the window |x - x*| <= r, |y - y*| <= r around the argmax, clipped to the grid, over S0
+//   10, 11 mean x, y of the window   12, 13, 14 its var_xx, cov_xy, var_yy about that mean   (weights h / the window's sum)   15 its cells
+// from float64 sums (h times a coordinate product below 2^18 is exact in float64).  pose_argmax_kernel computes it for the heatmap it
+// recomputes; launch_belief_summary for a stored map: grid (64 chunks, B), one launch, the same accumulation and reduction code.
+static constexpr int SUMMARY_COLS = 16, SUMMARY_PART = 8, SUMMARY_MAX_R = 32;
+struct BeliefSummaryParams {
+    const float* belief;       // [B][512*512], 4-byte aligned (16-byte aligned maps are read as float4)
+    int B, r;
+    float* pairs;              // [B][64][2] (max, index) hand-off
+    double* summ_part;         // [B][64][SUMMARY_PART]
+    unsigned* tickets;         // [B] counters, zero before and after every launch
+    float* summary;            // [B][SUMMARY_COLS]; S0 == 0: (0, 0, 0, NaN ...)
+};
+void launch_belief_summary(const BeliefSummaryParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
 void launch_pose_gather(const float* ori, const int* index, int B, int n, float* rows, hipStream_t s);
 

@@ -254,6 +254,116 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
 }
 
 // ------------------------------------------------------------------------------------------------
+// Posterior summary (the row is defined in kernels.h): the accumulation and reduction steps pose_argmax_kernel<.., SUMM>
+// (values recomputed from the logits) and belief_summary_kernel (a stored map) share, so that the two forms are one definition.
+// Seven float64 sums per map - S0, Sx, Sy, Sxx, Sxy, Syy, S(h ln h) - over the 64 chunk workgroups: every thread adds its values, the
+// wave reduces with xor shuffles, the four waves meet in LDS (wave order), thread 0 hands the chunk's sums to the sample's last
+// arriver (ticket.h) beside the (max, index) pair.  The last arriver adds the 64 chunks' sums (lane = chunk, then the xor shuffles),
+// runs the window pass around the argmax with all its threads (six sums of at most 65 x 65 values, reduced the same way) and thread 0
+// writes the row.  Every order is fixed: the same map gives the same bits whoever arrives last.
+// ------------------------------------------------------------------------------------------------
+static constexpr int SM_HW = 512;                   // map side (CCVPE_OUT_HW)
+static constexpr int SM_SUMS = 7, SM_WIN = 6;       // sums per map, per window (no entropy term)
+static_assert(SM_SUMS <= SUMMARY_PART && PP_CHUNKS == 64, "one lane of the last arriver's first wave per chunk");
+
+// h at index i into a[0 .. n): S0, Sx, Sy, Sxx, Sxy, Syy and, n == 7, S(h ln h) (h == 0 adds 0).  h * x and h * y are exact in float64,
+// h * x * x below 2^42 as well: every fused multiply-add rounds once, like the add alone
+template <int n>
+__device__ __forceinline__ void summ_take(double (&a)[n], float h, int i) {
+    const double hd = (double)h, x = (double)(i & (SM_HW - 1)), y = (double)(i >> 9);
+    const double hx = hd * x, hy = hd * y;
+    a[0] += hd; a[1] += hx; a[2] += hy;
+    a[3] = fma(hx, x, a[3]); a[4] = fma(hx, y, a[4]); a[5] = fma(hy, y, a[5]);
+    if constexpr (n > SM_WIN) a[6] = fma(hd, h > 0.f ? (double)logf(h) : 0.0, a[6]);
+}
+
+// every thread: its sums -> the wave's (all lanes), lane 0 of each wave -> lds[wave][n]; the caller meets at a barrier, then ...
+template <int n>
+__device__ __forceinline__ void summ_wave_to_lds(double (&a)[n], double* lds) {
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_xor(a[k], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) lds[(threadIdx.x >> 6) * n + k] = a[k];
+    }
+}
+// ... thread 0: the workgroup's sums, waves in order
+template <int n>
+__device__ __forceinline__ void summ_from_lds(double (&a)[n], const double* lds) {
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+#pragma unroll
+        for (int k = 0; k < n; ++k) a[k] += lds[w * n + k];
+    }
+}
+// thread 0 of chunk c: the chunk's sums to the hand-off (agent-scope stores, before ticket_arrive)
+__device__ __forceinline__ void summ_publish(const double (&a)[SM_SUMS], double* part) {
+#pragma unroll
+    for (int k = 0; k < SM_SUMS; ++k) st_sc1(part + k, a[k]);
+}
+
+// All 256 threads of a sample's last arriver, behind ticket_arrive and a barrier that made (bi, best) uniform.  part: the sample's
+// [64][SUMMARY_PART] hand-off; h_at(i): the map's value at index i in [0, 512 * 512), the expression the sums were taken of; lds:
+// 4 * SM_SUMS doubles nobody else touches; ok: the sample has a posterior (else the row is (-1, NaN, NaN ...)).  The window loads
+// go out SM_UB per thread at a time: r = 8 is one trip to memory, r = 32 three.
+static constexpr int SM_UB = 6;
+template <class HAt>
+__device__ __forceinline__ void summ_finish(const double* part, int bi, float best, bool ok, int r, HAt h_at, double* lds, float* row) {
+    double g[SM_SUMS];
+    if (threadIdx.x < 64) {
+#pragma unroll
+        for (int k = 0; k < SM_SUMS; ++k) g[k] = ld_sc1(part + threadIdx.x * SUMMARY_PART + k);
+#pragma unroll
+        for (int k = 0; k < SM_SUMS; ++k) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) g[k] += __shfl_xor(g[k], off);
+        }
+    }
+    const int xs = bi & (SM_HW - 1), ys = bi >> 9;
+    const int x0 = max(xs - r, 0), x1 = min(xs + r, SM_HW - 1), y0 = max(ys - r, 0), y1 = min(ys + r, SM_HW - 1);
+    const int ww = x1 - x0 + 1, cells = ww * (y1 - y0 + 1);
+    double w[SM_WIN] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i0 = threadIdx.x; i0 < cells; i0 += 256 * SM_UB) {
+        float hv[SM_UB];
+        int at[SM_UB];
+#pragma unroll
+        for (int u = 0; u < SM_UB; ++u) {
+            const int i = i0 + u * 256;
+            const int ly = i / ww;
+            at[u] = i < cells ? (y0 + ly) * SM_HW + x0 + (i - ly * ww) : bi;   // (past the window: a read inside the map that adds 0)
+            hv[u] = h_at(at[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < SM_UB; ++u) summ_take(w, i0 + u * 256 < cells ? hv[u] : 0.f, at[u]);
+    }
+    summ_wave_to_lds(w, lds);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    summ_from_lds(w, lds);
+    const float nan = NAN;
+    row[0] = ok ? (float)bi : -1.f;
+    row[1] = ok ? best : nan;
+    const double S0 = g[0], W0 = w[0];
+    row[2] = ok ? (float)S0 : nan;
+    if (!ok || S0 == 0.0) {
+#pragma unroll
+        for (int k = 3; k < SUMMARY_COLS; ++k) row[k] = nan;
+        return;
+    }
+    const double mx = g[1] / S0, my = g[2] / S0, wx = w[1] / W0, wy = w[2] / W0;
+    row[3] = (float)(log(S0) - g[6] / S0);
+    row[4] = (float)mx; row[5] = (float)my;
+    row[6] = (float)(g[3] / S0 - mx * mx); row[7] = (float)(g[4] / S0 - mx * my); row[8] = (float)(g[5] / S0 - my * my);
+    row[9] = (float)(W0 / S0);
+    row[10] = (float)wx; row[11] = (float)wy;
+    row[12] = (float)(w[3] / W0 - wx * wx); row[13] = (float)(w[4] / W0 - wx * wy); row[14] = (float)(w[5] / W0 - wy * wy);
+    row[15] = (float)cells;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Pose plans (ccvpe_localize): postprocess_kernel's argmax over a heatmap that is never stored.  Chunk c of sample b is postprocess_kernel's
 // chunk c (4096 values); its values are recomputed from the logits as __expf(v - m) * inv with softmax_final_kernel's (m, inv), i.e. the
 // bits that kernel would store, so index and prob are those ccvpe_postprocess_rows reads from the heatmap, ties included (strictly greater
@@ -265,13 +375,18 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
 // POST (ccvpe_track_update*): the values the chunk has just recomputed are also stored, as float4, to posterior[b] - the
 // map softmax_final_kernel would store for l'.  Every workgroup knows (m, inv), so each applies the rule for a sample without a finite
 // posterior to its own chunk: all zeros.
+// SUMM (ccvpe_*_summary): the summary row of that map, from the values in registers - the chunk's seven float64 sums go
+// to the last arriver beside its (max, index) pair, and the last arriver, the argmax in hand, recomputes the window around it with
+// take()'s expression (summ_finish).  A sample without a finite posterior: (-1, NaN, NaN ...), with or without a prior.
 // ------------------------------------------------------------------------------------------------
-template <bool PRIOR, bool POST = false>
+template <bool PRIOR, bool POST = false, bool SUMM = false>
 __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams p) {
     __shared__ float gm, gs;
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ unsigned flag;
+    __shared__ double sd[SUMM ? 4 * SM_SUMS : 1];
+    double acc[SM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int b = blockIdx.y, c = blockIdx.x;
     softmax_stats(p.partial, b, p.chunks, gm, gs);
     const int per = p.n / p.chunks;                   // 4096: a multiple of 4 x 256
@@ -302,11 +417,29 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
     if constexpr (POST) {
         float4* dst = reinterpret_cast<float4*>(p.posterior + (size_t)b * p.n + lo);
         const bool fin = isfinite(m) && isfinite(inv);
+        // SUMM: the same 16 bytes through a buffer descriptor over the chunk.  Beside the float64 sums the scheduler fills the slot
+        // behind a global 16-byte store with the next store's address computation, on the address registers of the first - harmless,
+        // but tests/test_isa_hazard.py reads a store's first operand as its data; a buffer store names its data first.
+        const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, SUMM ? per * (int)sizeof(float) : 0, 0x00020000);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {   // take()'s expression: the bits rows[b][1] carries at the argmax
             const float4 h = make_float4(__expf(v[u].x - m) * inv, __expf(v[u].y - m) * inv, __expf(v[u].z - m) * inv, __expf(v[u].w - m) * inv);
-            dst[threadIdx.x + u * 256] = fin ? h : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (SUMM) {
+                const tk_f32x4 o = fin ? tk_f32x4{h.x, h.y, h.z, h.w} : tk_f32x4{0.f, 0.f, 0.f, 0.f};
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tk_u32x4, o), prs, (threadIdx.x + u * 256) * 16u, 0, 0);
+            } else {
+                dst[threadIdx.x + u * 256] = fin ? h : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         }
+    }
+    if constexpr (SUMM) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {   // take()'s expression again: the values of the map
+            const int e = lo + (threadIdx.x + u * 256) * 4;
+            summ_take(acc, __expf(v[u].x - m) * inv, e); summ_take(acc, __expf(v[u].y - m) * inv, e + 1);
+            summ_take(acc, __expf(v[u].z - m) * inv, e + 2); summ_take(acc, __expf(v[u].w - m) * inv, e + 3);
+        }
+        summ_wave_to_lds(acc, sd);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -321,6 +454,10 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
         st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2, best);
         st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2 + 1, __int_as_float(bi));
+        if constexpr (SUMM) {
+            summ_from_lds(acc, sd);
+            summ_publish(acc, p.summ_part + ((size_t)b * p.chunks + c) * SUMMARY_PART);
+        }
     }
     if (!ticket_arrive(p.tickets + b, 1u, (unsigned)p.chunks, &flag)) return;
     if (threadIdx.x < 64) {
@@ -336,7 +473,9 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             const int i2 = __shfl_xor(bi, off);
             if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
         }
-        if (threadIdx.x == 0) {
+        if constexpr (SUMM) {
+            if (threadIdx.x == 0) { sv[0] = best; si[0] = bi; }
+        } else if (threadIdx.x == 0) {
             if constexpr (PRIOR || POST) {
                 if (!(isfinite(m) && isfinite(inv))) { p.index[b] = 0; p.rows[b * 5 + 0] = -1.f; p.rows[b * 5 + 1] = NAN; return; }
             }
@@ -345,13 +484,113 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             p.rows[b * 5 + 1] = best;
         }
     }
+    if constexpr (SUMM) {
+        __syncthreads();
+        const bool ok = isfinite(m) && isfinite(inv);
+        best = sv[0]; bi = ok ? min(max(si[0], 0), p.n - 1) : 0;   // (a position of the map by construction; the clamp keeps the window reads inside it regardless)
+        if (threadIdx.x == 0) {
+            p.index[b] = bi;
+            p.rows[b * 5 + 0] = ok ? (float)bi : -1.f;
+            p.rows[b * 5 + 1] = ok ? best : NAN;
+        }
+        const float* lg = p.logits + (size_t)b * p.n;
+        const float* lp = PRIOR ? p.prior + (size_t)b * p.prior_stride : nullptr;
+        auto h_at = [&](int i) {
+            float x = lg[i];
+            if constexpr (PRIOR) x += lp[i];
+            return __expf(x - m) * inv;
+        };
+        summ_finish(p.summ_part + (size_t)b * p.chunks * SUMMARY_PART, bi, best, ok, p.summary_r, h_at, sd, p.summary + (size_t)b * SUMMARY_COLS);
+    }
 }
 
 void launch_pose_argmax(const PoseArgmaxParams& p, hipStream_t s) {
+    if (p.summary) {
+        if (p.posterior && p.prior) CCVPE_LAUNCH((pose_argmax_kernel<true, true, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+        else if (p.posterior) CCVPE_LAUNCH((pose_argmax_kernel<false, true, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+        else if (p.prior) CCVPE_LAUNCH((pose_argmax_kernel<true, false, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+        else CCVPE_LAUNCH((pose_argmax_kernel<false, false, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
+        return;
+    }
     if (p.posterior && p.prior) CCVPE_LAUNCH((pose_argmax_kernel<true, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
     else if (p.posterior) CCVPE_LAUNCH((pose_argmax_kernel<false, true>), dim3(p.chunks, p.B), dim3(256), 0, s, p);
     else if (p.prior) CCVPE_LAUNCH(pose_argmax_kernel<true>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
     else CCVPE_LAUNCH(pose_argmax_kernel<false>, dim3(p.chunks, p.B), dim3(256), 0, s, p);
+}
+
+// The summary of a stored map (ccvpe_belief_summary): postprocess_kernel's chunks (4096 values per workgroup, four float4 per thread in
+// one trip; a map that is not 16-byte aligned is read value by value) with pose_argmax_kernel's rules for the index - every thread
+// starts at the first position it scans, strictly greater within a thread, lowest index across threads and chunks, so NaN never wins
+// and the index is a position of the map whatever it holds - and the sums, hand-off and last arriver of the SUMM form.
+__global__ __launch_bounds__(256) void belief_summary_kernel(const BeliefSummaryParams p) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ unsigned flag;
+    __shared__ double sd[4 * SM_SUMS];
+    constexpr int n = SM_HW * SM_HW, per = n / PP_CHUNKS;   // 4096: a multiple of 4 x 256
+    const int b = blockIdx.y, c = blockIdx.x, lo = c * per;
+    const float* h = p.belief + (size_t)b * n;
+    double acc[SM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    float best = -INFINITY;
+    int bi;
+    auto take = [&](float v, int i) { if (v > best) { best = v; bi = i; } summ_take(acc, v, i); };
+    if ((reinterpret_cast<uintptr_t>(h) & 15) == 0) {
+        const float4* h4 = reinterpret_cast<const float4*>(h + lo);
+        bi = lo + 4 * (int)threadIdx.x;
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = h4[threadIdx.x + u * 256];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = lo + (threadIdx.x + u * 256) * 4;
+            take(v[u].x, e); take(v[u].y, e + 1); take(v[u].z, e + 2); take(v[u].w, e + 3);
+        }
+    } else {
+        bi = lo + (int)threadIdx.x;
+        float v[per / 256];
+#pragma unroll
+        for (int u = 0; u < per / 256; ++u) v[u] = h[lo + threadIdx.x + u * 256];
+#pragma unroll
+        for (int u = 0; u < per / 256; ++u) take(v[u], lo + threadIdx.x + u * 256);
+    }
+    summ_wave_to_lds(acc, sd);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float v2 = __shfl_xor(best, off);
+        const int i2 = __shfl_xor(bi, off);
+        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+    }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+        st_sc1(p.pairs + ((size_t)b * PP_CHUNKS + c) * 2, best);
+        st_sc1(p.pairs + ((size_t)b * PP_CHUNKS + c) * 2 + 1, __int_as_float(bi));
+        summ_from_lds(acc, sd);
+        summ_publish(acc, p.summ_part + ((size_t)b * PP_CHUNKS + c) * SUMMARY_PART);
+    }
+    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)PP_CHUNKS, &flag)) return;
+    if (threadIdx.x < 64) {
+        best = ld_sc1(p.pairs + ((size_t)b * PP_CHUNKS + threadIdx.x) * 2);
+        bi = __float_as_int(ld_sc1(p.pairs + ((size_t)b * PP_CHUNKS + threadIdx.x) * 2 + 1));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float v2 = __shfl_xor(best, off);
+            const int i2 = __shfl_xor(bi, off);
+            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+        }
+        if (threadIdx.x == 0) { sv[0] = best; si[0] = bi; }
+    }
+    __syncthreads();
+    best = sv[0];
+    bi = min(max(si[0], 0), n - 1);   // (a position of the map by construction; the clamp keeps the window reads inside it regardless)
+    summ_finish(p.summ_part + (size_t)b * PP_CHUNKS * SUMMARY_PART, bi, best, true, p.r, [&](int i) { return h[i]; }, sd,
+                p.summary + (size_t)b * SUMMARY_COLS);
+}
+
+void launch_belief_summary(const BeliefSummaryParams& p, hipStream_t s) {
+    CCVPE_LAUNCH(belief_summary_kernel, dim3(PP_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------

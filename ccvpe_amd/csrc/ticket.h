@@ -23,6 +23,9 @@ typedef unsigned tk_u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))))
 
 __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// float64 partials (the posterior summary): one 8-byte store / load of the same scope
+__device__ __forceinline__ void st_sc1(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double ld_sc1(const double* p) { return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // 16-byte forms through a buffer descriptor (aux bit 4 = sc1); `off` in bytes, out-of-range offsets store nothing / load zeros
 __device__ __forceinline__ void st_sc1_f4(__amdgpu_buffer_rsrc_t rsrc, unsigned off, tk_f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tk_u32x4, v), rsrc, off, 0, 16);

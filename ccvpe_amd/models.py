@@ -254,13 +254,14 @@ class _CVMBase(nn.Module):
             out.matching_score[k] = ms[k].data_ptr()
         return out, (logits, heat, ori, *ms)
 
-    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False):
+    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False, summary=False):
         """The skeleton forward and the pose forms share: validate and normalise grd and sat - or, sat=None, the cache and tile_index of a
         cached form -, ensure the handle, allocate the results, call ccvpe_<name> under the inputs' device on its current stream, check
         the return code, sync the tuning table.  args(B) holds the method's own argument checks, run after those of the inputs, and
         returns the C arguments between batch and the results; a tensor among them, the log_prior, must be on the inputs' device and is
         passed by pointer, None as a null pointer.  Returns the nine outputs (outputs=True) or rows [B, 5] (k = 0, the argmax forms) /
-        [B, k, 5] (k as the method received it: args has checked it), with the posterior [B, 512, 512] behind them if asked.
+        [B, k, 5] (k as the method received it: args has checked it), with the summary [B, 16] (the summary forms, whose C functions
+        take a nullable posterior behind it) and the posterior [B, 512, 512] behind them if asked.
         Cached forms: ccvpe_<name> takes a nullable tile_index if the name ends in _indexed; the older forms have two entry points each,
         ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it."""
         if sat is not None:
@@ -291,16 +292,18 @@ class _CVMBase(nn.Module):
                 ptrs = (C.byref(out),)
             else:
                 res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
+                if summary:
+                    res += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
                 if posterior:
                     res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
-                ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
+                ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res) + ((None,) if summary and not posterior else ())
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3], *src, B,
                                                        *extra, *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
         self._tuning_sync()
-        return res if outputs or posterior else res[0]
+        return res if outputs or posterior or summary else res[0]
 
     def forward(self, grd: torch.Tensor, sat: torch.Tensor):
         return self._call("forward", grd, sat, outputs=True)
@@ -578,9 +581,9 @@ class _CVMBase(nn.Module):
         return self._call("localize_prior_cached_indexed", grd, cache=cache, tile_index=tile_index,
                           args=lambda B: self._prior_args(log_prior, B, k, radius), k=k)
 
-    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False):
-        """postprocess_prior and track_update_logits: validate and normalise the forward outputs the caller holds, check the prior with
-        args(B) and take k (both as _call's), allocate rows (and the posterior) and call ccvpe_<name>."""
+    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False):
+        """postprocess_prior, track_update_logits and postprocess_summary: validate and normalise the forward outputs the caller holds,
+        check the prior with args(B) and take k (both as _call's), allocate rows (and the summary, the posterior) and call ccvpe_<name>."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
         B = logits.shape[0] if logits.dim() > 0 else 0
@@ -597,14 +600,17 @@ class _CVMBase(nn.Module):
         self._ensure_handle(dev)
         with torch.cuda.device(dev):
             res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
+            if summary:
+                res += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
             if posterior:
                 res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
+            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res) + ((None,) if summary and not posterior else ())
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, *extra,
-                                                       *(C.c_void_p(t.data_ptr()) for t in res), C.c_void_p(stream))
+                                                       *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
-        return res if posterior else res[0]
+        return res if posterior or summary else res[0]
 
     def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
                           ) -> torch.Tensor:
@@ -715,6 +721,75 @@ class _CVMBase(nn.Module):
                                                  C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
                                                  C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
         _lib.check(rc, "ccvpe_track_predict")
+        return out
+
+    # ---- posterior summary ------------------------------------------------------
+    @classmethod
+    def _summary_args(cls, log_prior, B: int, radius):
+        """(log_prior, radius) of the summary forms -> (tensor or None, prior_stride, radius): the prior as the update forms take it,
+        the window radius in 0..32."""
+        radius = int(radius)
+        if not 0 <= radius <= 32:
+            raise ValueError(f"radius must be in 0..32, got {radius}")
+        return cls._track_prior(log_prior, B) + (radius,)
+
+    def localize_summary(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                         posterior: bool = False):
+        """The pose and how sure it is: (rows [B, 5], summary [B, 16]), with the posterior [B, 512, 512] behind them if asked.  rows
+        and posterior are track_update(grd, sat, log_prior)'s; summary holds, per query, the columns aerial.SUMMARY_FIELDS of that
+        map - argmax and its value, total mass, entropy, mean and covariance, and the mass, mean and covariance of the
+        (2 radius + 1)^2 window around the argmax - in cells of the 512 grid (aerial.summary_to_metres scales them).  No launch is
+        added to localize_prior's.  A query without a finite posterior has the summary (-1, NaN, NaN ...) (ccvpe_localize_summary)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        own = self._summary_args(log_prior, grd.shape[0], radius)   # (before the inputs' checks)
+        return self._call("localize_summary", grd, sat, args=lambda B: own, posterior=posterior, summary=True)
+
+    def localize_summary_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                                posterior: bool = False, tile_index=None):
+        """localize_summary(grd, sat, log_prior, radius, posterior) with the aerial side taken from encode_aerial(sat); tile_index as
+        forward_cached (ccvpe_localize_summary_cached_indexed)."""
+        return self._call("localize_summary_cached_indexed", grd, cache=cache, tile_index=tile_index,
+                          args=lambda B: self._summary_args(log_prior, B, radius), posterior=posterior, summary=True)
+
+    def postprocess_summary(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                            posterior: bool = False):
+        """localize_summary from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
+        ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_summary)."""
+        return self._logits_call("postprocess_summary", logits, ori, lambda B: self._summary_args(log_prior, B, radius),
+                                 posterior=posterior, summary=True)
+
+    def belief_summary(self, belief: torch.Tensor, radius: int = 8) -> torch.Tensor:
+        """The summary [B, 16] of stored maps: belief [B,512,512] or [B,1,512,512], float32, contiguous, non-negative - a forward's
+        heatmap, a tracker belief; it need not sum to 1 (column 2 is its sum).  An all-zero map gives (0, 0, 0, NaN ...).  One launch
+        (ccvpe_belief_summary)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(belief, torch.Tensor):
+            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
+        shape = tuple(belief.shape)
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
+                                                                                       and shape[2:] == spec.OUT_HW):
+            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
+        if belief.dtype != torch.float32:
+            raise ValueError(f"belief must be float32, got {belief.dtype}")
+        if not belief.is_contiguous():
+            raise ValueError("belief must be contiguous")
+        if shape[0] > 4096:
+            raise ValueError(f"belief holds {shape[0]} maps, at most 4096 per call")
+        radius = int(radius)
+        if not 0 <= radius <= 32:
+            raise ValueError(f"radius must be in 0..32, got {radius}")
+        if not belief.is_cuda:
+            raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+        dev = belief.device
+        self._ensure_handle(dev)
+        with torch.cuda.device(dev):
+            out = torch.empty((shape[0], 16), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().ccvpe_belief_summary(self._handle, C.c_void_p(belief.detach().data_ptr()), shape[0], radius,
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_belief_summary")
         return out
 
     # ---- extras beyond the reference surface ------------------------------------------------

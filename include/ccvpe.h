@@ -340,6 +340,48 @@ int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* 
 int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps,
                         int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream);
 
+/* Posterior summary: how sure the pose is.  `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
+ * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
+ * ccvpe_belief_summary: the map given), in cells of the 512 grid, x = index % 512 the column, y = index / 512 the row:
+ *     0        argmax index as float: the first maximal index, NaN never wins, always a position inside the map
+ *     1        h at the argmax                      (columns 0 and 1 carry the bits of rows[b][0..1])
+ *     2        S0 = sum h                           (about 1 for a posterior; stored maps may be unnormalised)
+ *     3        entropy -sum over h > 0 of (h / S0) ln(h / S0), nats
+ *     4, 5     mean x, y = sum h x / S0, sum h y / S0
+ *     6, 7, 8  var_xx, cov_xy, var_yy about that mean
+ *     9        peak mass: sum h over the window |x - x*| <= radius, |y - y*| <= radius around the argmax (x*, y*), clipped to the
+ *              grid, over S0
+ *     10, 11   mean x, y of the window, weights h over the window's own sum
+ *     12 - 14  var_xx, cov_xy, var_yy of the window about its own mean - the spread of the mode the argmax belongs to, without
+ *              the distractors that inflate columns 6 - 8
+ *     15       cells of the clipped window, as float
+ * All sums are float64 (h times a coordinate product is exact there) in a fixed order: the same inputs give the same bits.
+ * radius in 0..32.  A query without a finite posterior: rows (-1, NaN, ...) as ccvpe_localize_prior, summary (-1, NaN, NaN ...).
+ * A stored map with S0 == 0: (0, 0, 0, NaN ...).  rows [batch][5] are exactly the k == 0 rows of the matching prior form
+ * (ccvpe_localize_prior, ccvpe_localize_prior_cached_indexed, ccvpe_postprocess_prior; log_prior NULL: ccvpe_track_update* without
+ * a prior, i.e. ccvpe_localize* except that logits without a finite (m', inv') - a NaN or +inf among them - give (-1, NaN) too).
+ * log_prior may be NULL (prior_stride is then ignored); posterior may be NULL, else it receives ccvpe_track_update's map.  No
+ * launch is added to the pose plans: the launch that finds the argmax reduces the sums, and its last workgroup recomputes the
+ * window; ccvpe_belief_summary is one launch.  The pose forms run plans of their own (the float64 partial sums live in their
+ * workspace) under the pose plans' launch names and tuning entries.  CCVPE_EINVAL, nothing launched, checked before the handle
+ * is used: the null-pointer and batch checks of the matching prior form (log_prior and posterior excepted), a null summary,
+ * radius outside 0..32, a bad prior_stride beside a prior, summary == rows, a posterior that is log_prior, logits, rows or
+ * summary; ccvpe_belief_summary: a null or misaligned belief, a null summary, radius, batch outside 1..4096, summary == belief.
+ * ccvpe_postprocess_summary and ccvpe_belief_summary: batch <= 4096, any handle, one call in flight per handle (they share the
+ * scratch of ccvpe_postprocess_prior). */
+int ccvpe_localize_summary(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                           const float* log_prior, int64_t prior_stride, int32_t radius, float* rows, float* summary,
+                           float* posterior, void* stream);
+int ccvpe_localize_summary_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                          int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                          int64_t prior_stride, int32_t radius, float* rows, float* summary, float* posterior,
+                                          void* stream);
+int ccvpe_postprocess_summary(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, int32_t radius, float* rows, float* summary, float* posterior, void* stream);
+/* The stored-map form: belief [batch][512*512] float32 DEVICE memory, 4-byte aligned (16-byte aligned maps are read faster) - a
+ * full forward's heatmap, a tracker belief, any non-negative map. */
+int ccvpe_belief_summary(ccvpe_handle h, const float* belief, int32_t batch, int32_t radius, float* summary, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
