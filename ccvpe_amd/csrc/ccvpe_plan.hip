@@ -45,7 +45,9 @@ static void plan_encoder(ccvpe_handle_s* h, Plan& pl, const EncoderW& ew, bool i
     int ch = conv_out(H, 3, 2), cw = conv_out(W, 3, 2);
     // stem + the depthwise conv of block 0 in one launch (block 0 has no expand conv; kernels_encoder.hip): the half-resolution 32-channel
     // stem output never reaches HBM.  CCVPE_STEM_DW=0: two launches
-    const bool stem_dw = h->sw.stem_dw && B0[0].e == 1 && B0[0].k == 3 && B0[0].s == 1 && B0[0].cin == 32 &&
+    // A circular encoder on an odd image width keeps the two launches too: the fused kernel wraps the halo columns of the stem output by
+    // wrapping the INPUT column, which is the same pixel only where W = 2 OW (213 -> 106: stem column -1 is 105 = input 210..212, not 211..213)
+    const bool stem_dw = h->sw.stem_dw && B0[0].e == 1 && B0[0].k == 3 && B0[0].s == 1 && B0[0].cin == 32 && !(circular && (W & 1)) &&
                          (size_t)B * 3 * H * W * sizeof(float) < ((size_t)1 << 31);   // (the kernel addresses its input through one 32-bit buffer descriptor)
     StemParams stem_sp{};
     stem_sp.B = B; stem_sp.H = H; stem_sp.W = W; stem_sp.OH = ch; stem_sp.OW = cw; stem_sp.pad_t = lo; stem_sp.pad_l = lo; stem_sp.circular = circular;
@@ -250,10 +252,26 @@ static int build_aerial_plan(ccvpe_handle_s* h, Plan& pl, int B);
 static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw);
 extern "C" int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t grd_h, int32_t grd_w);
 
-// Geometry of the ground feature volume (fh x fw) and the per-level descriptor lengths L[k] of a gh x gw ground image.
-static int grd_geometry(const VariantSpec& vs, int gh, int gw, int& fh, int& fw, int L[6]) {
-    fh = conv_out(gh, 3, 2); fw = conv_out(gw, 3, 2);
-    for (int i = 0; i < 16; ++i) { fh = conv_out(fh, B0[i].k, B0[i].s); fw = conv_out(fw, B0[i].k, B0[i].s); }
+// Geometry of the ground feature volume (fh x fw) and the per-level descriptor lengths L[k] of a gh x gw ground image, or EINVAL for a
+// size the reference itself cannot run: an image some layer's kernel does not fit into (widths below 32: torch refuses a kernel larger
+// than its padded input), and - circular encoders - a layer narrower than its padding (widths below 64: the late 5x5 blocks are one
+// pixel wide under a padding of 2, torch's circular pad refuses to wrap more than once, and the kernels wrap a column index once).
+static int grd_geometry(const VariantSpec& vs, bool circular, int gh, int gw, int& fh, int& fw, int L[6]) {
+    if (gh <= 0 || gw <= 0) return ccvpe_fail(CCVPE_EINVAL, "ground image size %d x %d is not positive", gh, gw);
+    fh = gh; fw = gw;
+    for (int i = -1; i < 16; ++i) {   // the stem (3x3, stride 2), then the 16 blocks' depthwise convs
+        const int k = i < 0 ? 3 : B0[i].k, s = i < 0 ? 2 : B0[i].s;
+        int lo, hi;
+        static_pad(k, s, lo, hi);
+        const std::string layer = i < 0 ? "the stem" : "block " + std::to_string(i);
+        if (fh + lo + hi < k || fw + lo + hi < k)
+            return ccvpe_fail(CCVPE_EINVAL, "ground image %d x %d is too small: it reaches the %d x %d kernel of %s as %d x %d", gh, gw, k, k,
+                              layer.c_str(), fh, fw);
+        if (circular && fw < std::max(lo, hi))
+            return ccvpe_fail(CCVPE_EINVAL, "ground image %d x %d is too narrow for circular padding: %s pads %d columns around a width of %d "
+                              "(the padding would wrap more than once)", gh, gw, layer.c_str(), std::max(lo, hi), fw);
+        fh = conv_out(fh, k, s); fw = conv_out(fw, k, s);
+    }
     if (fh != vs.feat_h)
         return ccvpe_fail(CCVPE_EINVAL, "ground image %dx%d gives a %d-row feature volume, the descriptor heads expect %d rows", gh, gw, fh, vs.feat_h);
     for (int k = 0; k < 6; ++k) {
@@ -268,7 +286,7 @@ static int grd_geometry(const VariantSpec& vs, int gh, int gw, int& fh, int& fw,
 // layout of the plans' `desc` tensor, level k at float offset sum_{j<k} round_up(L_j, 4).
 int ground_desc_floats(const ccvpe_handle_s* h, int gh, int gw) {
     int fh, fw, L[6];
-    if (int rc = grd_geometry(h->vs, gh, gw, fh, fw, L)) return rc;
+    if (int rc = grd_geometry(h->vs, h->cfg.circular_padding != 0, gh, gw, fh, fw, L)) return rc;
     int ltot = 0;
     for (int k = 0; k < 6; ++k) ltot += round_up(L[k], 4);
     return ltot;
@@ -351,7 +369,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
 
     // ---- geometry of the ground feature volume ----
     int fh, fw, L[6];
-    if (int rc = grd_geometry(vs, gh, gw, fh, fw, L)) return rc;
+    if (int rc = grd_geometry(vs, h->cfg.circular_padding != 0, gh, gw, fh, fw, L)) return rc;
 
     // ---- decoder concat buffers (allocated first: the aerial encoder's tap epilogues write into them) ----
     const int D = vs.sat_desc;
@@ -730,7 +748,7 @@ static int build_ground_plan(ccvpe_handle_s* h, Plan& pl, int B, int gh, int gw)
     pl.debug = false;
     pl.no_reuse = h->sw.no_reuse;
     int fh, fw, L[6];
-    if (int rc = grd_geometry(h->vs, gh, gw, fh, fw, L)) return rc;
+    if (int rc = grd_geometry(h->vs, h->cfg.circular_padding != 0, gh, gw, fh, fw, L)) return rc;
     pl.scratch = pl.alloc(1, 1, 1, (int)Plan::SPLITK_FLOATS);
     EncOut genc;
     plan_encoder(h, pl, h->grd_enc, true, B, gh, gw, h->cfg.circular_padding != 0, nullptr, genc, "grd");

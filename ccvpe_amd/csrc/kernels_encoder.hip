@@ -124,7 +124,8 @@ void launch_stem(const StemParams& p, hipStream_t s) {
 // bound by that traffic (4.4 / 5.2 TB/s).  Here a workgroup owns 32 x 8 outputs of the depthwise conv: it computes the 34 x 10 stem
 // pixels they depend on from a 69 x 21 x 3 input patch in LDS (the halo is recomputed: 1.33x of the stem's FMAs), keeps them in LDS
 // (zero outside the stem output where the reference pads with zeros, wrapped columns for the circular encoder: the patch fetch wraps
-// the INPUT column, which is the same thing since W = 2 OW), runs the depthwise taps from there and stores only its result plus one
+// the INPUT column, which is the same pixel only where W = 2 OW - a PRECONDITION of a circular launch: plan_encoder keeps the two
+// separate launches for a circular encoder on an odd W), runs the depthwise taps from there and stores only its result plus one
 // pooling partial row per tile.  Per output the FMA order of both convs is the one of the separate kernels (same bits up to the
 // squeeze-excite pooling order).  Thread = (channel quad, column); the stem phase computes 10 rows per thread plus, for 160 threads, one
 // pixel of the two halo columns 32 / 33; the next tile's patch arrives by LDS-DMA under the depthwise phase.

@@ -141,7 +141,9 @@ int ccvpe_tuning_generation(ccvpe_handle h);
 
 /* Largest micro_batch whose intermediate tensors all stay below the 2 GiB the kernels address with 32-bit byte offsets
  * (ccvpe_forward refuses a larger one with CCVPE_EINVAL instead of wrapping offsets).  Pure host arithmetic, no device
- * needed.  Negative on a ground size the variant's descriptor heads cannot take. */
+ * needed.  Negative on a ground size the variant's descriptor heads cannot take.  It has no handle and so plans for zero
+ * padding: for widths 32..63 it returns a positive batch although a handle created with circular_padding = 1 refuses them
+ * (ccvpe_forward and ccvpe_workspace_bytes of that handle decide). */
 int ccvpe_max_micro_batch(int32_t variant, float ori_noise, int32_t grd_h, int32_t grd_w);
 
 /* R_k of matching_score[level] (level 0..5) for this handle's variant / ori_noise. */
@@ -235,7 +237,8 @@ int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t
 /* Ground-side cache: the descriptor vector of each ground image, the ground encoder's only output.  Layout: float32
  * [batch][Ltot], DEVICE memory of ccvpe_ground_cache_bytes(h, batch, grd_h, grd_w) = batch * Ltot * 4 bytes, where
  * Ltot = sum over the six matching levels k of round_up(L_k, 4), L_k = (feature width) * (head channels of level k), and level
- * k's descriptor starts at float sum_{j<k} round_up(L_j, 4) of its row (padding floats unspecified).  batch <= micro_batch.
+ * k's descriptor starts at float sum_{j<k} round_up(L_j, 4) of its row; the round_up(L_k, 4) - L_k padding floats behind a level are
+ * written as 0 by every call, whatever the buffer held.  batch <= micro_batch.
  * The launches are the full forward's ground encoder, heads and descriptor launch: at the same batch the cache holds the bits
  * the full forward computes.  ccvpe_ground_cache_bytes returns 0 for a bad argument or ground geometry (ccvpe_last_error). */
 size_t ccvpe_ground_cache_bytes(ccvpe_handle h, int32_t batch, int32_t grd_h, int32_t grd_w);

@@ -1,4 +1,4 @@
-"""Capture tests/golden/reference_<variant>.npz from the REAL reference (build container only) - TEST INFRASTRUCTURE.
+"""Capture tests/golden/reference_<variant>[_fov<fov>].npz from the REAL reference (build container only) - TEST INFRASTRUCTURE.
 
     python -m oracle.make_reference_golden
 
@@ -53,10 +53,10 @@ def main():
     for case in gu.REFERENCE_CASES:
         variant = case[0]
         fx = capture(*case)
-        if variant == "kitti":
+        if variant == "kitti" and case[3] == 360.0:
             net = rh.build("kitti", weights.generate_state_dict("kitti", 0))
             fx["kitti/state_dict_keys"] = np.array(list(net.state_dict().keys()))
-        path = os.path.join(gu.GOLDEN_DIR, f"reference_{variant}.npz")
+        path = gu.reference_fixture(variant, case[3])
         np.savez_compressed(path, **fx)
         print(f"{path}: {len(fx)} arrays, {os.path.getsize(path) / 1024:.0f} KiB")
 

@@ -20,15 +20,26 @@ CONFIGS = {
 }
 
 # tests/test_oracle_vs_reference.py: (variant, circular, ori_noise, fov) at batch 1, seed 5 - all four model classes of the
-# reference; fixtures tests/golden/reference_<variant>.npz (oracle/make_reference_golden.py)
+# reference; fixtures tests/golden/reference_<variant>.npz (oracle/make_reference_golden.py) - and three cropped, odd ground widths, the
+# driver's crop grd[..., :int(W * fov / 360)]: fixtures reference_<variant>_fov<fov>.npz
 REFERENCE_CASES = [
     ("vigor_ori_prior", True, 36.0, 360.0),
     ("vigor", True, None, 360.0),
     ("kitti", False, None, 360.0),
     ("oxford", False, None, 360.0),
+    ("vigor", True, None, 270.0),      # width 480: feature width 15, L6 = 30
+    ("kitti", False, None, 120.0),     # width 341: 170, 85, 42, 21, 10 down the encoder
+    ("oxford", False, None, 312.0),    # width 200: feature width 6
 ]
 REFERENCE_SEED = 5
 REFERENCE_LATTICE = 16384
+
+
+def reference_fixture(variant: str, fov: float) -> str:
+    """Path of the fixture of a REFERENCE_CASES entry."""
+    name = f"reference_{variant}" + ("" if fov == 360.0 else f"_fov{int(fov)}")
+    return os.path.join(GOLDEN_DIR, name + ".npz")
+
 
 OUTPUT_NAMES = ["logits", "heatmap", "ori", "ms1", "ms2", "ms3", "ms4", "ms5", "ms6"]
 FULL_LIMIT = 32768

@@ -94,12 +94,20 @@ def match_cat(score, x):
 
 
 def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str, sd, grd: torch.Tensor, sat: torch.Tensor,
-                 circular: bool, ori_noise: Optional[float], samples: Optional[Sequence[int]] = None) -> List[StageResult]:
+                 circular: bool, ori_noise: Optional[float], samples: Optional[Sequence[int]] = None,
+                 stages: Optional[Sequence[str]] = None) -> List[StageResult]:
     """Every stage of the forward, see the module docstring.  `outputs`: the nine tensors of the forward (logits, heatmap, ori,
-    ms1..ms6) for the whole batch; `grd`, `sat`: the input images of the whole batch; `samples`: batch indices to check (default: all)."""
+    ms1..ms6) for the whole batch; `grd`, `sat`: the input images of the whole batch; `samples`: batch indices to check (default: all);
+    `stages`: prefixes of stage names - only those stages are computed, and only their taps read (default: every stage).
+    ("grd_", "match"): the ground encoder, its head and descriptors and the six matching levels, 42 rows; the aerial encoder and the
+    decoders are not run, the matching levels still take their x from the device's taps."""
     v = spec.VARIANTS[variant]
     prior = variant == "vigor_ori_prior"
     idx = torch.arange(grd.shape[0]) if samples is None else torch.tensor(list(samples))
+    prefixes = None if stages is None else tuple(stages)
+
+    def want(name):
+        return prefixes is None or name.startswith(prefixes)
     sd32 = {k: t.detach().cpu() for k, t in sd.items()}
     sd64 = _f64(sd32)
     cache = {}
@@ -109,7 +117,7 @@ def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str,
             cache[name] = read_tap(name).detach().cpu()[idx].float().clone()
         return cache[name]
 
-    outs = [o.detach().cpu()[idx].float() for o in outputs]
+    outs = [o.detach()[idx.to(o.device)].cpu().float() for o in outputs]
     out_logits, out_heat, out_ori, out_ms = outs[0], outs[1], outs[2], outs[3:]
     results: List[StageResult] = []
 
@@ -126,18 +134,23 @@ def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str,
     # ---- encoders ----
     for tag, img, circ in (("grd", grd[idx].float(), circular), ("sat", sat[idx].float(), False)):
         p = tag + "_efficientnet"
-        stage(f"{tag}_block0", lambda s, x: stem_block0(x, s, p, circ), [img], tap(f"{tag}_block0"), (f"{tag}.stem", f"{tag}.b0."))
+        if want(f"{tag}_block0"):
+            stage(f"{tag}_block0", lambda s, x: stem_block0(x, s, p, circ), [img], tap(f"{tag}_block0"), (f"{tag}.stem", f"{tag}.b0."))
         for i in range(1, len(spec.B0_BLOCKS)):
-            stage(f"{tag}_block{i}", lambda s, x: orc.mbconv(x, s, f"{p}._blocks.{i}", spec.B0_BLOCKS[i], circ),
-                  [tap(f"{tag}_block{i - 1}")], tap(f"{tag}_block{i}"), (f"{tag}.b{i}.",))
-        stage(f"{tag}_volume", lambda s, x: head_conv(x, s, p), [tap(f"{tag}_block15")], tap(f"{tag}_volume"), (f"{tag}.head",))
+            if want(f"{tag}_block{i}"):
+                stage(f"{tag}_block{i}", lambda s, x: orc.mbconv(x, s, f"{p}._blocks.{i}", spec.B0_BLOCKS[i], circ),
+                      [tap(f"{tag}_block{i - 1}")], tap(f"{tag}_block{i}"), (f"{tag}.b{i}.",))
+        if want(f"{tag}_volume"):
+            stage(f"{tag}_volume", lambda s, x: head_conv(x, s, p), [tap(f"{tag}_block15")], tap(f"{tag}_volume"), (f"{tag}.head",))
 
     # ---- descriptors ----
     for k in range(1, 7):
-        stage(f"grd_desc{k}", lambda s, x: orc.ground_descriptor(x, s, k), [tap("grd_volume")],
-              tap(f"grd_desc{k}").flatten(1), ("grd.heads", "grd.desc"))
-    stage("sat_descriptor_map", lambda s, x: orc.aerial_descriptor_map(x, s), [tap("sat_volume")], tap("sat_descriptor_map"),
-          ("sat.descmap",))
+        if want(f"grd_desc{k}"):
+            stage(f"grd_desc{k}", lambda s, x: orc.ground_descriptor(x, s, k), [tap("grd_volume")],
+                  tap(f"grd_desc{k}").flatten(1), ("grd.heads", "grd.desc"))
+    if want("sat_descriptor_map"):
+        stage("sat_descriptor_map", lambda s, x: orc.aerial_descriptor_map(x, s), [tap("sat_volume")], tap("sat_descriptor_map"),
+              ("sat.descmap",))
 
     # ---- matching levels: x and the ground descriptor -> ms{k}, the maximum over the rolls, loc_in{7-k} (and ori_in6 at level 1) ----
     def real_loc_in(n):
@@ -155,6 +168,9 @@ def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str,
 
     for k in range(1, 7):
         n = 7 - k
+        level = f"loc_level{n}" if n >= 2 else "logits"
+        if not (want(f"match{k}") or want(level)):
+            continue
         x = tap("sat_descriptor_map") if k == 1 else tap(f"loc_level{8 - k}")
         g = tap(f"grd_desc{k}").flatten(1)
         L = g.shape[1]
@@ -170,12 +186,15 @@ def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str,
                 out["ori_in6"] = torch.cat([out["ms"], F.normalize(x, p=2, dim=1)], dim=1)
             return out
 
-        dev = {"ms": out_ms[k - 1], "max": tap(f"loc_in{n}")[:, :1], f"loc_in{n}": real_loc_in(n)}
-        if k == 1:
-            dev["ori_in6"] = real_ori_in6()
-        stage(f"match{k}", match, [x, g], dev, (f"match{k}",))
+        if want(f"match{k}"):
+            dev = {"ms": out_ms[k - 1], "max": tap(f"loc_in{n}")[:, :1], f"loc_in{n}": real_loc_in(n)}
+            if k == 1:
+                dev["ori_in6"] = real_ori_in6()
+            stage(f"match{k}", match, [x, g], dev, (f"match{k}",))
 
         # ---- localisation decoder level n ----
+        if not want(level):
+            continue
         if n >= 2:
             skip = tap(f"sat_block{spec.TAP_BLOCKS[k - 1]}")
             stage(f"loc_level{n}", lambda s, x, sk: orc._decoder_level(x, sk, s, n, ""), [real_loc_in(n), skip], tap(f"loc_level{n}"),
@@ -189,16 +208,22 @@ def check_stages(read_tap: Callable[[str], torch.Tensor], outputs, variant: str,
         return {"": heat, "over_max": heat / heat.max(dim=1, keepdim=True).values}
 
     hd = out_heat.flatten(1)
-    stage("heatmap", softmax, [out_logits], {"": hd, "over_max": hd / hd.max(dim=1, keepdim=True).values}, ("softmax",))
+    if want("heatmap"):
+        stage("heatmap", softmax, [out_logits], {"": hd, "over_max": hd / hd.max(dim=1, keepdim=True).values}, ("softmax",))
 
     # ---- orientation decoder ----
     for n in range(6, 1, -1):
+        if not want(f"ori_level{n}"):
+            continue
         xo = real_ori_in6() if n == 6 else tap(f"ori_level{n + 1}")
         skip = tap(f"sat_block{spec.TAP_BLOCKS[6 - n]}")
         stage(f"ori_level{n}", lambda s, x, sk: orc._decoder_level(x, sk, s, n, "_ori"), [xo, skip], tap(f"ori_level{n}"), (f"ori{n}.",))
-    stage("ori_level1", lambda s, x: orc._decoder_level(x, None, s, 1, "_ori"), [tap("ori_level2")], tap("ori_level1_nchw"), ("ori1.",))
+    if want("ori_level1"):
+        stage("ori_level1", lambda s, x: orc._decoder_level(x, None, s, 1, "_ori"), [tap("ori_level2")], tap("ori_level1_nchw"), ("ori1.",))
 
     # ---- normalise: weighted by the magnitude of the un-normalised vector (tests/test_parity_gpu.py ori_weighted_error) ----
+    if not want("ori"):
+        return results
     raw = tap("ori_level1_nchw")
     mag = raw.double().pow(2).sum(dim=1, keepdim=True).sqrt()
     with torch.no_grad():

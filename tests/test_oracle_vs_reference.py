@@ -1,4 +1,5 @@
-"""Oracle vs the real reference on all four model classes, through the fixtures tests/golden/reference_<variant>.npz that
+"""Oracle vs the real reference on all four model classes - and at three cropped, odd ground widths (480, 341, 200) -, through the
+fixtures tests/golden/reference_<variant>[_fov<fov>].npz that
 oracle/make_reference_golden.py captured from the reference (data only: every output and the un-normalised orientation map
 on a ~16k-position lattice, everything for smaller tensors, plus whole-tensor sum / abs-sum / L2 / max)."""
 import numpy as np
@@ -13,8 +14,8 @@ RTOL = 2e-5
 N = gu.REFERENCE_LATTICE
 
 
-def _load(variant):
-    return np.load(f"{gu.GOLDEN_DIR}/reference_{variant}.npz", allow_pickle=False)
+def _load(variant, fov=360.0):
+    return np.load(gu.reference_fixture(variant, fov), allow_pickle=False)
 
 
 def _check(fx, name, got):
@@ -25,7 +26,7 @@ def _check(fx, name, got):
 
 @pytest.mark.parametrize("variant,circ,noise,fov", gu.REFERENCE_CASES)   # reference models.py:49, 346, 655, 954
 def test_full_tensor_agreement(variant, circ, noise, fov):
-    fx = _load(variant)
+    fx = _load(variant, fov)
     torch.set_num_threads(8)
     sd = weights.generate_state_dict(variant, gu.REFERENCE_SEED)
     grd, sat = weights.generate_inputs(variant, 1, gu.REFERENCE_SEED, fov)
