@@ -124,6 +124,7 @@ SYMBOLS = [
     ("ccvpe_op_conv2d", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
+    ("ccvpe_op_conv2d_ex", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ccvpe_op_level1", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 ]
@@ -251,6 +252,69 @@ def op_conv2d(x_nhwc, w, bias=None, stride=1, pad=0, act=0, tile=0, iters=0):
                              C.c_void_p(out.data_ptr()), iters, C.byref(ms), C.c_void_p(stream))
     check(rc, "ccvpe_op_conv2d")
     return out, (ms.value if iters > 0 else None)
+
+
+class OpConvDst(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("ld", C.c_int32), ("coff", C.c_int32)]
+
+
+class OpConvDesc(C.Structure):   # ccvpe_op_conv_desc
+    _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("in_ld", C.c_int32),
+                ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("Cout", C.c_int32), ("KH", C.c_int32), ("KW", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("act", C.c_int32),
+                ("tile", C.c_int32), ("mode", C.c_int32),
+                ("gate", C.c_void_p), ("resid", C.c_void_p), ("resid_ld", C.c_int32), ("ndst", C.c_int32), ("dst", OpConvDst * 3),
+                ("iters", C.c_int32), ("ms", C.POINTER(C.c_float)),
+                ("ran_tile", C.POINTER(C.c_int32)), ("ran_split", C.POINTER(C.c_int32)), ("requested_runs", C.POINTER(C.c_int32))]
+
+
+def op_conv2d_ex(x_nhwc, w, bias=None, stride=1, pad=0, act=0, tile=0, gate=None, resid=None, dsts=None, deconv=False):
+    """Kernel-level hook for the forms the plans launch (ccvpe_op_conv2d_ex).  x [B,H,W,in_ld] cuda fp32 with in_ld >= Cin (the
+    weight's input channels; the rest of a pixel is never read); w [Cout,Cin,KH,KW], or [Cin,Cout,2,2] with deconv=True
+    (ConvTranspose2d k2 s2: 2H x 2W output pixels); gate [B,Cin]; resid [B,OH,OW,resid_ld]; dsts: up to three (tensor
+    [B,OH',OW',ld], coff) pairs the caller allocated - the result lands in channels [coff, coff + Cout) of each, nothing else is
+    written; None: one dense output.  Returns (outs, ran_name, ran_split, requested_runs): the destination tensors, the name of the
+    tile that ran, the split code the launcher recorded (1: K whole, S: slabs + reduce launch, 64 + S: self-reducing, 255: tail
+    split) and whether the requested tile takes this launch (1 / 0; -1 for tile 0)."""
+    import torch
+    lib = load()
+    x = x_nhwc.contiguous()
+    B, H, W, in_ld = x.shape
+    w = w.contiguous().float()
+    if deconv:
+        Cin, Cout, KH, KW = w.shape
+        OH, OW = 2 * H, 2 * W
+    else:
+        Cout, Cin, KH, KW = w.shape
+        OH = (H + 2 * pad - KH) // stride + 1
+        OW = (W + 2 * pad - KW) // stride + 1
+    if dsts is None:
+        dsts = [(torch.empty((B, OH, OW, Cout), dtype=torch.float32, device=x.device), 0)]
+    b = bias.contiguous().float() if bias is not None else None
+    keep = [x, w, b]
+    d = OpConvDesc()
+    d.x = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.in_ld = B, H, W, Cin, in_ld
+    d.w = w.data_ptr(); d.bias = b.data_ptr() if b is not None else None
+    d.Cout, d.KH, d.KW, d.stride, d.pad, d.act, d.tile, d.mode = Cout, KH, KW, (2 if deconv else stride), pad, act, tile, (1 if deconv else 0)
+    if gate is not None:
+        g = gate.contiguous().float()
+        assert tuple(g.shape) == (B, Cin), tuple(g.shape)
+        keep.append(g)
+        d.gate = g.data_ptr()
+    if resid is not None:
+        assert resid.is_contiguous() and resid.dtype == torch.float32 and tuple(resid.shape[:3]) == (B, OH, OW)
+        d.resid = resid.data_ptr(); d.resid_ld = resid.shape[3]
+    assert 1 <= len(dsts) <= 3
+    d.ndst = len(dsts)
+    for i, (t, coff) in enumerate(dsts):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape[:3]) == (B, OH, OW), tuple(t.shape)
+        d.dst[i].ptr = t.data_ptr(); d.dst[i].ld = t.shape[3]; d.dst[i].coff = coff
+    ran_tile, ran_split, runs = C.c_int32(0), C.c_int32(0), C.c_int32(-2)
+    d.ran_tile, d.ran_split, d.requested_runs = C.pointer(ran_tile), C.pointer(ran_split), C.pointer(runs)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    rc = lib.ccvpe_op_conv2d_ex(C.byref(d), C.c_void_p(stream))
+    check(rc, "ccvpe_op_conv2d_ex")
+    return [t for t, _ in dsts], lib.ccvpe_op_tile_name(ran_tile.value).decode(), ran_split.value, runs.value
 
 
 def op_level1(x_nhwc, wd, bd, wa, ba, wt, bt, score=False, tile=1, max_wg=0):

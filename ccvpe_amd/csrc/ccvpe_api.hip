@@ -1202,69 +1202,128 @@ int ccvpe_debug_dump_plan(ccvpe_handle h, const char* path) {
 int ccvpe_op_num_tiles(void) { return conv_num_tiles(); }
 const char* ccvpe_op_tile_name(int32_t tile) { return conv_tile_name(tile); }
 
-int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
-                    int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, int32_t tile,
-                    float* out, int32_t iters, float* ms, void* stream) {
-    if (!in || !w || !out) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+// The body of both convolution hooks: argument checks (all before the first launch), the packer that serves ccvpe_create, the launch
+// parameters a plan would build for this form, one launch (plus `iters` timed ones).  wino_strict: the old hook's contract - a Winograd
+// id on a layer the tile does not take is an error; ccvpe_op_conv2d_ex reports the fallback instead.
+static int op_conv_run(const ccvpe_op_conv_desc& d, bool wino_strict, hipStream_t st) {
+    const int B = d.B, H = d.H, W = d.W, Cin = d.Cin, Cout = d.Cout, KH = d.KH, KW = d.KW, stride = d.stride, pad = d.pad;
+    if (!d.in || !d.w) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 8 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0)
         return ccvpe_fail(CCVPE_EINVAL, "bad conv geometry (Cin must be a multiple of 8)");
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
+    const bool deconv = d.mode == CCVPE_OP_DECONV;
+    if (d.mode != CCVPE_OP_CONV && !deconv) return ccvpe_fail(CCVPE_EINVAL, "unknown mode %d", d.mode);
+    if (deconv && (KH != 2 || KW != 2 || stride != 2 || pad != 0)) return ccvpe_fail(CCVPE_EINVAL, "the transposed conv is 2x2, stride 2, pad 0");
+    const int in_ld = d.in_ld ? d.in_ld : Cin;
+    if (in_ld < Cin || in_ld % 4) return ccvpe_fail(CCVPE_EINVAL, "in_ld must be >= Cin and a multiple of 4");
+    // GEMM rows: output pixels of a conv, input pixels of a transposed conv (whose four (dy, dx) column groups are shuffled on store)
+    const int OH = deconv ? H : (H + 2 * pad - KH) / stride + 1, OW = deconv ? W : (W + 2 * pad - KW) / stride + 1;
     if (OH <= 0 || OW <= 0) return ccvpe_fail(CCVPE_EINVAL, "empty output");
-    if ((double)B * H * W * Cin >= 2147483647.0 || (double)B * OH * OW * Cout >= 2147483647.0)
-        return ccvpe_fail(CCVPE_EINVAL, "tensor exceeds 2^31 elements");
+    const int N = deconv ? 4 * Cout : Cout;
+    const double opix = (double)B * OH * OW * (deconv ? 4 : 1);
+    if ((double)B * H * W * in_ld >= 2147483647.0 || opix * Cout >= 2147483647.0) return ccvpe_fail(CCVPE_EINVAL, "tensor exceeds 2^31 elements");
+    if (d.gate && (KH != 1 || KW != 1 || stride != 1 || pad != 0 || deconv)) return ccvpe_fail(CCVPE_EINVAL, "a gate goes with a 1x1 / stride 1 / pad 0 conv only");
+    if (d.resid) {
+        if (deconv) return ccvpe_fail(CCVPE_EINVAL, "no residual on a transposed conv");
+        if (d.act != 0) return ccvpe_fail(CCVPE_EINVAL, "a residual goes with act 0 only (no plan adds one behind an activation)");
+        if (d.resid_ld < N) return ccvpe_fail(CCVPE_EINVAL, "resid_ld must be >= Cout");
+        if ((double)B * OH * OW * d.resid_ld >= 2147483647.0) return ccvpe_fail(CCVPE_EINVAL, "tensor exceeds 2^31 elements");
+    }
+    if (d.ndst < 1 || d.ndst > 3) return ccvpe_fail(CCVPE_EINVAL, "ndst must be 1 .. 3");
+    for (int i = 0; i < d.ndst; ++i) {
+        if (!d.dst[i].ptr) return ccvpe_fail(CCVPE_EINVAL, "null destination %d", i);
+        if (d.dst[i].coff < 0 || d.dst[i].ld <= 0 || (long long)d.dst[i].coff + Cout > d.dst[i].ld) return ccvpe_fail(CCVPE_EINVAL, "destination %d: coff + Cout must be <= ld", i);
+        if (opix * d.dst[i].ld >= 2147483647.0) return ccvpe_fail(CCVPE_EINVAL, "tensor exceeds 2^31 elements");
+    }
+    const int tile = d.tile;
+    const int taps = deconv ? 1 : KH * KW;
     const size_t nw = (size_t)Cout * Cin * KH * KW;
-    std::vector<float> hw(nw), hb(Cout, 0.f);
-    HIPCHK(hipMemcpy(hw.data(), w, nw * sizeof(float), hipMemcpyDefault));
-    if (bias) HIPCHK(hipMemcpy(hb.data(), bias, Cout * sizeof(float), hipMemcpyDefault));
+    std::vector<float> hw(nw), hb(N, 0.f);
+    HIPCHK(hipMemcpy(hw.data(), d.w, nw * sizeof(float), hipMemcpyDefault));
+    if (d.bias) {
+        HIPCHK(hipMemcpy(hb.data(), d.bias, Cout * sizeof(float), hipMemcpyDefault));
+        if (deconv) for (int q = 1; q < 4; ++q) std::copy(hb.begin(), hb.begin() + Cout, hb.begin() + (size_t)q * Cout);
+    }
     ccvpe_handle_s tmp;   // only its dev_allocs list, precision flag and packer switches are used by the packer
     tmp.sw = read_switches();
     tmp.cfg.reserved[0] = 1;   // also pack the bf16x3 planes so every tile id can be exercised
     PackedConv pc;
-    const int taps = KH * KW;
-    int rc = pack_conv(&tmp, pc, Cout, taps, Cin, Cin, identity_map(Cin),
+    int rc;
+    if (deconv)   // ConvTranspose2d weight [Cin][Cout][2][2] -> rows n = (dy*2+dx)*Cout + o of a 1x1 GEMM, as build_decoder packs a level
+        rc = pack_conv(&tmp, pc, N, 1, Cin, Cin, identity_map(Cin),
+                       [&](int n, int, int c) { const int q = n / Cout, o = n % Cout; return hw[((size_t)c * Cout + o) * 4 + q]; }, hb, 1, 1);
+    else
+        rc = pack_conv(&tmp, pc, Cout, taps, Cin, Cin, identity_map(Cin),
                        [&](int n, int t, int c) { return hw[((size_t)n * Cin + c) * taps + t]; }, hb, KH, KW);
     auto cleanup = [&]() { for (void* p : tmp.dev_allocs) (void)hipFree(p); };
     if (rc) { cleanup(); return rc; }
-    ConvParams p = conv_params(pc, in, Cin, B, H, W, OH, OW, stride, pad, pad, act);
-    p.dst[0] = {out, Cout, 0}; p.ndst = 1;
-    hipStream_t st = (hipStream_t)stream;
+    ConvParams p = deconv ? conv_params(pc, d.in, in_ld, B, H, W, H, W, 1, 0, 0, d.act) : conv_params(pc, d.in, in_ld, B, H, W, OH, OW, stride, pad, pad, d.act);
+    if (deconv) { p.mode = MODE_DECONV; p.deconv_cout = Cout; }
+    p.gate = d.gate;
+    if (d.resid) { p.resid = d.resid; p.resid_ld = d.resid_ld; }
+    p.ndst = d.ndst;
+    for (int i = 0; i < d.ndst; ++i) p.dst[i] = {d.dst[i].ptr, d.dst[i].ld, d.dst[i].coff};
     if (((tile >> 8) & 0xff) > 1) {   // tile word = id | (split-K << 8): give the launch a slab (and ticket counters: 255 and the codes above SPLIT_FUSED reduce themselves)
         int sk = (tile >> 8) & 0xff;
         if (sk > SPLIT_FUSED && sk != 255) sk -= SPLIT_FUSED;
         {
-            void* d = nullptr;
-            if (hipMalloc(&d, CONV_TICKETS * sizeof(unsigned)) != hipSuccess || hipMemset(d, 0, CONV_TICKETS * sizeof(unsigned)) != hipSuccess) { cleanup(); return ccvpe_fail(CCVPE_ENOMEM, "ticket counters"); }
-            tmp.dev_allocs.push_back(d);
+            void* dd = nullptr;
+            if (hipMalloc(&dd, CONV_TICKETS * sizeof(unsigned)) != hipSuccess || hipMemset(dd, 0, CONV_TICKETS * sizeof(unsigned)) != hipSuccess) { cleanup(); return ccvpe_fail(CCVPE_ENOMEM, "ticket counters"); }
+            tmp.dev_allocs.push_back(dd);
             tmp.dev_alloc_bytes.push_back(CONV_TICKETS * sizeof(unsigned));
-            p.tickets = (unsigned*)d;
+            p.tickets = (unsigned*)dd;
         }
         const size_t fl = (size_t)(sk == 255 ? 8 : sk) * p.M * p.N;   // 255 = F(4x4) tail split: its slab is a fraction of 8 full ones
-        void* d = nullptr;
-        if (hipMalloc(&d, fl * sizeof(float)) != hipSuccess) { cleanup(); return ccvpe_fail(CCVPE_ENOMEM, "split-K slab"); }
-        tmp.dev_allocs.push_back(d);
+        void* dd = nullptr;
+        if (hipMalloc(&dd, fl * sizeof(float)) != hipSuccess) { cleanup(); return ccvpe_fail(CCVPE_ENOMEM, "split-K slab"); }
+        tmp.dev_allocs.push_back(dd);
         tmp.dev_alloc_bytes.push_back(fl * sizeof(float));
-        p.partial = (float*)d; p.partial_floats = fl;
+        p.partial = (float*)dd; p.partial_floats = fl;
     }
-    if (const ConvTile* t = conv_tile(tile); t && t->family == TILE_WINO && !conv_tile_runs(*t, p)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "layer is not Winograd-shaped (3x3, stride 1, pad 1, W %% 16 == 0, H %% 16 == 0, output channels a multiple of 4; F(4x4): >= 40 of them)"); }
+    const ConvTile* t = conv_tile(tile);
+    const int runs = t ? (conv_tile_runs(*t, p) ? 1 : 0) : -1;
+    if (d.requested_runs) *d.requested_runs = runs;
+    if (wino_strict && t && t->family == TILE_WINO && !runs) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "layer is not Winograd-shaped (3x3, stride 1, pad 1, W %% 16 == 0, H %% 16 == 0, output channels a multiple of 4; F(4x4): >= 40 of them)"); }
+    (void)conv_tile_last();
     if (launch_conv_igemm(p, tile, st) != 0) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "unsupported conv geometry (KH*KW <= 16, Cin %% 8 == 0)"); }
+    const int last = conv_tile_last();   // (reading it clears it: the timed launches below leave nothing behind)
+    if (d.ran_tile) *d.ran_tile = last & 0xff;
+    if (d.ran_split) *d.ran_split = (last >> 8) & 0xff;
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && iters > 0 && ms) {
+    if (e == hipSuccess && d.iters > 0 && d.ms) {
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, st);
-        for (int i = 0; i < iters; ++i) launch_conv_igemm(p, tile, st);
+        for (int i = 0; i < d.iters; ++i) launch_conv_igemm(p, tile, st);
         (void)hipEventRecord(e1, st);
         (void)hipEventSynchronize(e1);
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, e0, e1);
-        *ms = t / iters;
+        float tm = 0.f;
+        (void)hipEventElapsedTime(&tm, e0, e1);
+        *d.ms = tm / d.iters;
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        (void)conv_tile_last();
     }
     hipError_t e2 = hipStreamSynchronize(st);
     cleanup();
     if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "conv launch failed: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "conv execution failed: %s", hipGetErrorString(e2));
     return 0;
+}
+
+int ccvpe_op_conv2d_ex(const ccvpe_op_conv_desc* d, void* stream) {
+    if (!d) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    return op_conv_run(*d, false, (hipStream_t)stream);
+}
+
+int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w, const float* bias,
+                    int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, int32_t tile,
+                    float* out, int32_t iters, float* ms, void* stream) {
+    if (!in || !w || !out) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    ccvpe_op_conv_desc d{};
+    d.in = in; d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.in_ld = Cin; d.w = w; d.bias = bias;
+    d.Cout = Cout; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad; d.act = act; d.tile = tile; d.mode = CCVPE_OP_CONV;
+    d.ndst = 1; d.dst[0].ptr = out; d.dst[0].ld = Cout; d.dst[0].coff = 0;
+    d.iters = iters; d.ms = ms;
+    return op_conv_run(d, true, (hipStream_t)stream);
 }
 
 int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t score, const float* wd, const float* bd,

@@ -152,6 +152,7 @@ int conv_tile_splits(const ConvTile& t);
 double conv_tile_util(const ConvParams& p, const ConvTile& t);
 long long conv_tile_blocks(const ConvParams& p, const ConvTile& t);
 int conv_tile_last();        // cfg word of the most recent launch on this thread (then reset to 0)
+void conv_tile_note_unfused();   // called by a launcher that drops the self-reducing form of the split it was handed
 int conv_igemm_prepare(ConvParams& p);
 int conv_igemm_k_index(int cin, int taps, int tap, int c);   // packed-weight column of (tap, channel)
 int launch_conv_igemm(const ConvParams& p, int tile, hipStream_t s);   // 0, or -1 for unsupported geometry

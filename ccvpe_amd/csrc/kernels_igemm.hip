@@ -325,7 +325,7 @@ static void launch_cfg2(const ConvParams& p, hipStream_t s) {
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(kern), lds);
     dim3 grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, p.splitk > 1 ? p.splitk : 1);
     if (p.splitk <= 1 || p.tickets == nullptr || (long long)grid.x * grid.y > CONV_TICKETS) {
-        if (p.split_fused) { ConvParams q = p; q.split_fused = 0; CCVPE_LAUNCH(kern, grid, dim3(256), lds, s, q); if (q.splitk > 1) launch_splitk_reduce(q, s); return; }
+        if (p.split_fused) { ConvParams q = p; q.split_fused = 0; conv_tile_note_unfused(); CCVPE_LAUNCH(kern, grid, dim3(256), lds, s, q); if (q.splitk > 1) launch_splitk_reduce(q, s); return; }
     }
     CCVPE_LAUNCH(kern, grid, dim3(256), lds, s, p);
     if (p.splitk > 1 && !p.split_fused) launch_splitk_reduce(p, s);
@@ -442,6 +442,12 @@ static int pick_tile(const ConvParams& p) {
 
 static thread_local int g_last_tile = 0;
 int conv_tile_last() { int t = g_last_tile; g_last_tile = 0; return t; }
+// A launcher that was handed a self-reducing split (code 64 + S) and cannot run it - more output regions than ticket counters, a
+// persistent workgroup with more units than its ticket list holds - reduces with the launch instead: the recorded code becomes S.
+void conv_tile_note_unfused() {
+    const int sc = (g_last_tile >> 8) & 0xff;
+    if (sc > SPLIT_FUSED && sc <= SPLIT_FUSED + 32) g_last_tile = (g_last_tile & 0xff) | ((sc - SPLIT_FUSED) << 8);
+}
 
 // exact small-range division by multiplication: q = (g * mul) >> 20 for 0 <= g < limit
 static int find_div_mul(int d, int limit) {

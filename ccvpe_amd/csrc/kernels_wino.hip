@@ -390,7 +390,10 @@ static void launch_wino(const ConvParams& p_in, hipStream_t s) {
     // persistent grid: two workgroups per CU (the register budget allows no more) loop over the tiles
     const int resident = 2 * 256 / (p.splitk > 1 ? p.splitk : 1);
     dim3 grid(std::min(mblocks * nblocks, std::max(resident, 8)), 1, p.splitk > 1 ? p.splitk : 1);
-    if (p.splitk <= 1 || p.tickets == nullptr || mblocks * nblocks > CONV_TICKETS || (mblocks * nblocks + (int)grid.x - 1) / (int)grid.x + 1 > 64) p.split_fused = 0;
+    if (p.splitk <= 1 || p.tickets == nullptr || mblocks * nblocks > CONV_TICKETS || (mblocks * nblocks + (int)grid.x - 1) / (int)grid.x + 1 > 64) {
+        if (p.split_fused) conv_tile_note_unfused();
+        p.split_fused = 0;
+    }
     if (p.split_fused) {
         auto kern = conv_wino_kernel<NW, NM, GC, true>;
         ensure_dynamic_lds(attr_f, reinterpret_cast<const void*>(kern), lds);

@@ -383,7 +383,10 @@ static void launch_wino4_plain(const ConvParams& p_in, hipStream_t s) {
     const int resident = (NW == 4 ? 2 : 1) * 256 / S;   // 256-thread workgroups: two per CU, 512-thread: one
     dim3 grid(std::min(mblocks * nblocks, std::max(resident, 8)), 1, S);
     const int per_wg = (mblocks * nblocks + (int)grid.x - 1) / (int)grid.x + 8;   // (upper bound of a workgroup's units)
-    if (S <= 1 || p.tickets == nullptr || mblocks * nblocks > CONV_TICKETS || per_wg > 64) p.split_fused = 0;
+    if (S <= 1 || p.tickets == nullptr || mblocks * nblocks > CONV_TICKETS || per_wg > 64) {
+        if (p.split_fused) conv_tile_note_unfused();
+        p.split_fused = 0;
+    }
     const dim3 block(NW * 64);
     if (p.split_fused) { auto kern = conv_wino4_kernel<NW, true>; ensure_dynamic_lds(attr_f, reinterpret_cast<const void*>(kern), lds); CCVPE_LAUNCH(kern, grid, block, lds, s, p); return; }
     auto kern = conv_wino4_kernel<NW, false>;

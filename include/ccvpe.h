@@ -475,6 +475,46 @@ int ccvpe_op_conv2d(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
                     int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, int32_t tile,
                     float* out, int32_t iters, float* ms, void* stream);
 
+/* The same hook for the forms the plans launch (parity tests; not on the product path): one descriptor.  Every field of
+ * ccvpe_op_conv2d keeps its meaning; beyond them:
+ *   in_ld     floats per input pixel, >= Cin and a multiple of 4 (0 = Cin): `in` is [B,H,W,in_ld], channels past Cin are not read.
+ *   gate      [B][Cin] device floats or NULL: the input is multiplied by gate[b][c] (squeeze-excite).  1x1 / stride 1 / pad 0
+ *             convs only.
+ *   resid     [B*OH*OW][resid_ld] device floats or NULL (resid_ld >= Cout), added to the result.  act must be 0: no plan adds a
+ *             residual behind an activation, and the hook defines no order for it.  Not with CCVPE_OP_DECONV.
+ *   dst, ndst 1 .. 3 destinations the caller allocates: destination i is [output pixels][ld], the Cout channels land at
+ *             [coff, coff + Cout) of every row (coff + Cout <= ld), the other floats of a row are left alone.
+ *   mode      CCVPE_OP_CONV, or CCVPE_OP_DECONV: ConvTranspose2d(kernel 2, stride 2), w [Cin,Cout,2,2] (KH = KW = stride = 2, pad 0),
+ *             packed as a decoder level is (GEMM column (dy*2+dx)*Cout + o, 1x1 taps, pixel shuffle on store); 2H x 2W output pixels.
+ *   ran_tile, ran_split, requested_runs   optional outputs: the tile id and split code the launcher recorded for the (first)
+ *             launch - another tile than `tile & 255` means the requested one does not take this layer and the shape heuristic
+ *             chose, split code 1 means K stayed whole, 64 + S that S slices reduced themselves - and whether the requested tile
+ *             takes these launch parameters (1 / 0; -1 for tile id 0).  A Winograd id on a layer it does not take falls back
+ *             like any other (ccvpe_op_conv2d refuses it).
+ * Refusals (CCVPE_EINVAL, before any launch): those of ccvpe_op_conv2d; in_ld, resid_ld, ld / coff outside the ranges above; a
+ * NULL destination; a gate or residual outside the uses above; any input, residual or destination of 2^31 elements or more.
+ * Not expressible here: the squeeze-excite prologue of the latency-form project conv (se_rows) and the split-bf16 input and
+ * destinations of the bf16x3 hand-off. */
+enum { CCVPE_OP_CONV = 0, CCVPE_OP_DECONV = 1 };
+typedef struct ccvpe_op_conv_dst { float* ptr; int32_t ld, coff; } ccvpe_op_conv_dst;
+typedef struct ccvpe_op_conv_desc {
+    const float* in;
+    int32_t B, H, W, Cin, in_ld;
+    const float* w;
+    const float* bias;
+    int32_t Cout, KH, KW, stride, pad, act, tile, mode;
+    const float* gate;
+    const float* resid;
+    int32_t resid_ld, ndst;
+    ccvpe_op_conv_dst dst[3];
+    int32_t iters;
+    float* ms;
+    int32_t* ran_tile;
+    int32_t* ran_split;
+    int32_t* requested_runs;
+} ccvpe_op_conv_desc;
+int ccvpe_op_conv2d_ex(const ccvpe_op_conv_desc* d, void* stream);
+
 /* Kernel-level hook for parity tests (not on the product path): the fused last decoder level on its own,
  * ConvTranspose2d(k2, s2, Cin -> 16) -> conv3x3(16 -> 16, pad 1) + ReLU -> conv3x3(16 -> Cout, pad 1), and for Cout == 2 the L2
  * normalisation over the channel (F.normalize, eps 1e-12).  H x W is the OUTPUT size (multiples of 16).  score != 0: channel 0 of the

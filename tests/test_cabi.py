@@ -83,3 +83,49 @@ def test_environment_is_read_only_by_read_switches():
         offenders += [f"{f}: {line.strip()}" for line in text.splitlines() if re.search(r"\bgetenv\s*\(", line)]
     assert readers == 1, "read_switches() is defined once"
     assert not offenders, "getenv outside read_switches():\n" + "\n".join(offenders)
+
+
+def test_conv_hook_descriptor_refusals(built_library):
+    """ccvpe_op_conv2d_ex refuses a bad descriptor before it touches the device: the pointers below are never dereferenced."""
+    lib = _lib.load()
+    assert C.sizeof(_lib.OpConvDesc) == 192 and C.sizeof(_lib.OpConvDst) == 16
+    assert lib.ccvpe_op_conv2d_ex(None, None) == -1
+    fake = 0x1000
+
+    def desc(**kw):
+        d = _lib.OpConvDesc()
+        d.x, d.w = fake, fake
+        d.B, d.H, d.W, d.Cin, d.in_ld = 1, 8, 8, 16, 16
+        d.Cout, d.KH, d.KW, d.stride, d.pad, d.act, d.tile, d.mode = 8, 1, 1, 1, 0, 0, 0, 0
+        d.ndst = 1
+        d.dst[0].ptr, d.dst[0].ld, d.dst[0].coff = fake, 8, 0
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def refused(d, text):
+        assert lib.ccvpe_op_conv2d_ex(C.byref(d), None) == -1
+        assert text in lib.ccvpe_last_error(), lib.ccvpe_last_error()
+
+    refused(desc(x=None), b"null argument")
+    refused(desc(Cin=12, in_ld=12), b"Cin must be a multiple of 8")
+    refused(desc(mode=2), b"unknown mode")
+    refused(desc(mode=1), b"transposed conv is 2x2")
+    refused(desc(in_ld=12), b"in_ld")
+    refused(desc(in_ld=18), b"in_ld")
+    refused(desc(B=1 << 15, H=1 << 8, W=1 << 8, in_ld=16), b"2^31")
+    refused(desc(gate=fake, KH=3, KW=3, pad=1), b"gate")
+    refused(desc(gate=fake, mode=1, KH=2, KW=2, stride=2), b"gate")
+    refused(desc(resid=fake, resid_ld=8, act=2), b"residual")
+    refused(desc(resid=fake, resid_ld=4), b"resid_ld")
+    refused(desc(resid=fake, resid_ld=8, mode=1, KH=2, KW=2, stride=2), b"residual")
+    refused(desc(ndst=0), b"ndst")
+    refused(desc(ndst=4), b"ndst")
+    d = desc(ndst=2)
+    refused(d, b"null destination 1")
+    d = desc()
+    d.dst[0].coff = 4
+    refused(d, b"coff + Cout")
+    d = desc(B=1 << 11, H=1 << 8, W=1 << 8)      # 2^27 pixels: the input fits, a 16-float destination row does not
+    d.dst[0].ld = 16
+    refused(d, b"2^31")

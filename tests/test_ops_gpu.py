@@ -1,11 +1,18 @@
-"""Kernel-level parity of the implicit-GEMM convolution (through the C ABI hook ccvpe_op_conv2d) against
-torch's fp32 conv on ragged / odd shapes: M and N not multiples of any tile, every tile id, strides,
-the 2x2 s2 form of the aerial descriptor map, activations.  Tolerance 2e-5 of the output scale."""
+"""Kernel-level parity of the implicit-GEMM convolution (through the C ABI hooks ccvpe_op_conv2d / ccvpe_op_conv2d_ex) against
+torch's fp64 conv on ragged / odd shapes: M and N not multiples of any tile, every tile id, strides,
+the 2x2 s2 form of the aerial descriptor map, activations.  Tolerance 2e-5 of the output scale.
+
+Every case that forces a tile goes through forced(): tests/tile_rules.py derives from the documented rules whether the tile takes the
+layer and which split code the request becomes, the hook's requested_runs / ran tile / ran split are asserted to agree, and a tile
+the rules refuse is asserted to have fallen back (its result is compared all the same).  Cases found to be fallbacks that way are
+listed in DESIGN.md 2.2."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 from ccvpe_amd import _lib
+from tests import tile_rules as tr
+from tests.tile_rules import WINO_SHAPES, X_WIDTHS
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +38,13 @@ def ref_conv(x, w, b, stride, pad, act):
     elif act == 2:
         y = y * torch.sigmoid(y)
     return y.permute(0, 2, 3, 1).float()
+
+
+def forced(x, w, b, stride, pad, act, name, code=0):
+    """One launch of tile `name` (split code `code`), checked against the rule table (tile_rules.run_checked): (out, the tile
+    that ran, the split code that ran, whether the rules admit the tile)."""
+    outs, ran, split, admitted = tr.run_checked(x, w, b, name, code, stride=stride, pad=pad, act=act)
+    return outs[0], ran, split, admitted
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -62,36 +76,19 @@ def test_every_tile_config_is_correct():
         if "wino" in name:       # 19 x 23 is not Winograd-shaped: covered by test_winograd_*
             with pytest.raises(_lib.CcvpeError):
                 _lib.op_conv2d(x, w, b, 1, 1, 0, t)
-            continue
-        out, _ = _lib.op_conv2d(x, w, b, 1, 1, 0, t)
+        # (the fifteen conv_pw_* / conv_proj_* / conv_projl_* ids are refused by rule on a 3x3 layer - forced() asserts that they
+        # fall back; they run as themselves in the pointwise and latency-form tests below and in test_ops_forms_gpu.py)
+        out, ran, _, admitted = forced(x, w, b, 1, 1, 0, name)
+        assert admitted == name.startswith(("conv_igemm_", "conv_bf16x3_")), name
         err = (out - ref).abs().max().item() / ref.abs().max().item()
         tol = 1e-4 if "bf16x3" in name else 2e-5      # the 3-term bf16 split carries ~2^-16 per product
-        assert err <= tol, f"tile {t} ({name}): {err:.3g}"
-
-
-X_WIDTHS = [32, 48, 64, 80, 96, 128]     # conv_wino4x_<width>: the xi-split F(4x4) form takes a layer in ONE n-block of its width
+        assert err <= tol, f"tile {t} ({name}, ran {ran}): {err:.3g}"
 
 
 def x_tile_applies(name, cout):
     """conv_wino4x_<w> serves exactly the layers whose narrowest fitting configuration it is (24 <= Cout <= w)."""
     w = int(name.rsplit("_", 1)[1])
     return cout >= 24 and next((x for x in X_WIDTHS if cout <= x), None) == w
-
-
-WINO_SHAPES = [
-    # B, H, W, Cin, Cout
-    (1, 16, 16, 8, 16),
-    (3, 16, 16, 64, 88),
-    (2, 48, 32, 24, 40),
-    (1, 32, 48, 104, 17),      # not a multiple of 4 channels: every Winograd tile refuses it
-    (1, 32, 48, 104, 20),      # a partly filled last 16-channel slice
-    (2, 16, 16, 200, 160),
-    (1, 64, 64, 16, 100),
-    (1, 32, 32, 48, 32),       # conv2_ori-shaped: the 32-wide xi-split configuration
-    (2, 16, 32, 88, 64),       # conv3_ori-shaped (64), Cin = 88: a half-filled last 16-channel group
-    (1, 32, 32, 104, 80),      # conv3-shaped: eight waves, 3 + 2 slices
-    (1, 16, 16, 24, 30),       # not a multiple of 4 channels: only the xi-split form (one channel per lane in its epilogue) takes it
-]
 
 
 @pytest.mark.parametrize("shape", WINO_SHAPES)
@@ -118,8 +115,10 @@ def test_winograd_tiles_match_torch(shape):
             if refuse:
                 with pytest.raises(_lib.CcvpeError):
                     _lib.op_conv2d(x, w, b, 1, 1, act, t)
-                continue
-            out, _ = _lib.op_conv2d(x, w, b, 1, 1, act, t)
+            out, ran, _, admitted = forced(x, w, b, 1, 1, act, name)   # (refused: the fallback's result is compared all the same)
+            assert admitted == (not refuse), f"tile {name}: the rule table and this test disagree"
+            if refuse:
+                f4 = "wino4" in ran
             err = (out - ref).abs().max().item() / ref.abs().max().item()
             # F(2x2): transforms only add / subtract (measured 2-12e-7).  F(4x4): constants up to 8 amplify the fp32 rounding
             # of the transforms (~1.4e-5 expected); both far inside the 1e-3 contract
@@ -143,13 +142,16 @@ def test_winograd_split_k(shape, splitk):
         name = lib.ccvpe_op_tile_name(t).decode()
         if "wino" not in name or ("wino4x" in name and not x_tile_applies(name, Cout)):
             continue
-        out, _ = _lib.op_conv2d(x, w, b, 1, 1, 1, t | (splitk << 8))
+        out, ran, split, _ = forced(x, w, b, 1, 1, 1, name, splitk)
+        assert (ran, split) == (name, splitk), f"tile {name} split-K {splitk}: ran {ran} split {split}"
         err = (out - ref).abs().max().item() / ref.abs().max().item()
         assert err <= (1e-4 if "wino4" in name else 2e-5), f"tile {name} split-K {splitk}: {err:.3g}"
         # round 4: the same split reducing itself (split code 64 + S: write-through slabs, a ticket per output region, the last K slice
         # sums the slabs in slice order) - the same bits as slab + reduce launch; three runs: whoever arrives last, the same bits
         for _ in range(3):
-            fused, _ = _lib.op_conv2d(x, w, b, 1, 1, 1, t | ((64 + splitk) << 8))
+            fused, ran, fsplit, _ = forced(x, w, b, 1, 1, 1, name, 64 + splitk)
+            # degraded by the launcher: the xi-split tiles have no self-reducing form (conv_tile_splits) - slabs + reduce launch again
+            assert (ran, fsplit) == (name, splitk if "wino4x" in name else 64 + splitk), f"tile {name}: ran {ran} split {fsplit}"
             assert torch.equal(fused, out), f"tile {name} self-reducing split-K {splitk}"
 
 
@@ -166,19 +168,21 @@ def test_implicit_gemm_self_reducing_split_k(shape, splitk):
     b = torch.randn(Cout, device="cuda", generator=g)
     ref = ref_conv(x, w, b, stride, pad, 2)
     for name in ("conv_igemm_64x32_m16", "conv_igemm_64x64_m32_s1", "conv_igemm_128x128_m16"):
-        t = _tile_id(name)
-        out, _ = _lib.op_conv2d(x, w, b, stride, pad, 2, t | (splitk << 8))
+        out, ran, split, _ = forced(x, w, b, stride, pad, 2, name, splitk)
+        assert (ran, split) == (name, splitk), f"{name}: ran {ran} split {split}"
         err = (out - ref).abs().max().item() / ref.abs().max().item()
         assert err <= 2e-5, f"{name}: {err:.3g}"
         for _ in range(3):
-            fused, _ = _lib.op_conv2d(x, w, b, stride, pad, 2, t | ((64 + splitk) << 8))
+            fused, ran, fsplit, _ = forced(x, w, b, stride, pad, 2, name, 64 + splitk)
+            assert (ran, fsplit) == (name, 64 + splitk), f"{name}: ran {ran} split {fsplit}"
             assert torch.equal(fused, out), name
 
 
 def test_winograd_tail_split():
     """cfg split code 255 of the F(4x4,3x3) tiles: 2 x 16 x 128 pixels = 16 pixel blocks x 33 channel blocks of 64 = 528 work items on
     512 resident workgroups -> 512 run whole, the last channel block (16 items) is split over K through slabs (the same grid
-    arithmetic as conv5.0 at batch 32: 640 items); the 128-channel form has no whole-block remainder and runs unsplit."""
+    arithmetic as conv5.0 at batch 32: 640 items); the 128-channel form has 16 x 17 = 272 items on 256 workgroups and splits its last
+    block the same way.  Both are asserted to report split code 255 (the launcher reports 1 when the tail did not apply)."""
     lib = _lib.load()
     B, H, W, Cin, Cout = 2, 16, 128, 64, 2112
     g = torch.Generator(device="cuda").manual_seed(77)
@@ -191,7 +195,8 @@ def test_winograd_tail_split():
             name = lib.ccvpe_op_tile_name(t).decode()
             if "wino4" not in name or "wino4x" in name:
                 continue
-            out, _ = _lib.op_conv2d(x, w, b, 1, 1, act, t | (255 << 8))
+            out, ran, split, _ = forced(x, w, b, 1, 1, act, name, 255)
+            assert (ran, split) == (name, 255), f"tile {name}: ran {ran} split {split}"
             err = (out - ref).abs().max().item() / ref.abs().max().item()
             assert err <= 1e-4, f"tile {name} tail split act {act}: {err:.3g}"
 
@@ -200,6 +205,17 @@ PW_SHAPES = [
     # B, H, W, Cin, Cout: 1x1 layers of the encoders (expand / project / head shapes, ragged M and N, K tails)
     (2, 16, 16, 16, 96), (1, 19, 23, 40, 240), (3, 8, 8, 112, 672), (2, 16, 16, 480, 80), (1, 16, 16, 24, 144), (2, 5, 7, 328, 40),
 ]
+
+
+# Refused by rule (conv_pw_fits: the weight slab [bn][Kpad + 4] and four 16 x (bn + 4) C patches within 150 KB of LDS); every
+# conv_pw_* tile runs as itself at the four shallower shapes above.
+PW_REFUSED = {
+    (480, "conv_pw_80"): "slab of 80 x (480 + 4) floats + C patches = 172 KB exceeds 150 KB",
+    (480, "conv_pw_128"): "slab of 128 x (480 + 4) floats + C patches = 275 KB exceeds 150 KB",
+    (480, "conv_pw_160"): "slab of 160 x (480 + 4) floats + C patches = 344 KB exceeds 150 KB",
+    (328, "conv_pw_128"): "slab of 128 x (352 + 4) floats + C patches = 211 KB exceeds 150 KB",
+    (328, "conv_pw_160"): "slab of 160 x (352 + 4) floats + C patches = 264 KB exceeds 150 KB",
+}
 
 
 @pytest.mark.parametrize("shape", PW_SHAPES)
@@ -217,9 +233,14 @@ def test_pointwise_persistent_tiles_match_torch(shape):
     for act in (0, 2):
         ref = ref_conv(x, w, b, 1, 0, act)
         for t in tiles:
-            out, _ = _lib.op_conv2d(x, w, b, 1, 0, act, t)
+            name = lib.ccvpe_op_tile_name(t).decode()
+            out, ran, _, admitted = forced(x, w, b, 1, 0, act, name)
+            if (Cin, name) in PW_REFUSED:
+                assert not admitted and ran != name, f"{name} at K {Cin}: expected a fallback, ran {ran}"
+            else:
+                assert admitted and ran == name, f"{name} at K {Cin}: ran {ran}"
             err = (out - ref).abs().max().item() / ref.abs().max().item()
-            assert err <= 2e-5, f"tile {lib.ccvpe_op_tile_name(t).decode()} act {act}: {err:.3g}"
+            assert err <= 2e-5, f"tile {name} (ran {ran}) act {act}: {err:.3g}"
 
 
 def test_conv2d_rejects_bad_geometry():
@@ -231,14 +252,6 @@ def test_conv2d_rejects_bad_geometry():
     w = torch.randn(4, 8, 5, 5, device="cuda")
     with pytest.raises(_lib.CcvpeError):
         _lib.op_conv2d(x, w, pad=2)       # 25 taps: outside the kernel's tap table
-
-
-def _tile_id(name):
-    lib = _lib.load()
-    for t in range(1, lib.ccvpe_op_num_tiles() + 1):
-        if lib.ccvpe_op_tile_name(t).decode() == name:
-            return t
-    raise KeyError(name)
 
 
 PROJL_SHAPES = [
@@ -263,16 +276,21 @@ def test_latency_form_deep_k_gemm_matches_torch(shape):
     ref = ref_conv(x, w, b, stride, 0, 0)
     # (..._r2 / _r4: two / four row tiles per workgroup - the weights of a 64-row layer are read once)
     for name in ("conv_projl_1", "conv_projl_2", "conv_projl_4", "conv_projl_r2", "conv_projl_r4"):
-        out, _ = _lib.op_conv2d(x, w, b, stride, 0, 0, _tile_id(name))   # (fewer rows than a workgroup takes: the library's own pick runs)
+        out, ran, _, admitted = forced(x, w, b, stride, 0, 0, name)
+        # refused by rule: conv_projl_r4 takes at least 64 rows - the 40-row map falls back; every other (shape, tile) runs as named
+        assert admitted == (not (name == "conv_projl_r4" and B * (H // stride) * (W // stride) < 64)), f"{name}: ran {ran}"
+        assert (ran == name) == admitted, f"{name}: ran {ran}"
         err = (out - ref).abs().max().item() / ref.abs().max().item()
         assert err <= 2e-5, f"{name}: {err:.3g}"
-        again, _ = _lib.op_conv2d(x, w, b, stride, 0, 0, _tile_id(name))
+        again, _, _, _ = forced(x, w, b, stride, 0, 0, name)
         assert torch.equal(out, again)
     # self-reducing split-K of the latency form (split code 64 + S): K slices on gridDim.z, slabs + ticket, the last slice sums in slice order
     for name, S in (("conv_projl_1", 2), ("conv_projl_r4", 4), ("conv_projl_2", 8)):
-        out, _ = _lib.op_conv2d(x, w, b, stride, 0, 0, _tile_id(name) | ((64 + S) << 8))
+        out, ran, split, admitted = forced(x, w, b, stride, 0, 0, name, 64 + S)
+        if admitted:      # (conv_projl_r4 on the 40-row map: the fallback takes the split)
+            assert (ran, split) == (name, 64 + S), f"{name} split {S}: ran {ran} split {split}"
         err = (out - ref).abs().max().item() / ref.abs().max().item()
         assert err <= 2e-5, f"{name} split {S}: {err:.3g}"
         for _ in range(3):
-            again, _ = _lib.op_conv2d(x, w, b, stride, 0, 0, _tile_id(name) | ((64 + S) << 8))
+            again, _, _, _ = forced(x, w, b, stride, 0, 0, name, 64 + S)
             assert torch.equal(out, again)
