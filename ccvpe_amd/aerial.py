@@ -391,6 +391,32 @@ def summary_to_metres(summary, metres_per_px):
     return out
 
 
+# ---- heading posterior ------------------------------------------------------------------------------------------
+
+# the 12 columns of model.localize_heading's heading rows, in order (include/ccvpe.h): angles in degrees [0, 360)
+HEADING_FIELDS = ("mass", "mean_cos", "mean_sin", "mean_deg", "resultant", "mode_bin", "mode_share",
+                  "peak_mass", "peak_mean_cos", "peak_mean_sin", "peak_mean_deg", "peak_resultant")
+
+
+def heading_bin_centres(bins: int) -> np.ndarray:
+    """The centre of every bin of model.localize_heading's hist, float64 [bins], degrees: bin b covers [b w, (b + 1) w) with
+    w = 360 / bins."""
+    bins = int(bins)
+    if not 4 <= bins <= 360:
+        raise ValueError(f"bins must be in 4..360, got {bins}")
+    return (np.arange(bins, dtype=np.float64) + 0.5) * (360.0 / bins)
+
+
+def heading_sigma_deg(resultant):
+    """The circular standard deviation sqrt(-2 ln R) in degrees of a mean resultant length R in [0, 1] (HEADING_FIELDS' "resultant"
+    / "peak_resultant"), float64 in the shape of R: 0 for R = 1, inf for R = 0, NaN outside [0, 1] - what an EKF takes as the
+    measurement noise of the mean heading."""
+    R = np.asarray(resultant.detach().cpu() if hasattr(resultant, "detach") else resultant, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.degrees(np.sqrt(-2.0 * np.log(R)))
+    return np.where((R >= 0.0) & (R <= 1.0), out, np.nan)
+
+
 # ---- tracking a frame stream (DESIGN.md 4.11) ------------------------------------------------------------------------------------
 
 def gaussian_taps(sigma_px, radius: int) -> np.ndarray:
@@ -439,12 +465,15 @@ class Tracker:
         self.belief = None
         self.origin = None
 
-    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None):
+    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None, heading_bins=None):
         """One frame of B parallel streams.  cache / tile_index: as model.localize_cached; origins [T,2]: the crop origin of every
         cached tile (oxford_tiles' "origin"; one per query when tile_index is None); motion_map_px [B,2] or [2]: the motion since
         the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5];
         with summary_radius (0..32) the update is model.localize_summary_cached - the same rows and belief - and the step returns
-        (rows, summary [B,16]): entropy, covariance and peak mass of the new belief (SUMMARY_FIELDS), to gate on."""
+        (rows, summary [B,16]): entropy, covariance and peak mass of the new belief (SUMMARY_FIELDS), to gate on.  With heading_bins
+        (4..360) the update is model.localize_heading_cached - the same rows, belief and summary - and (heading [B,12], hist
+        [B,heading_bins]) of the new belief (HEADING_FIELDS) are appended to what the step returns; their window radius is
+        summary_radius, or 8 without one."""
         org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
         B = grd.shape[0]
         now = org if tile_index is None else org[np.asarray(tile_index, dtype=np.int64)]
@@ -456,10 +485,18 @@ class Tracker:
                 raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
             prior = model.track_predict(self.belief, oxford_track_shift(self.origin, now, motion_map_px), taps, floor)
         summary = None
-        if summary_radius is None:
+        heading = None
+        if heading_bins is not None:
+            res = model.localize_heading_cached(grd, cache, prior, radius=8 if summary_radius is None else summary_radius, bins=heading_bins,
+                                                summary=summary_radius is not None, posterior=True, tile_index=tile_index)
+            rows, heading, self.belief = res[0], res[1:3], res[-1]
+            summary = res[3] if summary_radius is not None else None
+        elif summary_radius is None:
             rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
         else:
             rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
                                                                        tile_index=tile_index)
         self.origin = now.copy()
-        return rows if summary is None else (rows, summary)
+        if heading is None:
+            return rows if summary is None else (rows, summary)
+        return ((rows,) if summary is None else (rows, summary)) + tuple(heading)

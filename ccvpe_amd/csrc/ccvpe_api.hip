@@ -420,6 +420,10 @@ static int run_forward(ccvpe_handle h, const ForwardCall& fc) {
         if (fc.log_prior) { c.log_prior = fc.log_prior + (size_t)done * fc.prior_stride; c.prior_stride = fc.prior_stride; }
         if (fc.posterior) c.posterior = fc.posterior + (size_t)done * npx;
         if (fc.summary) { c.summary = fc.summary + (size_t)done * SUMMARY_COLS; c.summary_r = fc.summary_r; }
+        if (fc.heading) {
+            c.heading = fc.heading + (size_t)done * HEADING_COLS; c.hist = fc.hist + (size_t)done * fc.heading_bins;
+            c.heading_bins = fc.heading_bins; c.heading_r = fc.heading_r;
+        }
         if (key.topk) {
             c.rows = fc.rows + (size_t)done * fc.topk_k * 5;
             c.topk_k = fc.topk_k; c.topk_r = fc.topk_r;
@@ -520,12 +524,14 @@ static int ensure_scratch(ccvpe_handle_s::Scratch& buf, int batch, size_t (*byte
 }
 
 // The top-K scratch (topk_scratch_bytes) and the prior scratch for buf.batch samples: [PP_MAX_BATCH ticket counters][B x 64 x 64 keys]
-// [B x 64 indices] and, in the prior scratch only, [B x 64 x 2 softmax partials][B x 64 x 8 float64 sums of the summary forms]; the
-// argmax form's (max, index) hand-off pairs use the start of the key area.  Every area is a multiple of 8 bytes long.
+// [B x 64 indices] and, in the prior scratch only, [B x 64 x 2 softmax partials][B x 64 x 8 float64 sums of the summary forms]
+// [B x 64 x 4 float64 sums of the heading form][B x 360 fixed-point histogram bins of the heading form, zero between launches like the
+// counters]; the argmax form's (max, index) hand-off pairs use the start of the key area.  Every area is a multiple of 8 bytes long.
 static size_t prior_scratch_bytes(int B) {
-    return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float) + (size_t)B * 64 * SUMMARY_PART * sizeof(double);
+    return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float) + (size_t)B * 64 * SUMMARY_PART * sizeof(double) +
+           (size_t)B * 64 * HEADING_PART * sizeof(double) + (size_t)B * HEADING_MAX_BINS * sizeof(unsigned long long);
 }
-struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; double* summ; };
+struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; double* summ; double* head; unsigned long long* bins; };
 static TopkScratch topk_scratch_layout(const ccvpe_handle_s::Scratch& buf) {
     TopkScratch w;
     w.tickets = reinterpret_cast<unsigned*>(buf.ptr);
@@ -533,6 +539,8 @@ static TopkScratch topk_scratch_layout(const ccvpe_handle_s::Scratch& buf) {
     w.index = reinterpret_cast<int*>(w.keys + (size_t)buf.batch * 64 * TOPK_MAX_K);
     w.partial = reinterpret_cast<float*>(w.index + (size_t)buf.batch * TOPK_MAX_K);
     w.summ = reinterpret_cast<double*>(w.partial + (size_t)buf.batch * 64 * 2);   // (read by the summary forms alone)
+    w.head = w.summ + (size_t)buf.batch * 64 * SUMMARY_PART;                      // (these two by the heading form alone)
+    w.bins = reinterpret_cast<unsigned long long*>(w.head + (size_t)buf.batch * 64 * HEADING_PART);
     return w;
 }
 
@@ -1076,6 +1084,87 @@ int ccvpe_belief_summary(ccvpe_handle h, const float* belief, int32_t batch, int
     p.summary = summary;
     launch_belief_summary(p, (hipStream_t)stream);
     return launch_status("belief_summary launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Heading posterior: the argmax pose plans with the whole orientation field in the workspace and one more launch,
+// pose.heading, behind both decoders (plans of their own, PlanKey::heading; every other launch keeps the name and tuning entry it has
+// in the pose or the full plan), and the logits form on the prior scratch.  summary and posterior are optional outputs of pose.argmax
+// as in the summary forms.
+// ------------------------------------------------------------------------------------------------
+static int check_heading_args(const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, const float* rows,
+                              const float* heading, const float* hist, const float* summary, const float* posterior) {
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!heading) return ccvpe_fail(CCVPE_EINVAL, "null heading");
+    if (!hist) return ccvpe_fail(CCVPE_EINVAL, "null hist");
+    if (nbins < HEADING_MIN_BINS || nbins > HEADING_MAX_BINS)
+        return ccvpe_fail(CCVPE_EINVAL, "nbins must be in %d .. %d, got %d", HEADING_MIN_BINS, HEADING_MAX_BINS, nbins);
+    if (radius < 0 || radius > HEADING_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", HEADING_MAX_R, radius);
+    if (log_prior) if (int rc = check_prior_stride(prior_stride)) return rc;
+    if (heading == rows || hist == rows || heading == hist) return ccvpe_fail(CCVPE_EINVAL, "rows, heading and hist must not alias");
+    if (log_prior && (heading == log_prior || hist == log_prior)) return ccvpe_fail(CCVPE_EINVAL, "heading and hist must not alias log_prior");
+    if (summary && (summary == rows || summary == heading || summary == hist))
+        return ccvpe_fail(CCVPE_EINVAL, "summary must not alias rows, heading or hist");
+    if (posterior && log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    if (posterior && (posterior == rows || posterior == summary || posterior == heading || posterior == hist))
+        return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias rows, summary, heading or hist");
+    return 0;
+}
+
+static void heading_call(ForwardCall& fc, const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, float* rows,
+                         float* heading, float* hist, float* summary, float* posterior) {
+    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    fc.summary = summary; fc.summary_r = radius;
+    fc.heading = heading; fc.hist = hist; fc.heading_bins = nbins; fc.heading_r = radius;
+}
+
+int ccvpe_localize_heading(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                           const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading,
+                           float* hist, float* summary, float* posterior, void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (int rc = check_heading_args(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat;
+    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    return run_forward(h, fc);
+}
+
+int ccvpe_localize_heading_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                          const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride,
+                                          int32_t radius, int32_t nbins, float* rows, float* heading, float* hist, float* summary,
+                                          float* posterior, void* stream) {
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    if (int rc = check_heading_args(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior)) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    return run_forward(h, fc);
+}
+
+int ccvpe_postprocess_heading(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading, float* hist, float* summary,
+                              float* posterior, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (int rc = check_heading_args(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior)) return rc;
+    if (posterior && posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
+    if (heading == logits || heading == ori || hist == logits || hist == ori)
+        return ccvpe_fail(CCVPE_EINVAL, "heading and hist must not alias logits or ori");
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
+    const long long stride = log_prior ? prior_stride : 0;
+    launch_logits_argmax(w, logits, ori, batch, log_prior, stride, posterior, rows, (hipStream_t)stream, summary, radius);
+    HeadingParams p{};   // (behind pose.argmax on the same stream: its counters are back at zero, its index is written)
+    p.logits = logits; p.partial = w.partial; p.prior = log_prior; p.prior_stride = stride; p.ori = ori; p.index = w.index;
+    p.B = batch; p.nbins = nbins; p.r = radius; p.part = w.head; p.bins = w.bins; p.tickets = w.tickets; p.heading = heading; p.hist = hist;
+    launch_heading_reduce(p, (hipStream_t)stream);
+    return launch_status("postprocess_heading launch");
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

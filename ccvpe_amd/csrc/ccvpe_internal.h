@@ -256,6 +256,9 @@ struct Ctx {
     float* posterior = nullptr;        // pose plans: optional posterior map [mb][512*512] of this micro-batch (ccvpe_track_update*)
     float* summary = nullptr;          // summary pose plans: the [mb][16] summary rows of this micro-batch (ccvpe_localize_summary*) ...
     int summary_r = 0;                 // ... and the window radius 0..32 of this call
+    float* heading = nullptr;          // heading pose plans: the [mb][12] heading rows of this micro-batch (ccvpe_localize_heading*),
+    float* hist = nullptr;             // ... its [mb][heading_bins] histograms,
+    int heading_bins = 0, heading_r = 0;   // ... the bin count 4..360 and the window radius 0..32 of this call
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -279,8 +282,11 @@ struct PlanKey {
     bool topk = false;            // pose plans: the top-K tail of ccvpe_localize_topk (K and r per call, workspace for K = 64)
     bool summary = false;         // argmax pose plans: pose.argmax also writes the summary rows (ccvpe_localize_summary*); the only plans whose
                                   // workspace holds the float64 hand-off of the chunks' sums
+    bool heading = false;         // argmax pose plans: the whole orientation field in the workspace and the pose.heading launch behind both
+                                  // decoders (ccvpe_localize_heading*); combines with summary
     bool operator==(const PlanKey& o) const {
-        return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk && summary == o.summary;
+        return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk && summary == o.summary &&
+               heading == o.heading;
     }
 };
 
@@ -302,12 +308,16 @@ struct ForwardCall {
     float* posterior = nullptr;        // argmax pose plans, optional (ccvpe_track_update*): every slice also writes its own posterior maps
     float* summary = nullptr;          // argmax pose plans (ccvpe_localize_summary*): [batch][16] summary rows, every slice its own; selects the
     int summary_r = 0;                 //   summary plans.  The window radius, checked by the entry point
+    float* heading = nullptr;          // argmax pose plans (ccvpe_localize_heading*): [batch][12] heading rows and
+    float* hist = nullptr;             //   [batch][heading_bins] histograms, every slice its own; select the heading plans.
+    int heading_bins = 0, heading_r = 0;   // Bin count and window radius, checked by the entry point
     hipStream_t stream = nullptr;
     bool profile = false;              // ccvpe_profile_forward: a hipEvent pair around every launch
     PlanKey plan_key() const {         // (B: set per slice by the micro-batch loop)
         PlanKey key;
         key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = rows != nullptr; key.topk = rows && topk_k > 0;
         key.summary = rows && summary;
+        key.heading = rows && heading;
         return key;
     }
 };
@@ -557,7 +567,8 @@ struct ccvpe_handle_s {
     Scratch post_scratch;         // launch_postprocess: partial pairs and ticket counters
     Scratch topk_scratch;         // ccvpe_postprocess_topk: ticket counters, hand-off keys and indices
     Scratch prior_scratch;        // ccvpe_postprocess_prior, ccvpe_track_update_logits, ccvpe_postprocess_summary, ccvpe_belief_summary: the
-                                  // top-K scratch plus softmax partials plus the summary's float64 hand-off
+                                  // top-K scratch plus softmax partials plus the summary's float64 hand-off plus, for ccvpe_postprocess_heading,
+                                  // the heading sums' hand-off and the queries' fixed-point histograms
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;

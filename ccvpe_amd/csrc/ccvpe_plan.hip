@@ -333,6 +333,9 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
 // tail is topk.peaks (the K best peaks from recomputed heatmap values) and the orientation at those K pixels (ori1.topk:
 // the fused level 1 for each hypothesis' tile; without the fused level: ori1.tail + ori1.topk_gather).  K and r come with each call
 // (Ctx::topk_k / topk_r); the workspace is sized for K = 64.
+// Heading pose plans (heading = true, ccvpe_localize_heading*): the argmax pose plan with the WHOLE orientation field in
+// the workspace - level 1 of the orientation branch is the full plan's launch (ori1.fused, or ori1.tail without the fused level: the same
+// names and shapes, so the same tuning entries), ori1.gather fills rows[2..4] - and pose.heading behind both decoders' tails.
 // Pair plans (mode 4, pose, ccvpe_localize_region): the cached pose plan with the ground side from a ground cache as well - the ground
 // encoder, grd.heads and grd.desc give way to grd.cached_desc, a gather of each pair's query row (Ctx::query_index); the aerial
 // launches gather each pair's tile (Ctx::tile_index).  Every other launch keeps the cached pose plan's name and tuning entry.
@@ -342,6 +345,8 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     pl.key = key;
     pl.key.topk = pose && key.topk;
     pl.key.summary = pose && !key.topk && key.summary;
+    pl.key.heading = key.heading;
+    if (key.heading && (!pose || key.topk || mode == 4)) return ccvpe_fail(CCVPE_EINVAL, "heading plans are argmax pose plans (no top-K, no pairs)");
     if (mode == 1) return build_aerial_plan(h, pl, B);
     if (mode == 3) return build_ground_plan(h, pl, B, gh, gw);
     const bool cached = mode == 2 || mode == 4;
@@ -625,11 +630,14 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         }, 2.0 * B * 262144.0 * 144, 4.0 * B * 262144.0 * 17);
     }
     Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
+    Tensor pose_part;    // pose plans: the softmax partials, read again by pose.heading
+    const bool heading = pl.key.heading;
     if (pose) {
         static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
         const bool topk = pl.key.topk;
         Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, topk ? 2 * TOPK_MAX_K : 2);   // (argmax: the (max, index) hand-off pairs)
         pose_index = pl.alloc(B, 1, 1, topk ? TOPK_MAX_K : 1);
+        pose_part = part;
         // summary plans: the chunks' float64 sums, B x 64 x 8 doubles (tensors start on 256-byte granules); no other
         // plan allocates it, so theirs keep their workspace
         static_assert(sizeof(double) == 2 * sizeof(float), "the hand-off is allocated in floats");
@@ -673,10 +681,11 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         Tensor xo = ori_in6;
         Tensor ori_mid;
         Tensor raw;
+        Tensor ori_field;   // heading plans: the orientation field [B][2][512][512] in the workspace
         if (h->debug && !pose) { raw = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW); pl.taps["ori_level1_nchw"] = {raw, 0, -1}; }
         bool fused_done = false;
         for (int j = 0; j < 6; ++j) {
-            if (j == 5 && h->sw.fuse_level1 && pose) {   // the fused level for the tile of each sample's argmax / of each hypothesis (a wait on pose.argmax / topk.peaks)
+            if (j == 5 && h->sw.fuse_level1 && pose && !heading) {   // the fused level for the tile of each sample's argmax / of each hypothesis (a wait on pose.argmax / topk.peaks)
                 const DecoderW& dw = h->ori;
                 Level1Params lp{};
                 lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
@@ -696,6 +705,12 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
                     q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
                     launch_level1_pose(q, reinterpret_cast<const int*>(c.ptr(idx)), c.rows, c.stream);
                 }, flops, bytes);
+                fused_done = true;
+                break;
+            }
+            if (j == 5 && h->sw.fuse_level1 && heading) {   // heading plans: the whole field, the full plan's launch into the workspace
+                ori_field = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW);
+                plan_level1_fused(h->ori, xo, vs.ori[5].din, 2, true, raw, "ori1", ori_field);
                 fused_done = true;
                 break;
             }
@@ -729,7 +744,30 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             pl.add("ori1.gather", {ori_ws, idx}, [=](const Ctx& c) {
                 launch_pose_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
             }, 0, 12.0 * B);
+            ori_field = ori_ws;
         }
+        } else if (heading) {
+            const Tensor idx = pose_index, of = ori_field;
+            pl.add("ori1.gather", {of, idx}, [=](const Ctx& c) {
+                launch_pose_gather(c.ptr(of), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+            }, 0, 12.0 * B);
+        }
+        if (heading) {
+            // pose.heading (kernels_heading.hip): reads the logits, the softmax partials, the argmax and the field, so it waits for both
+            // streams' tails.  The float64 hand-off lives in the workspace; the queries' fixed-point histograms must be zero between
+            // launches like the counters, so they live beside them (never in the arena, which the autotuner fills).
+            static_assert(sizeof(double) == 2 * sizeof(float) && sizeof(unsigned long long) == 2 * sizeof(unsigned), "allocated in words");
+            const Tensor lg = logits_ws, part = pose_part, idx = pose_index, of = ori_field;
+            const Tensor hpart = pl.alloc(B, 1, 64, 2 * HEADING_PART);
+            const size_t toff = pl.alloc_tickets((size_t)B), boff = pl.alloc_tickets((size_t)B * HEADING_MAX_BINS * 2);
+            pl.add("pose.heading", {lg, part, idx, of, hpart}, [=](const Ctx& c) {
+                HeadingParams p{};
+                p.logits = c.ptr(lg); p.partial = c.ptr(part); p.prior = c.log_prior; p.prior_stride = c.prior_stride;
+                p.ori = c.ptr(of); p.index = reinterpret_cast<const int*>(c.ptr(idx)); p.B = B; p.nbins = c.heading_bins; p.r = c.heading_r;
+                p.part = reinterpret_cast<double*>(c.ptr(hpart)); p.bins = reinterpret_cast<unsigned long long*>(c.tickets + boff);
+                p.tickets = c.tickets + toff; p.heading = c.heading; p.hist = c.hist;
+                launch_heading_reduce(p, c.stream);
+            }, 0, 4.0 * B * 262144.0 * 3);
         }
     }
     // the ground / aerial inputs and the 2 x 512 x 512 orientation output are addressed the same way

@@ -418,6 +418,33 @@ void launch_belief_summary(const BeliefSummaryParams& p, hipStream_t s);
 // rows[b][2..4] = (cos, sin, angle_deg) of ori [B][2][n] at index[b] (pose plans without the fused level 1)
 void launch_pose_gather(const float* ori, const int* index, int B, int n, float* rows, hipStream_t s);
 
+// Heading posterior (kernels_heading.hip): the posterior h of pose_argmax_kernel (the same recomputed bits) as a
+// distribution over the orientation field (c, s) = ori [B][2][n].  A cell is valid when c and s are finite and not both zero; its angle is
+// pose_angle_deg(c, s) in [0, 360), its bin (int)(angle * nbins / 360), a result >= nbins wrapping to bin - nbins.  Per query
+//   hist[nbins]   sum of h over the valid cells of each bin (absolute mass), and heading[HEADING_COLS]:
+//   0 M = sum of h over valid cells   1, 2 C = sum h c / M, S = sum h s / M   3 atan2(S, C) in degrees [0, 360), NaN when R == 0
+//   4 R = sqrt(C^2 + S^2)   5 mode bin (first maximal hist value)   6 hist[mode] / M
+//   7 .. 11 columns 0 .. 4 over the window |x - x*| <= r, |y - y*| <= r around the argmax index[b], clipped to the grid.
+// A sample whose (max, 1/sum) is not finite: hist all zero, heading NaN with column 5 = -1.  One launch on a grid (64 chunks, B): the
+// histogram in 2^-52 fixed point (64-bit integer adds: LDS per workgroup, agent scope per query - no order to depend on), M, sum h c
+// and sum h s as float64 in the fixed order of the summary; the last arriver of a sample (ticket) totals, runs the window and writes.
+static constexpr int HEADING_COLS = 12, HEADING_PART = 4, HEADING_MIN_BINS = 4, HEADING_MAX_BINS = 360, HEADING_MAX_R = 32;
+struct HeadingParams {
+    const float* logits;       // [B][512*512]
+    const float* partial;      // [B][64][2] of softmax_partial_kernel (of logits + prior when there is one)
+    const float* prior;        // optional log-prior as PoseArgmaxParams::prior
+    long long prior_stride;
+    const float* ori;          // [B][2][512*512]
+    const int* index;          // [B] argmax of pose_argmax_kernel, an earlier launch (clamped to the map before it is used)
+    int B, nbins, r;           // nbins HEADING_MIN_BINS .. HEADING_MAX_BINS, r 0 .. HEADING_MAX_R: checked by the entry points
+    double* part;              // [B][64][HEADING_PART] float64 hand-off of the chunks' sums
+    unsigned long long* bins;  // [B][HEADING_MAX_BINS] the queries' fixed-point histograms: zero before and after every launch, like ...
+    unsigned* tickets;         // ... the [B] counters
+    float* heading;            // [B][HEADING_COLS]
+    float* hist;               // [B][nbins]
+};
+void launch_heading_reduce(const HeadingParams& p, hipStream_t s);
+
 // Top-K peaks (ccvpe_postprocess_topk / ccvpe_localize_topk).  Grid (64 tiles of 64 x 64, B): peaks of the heatmap
 // under a Chebyshev radius r (value descending, index ascending), the best k per tile handed to the sample's last arriver (ticket),
 // which writes index[b][k] (-1: no peak) and rows[b][k][0..1] - the whole row (-1, 0, 0, 0, 0) for a slot without a peak.

@@ -5,6 +5,7 @@
 // (models.py:628-629), F.normalize(x_ori, p=2, dim=1) (models.py:650), argmax / (cos,sin) lookup /
 // acos-sign rule (train_VIGOR.py:297-311).
 #include "kernels.h"
+#include "tail_shared.h"
 
 #include <algorithm>
 
@@ -80,12 +81,7 @@ void launch_tail_conv(const TailConvParams& p, hipStream_t s) {
 // Softmax over n = 262144 logits per sample, two launches: per-chunk online (max, sum exp) partials,
 // then every block re-derives the sample's (max, sum) from the partials and normalises its chunk.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void combine(float& m, float& s, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    if (mn == -INFINITY) { s = 0.f; return; }   // both sides empty: exp(-inf - -inf) would be NaN
-    s = s * __expf(m - mn) + s2 * __expf(m2 - mn);
-    m = mn;
-}
+// (combine() and softmax_stats(): tail_shared.h)
 
 // PRIOR: the partials of l' = fl32(l + prior), the prior read as float4 beside the logits; everything else - and so
 // every bit for a zero prior - as without it.  A prior excludes pixels with -inf, often whole stretches: a thread that has seen
@@ -118,22 +114,6 @@ __global__ __launch_bounds__(256) void softmax_partial_kernel(const SoftmaxParam
         for (int w = 1; w < 4; ++w) combine(m, s, sm[w], ss[w]);
         p.partial[((size_t)b * p.chunks + ch) * 2 + 0] = m;
         p.partial[((size_t)b * p.chunks + ch) * 2 + 1] = s;
-    }
-}
-
-// the sample's (max, 1 / sum) from its chunk partials, into LDS (gm, gs); the caller meets at a barrier before reading them.  Shared by
-// softmax_final_kernel and pose_argmax_kernel: the same order of combines, so the same bits
-__device__ __forceinline__ void softmax_stats(const float* partial, int b, int chunks, float& gm, float& gs) {
-    if (threadIdx.x < 64) {
-        float m = -INFINITY, s = 0.f;
-        for (int i = threadIdx.x; i < chunks; i += 64)
-            combine(m, s, partial[((size_t)b * chunks + i) * 2], partial[((size_t)b * chunks + i) * 2 + 1]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
-            combine(m, s, m2, s2);
-        }
-        if (threadIdx.x == 0) { gm = m; gs = 1.f / s; }
     }
 }
 
@@ -277,28 +257,7 @@ __device__ __forceinline__ void summ_take(double (&a)[n], float h, int i) {
     if constexpr (n > SM_WIN) a[6] = fma(hd, h > 0.f ? (double)logf(h) : 0.0, a[6]);
 }
 
-// every thread: its sums -> the wave's (all lanes), lane 0 of each wave -> lds[wave][n]; the caller meets at a barrier, then ...
-template <int n>
-__device__ __forceinline__ void summ_wave_to_lds(double (&a)[n], double* lds) {
-#pragma unroll
-    for (int k = 0; k < n; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_xor(a[k], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < n; ++k) lds[(threadIdx.x >> 6) * n + k] = a[k];
-    }
-}
-// ... thread 0: the workgroup's sums, waves in order
-template <int n>
-__device__ __forceinline__ void summ_from_lds(double (&a)[n], const double* lds) {
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-#pragma unroll
-        for (int k = 0; k < n; ++k) a[k] += lds[w * n + k];
-    }
-}
+// (summ_wave_to_lds() and summ_from_lds(), the wave and workgroup steps: tail_shared.h)
 // thread 0 of chunk c: the chunk's sums to the hand-off (agent-scope stores, before ticket_arrive)
 __device__ __forceinline__ void summ_publish(const double (&a)[SM_SUMS], double* part) {
 #pragma unroll

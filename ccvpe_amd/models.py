@@ -254,14 +254,16 @@ class _CVMBase(nn.Module):
             out.matching_score[k] = ms[k].data_ptr()
         return out, (logits, heat, ori, *ms)
 
-    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False, summary=False):
+    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False, summary=False,
+              heading=0):
         """The skeleton forward and the pose forms share: validate and normalise grd and sat - or, sat=None, the cache and tile_index of a
         cached form -, ensure the handle, allocate the results, call ccvpe_<name> under the inputs' device on its current stream, check
         the return code, sync the tuning table.  args(B) holds the method's own argument checks, run after those of the inputs, and
         returns the C arguments between batch and the results; a tensor among them, the log_prior, must be on the inputs' device and is
         passed by pointer, None as a null pointer.  Returns the nine outputs (outputs=True) or rows [B, 5] (k = 0, the argmax forms) /
         [B, k, 5] (k as the method received it: args has checked it), with the summary [B, 16] (the summary forms, whose C functions
-        take a nullable posterior behind it) and the posterior [B, 512, 512] behind them if asked.
+        take a nullable posterior behind it) and the posterior [B, 512, 512] behind them if asked.  heading = a bin count: the heading
+        forms, whose C functions take heading [B, 12] and hist [B, bins] behind rows, then a nullable summary and a nullable posterior.
         Cached forms: ccvpe_<name> takes a nullable tile_index if the name ends in _indexed; the older forms have two entry points each,
         ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it."""
         if sat is not None:
@@ -291,19 +293,35 @@ class _CVMBase(nn.Module):
                 out, res = self._alloc_outputs(B, dev)
                 ptrs = (C.byref(out),)
             else:
-                res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
-                if summary:
-                    res += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
-                if posterior:
-                    res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
-                ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res) + ((None,) if summary and not posterior else ())
+                res, ptrs = self._alloc_rows(B, dev, k, heading, summary, posterior)
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3], *src, B,
                                                        *extra, *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
         self._tuning_sync()
-        return res if outputs or posterior or summary else res[0]
+        return res if outputs or posterior or summary or heading else res[0]
+
+    @staticmethod
+    def _alloc_rows(B: int, dev, k: int, heading: int, summary: bool, posterior: bool):
+        """The results of a pose form and their C arguments: rows [B, 5] or [B, k, 5], then - heading forms - heading [B, 12] and hist
+        [B, heading], then the summary [B, 16] and the posterior [B, 512, 512] if asked.  The summary and heading forms take a null
+        pointer for an optional output that was not asked for."""
+        res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
+        if heading:
+            res += (torch.empty((B, 12), dtype=torch.float32, device=dev), torch.empty((B, heading), dtype=torch.float32, device=dev))
+        ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
+        opt = ()
+        if summary:
+            opt += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
+        elif heading:
+            ptrs += (None,)
+        if posterior:
+            opt += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
+        ptrs += tuple(C.c_void_p(t.data_ptr()) for t in opt)
+        if (summary or heading) and not posterior:
+            ptrs += (None,)
+        return res + opt, ptrs
 
     def forward(self, grd: torch.Tensor, sat: torch.Tensor):
         return self._call("forward", grd, sat, outputs=True)
@@ -581,7 +599,7 @@ class _CVMBase(nn.Module):
         return self._call("localize_prior_cached_indexed", grd, cache=cache, tile_index=tile_index,
                           args=lambda B: self._prior_args(log_prior, B, k, radius), k=k)
 
-    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False):
+    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False, heading=0):
         """postprocess_prior, track_update_logits and postprocess_summary: validate and normalise the forward outputs the caller holds,
         check the prior with args(B) and take k (both as _call's), allocate rows (and the summary, the posterior) and call ccvpe_<name>."""
         if self.training:
@@ -599,18 +617,13 @@ class _CVMBase(nn.Module):
         dev = logits.device
         self._ensure_handle(dev)
         with torch.cuda.device(dev):
-            res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
-            if summary:
-                res += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
-            if posterior:
-                res += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
-            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res) + ((None,) if summary and not posterior else ())
+            res, ptrs = self._alloc_rows(B, dev, k, heading, summary, posterior)
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, *extra,
                                                        *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
-        return res if posterior or summary else res[0]
+        return res if posterior or summary or heading else res[0]
 
     def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
                           ) -> torch.Tensor:
@@ -791,6 +804,45 @@ class _CVMBase(nn.Module):
                                                   C.c_void_p(out.data_ptr()), C.c_void_p(stream))
         _lib.check(rc, "ccvpe_belief_summary")
         return out
+
+    # ---- heading posterior ------------------------------------------------------
+    @classmethod
+    def _heading_args(cls, log_prior, B: int, radius, bins):
+        """(log_prior, radius, bins) of the heading forms -> (tensor or None, prior_stride, radius, bins): the prior and the window radius
+        as the summary forms take them, the bin count in 4..360."""
+        bins = int(bins)
+        if not 4 <= bins <= 360:
+            raise ValueError(f"bins must be in 4..360, got {bins}")
+        return cls._summary_args(log_prior, B, radius) + (bins,)
+
+    def localize_heading(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                         bins: int = 72, summary: bool = False, posterior: bool = False):
+        """The pose and the heading the network believes in: (rows [B, 5], heading [B, 12], hist [B, bins]), with the summary [B, 16]
+        and the posterior [B, 512, 512] behind them if asked.  rows, summary and posterior are localize_summary(grd, sat, log_prior,
+        radius)'s; hist is the posterior's mass per heading bin of 360 / bins degrees (aerial.heading_bin_centres), heading holds the
+        columns aerial.HEADING_FIELDS - mass with a heading, mean cos and sin, mean heading, resultant length, mode bin and its
+        share, and the same over the (2 radius + 1)^2 window around the argmax.  Computes the whole orientation field and adds one
+        launch to localize_prior's.  A query without a finite posterior has heading NaN with mode -1 and an all-zero hist
+        (ccvpe_localize_heading)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        own = self._heading_args(log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
+        return self._call("localize_heading", grd, sat, args=lambda B: own, posterior=posterior, summary=summary, heading=own[3])
+
+    def localize_heading_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                                bins: int = 72, summary: bool = False, posterior: bool = False, tile_index=None):
+        """localize_heading(grd, sat, log_prior, radius, bins, summary, posterior) with the aerial side taken from encode_aerial(sat);
+        tile_index as forward_cached (ccvpe_localize_heading_cached_indexed)."""
+        return self._call("localize_heading_cached_indexed", grd, cache=cache, tile_index=tile_index,
+                          args=lambda B: self._heading_args(log_prior, B, radius, bins), posterior=posterior, summary=summary,
+                          heading=self._heading_args(None, 1, radius, bins)[3])
+
+    def postprocess_heading(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
+                            bins: int = 72, summary: bool = False, posterior: bool = False):
+        """localize_heading from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
+        ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_heading)."""
+        return self._logits_call("postprocess_heading", logits, ori, lambda B: self._heading_args(log_prior, B, radius, bins),
+                                 posterior=posterior, summary=summary, heading=self._heading_args(None, 1, radius, bins)[3])
 
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -385,6 +385,49 @@ int ccvpe_postprocess_summary(ccvpe_handle h, const float* logits, const float* 
  * full forward's heatmap, a tracker belief, any non-negative map. */
 int ccvpe_belief_summary(ccvpe_handle h, const float* belief, int32_t batch, int32_t radius, float* summary, void* stream);
 
+/* Heading posterior: the heading the network believes in, as a distribution.  Per query, over the n = 512 * 512 cells i of the
+ * float32 map h the same call would store as its posterior (h' of the definition above) and the orientation field (c_i, s_i) =
+ * ccvpe_forward's ori [batch][2][n]:
+ *   - a cell is valid when c_i and s_i are finite and not both zero;
+ *   - its angle a_i is the one rows[b][4] would carry for (c_i, s_i): acos(clamp(c, -1, 1)) in degrees, mirrored to (180, 360)
+ *     for s < 0 - a float32 in [0, 360];
+ *   - with nbins bins of width w = 360 / nbins, bin b covers [b w, (b + 1) w); a result >= nbins wraps to b - nbins, -0.0 is bin 0.
+ *     Cells within about 1e-3 degree of an edge may land on either side of it.
+ * `hist` is float32 DEVICE memory [batch][nbins]: hist[b] = sum of h_i over the valid cells of bin b - absolute mass, summed in
+ * 2^-52 fixed point, so no result depends on the order of the additions.  `heading` is float32 DEVICE memory [batch][12]:
+ *     0        M = sum of h_i over valid cells      (against the summary's S0: the mass without a heading)
+ *     1, 2     C = sum h c / M, S = sum h s / M
+ *     3        mean heading atan2(S, C) in degrees [0, 360), evaluated in float64; NaN when R == 0
+ *     4        R = sqrt(C^2 + S^2), the mean resultant length; the circular variance is 1 - R
+ *     5        mode bin as float: the first index of the maximal hist value; -1 for a query without a finite posterior
+ *     6        hist[mode] / M
+ *     7        M_w: M over the window |x - x*| <= radius, |y - y*| <= radius around the argmax, clipped to the grid - the
+ *              window of the summary's columns 9 - 15
+ *     8, 9     C_w, S_w over that window
+ *     10, 11   mean heading and R of the window, by the rules of columns 3 and 4 - the heading of the mode the argmax belongs to
+ * M, sum h c and sum h s are float64 sums in a fixed order: the same inputs give the same bits.  nbins in 4..360, radius in 0..32.
+ * A query without a finite posterior: rows (-1, NaN, ...), heading NaN except column 5 = -1, hist all zero.  M == 0 with a
+ * finite posterior (no valid cell): columns 0 and 7 are 0, the ratios NaN, the mode 0, hist all zero.  rows, summary and posterior
+ * are ccvpe_localize_summary's for the same arguments; summary and posterior may be NULL, log_prior as well.  The pose forms run
+ * plans of their own: the argmax pose plan with the whole orientation field computed into the workspace (the level-1 launch of
+ * the full forward, under its name and tuning entry) and one more launch behind both decoders; the logits form is ccvpe_
+ * postprocess_summary's launches plus that one.  CCVPE_EINVAL, nothing launched, checked before the handle is used: the checks of
+ * the matching summary form (a null summary excepted), a null heading or hist, nbins outside 4..360, and heading or hist equal
+ * to each other or to rows, log_prior, summary, posterior, logits or ori.  ccvpe_postprocess_heading shares the scratch of
+ * ccvpe_postprocess_prior: batch <= 4096, one call in flight per handle. */
+#define CCVPE_HEADING_COLS 12
+#define CCVPE_HEADING_MAX_BINS 360
+int ccvpe_localize_heading(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                           const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading,
+                           float* hist, float* summary, float* posterior, void* stream);
+int ccvpe_localize_heading_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                          int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                          int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading,
+                                          float* hist, float* summary, float* posterior, void* stream);
+int ccvpe_postprocess_heading(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                              int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading, float* hist,
+                              float* summary, float* posterior, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
