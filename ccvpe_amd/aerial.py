@@ -500,3 +500,173 @@ class Tracker:
         if heading is None:
             return rows if summary is None else (rows, summary)
         return ((rows,) if summary is None else (rows, summary)) + tuple(heading)
+
+
+# ---- tracking across rotated or rescaled frames -----------------------------------------------------------------
+# Affine maps are float64 rows (m0..m5): (x, y) -> (m0 x + m1 y + m2, m3 x + m4 y + m5); every helper takes [6] or [B,6] and returns
+# the shape it was given (the broadcast of two).  model.track_predict_affine reads them as OUTPUT pixel index -> SOURCE index position.
+
+def _affine(m, what: str = "matrix") -> np.ndarray:
+    a = np.asarray(m, dtype=np.float64)
+    if a.ndim not in (1, 2) or a.shape[-1] != 6:
+        raise ValueError(f"{what} must be [6] or [B,6], got {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} must be finite")
+    return a
+
+
+def affine_compose(a, b) -> np.ndarray:
+    """The map p -> a(b(p)): b is applied first."""
+    a, b = _affine(a, "a"), _affine(b, "b")
+    a0, a1, a2, a3, a4, a5 = np.moveaxis(a, -1, 0)
+    b0, b1, b2, b3, b4, b5 = np.moveaxis(b, -1, 0)
+    return np.stack([a0 * b0 + a1 * b3, a0 * b1 + a1 * b4, a0 * b2 + a1 * b5 + a2,
+                     a3 * b0 + a4 * b3, a3 * b1 + a4 * b4, a3 * b2 + a4 * b5 + a5], axis=-1)
+
+
+def affine_invert(a) -> np.ndarray:
+    """The inverse map; a singular matrix is refused."""
+    a = _affine(a)
+    a0, a1, a2, a3, a4, a5 = np.moveaxis(a, -1, 0)
+    det = a0 * a4 - a1 * a3
+    if (det == 0).any():
+        raise ValueError("matrix is singular")
+    i0, i1, i3, i4 = a4 / det, -a1 / det, -a3 / det, a0 / det
+    return np.stack([i0, i1, -(i0 * a2 + i1 * a5), i3, i4, -(i3 * a2 + i4 * a5)], axis=-1)
+
+
+def affine_index_form(m_pil) -> np.ndarray:
+    """A Pillow-convention matrix (Image.transform's AFFINE data, ccvpe_preprocess_affine: it acts on the pixel CENTRE (x + 0.5,
+    y + 0.5) and gives a position whose pixel centres are at i + 0.5) as the same map between pixel INDICES: index x -> index
+    position m0 x + m1 y + (m2 + (m0 + m1 - 1) / 2), likewise y."""
+    m = _affine(m_pil).copy()
+    m[..., 2] += 0.5 * (m[..., 0] + m[..., 1] - 1.0)
+    m[..., 5] += 0.5 * (m[..., 3] + m[..., 4] - 1.0)
+    return m
+
+
+def affine_pillow_form(m_index) -> np.ndarray:
+    """The inverse of affine_index_form: an index-coordinate matrix as Pillow AFFINE data."""
+    m = _affine(m_index).copy()
+    m[..., 2] -= 0.5 * (m[..., 0] + m[..., 1] - 1.0)
+    m[..., 5] -= 0.5 * (m[..., 3] + m[..., 4] - 1.0)
+    return m
+
+
+def rigid_matrix(rotation_deg, shift_px, scale=1.0, centre=(255.5, 255.5)) -> np.ndarray:
+    """The OUTPUT -> SOURCE index map (model.track_predict_affine's matrix), float64 [B,6] ([6] when every argument is one value),
+    of a frame change under which the content moves as
+
+        p_new = centre + scale * R (p_old - centre) + shift_px,      R = [[cos a, sin a], [-sin a, cos a]],  a = rotation_deg
+
+    in index coordinates (x right, y down): the content turns by rotation_deg counter-clockwise as displayed, as
+    PIL.Image.rotate(rotation_deg) turns an image - what a viewer sees whose own frame has turned by rotation_deg clockwise -
+    about centre (the default is the middle of the 512 grid), grows by scale and moves by shift_px = (dx, dy).  rotation_deg
+    and scale are numbers or [B], shift_px [2] or [B,2].  Rotation 0 and scale 1 give (1, 0, -dx, 0, 1, -dy), track_predict's shift;
+    multiples of 90 degrees give integer entries (cos and sin are rounded at the 15th decimal, as PIL does)."""
+    scalar = np.ndim(rotation_deg) == 0 and np.ndim(scale) == 0 and np.ndim(shift_px) == 1
+    sh = np.asarray(shift_px, dtype=np.float64).reshape(-1, 2)
+    rot = np.asarray(rotation_deg, dtype=np.float64).reshape(-1)
+    sc = np.asarray(scale, dtype=np.float64).reshape(-1)
+    B = max(sh.shape[0], rot.shape[0], sc.shape[0])
+    for what, v in (("shift_px", sh), ("rotation_deg", rot), ("scale", sc)):
+        if v.shape[0] not in (1, B):
+            raise ValueError(f"{what} must hold 1 or {B} rows, got {v.shape[0]}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"{what} must be finite")
+    if not (sc > 0).all():
+        raise ValueError(f"scale must be positive, got {scale}")
+    cx, cy = (float(v) for v in centre)
+    a = np.radians(rot)
+    cos, sin = np.round(np.cos(a), 15) + 0.0, np.round(np.sin(a), 15) + 0.0
+    m0, m1, m3, m4 = cos / sc, -sin / sc, sin / sc, cos / sc          # R^T / scale
+    dx, dy = sh[:, 0], sh[:, 1]
+    m2 = (cx - m0 * cx - m1 * cy) - (m0 * dx + m1 * dy)
+    m5 = (cy - m3 * cx - m4 * cy) - (m3 * dx + m4 * dy)
+    out = np.stack(np.broadcast_arrays(m0, m1, m2, m3, m4, m5), axis=-1) + np.zeros((B, 6))
+    return out[0] if scalar else out
+
+
+def kitti_crop_to_tile(matrices, tile_hw: Sequence[int]) -> np.ndarray:
+    """kitti_matrices' stage matrices of one sample ([4,6]; [B,4,6] for a batch) and the centre crop (center_crop_box) as ONE
+    index-form matrix ([6] / [B,6]): pixel index of the 512 x 512 crop -> index position on the satellite tile it shows.  Stage k
+    reads stage k - 1 through its matrix, so the crop reads the tile through stage 0 o stage 1 o ... o the crop's offset."""
+    m = np.asarray(matrices, dtype=np.float64)
+    if m.ndim not in (2, 3) or m.shape[-1] != 6:
+        raise ValueError(f"matrices must be [S,6] or [B,S,6], got {m.shape}")
+    top, left = center_crop_box(int(tile_hw[0]), int(tile_hw[1]))
+    total = np.zeros(m.shape[:-2] + (6,)) + np.array([1.0, 0.0, float(left), 0.0, 1.0, float(top)])
+    for k in range(m.shape[-2] - 1, -1, -1):
+        total = affine_compose(m[..., k, :], total)
+    return affine_index_form(total)
+
+
+def kitti_track_matrix(mats_prev, mats_next, tile_hw: Sequence[int], centre_motion_px) -> np.ndarray:
+    """The matrix that carries the belief over the previous frame's crop into the next frame's (model.track_predict_affine):
+    invert(kitti_crop_to_tile(mats_prev)) o translate(centre_motion_px) o kitti_crop_to_tile(mats_next) - a pixel of the next crop
+    -> its position on the next tile -> the same ground point on the previous tile -> its position in the previous crop.
+    mats_prev, mats_next: kitti_matrices' output for the two frames ([4,6] or [B,4,6]); both tiles are tile_hw, north-up and at
+    one scale, and the next tile is centred centre_motion_px = (d col, d row) tile pixels from the previous one ([2] or [B,2])."""
+    mv = np.asarray(centre_motion_px, dtype=np.float64)
+    if mv.shape[-1:] != (2,) or mv.ndim not in (1, 2) or not np.isfinite(mv).all():
+        raise ValueError(f"centre_motion_px must be finite [2] or [B,2], got {mv.shape}")
+    move = np.zeros(mv.shape[:-1] + (6,)) + np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
+    move[..., 2], move[..., 5] = mv[..., 0], mv[..., 1]
+    return affine_compose(affine_invert(kitti_crop_to_tile(mats_prev, tile_hw)),
+                          affine_compose(move, kitti_crop_to_tile(mats_next, tile_hw)))
+
+
+class AffineTracker:
+    """Tracker for frames whose aerial grids differ by more than a translation (KITTI's heading-up tiles, tiles cut at another
+    zoom): holds the posterior map of the last frame (a device tensor [B,512,512]).  step() = model.track_predict_affine (the last
+    posterior resampled into this frame's grid through the caller's matrix, blurred, floored) + the update on this frame's
+    aerial image or cache; the first step has no prior."""
+
+    def __init__(self):
+        self.belief = None    # posterior of the last frame, or None before the first step
+
+    def reset(self) -> None:
+        self.belief = None
+
+    def step(self, model, grd, sat, matrix, taps, floor, summary_radius=None, heading_bins=None, cache=None, tile_index=None):
+        """One frame of B parallel streams.  sat: this frame's aerial images [B,3,512,512], or None with cache / tile_index as
+        model.localize_cached; matrix [B,6] or [6]: this frame's pixel index -> the position in the LAST frame's grid it shows
+        (rigid_matrix, kitti_track_matrix; ignored by the first step); taps, floor: as model.track_predict.  Returns what
+        Tracker.step returns: the rows [B,5]; with summary_radius (rows, summary [B,16]); with heading_bins (heading [B,12], hist
+        [B,heading_bins]) appended - the updates are model.track_update / localize_summary / localize_heading, or their _cached
+        forms beside a cache."""
+        if (sat is None) == (cache is None):
+            raise ValueError("give this frame's aerial side as sat or as cache, one of the two")
+        if sat is not None and tile_index is not None:
+            raise ValueError("tile_index belongs to a cache")
+        B = grd.shape[0]
+        prior = None
+        if self.belief is not None:
+            if self.belief.shape[0] != B:
+                raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
+            prior = model.track_predict_affine(self.belief, matrix, taps, floor)
+        radius = 8 if summary_radius is None else summary_radius
+        summary = None
+        heading = None
+        if heading_bins is not None:
+            if cache is None:
+                res = model.localize_heading(grd, sat, prior, radius=radius, bins=heading_bins, summary=summary_radius is not None,
+                                             posterior=True)
+            else:
+                res = model.localize_heading_cached(grd, cache, prior, radius=radius, bins=heading_bins,
+                                                    summary=summary_radius is not None, posterior=True, tile_index=tile_index)
+            rows, heading, self.belief = res[0], res[1:3], res[-1]
+            summary = res[3] if summary_radius is not None else None
+        elif summary_radius is None:
+            if cache is None:
+                rows, self.belief = model.track_update(grd, sat, prior)
+            else:
+                rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
+        elif cache is None:
+            rows, summary, self.belief = model.localize_summary(grd, sat, prior, radius=summary_radius, posterior=True)
+        else:
+            rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
+                                                                       tile_index=tile_index)
+        if heading is None:
+            return rows if summary is None else (rows, summary)
+        return ((rows,) if summary is None else (rows, summary)) + tuple(heading)

@@ -1009,6 +1009,30 @@ int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, cons
     return launch_status("track_predict launch");
 }
 
+// The predict step under an affine map per query: always one launch of track_predict_affine_kernel - a pure translation
+// is not re-routed to track_predict_kernel; choosing is the caller's business.
+int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batch, const double* matrix, const float* taps,
+                               int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream) {
+    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
+    if (!matrix) return ccvpe_fail(CCVPE_EINVAL, "null matrix");
+    if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
+    if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
+    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
+    if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
+    if (taps_stride != 0 && taps_stride != radius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
+                          taps_stride);
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (log_prior == belief) return ccvpe_fail(CCVPE_EINVAL, "log_prior must not alias belief");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackPredictAffineParams p{};
+    p.belief = belief; p.matrix = matrix; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
+    p.log_prior = log_prior; p.B = batch;
+    launch_track_predict_affine(p, (hipStream_t)stream);
+    return launch_status("track_predict_affine launch");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Posterior summary: the argmax pose plans with the summary row as one more output of pose.argmax (plans of their own,
 // PlanKey::summary, for the float64 hand-off in the workspace; the launches, names and tuning entries of the pose plans), the logits

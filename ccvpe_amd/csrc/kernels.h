@@ -549,6 +549,22 @@ struct TrackPredictParams {
 };
 void launch_track_predict(const TrackPredictParams& p, hipStream_t s);
 
+// The same step under an affine map per query (ccvpe_track_predict_affine, DESIGN.md 4.14, kernels_track_affine.hip): output pixel
+// index (x, y) reads the belief at index position (m0 x + m1 y + m2, m3 x + m4 y + m5), float64, bilinear weights from fractions
+// rounded once to float32, times (float)|m0 m4 - m1 m3|; then the blur, the floor and the logarithm of launch_track_predict.  One
+// launch, grid (256 tiles of 32 x 32, B).
+struct TrackPredictAffineParams {
+    const float* belief;       // [B][512*512]
+    const double* matrix;      // [B][6] output index -> source index position
+    const float* taps;         // [radius + 1] one-sided weights, one set (taps_stride 0) or one per query (taps_stride radius + 1)
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0, added before the logarithm
+    float* log_prior;          // [B][512*512], not aliasing belief
+    int B;
+};
+void launch_track_predict_affine(const TrackPredictAffineParams& p, hipStream_t s);
+
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call
 size_t postprocess_scratch_bytes(int B);            // partial (max, index) pairs + one ticket counter per sample (the counters zero before the first launch)

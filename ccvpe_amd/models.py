@@ -736,6 +736,71 @@ class _CVMBase(nn.Module):
         _lib.check(rc, "ccvpe_track_predict")
         return out
 
+    def track_predict_affine(self, belief: torch.Tensor, matrix, taps, floor) -> torch.Tensor:
+        """track_predict under an affine map per query: output pixel index (x, y) reads the belief, extended by zero,
+        at index position (m0 x + m1 y + m2, m3 x + m4 y + m5) with bilinear weights, times |m0 m4 - m1 m3|; then the blur, the floor
+        and the logarithm of track_predict (the definition in include/ccvpe.h, ccvpe_track_predict_affine).  matrix is [B,6] or [6]
+        (one map for every query), OUTPUT index -> SOURCE index position (aerial.rigid_matrix, aerial.kitti_track_matrix;
+        aerial.affine_index_form converts a Pillow-convention matrix): host data, which must be finite, or a float64 tensor on the
+        belief's device, which is not looked at (non-finite entries there may give NaN, never a read outside the belief).  belief,
+        taps and floor as in track_predict.  One launch, always the affine kernel: (1, 0, -dx, 0, 1, -dy) is track_predict's shift
+        (dx, dy), bit for bit at integer shifts."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(belief, torch.Tensor):
+            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
+        shape = tuple(belief.shape)
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
+                                                                                       and shape[2:] == spec.OUT_HW):
+            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
+        if belief.dtype != torch.float32:
+            raise ValueError(f"belief must be float32, got {belief.dtype}")
+        if not belief.is_contiguous():
+            raise ValueError("belief must be contiguous")
+        B = shape[0]
+        if B > 4096:
+            raise ValueError(f"belief holds {B} maps, at most 4096 per call")
+        on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
+        if on_device:
+            mt = matrix.detach()
+            if mt.dtype != torch.float64:
+                raise ValueError(f"matrix on the device must be float64, got {mt.dtype}")
+        else:
+            mt = torch.as_tensor(np.asarray(matrix.detach() if isinstance(matrix, torch.Tensor) else matrix, dtype=np.float64))
+        if tuple(mt.shape) not in ((6,), (B, 6)):
+            raise ValueError(f"matrix must be [6] or [{B}, 6], got {tuple(mt.shape)}")
+        if not on_device and not bool(torch.isfinite(mt).all()):
+            raise ValueError("matrix must be finite")
+        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
+        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
+            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
+        radius = int(tshape[-1]) - 1
+        if radius > 32:
+            raise ValueError(f"taps give radius {radius}, must be in 0..32")
+        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
+        if fshape == () and not float(floor) >= 0.0:
+            raise ValueError(f"floor must be >= 0, got {floor}")
+        dev = belief.device
+        host = torch.device("cpu")
+        # shapes and values first (so that they are refused without a device), then the copies
+        tp = self._track_vec(taps, "taps", tshape, host if not belief.is_cuda else dev)
+        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
+              else self._track_vec(floor, "floor", (B,), dev))
+        if not belief.is_cuda:
+            raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+        if on_device and mt.device != dev:
+            raise ValueError(f"matrix is on {mt.device}, belief on {dev}")
+        mt = mt.expand(B, 6).to(dev).contiguous()
+        self._ensure_handle(dev)
+        out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = _lib.load().ccvpe_track_predict_affine(self._handle, C.c_void_p(belief.data_ptr()), B, C.c_void_p(mt.data_ptr()),
+                                                        C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
+                                                        C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_track_predict_affine")
+        return out
+
     # ---- posterior summary (DESIGN.md 4.12) ------------------------------------------------------
     @classmethod
     def _summary_args(cls, log_prior, B: int, radius):

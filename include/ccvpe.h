@@ -342,6 +342,27 @@ int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* 
  * log_prior == belief. */
 int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps,
                         int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream);
+/* Predict under an affine map: the belief of a frame whose grid is a rotated, rescaled or sheared view of this frame's (KITTI's
+ * heading-up tiles, a zoom change).  matrix is float64 DEVICE memory [batch][6], M = (m0..m5) per query; the other arguments are
+ * ccvpe_track_predict's.  M maps an OUTPUT pixel to the SOURCE position it reads - the direction of Pillow's AFFINE data and of
+ * ccvpe_preprocess_affine - but in INDEX coordinates: belief[j][i] sits at position (i, j), not at Pillow's pixel centre
+ * (i + 0.5, j + 0.5).  Per query, with the belief extended by zero outside its grid, on the infinite plane, for integer x, y
+ *     (sx, sy)  = (m0 x + m1 y + m2, m3 x + m4 y + m5)                          float64
+ *     s(x, y)   = |m0 m4 - m1 m3| * bilinear sample of the belief at (sx, sy)
+ *     c         = s convolved with t[|i|], i = -radius..radius, along x, then along y
+ *     out(x, y) = logf(c(x, y) + floor)                                          for the 512 x 512 window only
+ * ccvpe_track_predict is the case M = (1, 0, -dx, 0, 1, -dy), and for integer dx, dy the two give the same bits.  |det|, rounded
+ * once to float32, keeps the mass of a belief that stays inside the window when the map changes scale; det = 0 gives logf(floor)
+ * everywhere.  Arithmetic: coordinates float64; ix = floor(sx); the fraction (float)(sx - ix) is rounded once to float32, the
+ * weights are 1.f - f and f, the sample is a float32 sum of non-negative terms, a fraction of exactly 0 weighs the one source
+ * pixel with exactly 1; a pass is 2 radius + 1 fused multiply-adds.  c is within (4 radius + 12) * 2^-24 * c + 2^-38 * max(belief)
+ * of the exact value: the first term counts the roundings of non-negative terms, the second covers what a coordinate rounding of
+ * 2^-42 px can move a sample by (for |det| <= 4 and positions within +-1024).  Non-finite matrix entries may give NaN, but no launch reads outside its tensors whatever the
+ * inputs hold: the integer parts are clamped to +-2048 (NaN included) before they are converted and every read is checked against
+ * the grid.  One launch; a pure translation is NOT re-routed to ccvpe_track_predict.  CCVPE_EINVAL as ccvpe_track_predict (a null
+ * matrix for a null shift). */
+int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batch, const double* matrix, const float* taps,
+                               int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream);
 
 /* Posterior summary: how sure the pose is.  `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
  * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
