@@ -42,6 +42,7 @@ Switches read_switches() {
     if (const char* e = getenv("CCVPE_FUSE_MBCONV")) s.fuse_mbconv = std::atoi(e);
     if (const char* e = getenv("CCVPE_FUSE_L1")) s.fuse_level1 = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_L1_TILE")) s.l1_tile = std::atoi(e);
+    if (const char* e = getenv("CCVPE_COMPOSE_L6")) s.compose_l6 = std::atoi(e);
     if (const char* e = getenv("CCVPE_WINOGRAD")) s.wino = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_GRAPH")) s.graph_mode = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_STREAMS")) s.two_streams = std::atoi(e) >= 2;
@@ -150,6 +151,7 @@ int ccvpe_destroy(ccvpe_handle h) {
     if (!h) return 0;
     (void)hipSetDevice(h->cfg.device);
     for (void* p : h->dev_allocs) (void)hipFree(p);
+    release_level6(h);
     if (h->arena) (void)hipFree(h->arena);
     for (auto* buf : {&h->post_scratch, &h->topk_scratch, &h->prior_scratch}) if (buf->ptr) (void)hipFree(buf->ptr);
     h->plans.clear();

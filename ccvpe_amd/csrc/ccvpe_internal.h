@@ -121,6 +121,9 @@ struct Switches {
     int fuse_mbconv = 1;                  // CCVPE_FUSE_MBCONV: 0 never, 1 where measured profitable (3x3 blocks), 2 every supported block
     bool fuse_level1 = true;              // CCVPE_FUSE_L1=0 falls back to deconv / conv / tail launches
     int l1_tile = 1;                      // CCVPE_L1_TILE=0: the fused last level on 16 x 16 output tiles (1: 32 wide x 16 high)
+    // CCVPE_COMPOSE_L6: unset = fp32 plans of at least LEVEL6_AUTO_MIN_BATCH samples run decoder level 6 composed, 0 = never
+    // (deconv, conv_a and its reduction as before), 1 = every fp32 plan, as F(4x4,2x2); 2 = every fp32 plan, as F(2x2,2x2) (for A/B runs)
+    std::optional<int> compose_l6;
     // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
     // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
     bool wino = true;
@@ -219,7 +222,21 @@ struct DecoderW {
     float *l1_wc = nullptr, *l1_ws = nullptr, *l1_bc = nullptr;   // composed deconv + conv_a weights, score k-step, bias table (Level1Params)
     int l1_cx = 0, l1_cxp = 0, l1_c0 = 0, l1_ng = 0, l1_score = 0;
 };
+// Composed level 6 (kernels_level6.hip): derived from the packed weights of deconv[0] and conva[0] by ensure_level6, on the first plan
+// that runs the composed path - never part of a packed-weight file (~0.35 GB per decoder)
+struct Level6W {
+    float* wc = nullptr;          // [4 P][Npad][Kc]
+    float* bc = nullptr;          // [9][N]
+    PackedConv skip;              // conv6.0's skip half (columns 1024 .. 1344) as a 3x3 convolution of its own, zero bias
+    int K = 0, Kc = 0, N = 0, Npad = 0;
+};
+static constexpr int LEVEL6_AUTO_MIN_BATCH = 8;   // the smallest batch at which the composed path measured faster (8, 16, 32 tried)
 struct ccvpe_handle_s;
+struct DecoderW;
+// sizes of a decoder's composed level 6 from its packed descriptors (no device work); != 0: these weights cannot be composed
+int level6_shape(const ccvpe_handle_s* h, const DecoderW& d, const struct DecLevel& l, int& K, int& Kc, int& N, int& Npad);
+int ensure_level6(ccvpe_handle_s* h, int wm);   // 0, or an error code; wm = 4 or 2
+void release_level6(ccvpe_handle_s* h);
 // the fused level's weights from the reference's layouts (ccvpe_weights.hip; the plan and ccvpe_op_level1 share them)
 int compose_level1(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& wa,
                    const std::vector<float>& ba, int cin, int nscore);
@@ -368,6 +385,7 @@ struct Plan {
     size_t ticket_words = 0;
     unsigned* tickets = nullptr;
     size_t alloc_tickets(size_t n) { const size_t o = ticket_words; ticket_words += (n + 15) & ~(size_t)15; return o; }
+    int l6_wm = 0;                // composed level 6: the Winograd form its launches run (0: the three launches); get_plan derives the weights
     bool tiles_checked = false;   // the first issue compared every tiled launch with its plan entry (ccvpe_api.hip: check_issued_tile)
     // Two-stream execution: the aerial encoder and the orientation decoder are issued on a second stream, so the
     // ramp-up / drain of the ~330 short kernels of one chain is filled by the other chain.  Dependencies come from
@@ -550,6 +568,10 @@ struct ccvpe_handle_s {
     float* grd_wh[6] = {nullptr};
     float grd_b2[6] = {0};
     DecoderW loc, ori;
+    Level6W l6[2];                // loc, ori (ensure_level6)
+    int l6_wm = 0;                // the Winograd form l6 was derived for (0: not derived)
+    std::vector<void*> l6_allocs;
+    bool l6_failed = false;       // the derivation failed once (out of memory): plans under the automatic rule keep the three launches
     std::vector<std::unique_ptr<Plan>> plans;
     Plan* last_plan = nullptr;    // plan of the most recent forward (ccvpe_debug_dump_plan)
     float* snap[2] = {nullptr, nullptr};   // CCVPE_DIAG_SNAP: the named launch's tensors before / after it

@@ -391,6 +391,30 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         // consumers' K loops carry no fp32->bf16 conversion; level 1 (j == 5) feeds the fp32 tail and stays fp32
         if (h->cfg.reserved[0] == 1 && j < 5 && h->sw.split_planes) { loc_cat[j].split = true; ori_cat[j].split = true; }
     }
+    // Level 6 composed (kernels_level6.hip): fp32 plans on a handle with weights; automatic from LEVEL6_AUTO_MIN_BATCH
+    // samples (batch-1 plans keep the three launches and their launch count), CCVPE_COMPOSE_L6 = 0 / 1 / 2 never / always / always as
+    // F(2x2,2x2).  The level-6 concat buffers are then never written: block 15 keeps its own dense tensor only.  Only the shapes are
+    // needed here (level6_shape: no device work, so a size query stays one); get_plan derives the weights before the plan first runs,
+    // and where that fails under the automatic rule it builds the plan again with the three launches (h->l6_failed).
+    const bool l6_forced = h->sw.compose_l6 && (*h->sw.compose_l6 == 1 || *h->sw.compose_l6 == 2);
+    int l6_wm = !h->finalized || h->cfg.reserved[0] != 0 || !h->sw.wino ? 0
+                : h->sw.compose_l6 ? (*h->sw.compose_l6 == 1 ? 4 : *h->sw.compose_l6 == 2 ? 2 : 0)
+                : (B >= LEVEL6_AUTO_MIN_BATCH && !h->l6_failed) ? 4 : 0;
+    Level6Params l6p[2] = {};   // loc, ori: the sizes of the composed launches
+    if (l6_wm) {
+        bool ok = true;
+        for (int d = 0; d < 2; ++d) {
+            Level6Params& q = l6p[d];
+            q.wm = l6_wm; q.B = B;
+            ok = ok && level6_shape(h, d ? h->ori : h->loc, d ? vs.ori[0] : vs.loc[0], q.K, q.Kc, q.N, q.Npad) == 0;
+            q.R = level6_rows(B, l6_wm, &q.bm);
+            ok = ok && level6_supported(q) && q.K == (d ? rpad + D : loc_in[0].C);
+        }
+        if (!ok && l6_forced) return ccvpe_fail(CCVPE_ESTATE, "composed level 6: the packed weights do not fit the plan's level-6 inputs");
+        if (!ok) l6_wm = 0;
+    }
+    pl.l6_wm = l6_wm;
+    Tensor skip15;   // composed level 6: sat_block15's dense tensor [B, 16, 16, 320]
     ori_in6 = pl.alloc(B, 8, 8, rpad + D);
     pl.taps["ori_in6"] = {ori_in6, 0, ori_in6.C};   // (read by debug handles only, like every tap: [rfull scores | pad to rpad | D])
 
@@ -403,11 +427,14 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         td[t].t[0] = loc_cat[t]; td[t].coff[0] = deconv_width(vs.loc[t], h->sw.pad_concat);
         td[t].t[1] = ori_cat[t]; td[t].coff[1] = deconv_width(vs.ori[t], h->sw.pad_concat);
     }
+    if (l6_wm) td[0].n = 0;
     size_t coff[6];
     cache_layout(vs, B, coff);
     if (!cached) {
         plan_encoder(h, pl, h->sat_enc, false, B, CCVPE_SAT_HW, CCVPE_SAT_HW, false, td, senc, "sat");
+        skip15 = senc.tap[TAP_BLOCK[0]];
     } else {
+        if (l6_wm) skip15 = pl.alloc(B, 16, 16, TAP_C[0]);
         // The six launches that read the cache.  Indexed calls (Ctx::tile_index set) run the same plan with a gather in their place:
         // the cache then holds n_tiles samples, so each section starts at its one-sample offset times n_tiles, and sample b reads
         // tile tile_index[b].  The indices go by value in the launch arguments - safe because cached plans are never captured
@@ -420,6 +447,16 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             const size_t src_off = coff[t + 1], src_off1 = one[t + 1];
             const int C = TAP_C[t], hw = TAP_HW[t];
             const long long P = (long long)B * TAP_HW[t];
+            if (t == 0 && l6_wm) {   // composed level 6: one dense copy instead of the two concat slices
+                const Tensor sk = skip15;
+                pl.add("sat.cached_tap" + std::to_string(TAP_BLOCK[t]), {sk}, [=](const Ctx& c) {
+                    if (c.tile_index)
+                        launch_gather_channels(c.cache_in + src_off1 * c.n_tiles, C, hw, c.tile_index, B, c.dst(sk), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
+                    else
+                        launch_scatter_channels(c.cache_in + src_off, C, P, c.dst(sk), Dst{nullptr, 0, 0, 0, 0}, 1, c.stream);
+                }, 0, 4.0 * P * C * 2);
+                continue;
+            }
             pl.add("sat.cached_tap" + std::to_string(TAP_BLOCK[t]), {lc, oc}, [=](const Ctx& c) {
                 if (c.tile_index)
                     launch_gather_channels(c.cache_in + src_off1 * c.n_tiles, C, hw, c.tile_index, B, c.dst(lc, lcoff), c.dst(oc, ocoff), 2, c.stream);
@@ -472,33 +509,69 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     auto plan_level = [&](const DecoderW& dw, const DecLevel* lv, int j, Tensor din, Tensor cat, const std::string& tag) -> Tensor {
         const int hin = 8 << j, hout = hin * 2;
         const DecLevel& l = lv[j];
-        {
-            const PackedConv* pc = &dw.deconv[j];
-            const int cout = deconv_width(l, h->sw.pad_concat);   // (columns past l.dout: zero weights and biases, written as zeros)
-            pl.add_conv(tag + ".deconv", {din, cat}, B * hin * hin, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
-                ConvParams p = conv_params(*pc, c.ptr(din), din.C, B, hin, hin, hin, hin, 1, 0, 0, ACT_NONE);
-                p.mode = MODE_DECONV; p.deconv_cout = cout;
-                p.dst[0] = c.dst(cat); p.ndst = 1;
-                c.launch_conv(p, tile);
-            }, 2.0 * B * hin * hin * (double)l.din * 4 * l.dout, 4.0 * B * hin * hin * ((double)din.C + 4.0 * l.dout));
-            pl.ops.back().is_pw = !din.split;
-            pl.ops.back().proj_ok = pc->proj != nullptr && !din.split && h->cfg.reserved[0] == 0;
-        }
         Tensor mid = pl.alloc(B, hout, hout, l.mid);
-        mid.split = cat.split;   // bf16x3 mode: conv_a -> conv_b hand-off stays in split bf16 form
-        {
-            const PackedConv* pc = &dw.conva[j];
-            pl.add_conv(tag + ".conv_a", {cat, mid}, B * hout * hout, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
-                ConvParams p = conv_params(*pc, c.ptr(cat), cat.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_RELU);
-                p.in_split = cat.split; p.in_plane_bytes = (unsigned)(cat.numel() * 2);
-                p.dst[0] = c.dst(mid); p.ndst = 1;
-                c.launch_conv(p, tile);
-            }, 2.0 * B * hout * hout * 9.0 * cat.C * l.mid, 4.0 * B * hout * hout * ((double)cat.C + l.mid));
-            pl.ops.back().bf16x3_only = cat.split;
-            pl.ops.back().conv_cin = cat.C;
-            pl.ops.back().wino_ok = pc->wino != nullptr && !cat.split && h->sw.wino && h->cfg.reserved[0] == 0;
-            pl.ops.back().wino4_ok = pl.ops.back().wino_ok && pc->wino4 != nullptr;
-            pl.ops.back().wino4x_ok = pl.ops.back().wino_ok && pc->wino4x != nullptr;
+        if (j == 0 && l6_wm) {
+            // transform, grouped GEMM, the skip half as a 3x3 convolution of its own (a tiled launch: the tuner picks its tile and
+            // split), combine (output transform + skip half + border-case bias + ReLU)
+            const Level6W* w6 = &h->l6[&dw == &h->ori ? 1 : 0];   // filled by ensure_level6 before the plan first runs: read at launch
+            const Level6Params lp = l6p[&dw == &h->ori ? 1 : 0];
+            const int G = 4 * level6_positions(l6_wm);
+            Tensor V = pl.alloc(G, 1, lp.R, lp.Kc), Mp = pl.alloc(G, 1, lp.R, lp.N), sk = pl.alloc(B, hout, hout, l.mid);
+            const Tensor s15 = skip15;
+            pl.add(tag + ".l6_transform", {din, V}, [=](const Ctx& c) {
+                Level6Params q = lp; q.x = c.ptr(din); q.v = c.ptr(V);
+                launch_level6_transform(q, c.stream);
+            }, 0.0, 4.0 * ((double)din.numel() + (double)V.numel()));
+            pl.add(tag + ".l6_gemm", {V, Mp}, [=](const Ctx& c) {
+                Level6Params q = lp; q.v = c.ptr(V); q.wc = w6->wc; q.mp = c.ptr(Mp);
+                launch_level6_gemm(q, c.stream);
+            }, 2.0 * G * lp.R * (double)lp.N * lp.Kc, 4.0 * ((double)V.numel() + (double)G * lp.Npad * lp.Kc + (double)Mp.numel()));
+            {
+                // the skip layer's packed forms exist once ensure_level6 has run; its GEMM shape is known now (N, 9 taps of l.skip channels)
+                const PackedConv* pc = &w6->skip;
+                pl.add_conv(tag + ".conv_skip", {s15, sk}, B * hout * hout, lp.N, round_up(9 * l.skip, 32), [=](const Ctx& c, int tile) {
+                    ConvParams p = conv_params(*pc, c.ptr(s15), s15.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_NONE);
+                    p.dst[0] = c.dst(sk); p.ndst = 1;
+                    c.launch_conv(p, tile);
+                }, 2.0 * B * hout * hout * 9.0 * s15.C * l.mid, 4.0 * B * hout * hout * ((double)s15.C + l.mid));
+                pl.ops.back().conv_cin = s15.C;
+                // (what pack_conv packs for a 3x3 layer of these sizes, pack_conv's own conditions: the tuning key is made from them)
+                pl.ops.back().wino_ok = l.skip % 8 == 0;
+                pl.ops.back().wino4_ok = pl.ops.back().wino_ok && lp.N >= h->sw.wino4_min_n && !h->sw.no_wino4;
+                pl.ops.back().wino4x_ok = pl.ops.back().wino_ok && lp.N >= 24 && conv_wino4x_config(lp.N) >= 0 && !h->sw.no_wino4x;
+            }
+            pl.add(tag + ".l6_combine", {Mp, sk, mid}, [=](const Ctx& c) {
+                Level6Params q = lp; q.mp = c.ptr(Mp); q.skip = c.ptr(sk); q.bc = w6->bc; q.out = c.ptr(mid);
+                launch_level6_combine(q, c.stream);
+            }, 0.0, 4.0 * ((double)Mp.numel() + 2.0 * (double)mid.numel()));
+        } else {
+            {
+                const PackedConv* pc = &dw.deconv[j];
+                const int cout = deconv_width(l, h->sw.pad_concat);   // (columns past l.dout: zero weights and biases, written as zeros)
+                pl.add_conv(tag + ".deconv", {din, cat}, B * hin * hin, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
+                    ConvParams p = conv_params(*pc, c.ptr(din), din.C, B, hin, hin, hin, hin, 1, 0, 0, ACT_NONE);
+                    p.mode = MODE_DECONV; p.deconv_cout = cout;
+                    p.dst[0] = c.dst(cat); p.ndst = 1;
+                    c.launch_conv(p, tile);
+                }, 2.0 * B * hin * hin * (double)l.din * 4 * l.dout, 4.0 * B * hin * hin * ((double)din.C + 4.0 * l.dout));
+                pl.ops.back().is_pw = !din.split;
+                pl.ops.back().proj_ok = pc->proj != nullptr && !din.split && h->cfg.reserved[0] == 0;
+            }
+            mid.split = cat.split;   // bf16x3 mode: conv_a -> conv_b hand-off stays in split bf16 form
+            {
+                const PackedConv* pc = &dw.conva[j];
+                pl.add_conv(tag + ".conv_a", {cat, mid}, B * hout * hout, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
+                    ConvParams p = conv_params(*pc, c.ptr(cat), cat.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_RELU);
+                    p.in_split = cat.split; p.in_plane_bytes = (unsigned)(cat.numel() * 2);
+                    p.dst[0] = c.dst(mid); p.ndst = 1;
+                    c.launch_conv(p, tile);
+                }, 2.0 * B * hout * hout * 9.0 * cat.C * l.mid, 4.0 * B * hout * hout * ((double)cat.C + l.mid));
+                pl.ops.back().bf16x3_only = cat.split;
+                pl.ops.back().conv_cin = cat.C;
+                pl.ops.back().wino_ok = pc->wino != nullptr && !cat.split && h->sw.wino && h->cfg.reserved[0] == 0;
+                pl.ops.back().wino4_ok = pl.ops.back().wino_ok && pc->wino4 != nullptr;
+                pl.ops.back().wino4x_ok = pl.ops.back().wino_ok && pc->wino4x != nullptr;
+            }
         }
         if (j == 5) return mid;   // tail conv handled by the caller
         Tensor o = pl.alloc(B, hout, hout, l.out);

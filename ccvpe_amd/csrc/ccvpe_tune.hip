@@ -205,6 +205,15 @@ int get_plan(ccvpe_handle_s* h, const PlanKey& key, Plan** out) {
     auto pl = std::make_unique<Plan>();
     int rc = build_plan(h, *pl, key);
     if (rc) return rc;
+    // composed level 6: its weights are derived when the first plan that runs them is made (ensure_level6).  Under the automatic rule a
+    // failed derivation (out of device memory) is not an error: this and every later plan keep the three launches.
+    if (pl->l6_wm && (rc = ensure_level6(h, pl->l6_wm)) != 0) {
+        if (h->sw.compose_l6) return rc;
+        (void)hipGetLastError();
+        h->l6_failed = true;
+        pl = std::make_unique<Plan>();
+        if ((rc = build_plan(h, *pl, key))) return rc;
+    }
     if (pl->total > h->arena_floats) {
         // growing the arena is the only synchronising step; it happens on the first call per shape
         HIPCHK(hipDeviceSynchronize());

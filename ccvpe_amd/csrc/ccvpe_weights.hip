@@ -348,6 +348,110 @@ static int build_decoder(ccvpe_handle_s* h, DecoderW& d, const DecLevel* lv, con
     return 0;
 }
 
+// ---- composed decoder level 6 (kernels_level6.hip) ---------------------------------------------------------------
+// Derived from the handle's PACKED weights (the state_dict is gone after ccvpe_finalize_weights and was never there after
+// ccvpe_load_packed), on the first plan that runs the composed path: the composed Winograd-domain weights by two device launches in
+// double (~30 G multiply-adds per VIGOR decoder), the border-case bias table and the skip half's own 3x3 layer on the host.  The
+// buffers live in h->l6_allocs, outside dev_allocs: ccvpe_save_packed never writes them.
+void release_level6(ccvpe_handle_s* h) {
+    for (void* p : h->l6_allocs) (void)hipFree(p);
+    h->l6_allocs.clear();
+    h->l6[0] = Level6W{}; h->l6[1] = Level6W{};
+    h->l6_wm = 0;
+}
+
+int level6_shape(const ccvpe_handle_s* h, const DecoderW& d, const DecLevel& l, int& K, int& Kc, int& N, int& Npad) {
+    const PackedConv& dc = d.deconv[0];
+    const PackedConv& ac = d.conva[0];
+    const int cw = deconv_width(l, h->sw.pad_concat);
+    if (!dc.w || !ac.w || ac.cinp != cw + l.skip || dc.N != 4 * cw || l.dout % 8 || dc.cinp % 4 || ac.N % 4 || l.skip % 8) return -1;
+    K = dc.cinp; Kc = round_up(K, 32); N = ac.N; Npad = round_up(N, 128);
+    return 0;
+}
+
+// While alive, what upload / pack_conv allocate lands in h->l6_allocs instead of h->dev_allocs (whose buffers ccvpe_save_packed writes):
+// the handle's own list is set aside and put back by the destructor, on every path out of the scope.
+struct Level6AllocScope {
+    ccvpe_handle_s* h;
+    std::vector<void*> allocs;
+    std::vector<size_t> bytes;
+    explicit Level6AllocScope(ccvpe_handle_s* h_) : h(h_) { allocs.swap(h->dev_allocs); bytes.swap(h->dev_alloc_bytes); }
+    ~Level6AllocScope() {
+        h->l6_allocs.insert(h->l6_allocs.end(), h->dev_allocs.begin(), h->dev_allocs.end());
+        h->dev_allocs.swap(allocs); h->dev_alloc_bytes.swap(bytes);
+    }
+    Level6AllocScope(const Level6AllocScope&) = delete;
+    Level6AllocScope& operator=(const Level6AllocScope&) = delete;
+};
+
+static int derive_level6(ccvpe_handle_s* h, Level6W& o, const DecoderW& d, const DecLevel& l, int wm) {
+    const PackedConv& dc = d.deconv[0];
+    const PackedConv& ac = d.conva[0];
+    if (level6_shape(h, d, l, o.K, o.Kc, o.N, o.Npad)) return ccvpe_fail(CCVPE_ESTATE, "level 6 cannot be composed from these packed weights");
+    const int cw = deconv_width(l, h->sw.pad_concat), cinw = cw + l.skip, N = ac.N;
+    // host copies of conv6.0 (skip columns, bias table) and the two bias vectors
+    const size_t arows = (size_t)round_up(N, conv_igemm_npad());
+    std::vector<float> aw(arows * ac.Kpad), ba(N), bd(4 * cw);
+    HIPCHK(hipMemcpy(aw.data(), ac.w, aw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ba.data(), ac.bias, ba.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(bd.data(), dc.bias, bd.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const auto wa = [&](int n, int t, int c) { return aw[(size_t)n * ac.Kpad + conv_igemm_k_index(cinw, 9, t, c)]; };
+    // bc[case][n] = ba[n] + sum over in-image taps of Wa[n][.][tap] . bd (compose_level1)
+    std::vector<double> tapsum((size_t)9 * N, 0.0);
+    for (int n = 0; n < N; ++n)
+        for (int t = 0; t < 9; ++t) {
+            double acc = 0.0;
+            for (int m = 0; m < l.dout; ++m) acc += (double)wa(n, t, m) * (double)bd[m];
+            tapsum[(size_t)t * N + n] = acc;
+        }
+    std::vector<float> bc((size_t)9 * N);
+    for (int rcase = 0; rcase < 3; ++rcase)
+        for (int ccase = 0; ccase < 3; ++ccase)
+            for (int n = 0; n < N; ++n) {
+                double acc = ba[n];
+                for (int ky = 0; ky < 3; ++ky)
+                    for (int kx = 0; kx < 3; ++kx) {
+                        if ((rcase == 1 && ky == 0) || (rcase == 2 && ky == 2) || (ccase == 1 && kx == 0) || (ccase == 2 && kx == 2)) continue;
+                        acc += tapsum[(size_t)(ky * 3 + kx) * N + n];
+                    }
+                bc[(size_t)(rcase * 3 + ccase) * N + n] = (float)acc;
+            }
+    {
+        Level6AllocScope scope(h);
+        if (int rc = upload(h, bc, &o.bc)) return rc;
+        if (int rc = pack_conv(h, o.skip, N, 9, l.skip, l.skip, identity_map(l.skip), [&](int n, int t, int c) { return wa(n, t, cw + c); },
+                               std::vector<float>(N, 0.f), 3, 3)) return rc;
+    }
+    // the composed weights
+    const int P = level6_positions(wm);
+    const size_t wc_bytes = (size_t)4 * P * o.Npad * o.Kc * sizeof(float), w2_bytes = (size_t)16 * N * o.Kc * sizeof(double);
+    void *wc = nullptr, *w2 = nullptr;
+    HIPCHK(hipMalloc(&wc, wc_bytes));
+    h->l6_allocs.push_back(wc);
+    o.wc = (float*)wc;
+    HIPCHK(hipMemset(wc, 0, wc_bytes));
+    HIPCHK(hipMalloc(&w2, w2_bytes));
+    Level6ComposeParams cp{};
+    cp.wm = wm; cp.dw = dc.w; cp.cw = cw; cp.dout = l.dout; cp.dkpad = dc.Kpad; cp.aw = ac.w; cp.cinw = cinw; cp.akpad = ac.Kpad;
+    cp.K = o.K; cp.Kc = o.Kc; cp.N = N; cp.Npad = o.Npad; cp.w2 = (double*)w2; cp.wc = o.wc;
+    launch_level6_compose(cp, nullptr);
+    const hipError_t e = hipDeviceSynchronize();
+    (void)hipFree(w2);
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "composing level 6 failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int ensure_level6(ccvpe_handle_s* h, int wm) {
+    if (h->l6_wm == wm) return 0;
+    if (!h->finalized) return ccvpe_fail(CCVPE_ESTATE, "ccvpe_finalize_weights has not been called");
+    release_level6(h);
+    int rc = derive_level6(h, h->l6[0], h->loc, h->vs.loc[0], wm);
+    if (!rc) rc = derive_level6(h, h->l6[1], h->ori, h->vs.ori[0], wm);
+    if (rc) { release_level6(h); return rc; }
+    h->l6_wm = wm;
+    return 0;
+}
+
 // ---- packed-weight cache --------------------------------------------------------------------------
 // ccvpe_finalize_weights folds BatchNorm, repacks ~60 M parameters into the kernels' layouts and runs the Winograd weight
 // transforms in double precision: seconds per handle.  Its result is a set of device buffers plus plain-data descriptor
@@ -407,6 +511,8 @@ int ccvpe_finalize_weights(ccvpe_handle h) {
         if (!h->host.count(k) && !optional) return ccvpe_fail(CCVPE_EKEY, "key '%s' was skipped but is required", k.c_str());
     }
     // drop previous device copies (re-finalize after a new load_state_dict)
+    release_level6(h);
+    h->l6_failed = false;
     for (void* p : h->dev_allocs) (void)hipFree(p);
     h->dev_allocs.clear();
     h->dev_alloc_bytes.clear();
@@ -510,6 +616,8 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
     if (h->sw.pack_group() != hd.pack_group) return bad("packed under other packer switches (CCVPE_NO_PROJ, CCVPE_WINO4_MIN_N, CCVPE_NO_WINO4, CCVPE_NO_WINO4X, CCVPE_PAD_CONCAT)");
     if (hd.sz_encoder != sizeof(EncoderW) || hd.sz_decoder != sizeof(DecoderW) || hd.sz_conv != sizeof(PackedConv)) return bad("descriptor layout mismatch");
     if (hd.n_allocs == 0 || hd.n_allocs > 100000 || hd.n_relocs > 100000) return bad("implausible buffer / relocation counts");
+    release_level6(h);
+    h->l6_failed = false;
     for (void* p : h->dev_allocs) (void)hipFree(p);
     h->dev_allocs.clear(); h->dev_alloc_bytes.clear(); h->plans.clear(); h->last_plan = nullptr; h->finalized = false;
     bool ok = true;

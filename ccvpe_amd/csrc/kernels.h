@@ -357,6 +357,42 @@ void launch_level1_pose(const Level1Params& p, const int* index, float* rows, hi
 // Top-K pose plans: grid (k, B), workgroup (j, b) runs the tile of index[b][j] and writes rows[b][j][2..4]; index -1 exits at once.
 void launch_level1_topk(const Level1Params& p, const int* index, int k, float* rows, hipStream_t s);
 
+// Composed decoder level 6 (kernels_level6.hip): deconv6 composed into the 1024-channel half of conv6.0, per output
+// parity class a 2x2-tap convolution on the 8x8 grid, run as Winograd F(wm x wm, 2x2): P = (wm + 1)^2 positions, 4 P groups.
+struct Level6Params {
+    int wm;                    // Winograd output tile edge: 4 (25 positions) or 2 (9 positions)
+    int B;
+    int K, Kc;                 // floats per input pixel (score pad + descriptor channels, multiple of 4); K rounded up to 32
+    int N, Npad;               // conv6.0's output channels (multiple of 4); rows of a weight panel (N rounded up to 128, zero rows)
+    int R, bm;                 // rows of a group = level6_rows(B, wm, &bm): B (8 / wm)^2 tiles, zero rows up to the GEMM's tile height bm
+    const float* x;            // NHWC [B, 8, 8, K]
+    float* v;                  // [4 P][R][Kc] transformed input
+    const float* wc;           // [4 P][Npad][Kc] composed weights in the Winograd domain
+    float* mp;                 // [4 P][R][N] products
+    const float* skip;         // NHWC [B, 16, 16, N]: the skip half of conv6.0 (no bias, no activation)
+    const float* bc;           // [9][N] conv6.0's bias + the transposed conv's bias through the in-image taps, by border case
+                               // (3 * row case + column case; 0 interior, 1 first, 2 last)
+    float* out;                // NHWC [B, 16, 16, N] = ReLU(conv6.0(cat[deconv6(x), skip input]))
+};
+int level6_positions(int wm);
+int level6_rows(int B, int wm, int* bm_out);
+bool level6_supported(const Level6Params& p);   // sizes only (pointers are not looked at)
+void launch_level6_transform(const Level6Params& p, hipStream_t s);
+void launch_level6_gemm(const Level6Params& p, hipStream_t s);
+void launch_level6_combine(const Level6Params& p, hipStream_t s);
+// the composed weights from the two layers' packed fp32 weights, in double, rounded once (two launches; `w2` is the scratch between them)
+struct Level6ComposeParams {
+    int wm;
+    const float* dw;           // transposed conv, pack_conv layout [4 cw rows (qd * cw + m)][dkpad], column = packed input channel
+    int cw, dout, dkpad;       // row pitch of a (dy, dx) group, real output channels (multiple of 8), row length
+    const float* aw;           // conv6.0, pack_conv layout [n][akpad], column = conv_igemm_k_index(cinw, 9, tap, channel)
+    int cinw, akpad;
+    int K, Kc, N, Npad;        // as Level6Params
+    double* w2;                // [16 = class * 4 + window][N][Kc]
+    float* wc;                 // [4 P][Npad][Kc], rows N .. Npad zero before the launch
+};
+void launch_level6_compose(const Level6ComposeParams& p, hipStream_t s);
+
 // the angle of the test loops (train_VIGOR.py:307-311) in the fp32 form the post-processing kernels write
 __device__ __forceinline__ float pose_angle_deg(float cs, float sn) {
     float ang = acosf(fminf(fmaxf(cs, -1.f), 1.f)) * 57.29577951308232f;
