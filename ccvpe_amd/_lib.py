@@ -136,6 +136,7 @@ SYMBOLS = [
     ("ccvpe_op_conv2d_ex", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ccvpe_op_level1", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ccvpe_op_pose_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 ]
 
 
@@ -345,6 +346,20 @@ def op_level1(x_nhwc, wd, bd, wa, ba, wt, bt, score=False, tile=1, max_wg=0):
                              Cout, tile | (max_wg << 8), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
     check(rc, "ccvpe_op_level1")
     return out, rc
+
+
+def op_pose_rows(handle, logits, ori):
+    """Kernel-level hook: the tail of the plain pose plan (ccvpe_localize behind its decoders) on logits [B, 512*512] and ori
+    [B, 2, 512, 512] (cuda fp32) the caller holds, on a model's handle.  Returns rows [B, 5]."""
+    import torch
+    lib = load()
+    logits, ori = logits.detach().float().contiguous(), ori.detach().float().contiguous()
+    B = logits.shape[0]
+    rows = torch.empty((B, 5), dtype=torch.float32, device=logits.device)
+    stream = torch.cuda.current_stream(logits.device).cuda_stream
+    check(lib.ccvpe_op_pose_rows(handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, C.c_void_p(rows.data_ptr()),
+                                 C.c_void_p(stream)), "ccvpe_op_pose_rows")
+    return rows
 
 
 _lib = None

@@ -927,6 +927,17 @@ int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* or
     return launch_status("postprocess_prior launch");
 }
 
+// Kernel-level hook: the tail of the plain argmax pose plan (no prior, no posterior, no summary) on logits the caller holds
+int ccvpe_op_pose_rows(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, float* rows, void* stream) {
+    if (!logits || !ori || !rows) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, nullptr, 0, nullptr, rows, (hipStream_t)stream);
+    return launch_status("op_pose_rows launch");
+}
+
 int ccvpe_localize_region_prior(ccvpe_handle h, const void* grd_cache, int32_t n_queries, int32_t grd_h, int32_t grd_w, const void* sat_cache,
                                 int32_t n_tiles, const int32_t* offsets, const int32_t* tiles, const float* pair_log_prior,
                                 int64_t prior_stride, float* rows, int32_t* best_pair, float* pair_rows, float* pair_stats, float* tile_prob,

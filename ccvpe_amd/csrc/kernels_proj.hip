@@ -141,8 +141,10 @@ static constexpr int PL_WAVES = 16;
 // (a) the gated project convs (1x1), (b) 1x1 layers without a gate: the ground descriptor heads (models.py:355-395) and the transposed
 // convs of the first decoder levels (models.py:407-446; k2s2 transposed = 1x1 with a pixel-shuffle epilogue, emit_out4), (c) the aerial
 // descriptor conv k2s2 (models.py:471-482): four taps on disjoint pixels, K = (tap, channel), a lane keeps one base address per tap.
-// Channels are padded to 16 per tap (zero weights; the activation read runs into the next pixel's first channels - finite numbers - or
-// past the tensor - zeros).
+// Channels are padded to 16 per tap with zero weights.  The activation quads past Cin are not read (an out-of-range offset: zeros, no
+// traffic): they belong to the next pixel - the next sample's first pixel behind a sample's last - and a NaN or an infinity there times
+// a zero weight is a NaN.  Two rules of conv_proj_supported() carry this: in_ld % 4 == 0 (quads start at multiples of 4 channels, so a
+// quad that straddles Cin ends in the row's own pad channels, never in the next pixel) and Cin % 16 == 0 with a gate (no pad step).
 // SEP (GATE must be set too): the squeeze-excite gates are computed HERE, once per workgroup, with ONE trip to memory for everything the
 // workgroup needs.  Requested together at the start: the front kernel's squeeze rows (a row of SQ floats per work item; G groups of SQ
 // threads take rows g, g + G, ...), both bias vectors, the excite matrix (thread = (channel quad q, third h of the SQ rows): <= 16 loads of
@@ -244,8 +246,9 @@ __global__ __launch_bounds__(64 * PL_WAVES) void conv_proj_lat_kernel(const Conv
             const int tap = (SEP || taps == 1) ? 0 : s / spt;        // (scalar: s is wave-uniform; SEP: one tap)
             const int sub = s - tap * spt;
             const int tap_off = (SEP || taps == 1) ? 0 : ((tap / p.KW) * p.W + tap % p.KW) * p.in_ld * 4;   // (scalar)
+            const bool mine = live && (GATE || sub * 16 + kq4 < p.Cin);   // (the last step of a tap: quads past Cin are not this layer's; a gate: Cin % 16 == 0)
 #pragma unroll
-            for (int r = 0; r < RTB; ++r) a[i][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, live ? a_row[r] : OOB, tap_off + sub * 64, 0));
+            for (int r = 0; r < RTB; ++r) a[i][r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, mine ? a_row[r] : OOB, tap_off + sub * 64, 0));
             if (GATE && !SEP) g[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(g_rsrc, live ? g_off : OOB, sub * 64, 0));
             if (!SEP) {   // (SEP: the weight fragments follow once the excite rows have left their registers)
 #pragma unroll
@@ -417,7 +420,7 @@ bool conv_proj_supported(const ConvParams& p, int rt) {
         const bool k2s2 = p.KH == 2 && p.KW == 2 && p.stride == 2 && p.OH * 2 == p.H && p.OW * 2 == p.W && p.gate == nullptr && p.mode == MODE_CONV;
         if (!(p.proj_w != nullptr && (one || k2s2) && p.pad_t == 0 && p.pad_l == 0 && !p.in_split && (p.mode == MODE_CONV || p.mode == MODE_DECONV) &&
               p.in_ld % 4 == 0 && p.Cin >= 64 && p.M <= 4096)) return false;
-        if ((p.gate != nullptr || p.se_rows != nullptr) && p.Cin % 16 != 0) return false;      // (the gate vector has exactly Cin entries per sample)
+        if ((p.gate != nullptr || p.se_rows != nullptr) && p.Cin % 16 != 0) return false;      // (the gate vector has exactly Cin entries per sample; the kernel's pad-quad test relies on it, as on in_ld % 4 above)
         if (rt == 104 && p.gate != nullptr) return false;              // (gates + four column tiles of weights per step: past the 128 registers of a wave)
         if (rt > 104 && (p.gate != nullptr || p.se_rows != nullptr || p.M < 16 * ((rt - 100) / 10) || p.M > 1024)) return false;   // the multi-row forms: no gate, at least one full workgroup of rows
         if (p.se_rows != nullptr) {   // gates computed in the prologue: one group per wave, every wave busy, a row tile inside one sample, <= 64 squeeze outputs

@@ -143,7 +143,8 @@ void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Post-processing: argmax (first maximal index, as numpy.argmax), prob, (cos, sin), angle in degrees.
+// Post-processing: argmax (first maximal index, as numpy.argmax on a map without NaN; NaN never wins: DESIGN.md 2.3), prob, (cos, sin),
+// angle in degrees.
 // ------------------------------------------------------------------------------------------------
 // Round 4: one workgroup per sample scanned its 262144 values in sixteen rounds of loads - 16 trips to memory for ONE workgroup at batch 1
 // (17 us).  Now PP_CHUNKS workgroups per sample take 4096 values each (all their loads in one trip), leave (max, first index) per chunk
@@ -207,9 +208,14 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* heat, con
             if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
         }
         if (threadIdx.x == 0) {
-            const float cs = ori[((size_t)b * 2 + 0) * n + bi];
-            const float sn = ori[((size_t)b * 2 + 1) * n + bi];
+            // no value above -inf anywhere (all NaN, all -inf, a mix): nothing was taken and bi is still the sentinel.  The sample has no
+            // posterior: index -1, prob NaN, the orientation of pixel 0.  The clamp keeps the reads inside ori regardless.
+            const bool ok = bi != 0x7fffffff;
+            const int at = ok ? min(max(bi, 0), n - 1) : 0;
+            const float cs = ori[((size_t)b * 2 + 0) * n + at];
+            const float sn = ori[((size_t)b * 2 + 1) * n + at];
             const float ang = pose_angle_deg(cs, sn);
+            if (!ok) { bi = -1; best = NAN; }
             if (rows) {
                 rows[b * 5 + 0] = (float)bi; rows[b * 5 + 1] = best; rows[b * 5 + 2] = cs; rows[b * 5 + 3] = sn; rows[b * 5 + 4] = ang;
             } else {
@@ -435,9 +441,8 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
         if constexpr (SUMM) {
             if (threadIdx.x == 0) { sv[0] = best; si[0] = bi; }
         } else if (threadIdx.x == 0) {
-            if constexpr (PRIOR || POST) {
-                if (!(isfinite(m) && isfinite(inv))) { p.index[b] = 0; p.rows[b * 5 + 0] = -1.f; p.rows[b * 5 + 1] = NAN; return; }
-            }
+            // (every form: without a prior the map softmax_final_kernel would store is then all NaN, which postprocess_kernel answers alike)
+            if (!(isfinite(m) && isfinite(inv))) { p.index[b] = 0; p.rows[b * 5 + 0] = -1.f; p.rows[b * 5 + 1] = NAN; return; }
             p.index[b] = bi;
             p.rows[b * 5 + 0] = (float)bi;
             p.rows[b * 5 + 1] = best;
@@ -544,6 +549,7 @@ __global__ __launch_bounds__(256) void belief_summary_kernel(const BeliefSummary
     __syncthreads();
     best = sv[0];
     bi = min(max(si[0], 0), n - 1);   // (a position of the map by construction; the clamp keeps the window reads inside it regardless)
+    if (best == -INFINITY) best = h[bi];   // nothing was taken (no value above -inf): column 1 is the map's value at the index, like any other row's
     summ_finish(p.summ_part + (size_t)b * PP_CHUNKS * SUMMARY_PART, bi, best, true, p.r, [&](int i) { return h[i]; }, sd,
                 p.summary + (size_t)b * SUMMARY_COLS);
 }
@@ -828,10 +834,10 @@ __global__ __launch_bounds__(64) void metrics_kernel(const PoseOut* pose, const 
     const int py = pi / W, px = pi - py * W, gy = gi / W, gx = gi - gy * W;
     const double dy = (double)(gy - py), dx = (double)(gx - px);
     MetricsOut m;
-    m.pixel_distance = sqrt(dy * dy + dx * dx);
-    m.meter_distance = m.pixel_distance * meter_per_pixel[b];
-    m.prob_at_gt = (double)heat[(size_t)b * n + gi];
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    m.pixel_distance = pi < 0 ? nan : sqrt(dy * dy + dx * dx);   // (index -1: the sample has no posterior, DESIGN.md 2.3 - NaN distances)
+    m.meter_distance = m.pixel_distance * meter_per_pixel[b];
+    m.prob_at_gt = (unsigned)gi < (unsigned)n ? (double)heat[(size_t)b * n + gi] : nan;   // (a ground truth outside the map: no read)
     const double cp = (double)pose[b].cos_v, sp = (double)pose[b].sin_v;
     m.angle_pred_deg = m.angle_gt_deg = m.orientation_error_deg = nan;
     if (fabs(cp) <= 1.0 && fabs(sp) <= 1.0) {    // the reference skips the orientation error otherwise (train_VIGOR.py:306)

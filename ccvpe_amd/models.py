@@ -501,7 +501,9 @@ class _CVMBase(nn.Module):
     # ---- pose-only forward -------------------------------------------------------------------
     def localize(self, grd: torch.Tensor, sat: torch.Tensor) -> torch.Tensor:
         """The pose of every query without the nine forward outputs: float32 [B, 5] on the device, the postprocess_rows layout
-        (index, prob, cos, sin, angle_deg).  Bit-identical to postprocess_rows(*forward(grd, sat)[1:3]) (ccvpe_localize)."""
+        (index, prob, cos, sin, angle_deg).  Bit-identical to postprocess_rows(*forward(grd, sat)[1:3]), also for a query without a
+        finite posterior (one NaN or +inf logit: the heatmap is all NaN), whose row is (-1, NaN, cos, sin, angle_deg of pixel 0) in
+        both (ccvpe_localize)."""
         return self._call("localize", grd, sat)
 
     def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor, tile_index=None) -> torch.Tensor:
@@ -839,7 +841,8 @@ class _CVMBase(nn.Module):
 
     def belief_summary(self, belief: torch.Tensor, radius: int = 8) -> torch.Tensor:
         """The summary [B, 16] of stored maps: belief [B,512,512] or [B,1,512,512], float32, contiguous, non-negative - a forward's
-        heatmap, a tracker belief; it need not sum to 1 (column 2 is its sum).  An all-zero map gives (0, 0, 0, NaN ...).  One launch
+        heatmap, a tracker belief; it need not sum to 1 (column 2 is its sum).  An all-zero map gives (0, 0, 0, NaN ...); NaN never
+        wins the argmax, and a map without a value above -inf gives index 0 with the map's value there.  One launch
         (ccvpe_belief_summary)."""
         if self.training:
             raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
@@ -911,7 +914,9 @@ class _CVMBase(nn.Module):
 
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Device-side version of the per-sample loop in train_VIGOR.py:297-316."""
+        """Device-side version of the per-sample loop in train_VIGOR.py:297-316.  The argmax is the largest value above -inf, the first
+        index on ties; NaN never wins (numpy.argmax returns the first NaN).  A map without such a value - all NaN, which one NaN or
+        +inf logit makes of the softmax, all -inf, a mix - gives index -1, prob NaN and the orientation of pixel 0."""
         B = heatmap.shape[0]
         self._ensure_handle(heatmap.device)
         buf = torch.empty((B, 5), dtype=torch.int32, device=heatmap.device)
@@ -925,7 +930,8 @@ class _CVMBase(nn.Module):
 
     def postprocess_rows(self, heatmap: torch.Tensor, ori: torch.Tensor) -> torch.Tensor:
         """postprocess() as ONE float32 tensor [B, 5] = (index, prob, cos, sin, angle_deg): the 20-byte rows a data-parallel
-        evaluation gathers, written by the post-processing launch itself (no conversion / stack launches behind it)."""
+        evaluation gathers, written by the post-processing launch itself (no conversion / stack launches behind it).  A map without a
+        value above -inf: (-1, NaN, cos, sin, angle_deg of pixel 0), as postprocess()."""
         B = heatmap.shape[0]
         self._ensure_handle(heatmap.device)
         rows = torch.empty((B, 5), dtype=torch.float32, device=heatmap.device)
@@ -944,7 +950,8 @@ class _CVMBase(nn.Module):
         """Device-side version of the whole per-sample test loop (train_VIGOR.py:290-326, train_KITTI.py:309-343): argmax /
         orientation lookup (postprocess) plus the ground-truth side - pixel and metre distance, probability at the
         ground-truth pixel, orientation error, lateral / longitudinal split.  Returns float64 tensors [B] (NaN where the
-        reference produces no value for the query)."""
+        reference produces no value for the query).  A query without an argmax (index -1, see postprocess) has NaN distances; a
+        gt_index outside the map has prob_at_gt NaN."""
         B = heatmap.shape[0]
         dev = heatmap.device
         self._ensure_handle(dev)

@@ -76,9 +76,9 @@ typedef struct ccvpe_outputs {
 
 /* Compact per-sample result of the test-loop post-processing (train_VIGOR.py:297-316). */
 typedef struct ccvpe_pose {
-    int32_t index;              /* argmax of the heatmap, y*512 + x */
-    float   prob;               /* heatmap value there */
-    float   cos_v, sin_v;       /* orientation field at that pixel */
+    int32_t index;              /* argmax of the heatmap, y*512 + x; -1: the map holds no value above -inf (below) */
+    float   prob;               /* heatmap value there; NaN for index -1 */
+    float   cos_v, sin_v;       /* orientation field at that pixel; at pixel 0 for index -1 */
     float   angle_deg;          /* acos/sign rule of train_VIGOR.py:307-311, in [0, 360) */
 } ccvpe_pose;
 
@@ -157,7 +157,10 @@ int ccvpe_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w
                   int32_t batch, const ccvpe_outputs* out, void* stream);
 
 /* Device-side test-loop post-processing on forward outputs: poses[B] is DEVICE memory.  batch <= 4096 per call; one call in flight per
- * handle (the launch keeps per-sample partial results and ticket counters in a scratch buffer of the handle). */
+ * handle (the launch keeps per-sample partial results and ticket counters in a scratch buffer of the handle).
+ * The argmax: the largest value above -inf, the first index on ties; NaN compares false and never wins, unlike
+ * numpy.argmax, which returns the first NaN.  A map without a value above -inf (all NaN - what the softmax makes of one NaN or +inf
+ * logit -, all -inf, a mix) has no argmax: index -1, prob NaN, and cos / sin / angle of pixel 0.  Nothing is read outside the maps. */
 int ccvpe_postprocess(ccvpe_handle h, const float* heatmap, const float* ori, int32_t batch,
                       ccvpe_pose* poses, void* stream);
 /* The same five numbers per query as one float row - rows[B][5] = (index, prob, cos, sin, angle_deg), DEVICE memory: the 20-byte
@@ -179,7 +182,8 @@ int ccvpe_postprocess_topk(ccvpe_handle h, const float* heatmap, const float* or
  * argmax(gt map) (y*512 + x), `gt_cos_sin[B][2]` = ground-truth orientation at that pixel (NULL: no orientation error),
  * `meter_per_pixel[B]` = metres per OUTPUT pixel (VIGOR: city constant / 512 * 640, train_VIGOR.py:301-308; KITTI:
  * test_set.meter_per_pixel), `heading_deg[B]` = orientation_angle of train_KITTI.py:310 (NULL: no lateral / longitudinal
- * split).  All pointers are DEVICE memory; out[B] likewise. */
+ * split).  All pointers are DEVICE memory; out[B] likewise.  A pose with index < 0 (no argmax) gives NaN distances (pixel, metre,
+ * longitudinal, lateral); a gt_index outside [0, 512*512) gives prob_at_gt = NaN and the heatmap is not read there. */
 int ccvpe_eval_metrics(ccvpe_handle h, const ccvpe_pose* poses, const float* heatmap, int32_t batch, const int32_t* gt_index,
                        const float* gt_cos_sin, const double* meter_per_pixel, const double* heading_deg, ccvpe_metrics* out,
                        void* stream);
@@ -197,7 +201,9 @@ int ccvpe_forward_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32_
 /* Pose-only forward: rows[B][5] = (index, prob, cos, sin, angle_deg), DEVICE memory, bit-identical to
  * ccvpe_forward + ccvpe_postprocess_rows on the same inputs, without writing the nine forward outputs (no heatmap, no
  * matching-score stacks; the orientation field is computed only around each sample's argmax).  Arguments as ccvpe_forward;
- * larger batches than the micro-batch loop the same way.  CCVPE_EINVAL for a null `rows`, CCVPE_ESTATE on a handle with debug
+ * larger batches than the micro-batch loop the same way.  A query whose softmax statistics are not finite (a NaN or +inf logit,
+ * -inf everywhere: the forward's heatmap is then all NaN) gets ccvpe_postprocess_rows' row for such a map, (-1, NaN, cos / sin /
+ * angle of pixel 0), as the prior, tracking, summary and heading forms do.  CCVPE_EINVAL for a null `rows`, CCVPE_ESTATE on a handle with debug
  * taps on (ccvpe_set_debug).  Pose plans run eagerly, never as a captured hipGraph (CCVPE_GRAPH=1 included). */
 int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat,
                    int32_t batch, float* rows, void* stream);
@@ -279,7 +285,7 @@ int ccvpe_localize_region(ccvpe_handle h, const void* grd_cache, int32_t n_queri
  * k == 0 (radius 0): rows[B][5] = (index, prob, cos, sin, angle_deg) at the first maximal h', prob = h' there, the orientation
  * field at that pixel, as ccvpe_localize.  k in 1..64, radius in 0..32: rows[B][k][5] with ccvpe_postprocess_topk's peaks,
  * order and (-1, 0, 0, 0, 0) padding applied to h'.  A query without a finite posterior (m' or inv' not finite: a prior of -inf
- * over the whole map, a +inf or a NaN anywhere) has the argmax row (-1, NaN, unspecified cos / sin / angle) and top-K rows all
+ * over the whole map, a +inf or a NaN anywhere) has the argmax row (-1, NaN, cos / sin / angle of pixel 0) and top-K rows all
  * (-1, 0, 0, 0, 0); no launch reads outside its tensors whatever the prior holds.  An all-zero prior gives the bits of the
  * forms without a prior (logits without NaN or inf).  No launch is added: the prior is read where the logits are.
  * CCVPE_EINVAL, with nothing launched and checked before the handle is used: a null pointer, prior_stride other than 0 or
@@ -381,9 +387,10 @@ int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batc
  *     15       cells of the clipped window, as float
  * All sums are float64 (h times a coordinate product is exact there) in a fixed order: the same inputs give the same bits.
  * radius in 0..32.  A query without a finite posterior: rows (-1, NaN, ...) as ccvpe_localize_prior, summary (-1, NaN, NaN ...).
- * A stored map with S0 == 0: (0, 0, 0, NaN ...).  rows [batch][5] are exactly the k == 0 rows of the matching prior form
+ * A stored map with S0 == 0: (0, 0, 0, NaN ...); one without a value above -inf (a belief is non-negative: outside the contract):
+ * index 0, the map's value there, NaN moments - a position of the map whatever it holds.  rows [batch][5] are exactly the k == 0 rows of the matching prior form
  * (ccvpe_localize_prior, ccvpe_localize_prior_cached_indexed, ccvpe_postprocess_prior; log_prior NULL: ccvpe_track_update* without
- * a prior, i.e. ccvpe_localize* except that logits without a finite (m', inv') - a NaN or +inf among them - give (-1, NaN) too).
+ * a prior, i.e. ccvpe_localize*: logits without a finite (m', inv') - a NaN or +inf among them - give (-1, NaN) in every form).
  * log_prior may be NULL (prior_stride is then ignored); posterior may be NULL, else it receives ccvpe_track_update's map.  No
  * launch is added to the pose plans: the launch that finds the argmax reduces the sums, and its last workgroup recomputes the
  * window; ccvpe_belief_summary is one launch.  The pose forms run plans of their own (the float64 partial sums live in their
@@ -591,6 +598,13 @@ int ccvpe_op_conv2d_ex(const ccvpe_op_conv_desc* d, void* stream);
  * (device, NCHW).  Returns the tile that ran (0 or 1), or a negative error code. */
 int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t score, const float* wd, const float* bd,
                     const float* wa, const float* ba, const float* wt, const float* bt, int32_t Cout, int32_t tile, float* out, void* stream);
+
+/* Kernel-level hook (tests): the launches ccvpe_localize runs behind its decoders - softmax partials, the argmax without a prior,
+ * posterior or summary, the orientation gather - on logits [batch][512*512] and ori [batch][2][512][512] the caller holds: rows
+ * [batch][5], DEVICE memory, the bits ccvpe_postprocess_rows gives on ccvpe_forward's heatmap of those logits.  ccvpe_postprocess_prior
+ * refuses a null prior and ccvpe_track_update_logits stores a map, so no other entry runs this form on given logits.  batch <= 4096,
+ * any handle, the scratch of ccvpe_postprocess_prior. */
+int ccvpe_op_pose_rows(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, float* rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,87 @@ def test_winograd_offset_destination(shape, coff):
             check(x, w, b, name, code, ref, f"wino {shape} coff {coff}", pad=1, act=1, dst_specs=[(cout + 16, coff)])
 
 
+# ---- case 5: a poisoned sample does not move its batch neighbours ------------------------------------------------------------
+def poisoned(t):
+    """sample 1 of a [3, ...] tensor all NaN"""
+    p = t.clone()
+    p[1] = float("nan")
+    return p
+
+
+def check_isolated(x, w, b, name, code, what, **form):
+    """run_checked on the clean launch and on the same launch with sample 1 of x (and of its gate and residual) all NaN: the same
+    tile and split, samples 0 and 2 of every destination the same bits, nothing written outside the destinations either time.
+    Neither launch is held to an error bound here, so neither is recorded as "ran as requested" (tile_rules.RAN): that record stays
+    with the cases that compare with the fp64 reference.  With an activation (act = 1: the device's ReLU is a maximum, which returns 0
+    for a NaN) sample 1 of the result need not be NaN; the NaN is in every input tile the kernel reads all the same."""
+    clean, ran, split, _ = tr.run_checked(x, w, b, name, code, what=what, record=False, **form)
+    bad_form = {k: (poisoned(v) if k in ("gate", "resid") else v) for k, v in form.items()}
+    bad, ran2, split2, _ = tr.run_checked(poisoned(x), w, b, name, code, what=what + " poisoned", record=False, **bad_form)
+    assert (ran2, split2) == (ran, split), f"{what} tile {name} code {code}: {ran} / {split} clean, {ran2} / {split2} poisoned"
+    for k, (c, p) in enumerate(zip(clean, bad)):
+        assert not bool(torch.isnan(c).any())
+        for s in (0, 2):
+            assert torch.equal(c[s], p[s]), (f"{what} tile {name} code {code} (ran {ran} split {split}) destination {k}: sample {s} moved "
+                                             f"at {(c[s] != p[s]).nonzero()[:4].tolist()} when sample 1 was poisoned")
+        if not form.get("act"):
+            assert bool(torch.isnan(p[1]).all()), f"{what} tile {name} code {code}: the poison did not reach sample 1"
+
+
+ISOLATION_CODES = (0, 4, 64 + 4)
+
+
+@pytest.mark.parametrize("n", [80, 192])
+def test_poisoned_sample_gated_project(n):
+    """project_case: 3 samples of 35 rows, every row tile straddles samples; gate, residual and two destinations (the form that
+    holds every operand a sample owns: its rows of x, its gate vector, its residual rows), at 5 and 12 column tiles"""
+    x, w, b, form, _ = project_case(192, n, "gate_resid_dst2", 6000 + n)
+    for name in family_names(*NON_WINO):
+        for code in ISOLATION_CODES:
+            check_isolated(x, w, b, name, code, f"isolation project N {n}", **form)
+
+
+@pytest.mark.parametrize("ch", [(1288, 64), (320, 40)])
+def test_poisoned_sample_transposed_conv_offset(ch):
+    x, w, b, form, _ = deconv_case(3, (5, 7), ch, True)
+    for name in family_names(*NON_WINO):
+        check_isolated(x, w, b, name, 0, f"isolation deconv {ch}", **form)
+    for name in list(SPLIT_TILES) + family_names("conv_projl_") + ["conv_bf16x3_64x64_m32", "conv_pw_16"]:
+        for code in ISOLATION_CODES[1:]:
+            check_isolated(x, w, b, name, code, f"isolation deconv {ch}", **form)
+
+
+def test_poisoned_sample_winograd():
+    B, H, W, cin, cout = tr.WINO_SHAPES[1]          # 3 x 16 x 16 x 64 -> 88
+    assert B == 3
+    g = torch.Generator(device="cuda").manual_seed(6500)
+    x = rand(g, B, H, W, cin)
+    w = rand(g, cout, cin, 3, 3) / (cin * 9) ** 0.5
+    b = rand(g, cout)
+    for name in family_names("conv_wino", "conv_igemm_", "conv_bf16x3_"):
+        for code in ISOLATION_CODES:
+            check_isolated(x, w, b, name, code, "isolation wino", pad=1, act=1, dst_specs=[(cout + 16, 8)])
+
+
+@pytest.mark.parametrize("width", [(40, True, 1), (32, True, 1), (32, False, 2), (24, True, 1)])
+def test_poisoned_sample_level1(width):
+    """ccvpe_op_level1 at B = 3: 48 x 96 outputs are 3 x 3 tiles of 32 x 16 per sample, 8 workgroups loop over the 27 tiles (54 of
+    16 x 16), so a workgroup's run crosses both sample boundaries"""
+    from ccvpe_amd import _lib
+    cd, score, cout = width
+    cin = cd + (1 if score else 0)
+    g = torch.Generator(device="cuda").manual_seed(6600 + cd + cout)
+    x = rand(g, 3, 24, 48, cin)
+    ws = [rand(g, cin, 16, 2, 2) / (4 * cin) ** 0.5, rand(g, 16), rand(g, 16, 16, 3, 3) / 12.0, rand(g, 16) * 0.5,
+          rand(g, cout, 16, 3, 3) / 12.0, rand(g, cout) * 0.5]
+    for tile in (0, 1):
+        clean, ran = _lib.op_level1(x, *ws, score=score, tile=tile, max_wg=8)
+        bad, ran2 = _lib.op_level1(poisoned(x), *ws, score=score, tile=tile, max_wg=8)
+        assert ran == ran2 == tile and not bool(torch.isnan(clean).any())
+        for s in (0, 2):
+            assert torch.equal(clean[s], bad[s]), f"level1 {width} tile {tile}: sample {s} moved when sample 1 was poisoned"
+
+
 # ---- every tile of the registry ran somewhere ----------------------------------------------------------------------------
 def test_every_registry_tile_ran():
     """Every name of the registry must have been seen to run as requested by a checked launch.  The launches below give each

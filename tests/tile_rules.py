@@ -202,11 +202,11 @@ def tol_for(name):
     return 1e-4 if ("bf16x3" in name or "wino4" in name) else 2e-5
 
 
-def run_checked(x, w, b, name, code=0, *, stride=1, pad=0, act=0, gate=None, resid=None, deconv=False, dst_specs=None, what=""):
+def run_checked(x, w, b, name, code=0, *, stride=1, pad=0, act=0, gate=None, resid=None, deconv=False, dst_specs=None, what="", record=True):
     """One launch of tile `name` with split code `code` through ccvpe_op_conv2d_ex into pre-filled destinations.  Asserts that
     the library's requested_runs agrees with tile_runs(); that the tile ran as requested with the split expected_split() derives,
     or - refused by rule - that another tile ran; that nothing outside [coff, coff + Cout) of any destination row (and the guard
-    row behind the last) was written.  Returns (the [.., Cout] result regions of the destinations, ran_name, ran_split, ran as
+    row behind the last) was written.  record=False: the launch is not entered in RAN (its caller holds the result to no error bound).  Returns (the [.., Cout] result regions of the destinations, ran_name, ran_split, ran as
     requested)."""
     from ccvpe_amd import _lib
     from tests import conv_ref
@@ -230,7 +230,8 @@ def run_checked(x, w, b, name, code=0, *, stride=1, pad=0, act=0, gate=None, res
         assert ran == name, f"{tag}: ran {ran}"
         exp, srule = expected_split(name, L, code)
         assert split == exp, f"{tag}: split code {split}, expected {exp} ({srule})"
-        RAN.add(name)
+        if record:
+            RAN.add(name)
     else:
         assert rule and ran != name and ran != "", f"{tag}: refused by rule ({rule}) but ran {ran!r}"
     for (flat, view), (ld, coff) in zip(bufs, L.dsts):
