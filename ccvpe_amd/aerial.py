@@ -417,6 +417,34 @@ def heading_sigma_deg(resultant):
     return np.where((R >= 0.0) & (R <= 1.0), out, np.nan)
 
 
+def von_mises_heading_log_prior(mean_deg, kappa, bins: int, none_log=None) -> np.ndarray:
+    """A heading prior for model.localize_heading_prior / heading_prior_map from a heading measurement: float32
+    [bins+1] (mean_deg and kappa numbers) or [B, bins+1] (either one [B]).  Entry b < bins is the von Mises log-density at the centre
+    of bin b times the bin width, kappa cos(centre_b - mean) - log(2 pi I0(kappa)) + log(w in radians), evaluated in float64 - so
+    exp of the entries sums to about 1; the last entry, the weight of a cell without a heading, is none_log or by default
+    log(1 / bins), what a flat prior gives a bin.  Angles as rows[:, 4] and heading_bin_centres; kappa >= 0 is about
+    1 / sigma^2 in radians."""
+    centres = np.radians(heading_bin_centres(bins))
+    bins = int(bins)
+    scalar = np.ndim(mean_deg) == 0 and np.ndim(kappa) == 0
+    mean = np.radians(np.asarray(mean_deg, dtype=np.float64).reshape(-1, 1))
+    kap = np.asarray(kappa, dtype=np.float64).reshape(-1, 1)
+    if mean.shape[0] != kap.shape[0] and 1 not in (mean.shape[0], kap.shape[0]):
+        raise ValueError(f"mean_deg and kappa must hold one value or one per query each, got {mean.shape[0]} and {kap.shape[0]}")
+    if not np.isfinite(mean).all():
+        raise ValueError("mean_deg must be finite")
+    if not (np.isfinite(kap).all() and (kap >= 0).all()):
+        raise ValueError("kappa must be finite and >= 0")
+    # log I0(kappa) = kappa + log(i0e(kappa)): no overflow at large kappa
+    log_i0 = kap + np.log(np.i0(np.minimum(kap, 500.0)) * np.exp(-np.minimum(kap, 500.0)))
+    big = kap > 500.0                                   # asymptotically I0(k) e^-k = 1 / sqrt(2 pi k)
+    log_i0 = np.where(big, kap - 0.5 * np.log(2.0 * np.pi * np.maximum(kap, 1.0)), log_i0)
+    body = kap * np.cos(centres[None, :] - mean) - np.log(2.0 * np.pi) - log_i0 + np.log(2.0 * np.pi / bins)
+    last = np.full((body.shape[0], 1), np.log(1.0 / bins) if none_log is None else float(none_log))
+    out = np.concatenate([body, last], axis=1).astype(np.float32)
+    return out[0] if scalar else out
+
+
 # ---- tracking a frame stream (DESIGN.md 4.11) ------------------------------------------------------------------------------------
 
 def gaussian_taps(sigma_px, radius: int) -> np.ndarray:
@@ -452,6 +480,28 @@ def oxford_track_shift(origin_prev, origin_next, motion_map_px) -> np.ndarray:
     return (a - b + m) * (SAT_HW / OXFORD_WIN) + np.zeros((B, 2))
 
 
+def _heading_filter_args(heading_bins, turn_deg, taps, floor) -> bool:
+    """The heading half of a tracker step is on when heading_turn_deg, heading_taps and heading_floor are given - all three, beside
+    heading_bins."""
+    given = [a is not None for a in (turn_deg, taps, floor)]
+    if not any(given):
+        return False
+    if not all(given):
+        raise ValueError("heading_turn_deg, heading_taps and heading_floor go together: give all three or none")
+    if heading_bins is None:
+        raise ValueError("heading_turn_deg, heading_taps and heading_floor require heading_bins")
+    return True
+
+
+def _heading_table(model, hist, B: int, heading_bins, turn_deg, taps, floor):
+    """the heading prior of this step from the hist the tracker holds (None before it holds one: the first step has no heading prior)"""
+    if hist is None:
+        return None
+    if tuple(hist.shape) != (B, int(heading_bins)):
+        raise ValueError(f"the tracker holds a hist of shape {tuple(hist.shape)}, this step has {B} streams and heading_bins={heading_bins}")
+    return model.heading_predict(hist, turn_deg, taps, floor)
+
+
 class Tracker:
     """A histogram filter over the Oxford windows, host side: holds the posterior map of the last frame (a device tensor
     [B,512,512]) and the window origin it lives in.  step() = model.track_predict (the last posterior moved into this frame's
@@ -460,12 +510,15 @@ class Tracker:
     def __init__(self):
         self.belief = None    # posterior of the last frame, or None before the first step
         self.origin = None    # [B,2] int64 window origin (x0, y0) of each query's belief
+        self.hist = None      # heading filter: hist [B,heading_bins] of the last frame, or None
 
     def reset(self) -> None:
         self.belief = None
         self.origin = None
+        self.hist = None
 
-    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None, heading_bins=None):
+    def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None, heading_bins=None,
+             heading_turn_deg=None, heading_taps=None, heading_floor=None):
         """One frame of B parallel streams.  cache / tile_index: as model.localize_cached; origins [T,2]: the crop origin of every
         cached tile (oxford_tiles' "origin"; one per query when tile_index is None); motion_map_px [B,2] or [2]: the motion since
         the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5];
@@ -473,7 +526,11 @@ class Tracker:
         (rows, summary [B,16]): entropy, covariance and peak mass of the new belief (SUMMARY_FIELDS), to gate on.  With heading_bins
         (4..360) the update is model.localize_heading_cached - the same rows, belief and summary - and (heading [B,12], hist
         [B,heading_bins]) of the new belief (HEADING_FIELDS) are appended to what the step returns; their window radius is
-        summary_radius, or 8 without one."""
+        summary_radius, or 8 without one.  With heading_turn_deg (a number or [B]: the heading change since the last step, positive
+        when the heading angle grows), heading_taps and heading_floor (as model.heading_predict; they require heading_bins) the
+        heading is filtered too: the tracker keeps the last hist, and every step after the first runs model.heading_predict on it
+        and takes the result as the heading prior of model.localize_heading_prior_cached.  Returns are unchanged."""
+        filt = _heading_filter_args(heading_bins, heading_turn_deg, heading_taps, heading_floor)
         org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
         B = grd.shape[0]
         now = org if tile_index is None else org[np.asarray(tile_index, dtype=np.int64)]
@@ -486,7 +543,14 @@ class Tracker:
             prior = model.track_predict(self.belief, oxford_track_shift(self.origin, now, motion_map_px), taps, floor)
         summary = None
         heading = None
-        if heading_bins is not None:
+        table = _heading_table(model, self.hist, B, heading_bins, heading_turn_deg, heading_taps, heading_floor) if filt else None
+        if table is not None:
+            res = model.localize_heading_prior_cached(grd, cache, table, prior, radius=8 if summary_radius is None else summary_radius,
+                                                      bins=heading_bins, summary=summary_radius is not None, posterior=True,
+                                                      tile_index=tile_index)
+            rows, heading, self.belief = res[0], res[1:3], res[-1]
+            summary = res[3] if summary_radius is not None else None
+        elif heading_bins is not None:
             res = model.localize_heading_cached(grd, cache, prior, radius=8 if summary_radius is None else summary_radius, bins=heading_bins,
                                                 summary=summary_radius is not None, posterior=True, tile_index=tile_index)
             rows, heading, self.belief = res[0], res[1:3], res[-1]
@@ -497,6 +561,7 @@ class Tracker:
             rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
                                                                        tile_index=tile_index)
         self.origin = now.copy()
+        self.hist = heading[1] if filt else None
         if heading is None:
             return rows if summary is None else (rows, summary)
         return ((rows,) if summary is None else (rows, summary)) + tuple(heading)
@@ -624,17 +689,24 @@ class AffineTracker:
 
     def __init__(self):
         self.belief = None    # posterior of the last frame, or None before the first step
+        self.hist = None      # heading filter: hist [B,heading_bins] of the last frame, or None
 
     def reset(self) -> None:
         self.belief = None
+        self.hist = None
 
-    def step(self, model, grd, sat, matrix, taps, floor, summary_radius=None, heading_bins=None, cache=None, tile_index=None):
+    def step(self, model, grd, sat, matrix, taps, floor, summary_radius=None, heading_bins=None, cache=None, tile_index=None,
+             heading_turn_deg=None, heading_taps=None, heading_floor=None):
         """One frame of B parallel streams.  sat: this frame's aerial images [B,3,512,512], or None with cache / tile_index as
         model.localize_cached; matrix [B,6] or [6]: this frame's pixel index -> the position in the LAST frame's grid it shows
         (rigid_matrix, kitti_track_matrix; ignored by the first step); taps, floor: as model.track_predict.  Returns what
         Tracker.step returns: the rows [B,5]; with summary_radius (rows, summary [B,16]); with heading_bins (heading [B,12], hist
         [B,heading_bins]) appended - the updates are model.track_update / localize_summary / localize_heading, or their _cached
-        forms beside a cache."""
+        forms beside a cache.  heading_turn_deg, heading_taps, heading_floor: the heading filter of Tracker.step (the updates are
+        then model.localize_heading_prior / _cached).  The orientation field is expressed in each frame's own grid, so here the turn
+        must include the rotation between the two grids: the change of the heading angle as THIS frame's grid measures it against
+        the last frame's, not the vehicle's turn alone."""
+        filt = _heading_filter_args(heading_bins, heading_turn_deg, heading_taps, heading_floor)
         if (sat is None) == (cache is None):
             raise ValueError("give this frame's aerial side as sat or as cache, one of the two")
         if sat is not None and tile_index is not None:
@@ -648,7 +720,17 @@ class AffineTracker:
         radius = 8 if summary_radius is None else summary_radius
         summary = None
         heading = None
-        if heading_bins is not None:
+        table = _heading_table(model, self.hist, B, heading_bins, heading_turn_deg, heading_taps, heading_floor) if filt else None
+        if table is not None:
+            if cache is None:
+                res = model.localize_heading_prior(grd, sat, table, prior, radius=radius, bins=heading_bins,
+                                                   summary=summary_radius is not None, posterior=True)
+            else:
+                res = model.localize_heading_prior_cached(grd, cache, table, prior, radius=radius, bins=heading_bins,
+                                                          summary=summary_radius is not None, posterior=True, tile_index=tile_index)
+            rows, heading, self.belief = res[0], res[1:3], res[-1]
+            summary = res[3] if summary_radius is not None else None
+        elif heading_bins is not None:
             if cache is None:
                 res = model.localize_heading(grd, sat, prior, radius=radius, bins=heading_bins, summary=summary_radius is not None,
                                              posterior=True)
@@ -667,6 +749,7 @@ class AffineTracker:
         else:
             rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
                                                                        tile_index=tile_index)
+        self.hist = heading[1] if filt else None
         if heading is None:
             return rows if summary is None else (rows, summary)
         return ((rows,) if summary is None else (rows, summary)) + tuple(heading)

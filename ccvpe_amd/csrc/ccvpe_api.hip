@@ -426,6 +426,9 @@ static int run_forward(ccvpe_handle h, const ForwardCall& fc) {
             c.heading = fc.heading + (size_t)done * HEADING_COLS; c.hist = fc.hist + (size_t)done * fc.heading_bins;
             c.heading_bins = fc.heading_bins; c.heading_r = fc.heading_r;
         }
+        if (key.hprior) {   // (a per-query table: every slice its own rows)
+            c.hprior_table = fc.hprior_table + (size_t)done * fc.hprior_stride; c.hprior_stride = fc.hprior_stride; c.hprior_nb = fc.hprior_nb;
+        }
         if (key.topk) {
             c.rows = fc.rows + (size_t)done * fc.topk_k * 5;
             c.topk_k = fc.topk_k; c.topk_r = fc.topk_r;
@@ -1202,6 +1205,108 @@ int ccvpe_postprocess_heading(ccvpe_handle h, const float* logits, const float* 
     p.B = batch; p.nbins = nbins; p.r = radius; p.part = w.head; p.bins = w.bins; p.tickets = w.tickets; p.heading = heading; p.hist = hist;
     launch_heading_reduce(p, (hipStream_t)stream);
     return launch_status("postprocess_heading launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Heading prior: a table of nb + 1 log-weights per query, read through the orientation field into a combined prior map
+// (heading_prior_map_kernel) that every prior form takes as its log_prior.  The network forms run the heading plans with that map in
+// the workspace (PlanKey::hprior: one launch more, pose.hprior, and the tail behind the orientation decoder); ccvpe_heading_prior_map
+// is the launch alone on forward outputs the caller holds; ccvpe_heading_predict turns a hist into the next frame's table.
+// ------------------------------------------------------------------------------------------------
+static int check_hprior_table(const float* table, int32_t table_stride, int32_t nb) {
+    if (!table) return ccvpe_fail(CCVPE_EINVAL, "null table");
+    if (nb < HEADING_MIN_BINS || nb > HEADING_MAX_BINS)
+        return ccvpe_fail(CCVPE_EINVAL, "nb must be in %d .. %d, got %d", HEADING_MIN_BINS, HEADING_MAX_BINS, nb);
+    if (table_stride != 0 && table_stride != nb + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "table_stride must be 0 (one table) or nb + 1 = %d (one per query), got %d", nb + 1, table_stride);
+    return 0;
+}
+
+int ccvpe_heading_prior_map(ccvpe_handle h, const float* ori, int32_t batch, const float* log_prior, int64_t prior_stride,
+                            const float* table, int32_t table_stride, int32_t nb, float* out_map, void* stream) {
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (!out_map) return ccvpe_fail(CCVPE_EINVAL, "null out_map");
+    if (int rc = check_hprior_table(table, table_stride, nb)) return rc;
+    if (log_prior) if (int rc = check_prior_stride(prior_stride)) return rc;
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (out_map == ori) return ccvpe_fail(CCVPE_EINVAL, "out_map must not alias ori");
+    if (log_prior && out_map == log_prior) return ccvpe_fail(CCVPE_EINVAL, "out_map must not alias log_prior");
+    if (out_map == table) return ccvpe_fail(CCVPE_EINVAL, "out_map must not alias table");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HeadingPriorMapParams p{};
+    p.ori = ori; p.prior = log_prior; p.prior_stride = log_prior ? prior_stride : 0; p.table = table; p.table_stride = table_stride; p.nb = nb;
+    p.out = out_map; p.B = batch;
+    launch_heading_prior_map(p, (hipStream_t)stream);
+    return launch_status("heading_prior_map launch");
+}
+
+// the heading prior's own arguments, then the checks of the matching heading form
+static int check_heading_prior_args(const float* table, int32_t table_stride, int32_t nb, const float* log_prior, int64_t prior_stride,
+                                    int32_t radius, int32_t nbins, const float* rows, const float* heading, const float* hist,
+                                    const float* summary, const float* posterior) {
+    if (int rc = check_hprior_table(table, table_stride, nb)) return rc;
+    if (int rc = check_heading_args(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior)) return rc;
+    if (table == rows || table == heading || table == hist || (summary && table == summary) || (posterior && table == posterior))
+        return ccvpe_fail(CCVPE_EINVAL, "table must not alias rows, heading, hist, summary or posterior");
+    return 0;
+}
+
+int ccvpe_localize_heading_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                                 const float* log_prior, int64_t prior_stride, const float* table, int32_t table_stride, int32_t nb,
+                                 int32_t radius, int32_t nbins, float* rows, float* heading, float* hist, float* summary, float* posterior,
+                                 void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (int rc = check_heading_prior_args(table, table_stride, nb, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior))
+        return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat;
+    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.hprior_table = table; fc.hprior_stride = table_stride; fc.hprior_nb = nb;
+    return run_forward(h, fc);
+}
+
+int ccvpe_localize_heading_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                                int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                                int64_t prior_stride, const float* table, int32_t table_stride, int32_t nb, int32_t radius,
+                                                int32_t nbins, float* rows, float* heading, float* hist, float* summary, float* posterior,
+                                                void* stream) {
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    if (int rc = check_heading_prior_args(table, table_stride, nb, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior))
+        return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.hprior_table = table; fc.hprior_stride = table_stride; fc.hprior_nb = nb;
+    return run_forward(h, fc);
+}
+
+int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int32_t nb, const float* turn_deg, const float* taps,
+                          int32_t taps_stride, int32_t radius, const float* floor, float* out, void* stream) {
+    if (!hist) return ccvpe_fail(CCVPE_EINVAL, "null hist");
+    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+    if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
+    if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
+    if (!out) return ccvpe_fail(CCVPE_EINVAL, "null out");
+    if (nb < HEADING_MIN_BINS || nb > HEADING_MAX_BINS)
+        return ccvpe_fail(CCVPE_EINVAL, "nb must be in %d .. %d, got %d", HEADING_MIN_BINS, HEADING_MAX_BINS, nb);
+    if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
+    if (2 * radius + 1 > nb) return ccvpe_fail(CCVPE_EINVAL, "radius %d needs 2 radius + 1 <= nb = %d: the blur must not wrap onto itself", radius, nb);
+    if (taps_stride != 0 && taps_stride != radius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
+                          taps_stride);
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (out == hist) return ccvpe_fail(CCVPE_EINVAL, "out must not alias hist");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HeadingPredictParams p{};
+    p.hist = hist; p.turn_deg = turn_deg; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor; p.out = out;
+    p.B = batch; p.nb = nb;
+    launch_heading_predict(p, (hipStream_t)stream);
+    return launch_status("heading_predict launch");
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

@@ -276,6 +276,8 @@ struct Ctx {
     float* heading = nullptr;          // heading pose plans: the [mb][12] heading rows of this micro-batch (ccvpe_localize_heading*),
     float* hist = nullptr;             // ... its [mb][heading_bins] histograms,
     int heading_bins = 0, heading_r = 0;   // ... the bin count 4..360 and the window radius 0..32 of this call
+    const float* hprior_table = nullptr;   // heading-prior plans (ccvpe_localize_heading_prior*): the table of this micro-batch's
+    int hprior_stride = 0, hprior_nb = 0;  // ... first sample, the floats between two samples' tables (0: one for all) and the table's bins 4..360
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -301,9 +303,11 @@ struct PlanKey {
                                   // workspace holds the float64 hand-off of the chunks' sums
     bool heading = false;         // argmax pose plans: the whole orientation field in the workspace and the pose.heading launch behind both
                                   // decoders (ccvpe_localize_heading*); combines with summary
+    bool hprior = false;          // heading plans: the combined prior map `comb` in the workspace, written by pose.hprior from the orientation
+                                  // field, read by the tail in place of the caller's prior (ccvpe_localize_heading_prior*); needs heading
     bool operator==(const PlanKey& o) const {
         return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk && summary == o.summary &&
-               heading == o.heading;
+               heading == o.heading && hprior == o.hprior;
     }
 };
 
@@ -328,6 +332,8 @@ struct ForwardCall {
     float* heading = nullptr;          // argmax pose plans (ccvpe_localize_heading*): [batch][12] heading rows and
     float* hist = nullptr;             //   [batch][heading_bins] histograms, every slice its own; select the heading plans.
     int heading_bins = 0, heading_r = 0;   // Bin count and window radius, checked by the entry point
+    const float* hprior_table = nullptr;   // heading plans (ccvpe_localize_heading_prior*): the heading prior's tables, every slice its own when
+    int hprior_stride = 0, hprior_nb = 0;  //   the stride is nb + 1 (0: one table for all); select the heading-prior plans.  Checked by the entry point
     hipStream_t stream = nullptr;
     bool profile = false;              // ccvpe_profile_forward: a hipEvent pair around every launch
     PlanKey plan_key() const {         // (B: set per slice by the micro-batch loop)
@@ -335,6 +341,7 @@ struct ForwardCall {
         key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = rows != nullptr; key.topk = rows && topk_k > 0;
         key.summary = rows && summary;
         key.heading = rows && heading;
+        key.hprior = key.heading && hprior_table;
         return key;
     }
 };

@@ -336,6 +336,9 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
 // Heading pose plans (heading = true, ccvpe_localize_heading*): the argmax pose plan with the WHOLE orientation field in
 // the workspace - level 1 of the orientation branch is the full plan's launch (ori1.fused, or ori1.tail without the fused level: the same
 // names and shapes, so the same tuning entries), ori1.gather fills rows[2..4] - and pose.heading behind both decoders' tails.
+// Heading-prior plans (hprior = true as well, ccvpe_localize_heading_prior*): the heading plan plus the workspace map `comb`
+// and pose.hprior, which writes it from the orientation field, the call's heading table and its position prior; softmax.partial,
+// pose.argmax and pose.heading read `comb` in place of the caller's prior, so they are added behind the field's launch.
 // Pair plans (mode 4, pose, ccvpe_localize_region): the cached pose plan with the ground side from a ground cache as well - the ground
 // encoder, grd.heads and grd.desc give way to grd.cached_desc, a gather of each pair's query row (Ctx::query_index); the aerial
 // launches gather each pair's tile (Ctx::tile_index).  Every other launch keeps the cached pose plan's name and tuning entry.
@@ -346,7 +349,9 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     pl.key.topk = pose && key.topk;
     pl.key.summary = pose && !key.topk && key.summary;
     pl.key.heading = key.heading;
+    pl.key.hprior = key.hprior;
     if (key.heading && (!pose || key.topk || mode == 4)) return ccvpe_fail(CCVPE_EINVAL, "heading plans are argmax pose plans (no top-K, no pairs)");
+    if (key.hprior && !key.heading) return ccvpe_fail(CCVPE_EINVAL, "heading-prior plans are heading plans");
     if (mode == 1) return build_aerial_plan(h, pl, B);
     if (mode == 3) return build_ground_plan(h, pl, B, gh, gw);
     const bool cached = mode == 2 || mode == 4;
@@ -705,7 +710,18 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
     Tensor pose_part;    // pose plans: the softmax partials, read again by pose.heading
     const bool heading = pl.key.heading;
-    if (pose) {
+    // Heading-prior plans: the tail reads the combined map `comb` that pose.hprior writes from the orientation field, so
+    // its launches are added behind the orientation decoder's whole-field launch (add_tail below is then called from there); every other
+    // plan adds them here, in the program order it always had.
+    const bool hprior = pl.key.hprior;
+    const Tensor comb = hprior ? pl.alloc(B, 1, CCVPE_OUT_HW, CCVPE_OUT_HW) : Tensor{};
+    // the position prior a tail launch reads: the caller's, or the plan's combined map
+    auto prior_of = [=](const Ctx& c, long long& stride) -> const float* {
+        if (hprior) { stride = (long long)CCVPE_OUT_HW * CCVPE_OUT_HW; return c.ptr(comb); }
+        stride = c.prior_stride;
+        return c.log_prior;
+    };
+    auto add_tail = [&]() {
         static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
         const bool topk = pl.key.topk;
         Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, topk ? 2 * TOPK_MAX_K : 2);   // (argmax: the (max, index) hand-off pairs)
@@ -717,10 +733,12 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         const bool summ = pl.key.summary;
         const Tensor spart = summ ? pl.alloc(B, 1, 64, 2 * SUMMARY_PART) : Tensor{};
         const Tensor lg = logits_ws, idx = pose_index;
-        pl.add("softmax.partial", {lg, part}, [=](const Ctx& c) {
+        std::vector<Tensor> sm_uses = {lg, part};
+        if (hprior) sm_uses.push_back(comb);
+        pl.add("softmax.partial", sm_uses, [=](const Ctx& c) {
             SoftmaxParams p{};
             p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
-            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
+            p.prior = prior_of(c, p.prior_stride);
             launch_softmax_partial(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
         const size_t toff = pl.alloc_tickets((size_t)B);
@@ -732,15 +750,20 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             p.prior = c.log_prior; p.prior_stride = c.prior_stride;
             launch_topk_peaks(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
-        else pl.add("pose.argmax", summ ? std::vector<Tensor>{lg, part, keys, idx, spart} : std::vector<Tensor>{lg, part, keys, idx}, [=](const Ctx& c) {
+        std::vector<Tensor> am_uses = {lg, part, keys, idx};
+        if (summ) am_uses.push_back(spart);
+        if (hprior) am_uses.push_back(comb);
+        if (!topk) pl.add("pose.argmax", am_uses, [=](const Ctx& c) {
             PoseArgmaxParams p{};
             p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
             p.pairs = c.ptr(keys); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
-            p.stats = c.stats; p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.posterior = c.posterior;
+            p.stats = c.stats; p.prior = prior_of(c, p.prior_stride); p.posterior = c.posterior;
             if (summ) { p.summary = c.summary; p.summ_part = reinterpret_cast<double*>(c.ptr(spart)); p.summary_r = c.summary_r; }
             launch_pose_argmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0);
-    } else {
+    };
+    if (pose && !hprior) add_tail();
+    if (!pose) {
         Tensor part = pl.alloc(B, 1, 64, 2);
         pl.add("softmax", {part}, [=](const Ctx& c) {
             SoftmaxParams p{};
@@ -749,6 +772,17 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             launch_softmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0 * 3);
     }
+    // heading-prior plans: pose.hprior (kernels_hprior.hip) right behind the launch that writes the whole field, then the tail.  The name
+    // prefix keeps it on stream 0 (Plan::schedule), where it waits for that launch of stream 1 - a dependency from the tensor lists
+    auto add_hprior = [&](Tensor of) {
+        pl.add("pose.hprior", {of, comb}, [=](const Ctx& c) {
+            HeadingPriorMapParams p{};
+            p.ori = c.ptr(of); p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.table = c.hprior_table; p.table_stride = c.hprior_stride;
+            p.nb = c.hprior_nb; p.out = c.ptr(comb); p.B = B;
+            launch_heading_prior_map(p, c.stream);
+        }, 0, 4.0 * B * 262144.0 * 4);
+        add_tail();
+    };
     // orientation decoder
     {
         Tensor xo = ori_in6;
@@ -784,6 +818,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             if (j == 5 && h->sw.fuse_level1 && heading) {   // heading plans: the whole field, the full plan's launch into the workspace
                 ori_field = pl.alloc(B, 2, CCVPE_OUT_HW, CCVPE_OUT_HW);
                 plan_level1_fused(h->ori, xo, vs.ori[5].din, 2, true, raw, "ori1", ori_field);
+                if (hprior) add_hprior(ori_field);
                 fused_done = true;
                 break;
             }
@@ -807,6 +842,7 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             p.normalize = 1; p.out = pose ? c.ptr(ori_ws) : c.out.ori; p.raw = dbg ? c.ptr(raw) : nullptr;
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 288, 4.0 * B * 262144.0 * 18);
+        if (hprior) add_hprior(ori_ws);
         if (pl.key.topk) {
             const Tensor idx = pose_index;
             pl.add("ori1.topk_gather", {ori_ws, idx}, [=](const Ctx& c) {
@@ -833,9 +869,11 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             const Tensor lg = logits_ws, part = pose_part, idx = pose_index, of = ori_field;
             const Tensor hpart = pl.alloc(B, 1, 64, 2 * HEADING_PART);
             const size_t toff = pl.alloc_tickets((size_t)B), boff = pl.alloc_tickets((size_t)B * HEADING_MAX_BINS * 2);
-            pl.add("pose.heading", {lg, part, idx, of, hpart}, [=](const Ctx& c) {
+            std::vector<Tensor> hd_uses = {lg, part, idx, of, hpart};
+            if (hprior) hd_uses.push_back(comb);
+            pl.add("pose.heading", hd_uses, [=](const Ctx& c) {
                 HeadingParams p{};
-                p.logits = c.ptr(lg); p.partial = c.ptr(part); p.prior = c.log_prior; p.prior_stride = c.prior_stride;
+                p.logits = c.ptr(lg); p.partial = c.ptr(part); p.prior = prior_of(c, p.prior_stride);
                 p.ori = c.ptr(of); p.index = reinterpret_cast<const int*>(c.ptr(idx)); p.B = B; p.nbins = c.heading_bins; p.r = c.heading_r;
                 p.part = reinterpret_cast<double*>(c.ptr(hpart)); p.bins = reinterpret_cast<unsigned long long*>(c.tickets + boff);
                 p.tickets = c.tickets + toff; p.heading = c.heading; p.hist = c.hist;

@@ -601,6 +601,37 @@ struct TrackPredictAffineParams {
 };
 void launch_track_predict_affine(const TrackPredictAffineParams& p, hipStream_t s);
 
+// Heading prior (kernels_hprior.hip).  The combined prior map of a heading table T [nb + 1] (log-weights of the heading
+// bins of DESIGN.md 4.13, entry nb for a cell without a heading) and an optional position prior P: per cell
+// out = T[k] or fl32(P + T[k]), k = the cell's bin by heading_reduce_kernel's own expression, nb for an invalid cell.  One launch,
+// grid (64 chunks, B); the result is the log_prior (stride 512 * 512) of any prior form.
+struct HeadingPriorMapParams {
+    const float* ori;          // [B][2][512*512]
+    const float* prior;        // optional position log-prior as PoseArgmaxParams::prior
+    long long prior_stride;
+    const float* table;        // [nb + 1] one table (table_stride 0) or one per query (table_stride nb + 1)
+    int table_stride;
+    int nb;                    // HEADING_MIN_BINS .. HEADING_MAX_BINS: checked by the entry points
+    float* out;                // [B][512*512], not aliasing ori or prior
+    int B;
+};
+void launch_heading_prior_map(const HeadingPriorMapParams& p, hipStream_t s);
+
+// Motion update of a heading belief (ccvpe_heading_predict): per query hist [nb] turned by turn_deg (linear weights between the two
+// source bins, on the circle), blurred with the symmetric taps t[|j|], j = -radius..radius, and out[b] = logf(that + floor); out[nb],
+// the weight of a cell without a heading, is what the average bin gets.  One launch, grid (B).
+struct HeadingPredictParams {
+    const float* hist;         // [B][nb], non-negative
+    const float* turn_deg;     // [B]
+    const float* taps;         // [radius + 1] one-sided weights, one set (taps_stride 0) or one per query (taps_stride radius + 1)
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R, 2 radius + 1 <= nb
+    const float* floor;        // [B] >= 0, added before the logarithm
+    float* out;                // [B][nb + 1], not aliasing hist
+    int B, nb;
+};
+void launch_heading_predict(const HeadingPredictParams& p, hipStream_t s);
+
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call
 size_t postprocess_scratch_bytes(int B);            // partial (max, index) pairs + one ticket counter per sample (the counters zero before the first launch)

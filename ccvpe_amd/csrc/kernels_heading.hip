@@ -15,8 +15,6 @@ static_assert(HD_SUMS <= HEADING_PART, "hand-off row");
 #define CCVPE_HEADING_WAVE_COMBINE 1   // dev builds (tools/build_variant.sh): 0 = every lane adds for itself, what the combined path is timed against
 #endif
 
-__device__ __forceinline__ bool heading_valid(float c, float s) { return isfinite(c) && isfinite(s) && !(c == 0.f && s == 0.f); }
-
 // h at a cell with the field (c, s) into a[0 .. 3): an invalid cell adds 0.  h * c is exact in float64 (24 x 24 bits): every add rounds once
 __device__ __forceinline__ void heading_take(double (&a)[HD_SUMS], float h, float c, float s, bool valid) {
     const double hd = valid ? (double)h : 0.0;
@@ -85,9 +83,8 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
         const float h = __expf(x - m) * inv;          // pose_argmax_kernel's take()
         const bool valid = ok && heading_valid(cs, sn);
         heading_take(acc, h, cs, sn, valid);
-        int bin = (int)(pose_angle_deg(cs, sn) * scale);
-        if (bin >= nb) bin -= nb;
-        bin = valid ? min(max(bin, 0), nb - 1) : -1;
+        int bin = heading_bin(cs, sn, scale, nb);     // (tail_shared.h)
+        bin = valid ? bin : -1;
         const unsigned long long q = valid && h > 0.f ? (unsigned long long)(h * 4503599627370496.f) : 0ull;
         if (CCVPE_HEADING_WAVE_COMBINE && __all(bin == __builtin_amdgcn_readfirstlane(bin))) {   // one bin for the wave: one add
             unsigned long long t = q;

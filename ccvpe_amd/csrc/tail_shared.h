@@ -1,6 +1,7 @@
-// Device helpers the output-side kernels share across files (kernels_tail.hip, kernels_heading.hip): the softmax statistics of a
-// sample from its chunk partials, and the fixed-order float64 reduction of the posterior summary - thread -> xor
-// shuffles -> four waves in LDS.  One definition, so the same order of operations and the same bits wherever they are used.
+// Device helpers the output-side kernels share across files (kernels_tail.hip, kernels_heading.hip, kernels_hprior.hip): the softmax
+// statistics of a sample from its chunk partials, the fixed-order float64 reduction of the posterior summary - thread
+// -> xor shuffles -> four waves in LDS - and the heading bin of a field cell.  One definition, so the same order of operations and the
+// same bits wherever they are used.
 #pragma once
 #include "kernels.h"
 #include "ticket.h"
@@ -28,6 +29,16 @@ __device__ __forceinline__ void softmax_stats(const float* partial, int b, int c
         }
         if (threadIdx.x == 0) { gm = m; gs = 1.f / s; }
     }
+}
+
+// The heading of a cell of the orientation field, shared by heading_reduce_kernel and heading_prior_map_kernel: a cell
+// has a heading when c and s are finite and not both zero ...
+__device__ __forceinline__ bool heading_valid(float c, float s) { return isfinite(c) && isfinite(s) && !(c == 0.f && s == 0.f); }
+// ... and its bin of nb (scale = (float)nb / 360.f): a result >= nb wraps, the rest is clamped to [0, nb)
+__device__ __forceinline__ int heading_bin(float c, float s, float scale, int nb) {
+    int bin = (int)(pose_angle_deg(c, s) * scale);
+    if (bin >= nb) bin -= nb;
+    return min(max(bin, 0), nb - 1);
 }
 
 // every thread: its sums -> the wave's (all lanes), lane 0 of each wave -> lds[wave][n]; the caller meets at a barrier, then ...

@@ -912,6 +912,138 @@ class _CVMBase(nn.Module):
         return self._logits_call("postprocess_heading", logits, ori, lambda B: self._heading_args(log_prior, B, radius, bins),
                                  posterior=posterior, summary=summary, heading=self._heading_args(None, 1, radius, bins)[3])
 
+    # ---- heading prior ------------------------------------------------------------
+    @staticmethod
+    def _hprior_table(table, B: int):
+        """heading_log_prior of the heading-prior forms -> (contiguous float32 tensor, table_stride, nb): [nb+1] (one table for every
+        query: stride 0) or [B, nb+1] (stride nb + 1) log-weights, nb in 4..360; entry nb is the weight of a cell without a heading."""
+        if not isinstance(table, torch.Tensor):
+            raise ValueError("heading_log_prior must be a float32 cuda tensor [nb+1] or [B, nb+1]")
+        shape = tuple(table.shape)
+        if len(shape) not in (1, 2) or (len(shape) == 2 and shape[0] != B):
+            raise ValueError(f"heading_log_prior must be [nb+1] or [{B}, nb+1], got {shape}")
+        nb = shape[-1] - 1
+        if not 4 <= nb <= 360:
+            raise ValueError(f"heading_log_prior must hold nb + 1 entries with nb in 4..360, got {shape[-1]}")
+        if table.dtype != torch.float32:
+            raise ValueError(f"heading_log_prior must be float32, got {table.dtype}")
+        if not table.is_contiguous():
+            raise ValueError("heading_log_prior must be contiguous")
+        if not table.is_cuda:
+            raise ValueError(f"heading_log_prior must be a cuda tensor on the inputs' device, not a {table.device.type} tensor")
+        return table.detach(), (nb + 1 if len(shape) == 2 else 0), nb
+
+    @classmethod
+    def _heading_prior_args(cls, table, log_prior, B: int, radius, bins):
+        """The C arguments of the heading-prior forms between batch and the results: (log_prior or None, prior_stride, table,
+        table_stride, nb, radius, bins)."""
+        lp, stride, radius, bins = cls._heading_args(log_prior, B, radius, bins)
+        return (lp, stride) + cls._hprior_table(table, B) + (radius, bins)
+
+    def heading_prior_map(self, ori: torch.Tensor, heading_log_prior: torch.Tensor, log_prior: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The combined prior map [B, 512, 512] of a heading prior and an optional position prior, from a forward's ori
+        ([B, 2, 512, 512]): per cell heading_log_prior[bin of the cell's heading], entry nb for a cell without one, plus log_prior
+        there.  heading_log_prior is [nb+1] or [B, nb+1] (aerial.von_mises_heading_log_prior, heading_predict).  The map is the
+        log_prior of any prior form - postprocess_prior, postprocess_summary, postprocess_heading, track_update_logits.  One launch
+        (ccvpe_heading_prior_map)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(ori, torch.Tensor) or ori.dim() != 4 or ori.shape[0] < 1 or tuple(ori.shape[1:]) != (2,) + spec.OUT_HW:
+            raise ValueError(f"ori must be [B,2,512,512], got {tuple(ori.shape) if isinstance(ori, torch.Tensor) else type(ori)}")
+        B = ori.shape[0]
+        if B > 4096:
+            raise ValueError(f"ori holds {B} fields, at most 4096 per call")
+        lp, stride = self._track_prior(log_prior, B)
+        tb, tstride, nb = self._hprior_table(heading_log_prior, B)
+        if not ori.is_cuda:
+            raise RuntimeError("ccvpe_amd has no CPU path: ori must live on an MI355X (cuda) device")
+        if tb.device != ori.device or (lp is not None and lp.device != ori.device):
+            raise ValueError("ori, heading_log_prior and log_prior must be on one device")
+        ori = ori.detach().to(torch.float32).contiguous()
+        dev = ori.device
+        self._ensure_handle(dev)
+        with torch.cuda.device(dev):
+            out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().ccvpe_heading_prior_map(self._handle, C.c_void_p(ori.data_ptr()), B,
+                                                     C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
+                                                     C.c_void_p(tb.data_ptr()), tstride, nb, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_heading_prior_map")
+        return out
+
+    def localize_heading_prior(self, grd: torch.Tensor, sat: torch.Tensor, heading_log_prior: torch.Tensor,
+                               log_prior: Optional[torch.Tensor] = None, radius: int = 8, bins: int = 72, summary: bool = False,
+                               posterior: bool = False):
+        """localize_heading under a heading prior: what localize_heading(grd, sat, comb, radius, bins, summary, posterior) returns for
+        comb = heading_prior_map(ori, heading_log_prior, log_prior), without the detour through the full forward's outputs - bit for
+        bit.  heading_log_prior [nb+1] or [B, nb+1]; nb is independent of bins.  One launch more than localize_heading; the carried
+        heading belief is treated as independent of the position (ccvpe_localize_heading_prior)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        own = self._heading_prior_args(heading_log_prior, log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
+        return self._call("localize_heading_prior", grd, sat, args=lambda B: own, posterior=posterior, summary=summary, heading=own[6])
+
+    def localize_heading_prior_cached(self, grd: torch.Tensor, cache: torch.Tensor, heading_log_prior: torch.Tensor,
+                                      log_prior: Optional[torch.Tensor] = None, radius: int = 8, bins: int = 72, summary: bool = False,
+                                      posterior: bool = False, tile_index=None):
+        """localize_heading_prior with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
+        (ccvpe_localize_heading_prior_cached_indexed)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        own = self._heading_prior_args(heading_log_prior, log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
+        return self._call("localize_heading_prior_cached_indexed", grd, cache=cache, tile_index=tile_index, args=lambda B: own,
+                          posterior=posterior, summary=summary, heading=own[6])
+
+    def heading_predict(self, hist: torch.Tensor, turn_deg, taps, floor) -> torch.Tensor:
+        """The predict half of a filter step on the heading axis: the heading prior [B, nb+1] of the next frame from a hist [B, nb]
+        (localize_heading's).  hist is turned by turn_deg (a number or [B]: the heading change since that frame, positive when the
+        heading angle grows) with linear weights between the two source bins, blurred on the circle with the one-sided taps
+        t[0..radius] ([radius+1] or [B, radius+1]; aerial.gaussian_taps, 2 radius + 1 <= nb), and the result is log(. + floor), floor a
+        number or [B], >= 0; the last entry, for a cell without a heading, is what the average bin gets: the definition in
+        include/ccvpe.h (ccvpe_heading_predict).  One launch.  turn_deg, taps and floor may be host data or tensors on hist's device."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(hist, torch.Tensor) or hist.dim() != 2 or hist.shape[0] < 1:
+            raise ValueError("hist must be a float32 cuda tensor [B, nb]")
+        B, nb = int(hist.shape[0]), int(hist.shape[1])
+        if not 4 <= nb <= 360:
+            raise ValueError(f"hist must hold nb in 4..360 bins, got {nb}")
+        if hist.dtype != torch.float32:
+            raise ValueError(f"hist must be float32, got {hist.dtype}")
+        if not hist.is_contiguous():
+            raise ValueError("hist must be contiguous")
+        if B > 4096:
+            raise ValueError(f"hist holds {B} rows, at most 4096 per call")
+        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
+        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
+            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
+        radius = int(tshape[-1]) - 1
+        if radius > 32 or 2 * radius + 1 > nb:
+            raise ValueError(f"taps give radius {radius}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
+        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
+        if fshape == () and not float(floor) >= 0.0:
+            raise ValueError(f"floor must be >= 0, got {floor}")
+        scalar_turn = np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor)
+        dev = hist.device
+        host = torch.device("cpu")
+        # shapes and values first (so that they are refused without a device), then the copies
+        tp = self._track_vec(taps, "taps", tshape, host if not hist.is_cuda else dev)
+        tn = (torch.full((B,), float(turn_deg), dtype=torch.float32, device=dev) if scalar_turn
+              else self._track_vec(turn_deg, "turn_deg", (B,), dev))
+        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
+              else self._track_vec(floor, "floor", (B,), dev))
+        if not hist.is_cuda:
+            raise ValueError(f"hist must be a cuda tensor, not a {hist.device.type} tensor")
+        self._ensure_handle(dev)
+        out = torch.empty((B, nb + 1), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            rc = _lib.load().ccvpe_heading_predict(self._handle, C.c_void_p(hist.detach().data_ptr()), B, nb, C.c_void_p(tn.data_ptr()),
+                                                   C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
+                                                   C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_heading_predict")
+        return out
+
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Device-side version of the per-sample loop in train_VIGOR.py:297-316.  The argmax is the largest value above -inf, the first

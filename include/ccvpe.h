@@ -456,6 +456,53 @@ int ccvpe_postprocess_heading(ccvpe_handle h, const float* logits, const float* 
                               int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading, float* hist,
                               float* summary, float* posterior, void* stream);
 
+/* Heading prior: information about the heading coming in - a compass reading, a gyro-propagated heading, the heading posterior of
+ * the last frame.  The orientation field is the network's p(heading | position), so a prior over the heading is a per-cell
+ * log-weight on the position grid.  The heading prior of a query is a table T of nb + 1 float32 log-weights in DEVICE memory, nb in
+ * 4..360: entry b < nb belongs to heading bin b of the definition above ([b w, (b + 1) w), w = 360 / nb, the same angle and the
+ * same binning code as hist), entry nb to a cell without a heading (an invalid cell of that definition).  Log-weights need not be
+ * normalised; -inf excludes a bin.  table_stride is 0 (one table for every query) or nb + 1.  Per cell i of query b
+ *     k_i = valid(c_i, s_i) ? bin_nb(c_i, s_i) : nb,     comb_i = T[k_i],  or  fl32(P_i + T[k_i]) with a position prior P
+ * (one IEEE float add), and everything downstream is the position prior's definition with log_prior := comb, prior_stride :=
+ * 512 * 512: l' = fl32(l + comb), the softmax statistics, the posterior h', and rows, summary, heading and hist of that posterior.
+ * Every heading-prior form is bit-equal to the matching prior form fed the combined map; a query without a finite posterior - a
+ * +inf or NaN in T on a bin some cell uses, every used entry -inf - gets the rows of that rule.  Cells within about 1e-3 degree of
+ * a bin edge may take either neighbour's weight.  The approximation: the carried heading belief is treated as independent of the
+ * position.
+ *   ccvpe_heading_prior_map: one launch on forward outputs the caller holds (ori [batch][2][512*512]); out_map [batch][512*512]
+ *     feeds any logits form (ccvpe_postprocess_prior, top-K included, _summary, _heading, ccvpe_track_update_logits) as its
+ *     log_prior with stride 512 * 512.  log_prior may be NULL.  batch <= 4096, any handle, no scratch.
+ *   ccvpe_localize_heading_prior, ccvpe_localize_heading_prior_cached_indexed: the outputs of ccvpe_localize_heading* of the
+ *     posterior under both priors; nbins, the output histogram's bin count, is independent of nb.  tile_index may be NULL.  They
+ *     run the heading plans with comb in the workspace and one launch more; the localisation tail then waits for the orientation
+ *     decoder.  log_prior, summary and posterior may be NULL.
+ *   ccvpe_heading_predict: the predict step on the heading axis, one launch.  hist [batch][nb] (non-negative: the hist of the
+ *     last frame), turn_deg [batch] the heading change since that frame (positive: the heading angle grows), one-sided taps
+ *     t[0..radius] (taps_stride 0 or radius + 1), floor [batch] >= 0, all DEVICE float32; out [batch][nb + 1], not aliasing hist.
+ *     On the circle of nb bins: u = b - turn_deg / (360 / nb) in float64, i0 = floor(u), f = (float)(u - i0),
+ *     s(b) = (1 - f) hist[i0 mod nb] + f hist[(i0 + 1) mod nb] (f == 0 weighs the one source bin with exactly 1), c = s circularly
+ *     convolved with t[|j|], j = -radius..radius (2 radius + 1 fused multiply-adds), out[b] = logf(c(b) + floor) and
+ *     out[nb] = logf((float)(float64 sum of c / nb) + floor): a cell without a heading weighs what the average bin does.  radius in
+ *     0..32 with 2 radius + 1 <= nb.  An all-zero hist gives logf(floor) everywhere.  A non-finite turn_deg may give NaN, never a
+ *     read outside hist.  batch 1..4096, any handle.
+ * CCVPE_EINVAL, nothing launched, checked before the handle is used: a null pointer (log_prior, summary, posterior and tile_index
+ * excepted), nb outside 4..360, table_stride other than 0 or nb + 1, radius outside its range or 2 radius + 1 > nb, a bad
+ * taps_stride, the batch range, out_map equal to ori, log_prior or table, out == hist, a table that is an output, then the checks
+ * of the matching heading form.  A debug handle gets CCVPE_ESTATE on the two network forms. */
+int ccvpe_heading_prior_map(ccvpe_handle h, const float* ori, int32_t batch, const float* log_prior, int64_t prior_stride,
+                            const float* table, int32_t table_stride, int32_t nb, float* out_map, void* stream);
+int ccvpe_localize_heading_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                                 const float* log_prior, int64_t prior_stride, const float* table, int32_t table_stride, int32_t nb,
+                                 int32_t radius, int32_t nbins, float* rows, float* heading, float* hist, float* summary,
+                                 float* posterior, void* stream);
+int ccvpe_localize_heading_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                                int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                                int64_t prior_stride, const float* table, int32_t table_stride, int32_t nb,
+                                                int32_t radius, int32_t nbins, float* rows, float* heading, float* hist,
+                                                float* summary, float* posterior, void* stream);
+int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int32_t nb, const float* turn_deg, const float* taps,
+                          int32_t taps_stride, int32_t radius, const float* floor, float* out, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
