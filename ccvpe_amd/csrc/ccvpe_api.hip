@@ -419,22 +419,8 @@ static int run_forward(ccvpe_handle h, const ForwardCall& fc) {
         if (fc.tile_index) { c.tile_index = fc.tile_index + done; c.n_tiles = fc.n_tiles; }   // every slice reads its own indices of the one cache
         c.grd = fc.grd + (size_t)done * 3 * fc.gh * fc.gw;
         c.sat = fc.sat ? fc.sat + (size_t)done * 3 * CCVPE_SAT_HW * CCVPE_SAT_HW : nullptr;
-        if (fc.log_prior) { c.log_prior = fc.log_prior + (size_t)done * fc.prior_stride; c.prior_stride = fc.prior_stride; }
-        if (fc.posterior) c.posterior = fc.posterior + (size_t)done * npx;
-        if (fc.summary) { c.summary = fc.summary + (size_t)done * SUMMARY_COLS; c.summary_r = fc.summary_r; }
-        if (fc.heading) {
-            c.heading = fc.heading + (size_t)done * HEADING_COLS; c.hist = fc.hist + (size_t)done * fc.heading_bins;
-            c.heading_bins = fc.heading_bins; c.heading_r = fc.heading_r;
-        }
-        if (key.hprior) {   // (a per-query table: every slice its own rows)
-            c.hprior_table = fc.hprior_table + (size_t)done * fc.hprior_stride; c.hprior_stride = fc.hprior_stride; c.hprior_nb = fc.hprior_nb;
-        }
-        if (key.topk) {
-            c.rows = fc.rows + (size_t)done * fc.topk_k * 5;
-            c.topk_k = fc.topk_k; c.topk_r = fc.topk_r;
-        } else if (key.pose) {
-            c.rows = fc.rows + (size_t)done * 5;
-        } else {
+        c.tail = fc.tail.at(done);
+        if (!key.pose) {
             c.out.logits_flattened = fc.out->logits_flattened + done * npx;
             c.out.heatmap = fc.out->heatmap + done * npx;
             c.out.ori = fc.out->ori + done * 2 * npx;
@@ -468,7 +454,7 @@ int ccvpe_forward(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w
 int ccvpe_localize(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch, float* rows, void* stream) {
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.sat = sat; fc.rows = rows;
+    fc.sat = sat; fc.tail.rows = rows;
     return run_forward(h, fc);
 }
 
@@ -484,7 +470,7 @@ int ccvpe_localize_topk(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_topk_args(k, radius)) return rc;
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.sat = sat; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    fc.sat = sat; fc.tail.rows = rows; fc.tail.topk_k = k; fc.tail.topk_r = radius;
     return run_forward(h, fc);
 }
 
@@ -533,19 +519,22 @@ static int ensure_scratch(ccvpe_handle_s::Scratch& buf, int batch, size_t (*byte
 // [B x 64 x 4 float64 sums of the heading form][B x 360 fixed-point histogram bins of the heading form, zero between launches like the
 // counters]; the argmax form's (max, index) hand-off pairs use the start of the key area.  Every area is a multiple of 8 bytes long.
 static size_t prior_scratch_bytes(int B) {
-    return topk_scratch_bytes(B) + (size_t)B * 64 * 2 * sizeof(float) + (size_t)B * 64 * SUMMARY_PART * sizeof(double) +
-           (size_t)B * 64 * HEADING_PART * sizeof(double) + (size_t)B * HEADING_MAX_BINS * sizeof(unsigned long long);
+    return topk_scratch_bytes(B) + (size_t)B * TAIL_CHUNKS * 2 * sizeof(float) + (size_t)B * TAIL_CHUNKS * SUMMARY_PART * sizeof(double) +
+           (size_t)B * TAIL_CHUNKS * HEADING_PART * sizeof(double) + (size_t)B * HEADING_MAX_BINS * sizeof(unsigned long long);
 }
-struct TopkScratch { unsigned* tickets; unsigned long long* keys; int* index; float* partial; double* summ; double* head; unsigned long long* bins; };
-static TopkScratch topk_scratch_layout(const ccvpe_handle_s::Scratch& buf) {
-    TopkScratch w;
-    w.tickets = reinterpret_cast<unsigned*>(buf.ptr);
-    w.keys = reinterpret_cast<unsigned long long*>(w.tickets + PP_MAX_BATCH);
-    w.index = reinterpret_cast<int*>(w.keys + (size_t)buf.batch * 64 * TOPK_MAX_K);
+// ... as the tail's working memory over the forward outputs the caller holds.  pose.argmax and pose.heading share the one ticket
+// range: they run in order on one stream, and each leaves its counters at zero
+static TailBuffers scratch_buffers(const ccvpe_handle_s::Scratch& buf, const float* logits, const float* ori) {
+    TailBuffers w;
+    w.logits = logits; w.ori = ori;
+    w.tickets = w.head_tickets = reinterpret_cast<unsigned*>(buf.ptr);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(w.tickets + PP_MAX_BATCH);
+    w.keys = keys;
+    w.index = reinterpret_cast<int*>(keys + (size_t)buf.batch * TAIL_CHUNKS * TOPK_MAX_K);
     w.partial = reinterpret_cast<float*>(w.index + (size_t)buf.batch * TOPK_MAX_K);
-    w.summ = reinterpret_cast<double*>(w.partial + (size_t)buf.batch * 64 * 2);   // (read by the summary forms alone)
-    w.head = w.summ + (size_t)buf.batch * 64 * SUMMARY_PART;                      // (these two by the heading form alone)
-    w.bins = reinterpret_cast<unsigned long long*>(w.head + (size_t)buf.batch * 64 * HEADING_PART);
+    w.summ_part = reinterpret_cast<double*>(w.partial + (size_t)buf.batch * TAIL_CHUNKS * 2);   // (read by the summary forms alone)
+    w.head_part = w.summ_part + (size_t)buf.batch * TAIL_CHUNKS * SUMMARY_PART;               // (these two by the heading form alone)
+    w.bins = reinterpret_cast<unsigned long long*>(w.head_part + (size_t)buf.batch * TAIL_CHUNKS * HEADING_PART);
     return w;
 }
 
@@ -575,10 +564,10 @@ int ccvpe_postprocess_topk(ccvpe_handle h, const float* heatmap, const float* or
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "bad argument (batch 1 .. 4096)");
     HIPCHK(hipSetDevice(h->cfg.device));
     if (int rc = ensure_scratch(h->topk_scratch, batch, topk_scratch_bytes, "top-K post-processing scratch")) return rc;
-    const TopkScratch w = topk_scratch_layout(h->topk_scratch);   // (no partials: the peaks come from the heatmap)
+    const TailBuffers w = scratch_buffers(h->topk_scratch, nullptr, ori);   // (tickets, keys and indices only: the peaks come from the heatmap)
     TopkParams p{};
     p.heat = heatmap; p.logits = nullptr; p.partial = nullptr; p.B = batch; p.k = k; p.r = radius;
-    p.keys = w.keys; p.tickets = w.tickets; p.index = w.index; p.rows = rows;
+    p.keys = reinterpret_cast<unsigned long long*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = rows;
     launch_topk_peaks(p, (hipStream_t)stream);
     launch_topk_gather(ori, w.index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, (hipStream_t)stream);
     return launch_status("postprocess_topk launch");
@@ -688,7 +677,7 @@ int ccvpe_localize_cached(ccvpe_handle h, const float* grd, int32_t grd_h, int32
     if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.cache = (const float*)cache; fc.rows = rows;
+    fc.cache = (const float*)cache; fc.tail.rows = rows;
     return run_forward(h, fc);
 }
 
@@ -698,7 +687,7 @@ int ccvpe_localize_topk_cached(ccvpe_handle h, const float* grd, int32_t grd_h, 
     if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
     if (int rc = check_topk_args(k, radius)) return rc;
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.cache = (const float*)cache; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    fc.cache = (const float*)cache; fc.tail.rows = rows; fc.tail.topk_k = k; fc.tail.topk_r = radius;
     return run_forward(h, fc);
 }
 
@@ -742,7 +731,7 @@ int ccvpe_localize_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_
                                   const int32_t* tile_index, int32_t batch, float* rows, void* stream) {
     if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.rows = rows;
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.tail.rows = rows;
     return run_forward(h, fc);
 }
 
@@ -752,7 +741,7 @@ int ccvpe_localize_topk_cached_indexed(ccvpe_handle h, const float* grd, int32_t
     if (int rc = check_indexed_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
     if (int rc = check_topk_args(k, radius)) return rc;
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius;
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles; fc.tail.rows = rows; fc.tail.topk_k = k; fc.tail.topk_r = radius;
     return run_forward(h, fc);
 }
 
@@ -809,12 +798,12 @@ static int run_region(ccvpe_handle h, const void* grd_cache, int32_t n_queries, 
         for (int p = offsets[g]; p < offsets[g + 1]; ++p) query[p] = g;
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
+    TailCall pairs;
+    pairs.rows = pair_rows; pairs.stats = pair_stats; pairs.log_prior = pair_log_prior; pairs.prior_stride = pair_log_prior ? prior_stride : 0;
     auto slice = [&](Plan* pl, Ctx& c, int done, int) {
         c.cache_in = (const float*)sat_cache; c.tile_index = tiles + done; c.n_tiles = n_tiles;
         c.grd_cache_in = (const float*)grd_cache; c.query_index = query.data() + done; c.n_queries = n_queries;
-        c.rows = pair_rows + (size_t)done * 5;
-        c.stats = pair_stats + (size_t)done * 2;
-        if (pair_log_prior) { c.log_prior = pair_log_prior + (size_t)done * prior_stride; c.prior_stride = prior_stride; }
+        c.tail = pairs.at(done);
         return run_ops(h, *pl, c, s);
     };
     PlanKey key;   // (B: set per slice by the micro-batch loop)
@@ -864,7 +853,7 @@ int ccvpe_localize_prior(ccvpe_handle h, const float* grd, int32_t grd_h, int32_
     if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.sat = sat; fc.rows = rows; fc.topk_k = k; fc.topk_r = radius; fc.log_prior = log_prior; fc.prior_stride = prior_stride;
+    fc.sat = sat; fc.tail.rows = rows; fc.tail.topk_k = k; fc.tail.topk_r = radius; fc.tail.log_prior = log_prior; fc.tail.prior_stride = prior_stride;
     return run_forward(h, fc);
 }
 
@@ -876,32 +865,27 @@ int ccvpe_localize_prior_cached_indexed(ccvpe_handle h, const float* grd, int32_
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
-    fc.rows = rows; fc.topk_k = k; fc.topk_r = radius; fc.log_prior = log_prior; fc.prior_stride = prior_stride;
+    fc.tail.rows = rows; fc.tail.topk_k = k; fc.tail.topk_r = radius; fc.tail.log_prior = log_prior; fc.tail.prior_stride = prior_stride;
     return run_forward(h, fc);
 }
 
-// The logits-based tails over forward outputs the caller holds, in the prior scratch `w`.  softmax.partial (logits + prior): the first
-// launch of both ...
-static void launch_logits_softmax(const TopkScratch& w, const float* logits, int batch, const float* prior, long long stride, hipStream_t s) {
-    SoftmaxParams sp{};
-    sp.logits = logits; sp.B = batch; sp.n = CCVPE_OUT_HW * CCVPE_OUT_HW; sp.partial = w.partial; sp.chunks = 64; sp.out = nullptr;
-    sp.prior = prior; sp.prior_stride = stride;
-    launch_softmax_partial(sp, s);
-}
-
-// ... and softmax.partial -> pose.argmax -> pose.gather, the tail of an argmax pose plan (build_plan): prior, posterior and summary
-// (with its window radius) are optional
-static void launch_logits_argmax(const TopkScratch& w, const float* logits, const float* ori, int batch, const float* prior, long long stride,
-                                 float* posterior, float* rows, hipStream_t s, float* summary = nullptr, int summary_r = 0) {
+// The logits forms: the tail of a pose plan (build_plan) over forward outputs the caller holds, in the prior scratch - softmax.partial,
+// pose.argmax or topk.peaks, the gather, and pose.heading when the call asks for it
+static int run_logits_tail(ccvpe_handle h, const float* logits, const float* ori, int batch, const TailCall& t, hipStream_t s) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    const TailBuffers w = scratch_buffers(h->prior_scratch, logits, ori);
     const int n = CCVPE_OUT_HW * CCVPE_OUT_HW;
-    launch_logits_softmax(w, logits, batch, prior, stride, s);
-    PoseArgmaxParams p{};
-    p.logits = logits; p.partial = w.partial; p.B = batch; p.n = n; p.chunks = 64;
-    p.pairs = reinterpret_cast<float*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = rows; p.stats = nullptr;
-    p.prior = prior; p.prior_stride = stride; p.posterior = posterior;
-    if (summary) { p.summary = summary; p.summ_part = w.summ; p.summary_r = summary_r; }
-    launch_pose_argmax(p, s);
-    launch_pose_gather(ori, w.index, batch, n, rows, s);
+    issue_softmax_partial(w, t, batch, s);
+    if (t.topk_k > 0) {
+        issue_topk_peaks(w, t, batch, s);
+        launch_topk_gather(ori, w.index, batch, t.topk_k, n, t.rows, s);
+    } else {
+        issue_pose_argmax(w, t, batch, s);
+        launch_pose_gather(ori, w.index, batch, n, t.rows, s);
+    }
+    if (t.heading) issue_pose_heading(w, t, batch, s);   // (behind pose.argmax on the same stream: its counters are back at zero, its index is written)
+    return 0;
 }
 
 int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
@@ -912,21 +896,9 @@ int ccvpe_postprocess_prior(ccvpe_handle h, const float* logits, const float* or
     if (int rc = check_prior_args(log_prior, prior_stride, k, radius)) return rc;
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
-    hipStream_t s = (hipStream_t)stream;
-    if (k == 0) {
-        launch_logits_argmax(w, logits, ori, batch, log_prior, prior_stride, nullptr, rows, s);
-    } else {
-        launch_logits_softmax(w, logits, batch, log_prior, prior_stride, s);
-        TopkParams p{};
-        p.heat = nullptr; p.logits = logits; p.partial = w.partial; p.B = batch; p.k = k; p.r = radius;
-        p.keys = w.keys; p.tickets = w.tickets; p.index = w.index; p.rows = rows;
-        p.prior = log_prior; p.prior_stride = prior_stride;
-        launch_topk_peaks(p, s);
-        launch_topk_gather(ori, w.index, batch, k, CCVPE_OUT_HW * CCVPE_OUT_HW, rows, s);
-    }
+    TailCall t;
+    t.rows = rows; t.topk_k = k; t.topk_r = radius; t.log_prior = log_prior; t.prior_stride = prior_stride;
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
     return launch_status("postprocess_prior launch");
 }
 
@@ -935,9 +907,9 @@ int ccvpe_op_pose_rows(ccvpe_handle h, const float* logits, const float* ori, in
     if (!logits || !ori || !rows) return ccvpe_fail(CCVPE_EINVAL, "null argument");
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, nullptr, 0, nullptr, rows, (hipStream_t)stream);
+    TailCall t;
+    t.rows = rows;
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
     return launch_status("op_pose_rows launch");
 }
 
@@ -972,7 +944,7 @@ int ccvpe_track_update(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t 
     if (int rc = check_track_update_args(log_prior, prior_stride, rows, posterior)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.sat = sat; fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    fc.sat = sat; fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
     return run_forward(h, fc);
 }
 
@@ -984,7 +956,7 @@ int ccvpe_track_update_cached_indexed(ccvpe_handle h, const float* grd, int32_t 
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
-    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
+    fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
     return run_forward(h, fc);
 }
 
@@ -996,25 +968,39 @@ int ccvpe_track_update_logits(ccvpe_handle h, const float* logits, const float* 
     if (posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, log_prior, log_prior ? prior_stride : 0, posterior, rows,
-                         (hipStream_t)stream);
+    TailCall t;
+    t.rows = rows; t.log_prior = log_prior; t.prior_stride = log_prior ? prior_stride : 0; t.posterior = posterior;
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
     return launch_status("track_update_logits launch");
 }
 
-int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps, int32_t taps_stride,
-                        int32_t radius, const float* floor, float* log_prior, void* stream) {
-    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
-    if (!shift) return ccvpe_fail(CCVPE_EINVAL, "null shift");
+// The arguments the predict steps share (ccvpe_track_predict, ccvpe_track_predict_affine, ccvpe_heading_predict), checked in the order
+// every one of them always had: the five pointers by their names, then the blur's radius, the taps' stride and the batch.  circle: the
+// bins of a blur on the circle, which must not wrap onto itself (0: a blur on the plane)
+static int check_predict_ptrs(const void* in, const char* in_name, const void* motion, const char* motion_name, const void* taps,
+                              const void* floor, const void* out, const char* out_name) {
+    if (!in) return ccvpe_fail(CCVPE_EINVAL, "null %s", in_name);
+    if (!motion) return ccvpe_fail(CCVPE_EINVAL, "null %s", motion_name);
     if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
     if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
-    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
+    if (!out) return ccvpe_fail(CCVPE_EINVAL, "null %s", out_name);
+    return 0;
+}
+static int check_predict_blur(int32_t radius, int32_t taps_stride, int32_t batch, int32_t circle = 0) {
     if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
+    if (circle && 2 * radius + 1 > circle)
+        return ccvpe_fail(CCVPE_EINVAL, "radius %d needs 2 radius + 1 <= nb = %d: the blur must not wrap onto itself", radius, circle);
     if (taps_stride != 0 && taps_stride != radius + 1)
         return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
                           taps_stride);
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    return 0;
+}
+
+int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, const float* shift, const float* taps, int32_t taps_stride,
+                        int32_t radius, const float* floor, float* log_prior, void* stream) {
+    if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, log_prior, "log_prior")) return rc;
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
     if (log_prior == belief) return ccvpe_fail(CCVPE_EINVAL, "log_prior must not alias belief");
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -1029,16 +1015,8 @@ int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, cons
 // is not re-routed to track_predict_kernel; choosing is the caller's business.
 int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batch, const double* matrix, const float* taps,
                                int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream) {
-    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
-    if (!matrix) return ccvpe_fail(CCVPE_EINVAL, "null matrix");
-    if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
-    if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
-    if (!log_prior) return ccvpe_fail(CCVPE_EINVAL, "null log_prior");
-    if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
-    if (taps_stride != 0 && taps_stride != radius + 1)
-        return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
-                          taps_stride);
-    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (int rc = check_predict_ptrs(belief, "belief", matrix, "matrix", taps, floor, log_prior, "log_prior")) return rc;
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
     if (log_prior == belief) return ccvpe_fail(CCVPE_EINVAL, "log_prior must not alias belief");
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
@@ -1075,8 +1053,8 @@ int ccvpe_localize_summary(ccvpe_handle h, const float* grd, int32_t grd_h, int3
     if (int rc = check_summary_args(log_prior, prior_stride, radius, rows, summary, posterior)) return rc;
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
-    fc.sat = sat; fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
-    fc.summary = summary; fc.summary_r = radius;
+    fc.sat = sat; fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
+    fc.tail.summary = summary; fc.tail.summary_r = radius;
     return run_forward(h, fc);
 }
 
@@ -1088,8 +1066,8 @@ int ccvpe_localize_summary_cached_indexed(ccvpe_handle h, const float* grd, int3
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
-    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
-    fc.summary = summary; fc.summary_r = radius;
+    fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
+    fc.tail.summary = summary; fc.tail.summary_r = radius;
     return run_forward(h, fc);
 }
 
@@ -1101,10 +1079,10 @@ int ccvpe_postprocess_summary(ccvpe_handle h, const float* logits, const float* 
     if (posterior && posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    launch_logits_argmax(topk_scratch_layout(h->prior_scratch), logits, ori, batch, log_prior, log_prior ? prior_stride : 0, posterior, rows,
-                         (hipStream_t)stream, summary, radius);
+    TailCall t;
+    t.rows = rows; t.log_prior = log_prior; t.prior_stride = log_prior ? prior_stride : 0; t.posterior = posterior;
+    t.summary = summary; t.summary_r = radius;
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
     return launch_status("postprocess_summary launch");
 }
 
@@ -1118,9 +1096,9 @@ int ccvpe_belief_summary(ccvpe_handle h, const float* belief, int32_t batch, int
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
     if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
+    const TailBuffers w = scratch_buffers(h->prior_scratch, nullptr, nullptr);
     BeliefSummaryParams p{};
-    p.belief = belief; p.B = batch; p.r = radius; p.pairs = reinterpret_cast<float*>(w.keys); p.summ_part = w.summ; p.tickets = w.tickets;
+    p.belief = belief; p.B = batch; p.r = radius; p.pairs = reinterpret_cast<float*>(w.keys); p.summ_part = w.summ_part; p.tickets = w.tickets;
     p.summary = summary;
     launch_belief_summary(p, (hipStream_t)stream);
     return launch_status("belief_summary launch");
@@ -1151,11 +1129,13 @@ static int check_heading_args(const float* log_prior, int64_t prior_stride, int3
     return 0;
 }
 
-static void heading_call(ForwardCall& fc, const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, float* rows,
-                         float* heading, float* hist, float* summary, float* posterior) {
-    fc.rows = rows; fc.log_prior = log_prior; fc.prior_stride = log_prior ? prior_stride : 0; fc.posterior = posterior;
-    fc.summary = summary; fc.summary_r = radius;
-    fc.heading = heading; fc.hist = hist; fc.heading_bins = nbins; fc.heading_r = radius;
+static TailCall heading_call(const float* log_prior, int64_t prior_stride, int32_t radius, int32_t nbins, float* rows, float* heading,
+                             float* hist, float* summary, float* posterior) {
+    TailCall t;
+    t.rows = rows; t.log_prior = log_prior; t.prior_stride = log_prior ? prior_stride : 0; t.posterior = posterior;
+    t.summary = summary; t.summary_r = radius;
+    t.heading = heading; t.hist = hist; t.heading_bins = nbins; t.heading_r = radius;
+    return t;
 }
 
 int ccvpe_localize_heading(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
@@ -1167,7 +1147,7 @@ int ccvpe_localize_heading(ccvpe_handle h, const float* grd, int32_t grd_h, int3
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.sat = sat;
-    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.tail = heading_call(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
     return run_forward(h, fc);
 }
 
@@ -1180,7 +1160,7 @@ int ccvpe_localize_heading_cached_indexed(ccvpe_handle h, const float* grd, int3
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
-    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.tail = heading_call(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
     return run_forward(h, fc);
 }
 
@@ -1195,15 +1175,8 @@ int ccvpe_postprocess_heading(ccvpe_handle h, const float* logits, const float* 
         return ccvpe_fail(CCVPE_EINVAL, "heading and hist must not alias logits or ori");
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
-    const TopkScratch w = topk_scratch_layout(h->prior_scratch);
-    const long long stride = log_prior ? prior_stride : 0;
-    launch_logits_argmax(w, logits, ori, batch, log_prior, stride, posterior, rows, (hipStream_t)stream, summary, radius);
-    HeadingParams p{};   // (behind pose.argmax on the same stream: its counters are back at zero, its index is written)
-    p.logits = logits; p.partial = w.partial; p.prior = log_prior; p.prior_stride = stride; p.ori = ori; p.index = w.index;
-    p.B = batch; p.nbins = nbins; p.r = radius; p.part = w.head; p.bins = w.bins; p.tickets = w.tickets; p.heading = heading; p.hist = hist;
-    launch_heading_reduce(p, (hipStream_t)stream);
+    const TailCall t = heading_call(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
     return launch_status("postprocess_heading launch");
 }
 
@@ -1263,8 +1236,8 @@ int ccvpe_localize_heading_prior(ccvpe_handle h, const float* grd, int32_t grd_h
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.sat = sat;
-    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
-    fc.hprior_table = table; fc.hprior_stride = table_stride; fc.hprior_nb = nb;
+    fc.tail = heading_call(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.tail.hprior_table = table; fc.tail.hprior_stride = table_stride; fc.tail.hprior_nb = nb;
     return run_forward(h, fc);
 }
 
@@ -1279,26 +1252,17 @@ int ccvpe_localize_heading_prior_cached_indexed(ccvpe_handle h, const float* grd
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
     fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
-    heading_call(fc, log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
-    fc.hprior_table = table; fc.hprior_stride = table_stride; fc.hprior_nb = nb;
+    fc.tail = heading_call(log_prior, prior_stride, radius, nbins, rows, heading, hist, summary, posterior);
+    fc.tail.hprior_table = table; fc.tail.hprior_stride = table_stride; fc.tail.hprior_nb = nb;
     return run_forward(h, fc);
 }
 
 int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int32_t nb, const float* turn_deg, const float* taps,
                           int32_t taps_stride, int32_t radius, const float* floor, float* out, void* stream) {
-    if (!hist) return ccvpe_fail(CCVPE_EINVAL, "null hist");
-    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
-    if (!taps) return ccvpe_fail(CCVPE_EINVAL, "null taps");
-    if (!floor) return ccvpe_fail(CCVPE_EINVAL, "null floor");
-    if (!out) return ccvpe_fail(CCVPE_EINVAL, "null out");
+    if (int rc = check_predict_ptrs(hist, "hist", turn_deg, "turn_deg", taps, floor, out, "out")) return rc;
     if (nb < HEADING_MIN_BINS || nb > HEADING_MAX_BINS)
         return ccvpe_fail(CCVPE_EINVAL, "nb must be in %d .. %d, got %d", HEADING_MIN_BINS, HEADING_MAX_BINS, nb);
-    if (radius < 0 || radius > TRACK_MAX_R) return ccvpe_fail(CCVPE_EINVAL, "radius must be in 0 .. %d, got %d", TRACK_MAX_R, radius);
-    if (2 * radius + 1 > nb) return ccvpe_fail(CCVPE_EINVAL, "radius %d needs 2 radius + 1 <= nb = %d: the blur must not wrap onto itself", radius, nb);
-    if (taps_stride != 0 && taps_stride != radius + 1)
-        return ccvpe_fail(CCVPE_EINVAL, "taps_stride must be 0 (one set of taps) or radius + 1 = %d (one per query), got %d", radius + 1,
-                          taps_stride);
-    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (int rc = check_predict_blur(radius, taps_stride, batch, nb)) return rc;
     if (out == hist) return ccvpe_fail(CCVPE_EINVAL, "out must not alias hist");
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));

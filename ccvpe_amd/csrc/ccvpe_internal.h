@@ -248,6 +248,59 @@ struct Tensor {
     long long numel() const { return (long long)B * H * W * C; }
 };
 
+// ------------------------------------------------------------------------------------------------
+// The pose tail (softmax.partial -> pose.argmax or topk.peaks -> gather -> pose.heading): what a call asks of it, where its working
+// memory is, and the four launches.  One definition for the plans (build_plan) and for the logits forms on the prior scratch
+// (ccvpe_api.hip); every field is checked by the entry point that sets it.
+// ------------------------------------------------------------------------------------------------
+struct TailCall {
+    float* rows = nullptr;             // [batch][5] result rows; top-K: [batch][topk_k][5]
+    int topk_k = 0, topk_r = 0;        // topk_k > 0: the top-K tail (ccvpe_localize_topk*), hypotheses per query 1..64 and suppression radius 0..32
+    const float* log_prior = nullptr;  // optional log-prior ...
+    long long prior_stride = 0;        // ... and the floats between two queries' maps (0: one map for all)
+    float* stats = nullptr;            // optional [batch][2] softmax (max, 1/sum) of each query (ccvpe_localize_region)
+    float* posterior = nullptr;        // optional posterior maps [batch][512*512] (ccvpe_track_update*)
+    float* summary = nullptr;          // optional [batch][16] summary rows (ccvpe_*_summary); selects the summary plans ...
+    int summary_r = 0;                 // ... and their window radius 0..32
+    float* heading = nullptr;          // optional [batch][12] heading rows (ccvpe_*_heading) and
+    float* hist = nullptr;             //   [batch][heading_bins] histograms; select the heading plans ...
+    int heading_bins = 0, heading_r = 0;   // ... the bin count 4..360 and the window radius 0..32
+    const float* hprior_table = nullptr;   // heading plans, optional (ccvpe_localize_heading_prior*): the heading prior's tables,
+    int hprior_stride = 0, hprior_nb = 0;  //   the floats between two queries' tables (0: one for all) and the table's bins 4..360
+    // the view of the micro-batch that starts at query `done`: every per-query buffer advanced by its own row size
+    TailCall at(int done) const {
+        const size_t d = (size_t)done, npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
+        TailCall t = *this;
+        if (rows) t.rows += d * (topk_k > 0 ? topk_k : 1) * 5;
+        if (log_prior) t.log_prior += d * prior_stride;
+        if (stats) t.stats += d * 2;
+        if (posterior) t.posterior += d * npx;
+        if (summary) t.summary += d * SUMMARY_COLS;
+        if (heading) { t.heading += d * HEADING_COLS; t.hist += d * heading_bins; }
+        if (hprior_table) t.hprior_table += d * hprior_stride;
+        return t;
+    }
+};
+static_assert(TAIL_HW == CCVPE_OUT_HW, "the output-side kernels' map side");
+// Working memory of the tail for B queries: a plan's tensors and ticket ranges (build_plan) or the prior scratch (ccvpe_api.hip).  A
+// buffer no launch of the caller reads stays null.
+struct TailBuffers {
+    const float* logits = nullptr;     // [B][512*512]
+    const float* ori = nullptr;        // [B][2][512*512] (pose.heading)
+    float* partial = nullptr;          // [B][64][2] softmax partials
+    void* keys = nullptr;              // argmax: [B][64][2] (max, index) pairs; top-K: [B][64][k] 64-bit keys
+    int* index = nullptr;              // [B] argmax; top-K: [B][k]
+    double* summ_part = nullptr;       // [B][64][SUMMARY_PART] (summary forms)
+    double* head_part = nullptr;       // [B][64][HEADING_PART] and
+    unsigned long long* bins = nullptr;   //   [B][HEADING_MAX_BINS], zero between launches (pose.heading)
+    unsigned* tickets = nullptr;       // [B] counters of pose.argmax or topk.peaks ...
+    unsigned* head_tickets = nullptr;  // ... and of pose.heading (the same range where both run in order on one stream)
+};
+void issue_softmax_partial(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
+void issue_pose_argmax(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
+void issue_topk_peaks(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
+void issue_pose_heading(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
+
 struct Ctx {
     float* arena = nullptr;
     const std::vector<size_t>* off = nullptr;
@@ -260,24 +313,12 @@ struct Ctx {
     unsigned* tickets = nullptr;       // the plan's last-arriver counters (ticket.h); every launch that draws tickets owns a range
     const float* cache_in = nullptr;   // aerial cache consumed by a "cached" plan
     float* cache_out = nullptr;        // aerial cache produced by an "encode" plan
-    float* rows = nullptr;             // pose plans: the [B][5] result rows of this micro-batch (ccvpe_localize); top-K: [B][topk_k][5]
-    int topk_k = 0, topk_r = 0;        // top-K pose plans: hypotheses per sample (1..64) and suppression radius (0..32) of this call
+    TailCall tail;                     // pose plans: what this micro-batch asks of the tail, its own slice of every per-query buffer
     const int* tile_index = nullptr;   // indexed cached forms: HOST tile of each sample of this micro-batch (null: sample b reads tile b)
     int n_tiles = 0;                   // ... and the number of tiles cache_in was encoded for (its section layout)
     const float* grd_cache_in = nullptr;   // pair plans (ccvpe_localize_region): ground cache of ccvpe_encode_ground, [n_queries][Ltot]
     const int* query_index = nullptr;  // ... HOST query of each pair of this micro-batch
     int n_queries = 0;                 // ... and the number of queries grd_cache_in holds
-    float* stats = nullptr;            // pose plans: optional [B][2] softmax (max, 1/sum) of each sample (pose_argmax_kernel)
-    const float* log_prior = nullptr;  // pose plans: optional log-prior of this micro-batch's first sample ...
-    long long prior_stride = 0;        // ... and the floats between two samples' maps (0: one map for all)
-    float* posterior = nullptr;        // pose plans: optional posterior map [mb][512*512] of this micro-batch (ccvpe_track_update*)
-    float* summary = nullptr;          // summary pose plans: the [mb][16] summary rows of this micro-batch (ccvpe_localize_summary*) ...
-    int summary_r = 0;                 // ... and the window radius 0..32 of this call
-    float* heading = nullptr;          // heading pose plans: the [mb][12] heading rows of this micro-batch (ccvpe_localize_heading*),
-    float* hist = nullptr;             // ... its [mb][heading_bins] histograms,
-    int heading_bins = 0, heading_r = 0;   // ... the bin count 4..360 and the window radius 0..32 of this call
-    const float* hprior_table = nullptr;   // heading-prior plans (ccvpe_localize_heading_prior*): the table of this micro-batch's
-    int hprior_stride = 0, hprior_nb = 0;  // ... first sample, the floats between two samples' tables (0: one for all) and the table's bins 4..360
     float* ptr(const Tensor& t) const { return arena + (*off)[t.id]; }
     Dst dst(const Tensor& t, int coff = 0) const { return Dst{ptr(t), t.C, coff, t.split ? 1 : 0, t.numel()}; }
     mutable int conv_errors = 0;   // launches refused by launch_conv_igemm (unsupported geometry)
@@ -322,26 +363,15 @@ struct ForwardCall {
     int n_tiles = 0;                   // ... and the tiles the cache holds (range of tile_index checked by the entry point)
     int batch = 0;
     const ccvpe_outputs* out = nullptr;   // the nine outputs, or ...
-    float* rows = nullptr;             // ... pose plans (ccvpe_localize*): [batch][5] result rows, `out` is not read
-    int topk_k = 0, topk_r = 0;        // topk_k > 0: top-K pose plans (ccvpe_localize_topk*), rows [batch][topk_k][5]; range checked by the entry point
-    const float* log_prior = nullptr;  // pose plans, optional (ccvpe_localize_prior*, ccvpe_track_update*): every slice reads its own maps ...
-    long long prior_stride = 0;        // ... this many floats apart (0: one map for all; checked by the entry point)
-    float* posterior = nullptr;        // argmax pose plans, optional (ccvpe_track_update*): every slice also writes its own posterior maps
-    float* summary = nullptr;          // argmax pose plans (ccvpe_localize_summary*): [batch][16] summary rows, every slice its own; selects the
-    int summary_r = 0;                 //   summary plans.  The window radius, checked by the entry point
-    float* heading = nullptr;          // argmax pose plans (ccvpe_localize_heading*): [batch][12] heading rows and
-    float* hist = nullptr;             //   [batch][heading_bins] histograms, every slice its own; select the heading plans.
-    int heading_bins = 0, heading_r = 0;   // Bin count and window radius, checked by the entry point
-    const float* hprior_table = nullptr;   // heading plans (ccvpe_localize_heading_prior*): the heading prior's tables, every slice its own when
-    int hprior_stride = 0, hprior_nb = 0;  //   the stride is nb + 1 (0: one table for all); select the heading-prior plans.  Checked by the entry point
+    TailCall tail;                     // ... pose plans (ccvpe_localize*): tail.rows set, `out` is not read; the whole batch's buffers
     hipStream_t stream = nullptr;
     bool profile = false;              // ccvpe_profile_forward: a hipEvent pair around every launch
     PlanKey plan_key() const {         // (B: set per slice by the micro-batch loop)
         PlanKey key;
-        key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = rows != nullptr; key.topk = rows && topk_k > 0;
-        key.summary = rows && summary;
-        key.heading = rows && heading;
-        key.hprior = key.heading && hprior_table;
+        key.gh = gh; key.gw = gw; key.mode = cache ? 2 : 0; key.pose = tail.rows != nullptr; key.topk = tail.rows && tail.topk_k > 0;
+        key.summary = tail.rows && tail.summary;
+        key.heading = tail.rows && tail.heading;
+        key.hprior = key.heading && tail.hprior_table;
         return key;
     }
 };

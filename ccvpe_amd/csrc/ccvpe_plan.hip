@@ -321,6 +321,42 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
     return desc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The pose tail's four launches (ccvpe_internal.h): the kernel parameters from where the working memory is (w), what the call asks (t)
+// and the batch.  The plans below and the logits forms of ccvpe_api.hip issue the tail through these and nothing else.
+// ------------------------------------------------------------------------------------------------
+void issue_softmax_partial(const TailBuffers& w, const TailCall& t, int B, hipStream_t s) {
+    SoftmaxParams p{};
+    p.logits = w.logits; p.B = B; p.n = TAIL_HW * TAIL_HW; p.partial = w.partial; p.chunks = TAIL_CHUNKS; p.out = nullptr;
+    p.prior = t.log_prior; p.prior_stride = t.prior_stride;
+    launch_softmax_partial(p, s);
+}
+
+void issue_pose_argmax(const TailBuffers& w, const TailCall& t, int B, hipStream_t s) {
+    PoseArgmaxParams p{};
+    p.logits = w.logits; p.partial = w.partial; p.B = B; p.n = TAIL_HW * TAIL_HW; p.chunks = TAIL_CHUNKS;
+    p.pairs = reinterpret_cast<float*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = t.rows;
+    p.stats = t.stats; p.prior = t.log_prior; p.prior_stride = t.prior_stride; p.posterior = t.posterior;
+    if (t.summary) { p.summary = t.summary; p.summ_part = w.summ_part; p.summary_r = t.summary_r; }
+    launch_pose_argmax(p, s);
+}
+
+void issue_topk_peaks(const TailBuffers& w, const TailCall& t, int B, hipStream_t s) {
+    TopkParams p{};
+    p.heat = nullptr; p.logits = w.logits; p.partial = w.partial; p.B = B; p.k = t.topk_k; p.r = t.topk_r;
+    p.keys = reinterpret_cast<unsigned long long*>(w.keys); p.tickets = w.tickets; p.index = w.index; p.rows = t.rows;
+    p.prior = t.log_prior; p.prior_stride = t.prior_stride;
+    launch_topk_peaks(p, s);
+}
+
+void issue_pose_heading(const TailBuffers& w, const TailCall& t, int B, hipStream_t s) {
+    HeadingParams p{};
+    p.logits = w.logits; p.partial = w.partial; p.prior = t.log_prior; p.prior_stride = t.prior_stride;
+    p.ori = w.ori; p.index = w.index; p.B = B; p.nbins = t.heading_bins; p.r = t.heading_r;
+    p.part = w.head_part; p.bins = w.bins; p.tickets = w.head_tickets; p.heading = t.heading; p.hist = t.hist;
+    launch_heading_reduce(p, s);
+}
+
 // Pose plans (pose = true, ccvpe_localize): the launches of the full (mode 0) or cached (mode 2) plan up to and including the level-2
 // decoders, under the same names - so the same tuning-table entries - and a tail that writes only the [B][5] result rows of
 // ccvpe_postprocess_rows: no matching-score stacks (the match kernels skip the ms store), the logits in the workspace, the first softmax
@@ -332,7 +368,7 @@ static Tensor plan_grd_desc(ccvpe_handle_s* h, Plan& pl, int B, int fh, int fw, 
 // Top-K pose plans (topk = true as well, ccvpe_localize_topk): the same launches up to softmax.partial and the level-2 decoders; the
 // tail is topk.peaks (the K best peaks from recomputed heatmap values) and the orientation at those K pixels (ori1.topk:
 // the fused level 1 for each hypothesis' tile; without the fused level: ori1.tail + ori1.topk_gather).  K and r come with each call
-// (Ctx::topk_k / topk_r); the workspace is sized for K = 64.
+// (TailCall::topk_k / topk_r); the workspace is sized for K = 64.
 // Heading pose plans (heading = true, ccvpe_localize_heading*): the argmax pose plan with the WHOLE orientation field in
 // the workspace - level 1 of the orientation branch is the full plan's launch (ori1.fused, or ori1.tail without the fused level: the same
 // names and shapes, so the same tuning entries), ori1.gather fills rows[2..4] - and pose.heading behind both decoders' tails.
@@ -707,8 +743,22 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             launch_tail_conv(p, c.stream);
         }, 2.0 * B * 262144.0 * 144, 4.0 * B * 262144.0 * 17);
     }
-    Tensor pose_index;   // pose plans: [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
-    Tensor pose_part;    // pose plans: the softmax partials, read again by pose.heading
+    // pose plans: the tail's tensors and ticket ranges, and its working memory for a launch context (ids < 0: null)
+    struct TailTensors {
+        Tensor logits, ori;   // the logits and, heading plans, the whole orientation field in the workspace
+        Tensor part, keys;    // the softmax partials (read again by pose.heading); the (max, index) pairs or the top-K keys
+        Tensor index;         // [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
+        Tensor spart, hpart;  // the float64 hand-offs of the summary and the heading sums
+        size_t toff = 0, htoff = 0, boff = 0;   // ticket ranges: pose.argmax or topk.peaks, pose.heading, its fixed-point histograms
+        TailBuffers at(const Ctx& c) const {
+            auto ptr = [&](const Tensor& t) { return t.id < 0 ? nullptr : c.ptr(t); };
+            TailBuffers w;
+            w.logits = ptr(logits); w.ori = ptr(ori); w.partial = ptr(part); w.keys = ptr(keys); w.index = reinterpret_cast<int*>(ptr(index));
+            w.summ_part = reinterpret_cast<double*>(ptr(spart)); w.head_part = reinterpret_cast<double*>(ptr(hpart));
+            w.tickets = c.tickets + toff; w.head_tickets = c.tickets + htoff; w.bins = reinterpret_cast<unsigned long long*>(c.tickets + boff);
+            return w;
+        }
+    } tt;
     const bool heading = pl.key.heading;
     // Heading-prior plans: the tail reads the combined map `comb` that pose.hprior writes from the orientation field, so
     // its launches are added behind the orientation decoder's whole-field launch (add_tail below is then called from there); every other
@@ -718,56 +768,44 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     // the position prior a tail launch reads: the caller's, or the plan's combined map
     auto prior_of = [=](const Ctx& c, long long& stride) -> const float* {
         if (hprior) { stride = (long long)CCVPE_OUT_HW * CCVPE_OUT_HW; return c.ptr(comb); }
-        stride = c.prior_stride;
-        return c.log_prior;
+        stride = c.tail.prior_stride;
+        return c.tail.log_prior;
+    };
+    // what a tail launch is asked: the context's call, with the prior it reads
+    auto call_of = [=](const Ctx& c) {
+        TailCall t = c.tail;
+        t.log_prior = prior_of(c, t.prior_stride);
+        return t;
     };
     auto add_tail = [&]() {
-        static_assert(CCVPE_OUT_HW * CCVPE_OUT_HW == 64 * 4096, "pose_argmax_kernel: 64 chunks of 4096 values");
         const bool topk = pl.key.topk;
-        Tensor part = pl.alloc(B, 1, 64, 2), keys = pl.alloc(B, 1, 64, topk ? 2 * TOPK_MAX_K : 2);   // (argmax: the (max, index) hand-off pairs)
-        pose_index = pl.alloc(B, 1, 1, topk ? TOPK_MAX_K : 1);
-        pose_part = part;
+        tt.logits = logits_ws;
+        tt.part = pl.alloc(B, 1, TAIL_CHUNKS, 2); tt.keys = pl.alloc(B, 1, TAIL_CHUNKS, topk ? 2 * TOPK_MAX_K : 2);
+        tt.index = pl.alloc(B, 1, 1, topk ? TOPK_MAX_K : 1);
         // summary plans: the chunks' float64 sums, B x 64 x 8 doubles (tensors start on 256-byte granules); no other
         // plan allocates it, so theirs keep their workspace
         static_assert(sizeof(double) == 2 * sizeof(float), "the hand-off is allocated in floats");
         const bool summ = pl.key.summary;
-        const Tensor spart = summ ? pl.alloc(B, 1, 64, 2 * SUMMARY_PART) : Tensor{};
-        const Tensor lg = logits_ws, idx = pose_index;
-        std::vector<Tensor> sm_uses = {lg, part};
+        if (summ) tt.spart = pl.alloc(B, 1, TAIL_CHUNKS, 2 * SUMMARY_PART);
+        std::vector<Tensor> sm_uses = {tt.logits, tt.part};
         if (hprior) sm_uses.push_back(comb);
-        pl.add("softmax.partial", sm_uses, [=](const Ctx& c) {
-            SoftmaxParams p{};
-            p.logits = c.ptr(lg); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64; p.out = nullptr;
-            p.prior = prior_of(c, p.prior_stride);
-            launch_softmax_partial(p, c.stream);
-        }, 0, 4.0 * B * 262144.0);
-        const size_t toff = pl.alloc_tickets((size_t)B);
-        if (topk) pl.add("topk.peaks", {lg, part, keys, idx}, [=](const Ctx& c) {
-            TopkParams p{};
-            p.heat = nullptr; p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.k = c.topk_k; p.r = c.topk_r;
-            p.keys = reinterpret_cast<unsigned long long*>(c.ptr(keys)); p.tickets = c.tickets + toff;
-            p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
-            p.prior = c.log_prior; p.prior_stride = c.prior_stride;
-            launch_topk_peaks(p, c.stream);
-        }, 0, 4.0 * B * 262144.0);
-        std::vector<Tensor> am_uses = {lg, part, keys, idx};
-        if (summ) am_uses.push_back(spart);
+        const TailTensors w = tt;
+        pl.add("softmax.partial", sm_uses, [=](const Ctx& c) { issue_softmax_partial(w.at(c), call_of(c), B, c.stream); }, 0, 4.0 * B * 262144.0);
+        tt.toff = pl.alloc_tickets((size_t)B);
+        const TailTensors wt = tt;
+        if (topk) pl.add("topk.peaks", {tt.logits, tt.part, tt.keys, tt.index}, [=](const Ctx& c) { issue_topk_peaks(wt.at(c), call_of(c), B, c.stream); },
+                         0, 4.0 * B * 262144.0);
+        std::vector<Tensor> am_uses = {tt.logits, tt.part, tt.keys, tt.index};
+        if (summ) am_uses.push_back(tt.spart);
         if (hprior) am_uses.push_back(comb);
-        if (!topk) pl.add("pose.argmax", am_uses, [=](const Ctx& c) {
-            PoseArgmaxParams p{};
-            p.logits = c.ptr(lg); p.partial = c.ptr(part); p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.chunks = 64;
-            p.pairs = c.ptr(keys); p.tickets = c.tickets + toff; p.index = reinterpret_cast<int*>(c.ptr(idx)); p.rows = c.rows;
-            p.stats = c.stats; p.prior = prior_of(c, p.prior_stride); p.posterior = c.posterior;
-            if (summ) { p.summary = c.summary; p.summ_part = reinterpret_cast<double*>(c.ptr(spart)); p.summary_r = c.summary_r; }
-            launch_pose_argmax(p, c.stream);
-        }, 0, 4.0 * B * 262144.0);
+        if (!topk) pl.add("pose.argmax", am_uses, [=](const Ctx& c) { issue_pose_argmax(wt.at(c), call_of(c), B, c.stream); }, 0, 4.0 * B * 262144.0);
     };
     if (pose && !hprior) add_tail();
     if (!pose) {
-        Tensor part = pl.alloc(B, 1, 64, 2);
+        Tensor part = pl.alloc(B, 1, TAIL_CHUNKS, 2);
         pl.add("softmax", {part}, [=](const Ctx& c) {
             SoftmaxParams p{};
-            p.logits = c.out.logits_flattened; p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = 64;
+            p.logits = c.out.logits_flattened; p.B = B; p.n = CCVPE_OUT_HW * CCVPE_OUT_HW; p.partial = c.ptr(part); p.chunks = TAIL_CHUNKS;
             p.out = c.out.heatmap;
             launch_softmax(p, c.stream);
         }, 0, 4.0 * B * 262144.0 * 3);
@@ -777,8 +815,8 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     auto add_hprior = [&](Tensor of) {
         pl.add("pose.hprior", {of, comb}, [=](const Ctx& c) {
             HeadingPriorMapParams p{};
-            p.ori = c.ptr(of); p.prior = c.log_prior; p.prior_stride = c.prior_stride; p.table = c.hprior_table; p.table_stride = c.hprior_stride;
-            p.nb = c.hprior_nb; p.out = c.ptr(comb); p.B = B;
+            p.ori = c.ptr(of); p.prior = c.tail.log_prior; p.prior_stride = c.tail.prior_stride; p.table = c.tail.hprior_table;
+            p.table_stride = c.tail.hprior_stride; p.nb = c.tail.hprior_nb; p.out = c.ptr(comb); p.B = B;
             launch_heading_prior_map(p, c.stream);
         }, 0, 4.0 * B * 262144.0 * 4);
         add_tail();
@@ -798,19 +836,19 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
                 lp.x_ld = xo.C; lp.cx = dw.l1_cx; lp.cxp = dw.l1_cxp; lp.B = B; lp.H = CCVPE_OUT_HW; lp.W = CCVPE_OUT_HW;
                 lp.c0 = dw.l1_c0; lp.ng = dw.l1_ng; lp.score = dw.l1_score; lp.wc = dw.l1_wc; lp.ws = dw.l1_ws; lp.bc = dw.l1_bc; lp.wt = dw.l1_wt;
                 lp.bt[0] = dw.tail_b[0]; lp.bt[1] = dw.tail_b[1]; lp.cout = 2; lp.normalize = 1;
-                const Tensor din = xo, idx = pose_index;
+                const Tensor din = xo, idx = tt.index;
                 const bool topk = pl.key.topk;
                 const double px = (double)B * (topk ? 8 : 1) * 16 * 16, cin_real = vs.ori[5].din;   // (top-K: accounted at K = 8)
                 const double flops = px / 4 * 2.0 * cin_real * 64 + px * 2.0 * 144 * 16 + px * 2.0 * 144 * 2, bytes = 4.0 * px / 4 * lp.cx;
                 if (topk) pl.add("ori1.topk", {din, idx}, [=](const Ctx& c) {
                     Level1Params q = lp;
                     q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
-                    launch_level1_topk(q, reinterpret_cast<const int*>(c.ptr(idx)), c.topk_k, c.rows, c.stream);
+                    launch_level1_topk(q, reinterpret_cast<const int*>(c.ptr(idx)), c.tail.topk_k, c.tail.rows, c.stream);
                 }, flops, bytes);
                 else pl.add("ori1.pose", {din, idx}, [=](const Ctx& c) {
                     Level1Params q = lp;
                     q.x = c.ptr(din); q.out = nullptr; q.raw = nullptr;
-                    launch_level1_pose(q, reinterpret_cast<const int*>(c.ptr(idx)), c.rows, c.stream);
+                    launch_level1_pose(q, reinterpret_cast<const int*>(c.ptr(idx)), c.tail.rows, c.stream);
                 }, flops, bytes);
                 fused_done = true;
                 break;
@@ -844,21 +882,21 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         }, 2.0 * B * 262144.0 * 288, 4.0 * B * 262144.0 * 18);
         if (hprior) add_hprior(ori_ws);
         if (pl.key.topk) {
-            const Tensor idx = pose_index;
+            const Tensor idx = tt.index;
             pl.add("ori1.topk_gather", {ori_ws, idx}, [=](const Ctx& c) {
-                launch_topk_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, c.topk_k, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+                launch_topk_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, c.tail.topk_k, CCVPE_OUT_HW * CCVPE_OUT_HW, c.tail.rows, c.stream);
             }, 0, 12.0 * B * 8);
         } else if (pose) {
-            const Tensor idx = pose_index;
+            const Tensor idx = tt.index;
             pl.add("ori1.gather", {ori_ws, idx}, [=](const Ctx& c) {
-                launch_pose_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+                launch_pose_gather(c.ptr(ori_ws), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.tail.rows, c.stream);
             }, 0, 12.0 * B);
             ori_field = ori_ws;
         }
         } else if (heading) {
-            const Tensor idx = pose_index, of = ori_field;
+            const Tensor idx = tt.index, of = ori_field;
             pl.add("ori1.gather", {of, idx}, [=](const Ctx& c) {
-                launch_pose_gather(c.ptr(of), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.rows, c.stream);
+                launch_pose_gather(c.ptr(of), reinterpret_cast<const int*>(c.ptr(idx)), B, CCVPE_OUT_HW * CCVPE_OUT_HW, c.tail.rows, c.stream);
             }, 0, 12.0 * B);
         }
         if (heading) {
@@ -866,19 +904,13 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
             // streams' tails.  The float64 hand-off lives in the workspace; the queries' fixed-point histograms must be zero between
             // launches like the counters, so they live beside them (never in the arena, which the autotuner fills).
             static_assert(sizeof(double) == 2 * sizeof(float) && sizeof(unsigned long long) == 2 * sizeof(unsigned), "allocated in words");
-            const Tensor lg = logits_ws, part = pose_part, idx = pose_index, of = ori_field;
-            const Tensor hpart = pl.alloc(B, 1, 64, 2 * HEADING_PART);
-            const size_t toff = pl.alloc_tickets((size_t)B), boff = pl.alloc_tickets((size_t)B * HEADING_MAX_BINS * 2);
-            std::vector<Tensor> hd_uses = {lg, part, idx, of, hpart};
+            tt.ori = ori_field;
+            tt.hpart = pl.alloc(B, 1, TAIL_CHUNKS, 2 * HEADING_PART);
+            tt.htoff = pl.alloc_tickets((size_t)B); tt.boff = pl.alloc_tickets((size_t)B * HEADING_MAX_BINS * 2);
+            std::vector<Tensor> hd_uses = {tt.logits, tt.part, tt.index, tt.ori, tt.hpart};
             if (hprior) hd_uses.push_back(comb);
-            pl.add("pose.heading", hd_uses, [=](const Ctx& c) {
-                HeadingParams p{};
-                p.logits = c.ptr(lg); p.partial = c.ptr(part); p.prior = prior_of(c, p.prior_stride);
-                p.ori = c.ptr(of); p.index = reinterpret_cast<const int*>(c.ptr(idx)); p.B = B; p.nbins = c.heading_bins; p.r = c.heading_r;
-                p.part = reinterpret_cast<double*>(c.ptr(hpart)); p.bins = reinterpret_cast<unsigned long long*>(c.tickets + boff);
-                p.tickets = c.tickets + toff; p.heading = c.heading; p.hist = c.hist;
-                launch_heading_reduce(p, c.stream);
-            }, 0, 4.0 * B * 262144.0 * 3);
+            const TailTensors w = tt;
+            pl.add("pose.heading", hd_uses, [=](const Ctx& c) { issue_pose_heading(w.at(c), call_of(c), B, c.stream); }, 0, 4.0 * B * 262144.0 * 3);
         }
     }
     // the ground / aerial inputs and the 2 x 512 x 512 orientation output are addressed the same way

@@ -400,6 +400,11 @@ __device__ __forceinline__ float pose_angle_deg(float cs, float sn) {
     return ang;
 }
 
+// The output side's geometry: the map side (CCVPE_OUT_HW) and the chunks a map is reduced in - TAIL_CHUNKS workgroups per sample take
+// 4096 values each; the last arriver's first wave holds one chunk per lane
+static constexpr int TAIL_HW = 512, TAIL_CHUNKS = 64;
+static_assert(TAIL_HW * TAIL_HW == TAIL_CHUNKS * 4 * 4 * 256 && TAIL_CHUNKS == 64, "four float4 per thread per chunk, one lane of a wave per chunk");
+
 struct SoftmaxParams {
     const float* logits;       // [B][n]
     int B, n;

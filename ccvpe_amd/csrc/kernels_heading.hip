@@ -6,10 +6,7 @@
 
 namespace ccvpe {
 
-static constexpr int HD_HW = 512;                   // map side (CCVPE_OUT_HW)
-static constexpr int HD_CHUNKS = 64;                // pose_argmax_kernel's chunks: 4096 cells per workgroup
 static constexpr int HD_SUMS = 3;                   // M, sum h c, sum h s
-static constexpr int HD_UB = 6;                     // window cells in flight per thread (summ_finish's SM_UB)
 static_assert(HD_SUMS <= HEADING_PART, "hand-off row");
 #ifndef CCVPE_HEADING_WAVE_COMBINE
 #define CCVPE_HEADING_WAVE_COMBINE 1   // dev builds (tools/build_variant.sh): 0 = every lane adds for itself, what the combined path is timed against
@@ -33,8 +30,8 @@ __device__ __forceinline__ float heading_mean_deg(double S, double C, double R) 
 }
 
 // Grid (64 chunks, B), 256 threads: chunk c of sample b is pose_argmax_kernel's chunk c, read the same way (four float4 of logits, of
-// the prior, and two times four float4 of the field per thread, all in flight in one trip), its values recomputed with that kernel's
-// take() expression from softmax_stats' (m, inv): the bits of the posterior map.
+// the prior, and two times four float4 of the field per thread, all in flight in one trip), its values recomputed as that kernel's
+// (posterior_value) from softmax_stats' (m, inv): the bits of the posterior map.
 // Histogram: q = (unsigned long long)(h * 2^52) - an exact scaling (h <= 1) and one truncation - added as 64-bit integers into the
 // workgroup's LDS histogram, then into the query's bins[] with agent-scope integer adds (non-empty bins only).  Integer sums have no
 // order, so the bits do not depend on who arrives when.  The orientation field is smooth: the 64 cells a wave handles at once mostly
@@ -51,25 +48,17 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
     __shared__ unsigned long long lh[HEADING_MAX_BINS];
     __shared__ float lf[HEADING_MAX_BINS];
     __shared__ double sd[4 * HD_SUMS];
-    constexpr int n = HD_HW * HD_HW, per = n / HD_CHUNKS;   // 4096: a multiple of 4 x 256
+    constexpr int n = TAIL_HW * TAIL_HW, per = n / TAIL_CHUNKS;   // 4096: a multiple of 4 x 256
     const int b = blockIdx.y, c = blockIdx.x, lo = c * per;
     const int nb = min(max(p.nbins, HEADING_MIN_BINS), HEADING_MAX_BINS);
-    softmax_stats(p.partial, b, HD_CHUNKS, gm, gs);
+    softmax_stats(p.partial, b, TAIL_CHUNKS, gm, gs);
     for (int i = threadIdx.x; i < nb; i += 256) lh[i] = 0ull;
     const float* lg = p.logits + (size_t)b * n;
     const float* lp = PRIOR ? p.prior + (size_t)b * p.prior_stride : nullptr;
     const float* oc = p.ori + (size_t)b * 2 * n;
     const float* os = oc + n;
     float4 v[4], fc[4], fs[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = reinterpret_cast<const float4*>(lg + lo)[threadIdx.x + u * 256];
-    if constexpr (PRIOR) {
-        float4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = reinterpret_cast<const float4*>(lp + lo)[threadIdx.x + u * 256];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { v[u].x += q[u].x; v[u].y += q[u].y; v[u].z += q[u].z; v[u].w += q[u].w; }
-    }
+    load_chunk<PRIOR>(lg, lp, lo, v);
 #pragma unroll
     for (int u = 0; u < 4; ++u) fc[u] = reinterpret_cast<const float4*>(oc + lo)[threadIdx.x + u * 256];
 #pragma unroll
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
     const float scale = (float)nb / 360.f;
     double acc[HD_SUMS] = {0.0, 0.0, 0.0};
     auto cell = [&](float x, float cs, float sn) {
-        const float h = __expf(x - m) * inv;          // pose_argmax_kernel's take()
+        const float h = posterior_value(x, m, inv);    // pose_argmax_kernel's take()
         const bool valid = ok && heading_valid(cs, sn);
         heading_take(acc, h, cs, sn, valid);
         int bin = heading_bin(cs, sn, scale, nb);     // (tail_shared.h)
@@ -104,26 +93,18 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
     if (threadIdx.x == 0) {
         summ_from_lds(acc, sd);
 #pragma unroll
-        for (int k = 0; k < HD_SUMS; ++k) st_sc1(p.part + ((size_t)b * HD_CHUNKS + c) * HEADING_PART + k, acc[k]);
+        for (int k = 0; k < HD_SUMS; ++k) st_sc1(p.part + ((size_t)b * TAIL_CHUNKS + c) * HEADING_PART + k, acc[k]);
     }
     unsigned long long* bins = p.bins + (size_t)b * HEADING_MAX_BINS;
     for (int i = threadIdx.x; i < nb; i += 256) {
         const unsigned long long t = lh[i];
         if (t) (void)__hip_atomic_fetch_add(bins + i, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)HD_CHUNKS, &flag)) return;
+    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)TAIL_CHUNKS, &flag)) return;
 
     // ---- last arriver of sample b ----
     double g[HD_SUMS] = {0.0, 0.0, 0.0};
-    if (threadIdx.x < 64) {
-#pragma unroll
-        for (int k = 0; k < HD_SUMS; ++k) g[k] = ld_sc1(p.part + ((size_t)b * HD_CHUNKS + threadIdx.x) * HEADING_PART + k);
-#pragma unroll
-        for (int k = 0; k < HD_SUMS; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) g[k] += __shfl_xor(g[k], off);
-        }
-    }
+    sums_from_chunks(p.part + (size_t)b * TAIL_CHUNKS * HEADING_PART, HEADING_PART, g);
     for (int i = threadIdx.x; i < nb; i += 256) {
         const unsigned long long t = __hip_atomic_exchange(bins + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const float hf = (float)((double)t * 2.220446049250313e-16);   // 2^-52: a total below 2^53 is exact in float64
@@ -132,25 +113,22 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
     }
     const int r = min(max(p.r, 0), HEADING_MAX_R);
     const int bi = ok ? min(max(p.index[b], 0), n - 1) : 0;
-    const int xs = bi & (HD_HW - 1), ys = bi >> 9;
-    const int x0 = max(xs - r, 0), x1 = min(xs + r, HD_HW - 1), y0 = max(ys - r, 0), y1 = min(ys + r, HD_HW - 1);
-    const int ww = x1 - x0 + 1, cells = ww * (y1 - y0 + 1);
+    const Window win = window_around(bi, r);
+    const int cells = win.cells;
     double w[HD_SUMS] = {0.0, 0.0, 0.0};
-    for (int i0 = threadIdx.x; i0 < cells; i0 += 256 * HD_UB) {
-        float hv[HD_UB], cv[HD_UB], sv[HD_UB];
+    for (int i0 = threadIdx.x; i0 < cells; i0 += 256 * WINDOW_UB) {
+        float hv[WINDOW_UB], cv[WINDOW_UB], sv[WINDOW_UB];
 #pragma unroll
-        for (int u = 0; u < HD_UB; ++u) {
-            const int i = i0 + u * 256;
-            const int ly = i / ww;
-            const int at = i < cells ? (y0 + ly) * HD_HW + x0 + (i - ly * ww) : bi;   // (past the window: a read inside the map that adds 0)
+        for (int u = 0; u < WINDOW_UB; ++u) {
+            const int at = win.at(i0 + u * 256, bi);
             float x = lg[at];
             if constexpr (PRIOR) x += lp[at];
-            hv[u] = __expf(x - m) * inv;
+            hv[u] = posterior_value(x, m, inv);
             cv[u] = oc[at];
             sv[u] = os[at];
         }
 #pragma unroll
-        for (int u = 0; u < HD_UB; ++u) heading_take(w, hv[u], cv[u], sv[u], ok && i0 + u * 256 < cells && heading_valid(cv[u], sv[u]));
+        for (int u = 0; u < WINDOW_UB; ++u) heading_take(w, hv[u], cv[u], sv[u], ok && i0 + u * 256 < cells && heading_valid(cv[u], sv[u]));
     }
     summ_wave_to_lds(w, sd);
     __syncthreads();                                  // (lf[] is complete as well)
@@ -158,12 +136,7 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
     float bv = -1.f;
     int bm = 0x7fffffff;
     for (int i = threadIdx.x; i < nb; i += 64) { const float t = lf[i]; if (t > bv) { bv = t; bm = i; } }   // strictly greater keeps the first
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float v2 = __shfl_xor(bv, off);
-        const int i2 = __shfl_xor(bm, off);
-        if (v2 > bv || (v2 == bv && i2 < bm)) { bv = v2; bm = i2; }
-    }
+    argmax_wave(bv, bm);
     if (threadIdx.x != 0) return;
     summ_from_lds(w, sd);
     float* row = p.heading + (size_t)b * HEADING_COLS;
@@ -181,8 +154,8 @@ __global__ __launch_bounds__(256) void heading_reduce_kernel(const HeadingParams
 }
 
 void launch_heading_reduce(const HeadingParams& p, hipStream_t s) {
-    if (p.prior) CCVPE_LAUNCH(heading_reduce_kernel<true>, dim3(HD_CHUNKS, p.B), dim3(256), 0, s, p);
-    else CCVPE_LAUNCH(heading_reduce_kernel<false>, dim3(HD_CHUNKS, p.B), dim3(256), 0, s, p);
+    if (p.prior) CCVPE_LAUNCH(heading_reduce_kernel<true>, dim3(TAIL_CHUNKS, p.B), dim3(256), 0, s, p);
+    else CCVPE_LAUNCH(heading_reduce_kernel<false>, dim3(TAIL_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 
 }  // namespace ccvpe

@@ -8,9 +8,6 @@
 
 namespace ccvpe {
 
-static constexpr int HP_HW = 512;                   // map side (CCVPE_OUT_HW)
-static constexpr int HP_CHUNKS = 64;                // pose_argmax_kernel's and heading_reduce_kernel's chunks: 4096 cells per workgroup
-
 // Grid (64 chunks, B), 256 threads.  The query's table goes into LDS (nb + 1 <= 361 floats); per thread four float4 of c, of s and
 // (PRIOR) of P, all in flight in one trip, then four float4 stores of comb = T[k] or P + T[k] (one IEEE add), k = the cell's bin by
 // heading_reduce_kernel's own expression (tail_shared.h), nb for a cell without a heading.  No atomics, no tickets: every output word
@@ -19,7 +16,7 @@ static constexpr int HP_CHUNKS = 64;                // pose_argmax_kernel's and 
 template <bool PRIOR>
 __global__ __launch_bounds__(256) void heading_prior_map_kernel(const HeadingPriorMapParams p) {
     __shared__ float lt[HEADING_MAX_BINS + 1];
-    constexpr int n = HP_HW * HP_HW, per = n / HP_CHUNKS;   // 4096: a multiple of 4 x 256
+    constexpr int n = TAIL_HW * TAIL_HW, per = n / TAIL_CHUNKS;   // 4096: a multiple of 4 x 256
     const int b = blockIdx.y, lo = blockIdx.x * per;
     const int nb = min(max(p.nb, HEADING_MIN_BINS), HEADING_MAX_BINS);
     const float* tb = p.table + (size_t)b * p.table_stride;
@@ -52,8 +49,8 @@ __global__ __launch_bounds__(256) void heading_prior_map_kernel(const HeadingPri
 }
 
 void launch_heading_prior_map(const HeadingPriorMapParams& p, hipStream_t s) {
-    if (p.prior) CCVPE_LAUNCH(heading_prior_map_kernel<true>, dim3(HP_CHUNKS, p.B), dim3(256), 0, s, p);
-    else CCVPE_LAUNCH(heading_prior_map_kernel<false>, dim3(HP_CHUNKS, p.B), dim3(256), 0, s, p);
+    if (p.prior) CCVPE_LAUNCH(heading_prior_map_kernel<true>, dim3(TAIL_CHUNKS, p.B), dim3(256), 0, s, p);
+    else CCVPE_LAUNCH(heading_prior_map_kernel<false>, dim3(TAIL_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 
 // Grid (B), 256 threads: one workgroup per query, everything on the circle of nb bins in LDS.

@@ -81,7 +81,7 @@ void launch_tail_conv(const TailConvParams& p, hipStream_t s) {
 // Softmax over n = 262144 logits per sample, two launches: per-chunk online (max, sum exp) partials,
 // then every block re-derives the sample's (max, sum) from the partials and normalises its chunk.
 // ------------------------------------------------------------------------------------------------
-// (combine() and softmax_stats(): tail_shared.h)
+// (combine(), softmax_stats() and posterior_value(): tail_shared.h)
 
 // PRIOR: the partials of l' = fl32(l + prior), the prior read as float4 beside the logits; everything else - and so
 // every bit for a zero prior - as without it.  A prior excludes pixels with -inf, often whole stretches: a thread that has seen
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void softmax_final_kernel(const SoftmaxParams 
     float4* dst = reinterpret_cast<float4*>(p.out + (size_t)b * p.n + (size_t)ch * per);
     for (int i = threadIdx.x; i < per / 4; i += 256) {
         const float4 v = src[i];
-        dst[i] = make_float4(__expf(v.x - m) * inv, __expf(v.y - m) * inv, __expf(v.z - m) * inv, __expf(v.w - m) * inv);
+        dst[i] = make_float4(posterior_value(v.x, m, inv), posterior_value(v.y, m, inv), posterior_value(v.z, m, inv), posterior_value(v.w, m, inv));
     }
 }
 
@@ -147,18 +147,17 @@ void launch_softmax_partial(const SoftmaxParams& p, hipStream_t s) {
 // angle in degrees.
 // ------------------------------------------------------------------------------------------------
 // Round 4: one workgroup per sample scanned its 262144 values in sixteen rounds of loads - 16 trips to memory for ONE workgroup at batch 1
-// (17 us).  Now PP_CHUNKS workgroups per sample take 4096 values each (all their loads in one trip), leave (max, first index) per chunk
-// and draw a ticket (ticket.h); the workgroup that draws a sample's last one reduces the PP_CHUNKS pairs - the maximum with the
+// (17 us).  Now TAIL_CHUNKS workgroups per sample take 4096 values each (all their loads in one trip), leave (max, first index) per chunk
+// and draw a ticket (ticket.h); the workgroup that draws a sample's last one reduces the TAIL_CHUNKS pairs - the maximum with the
 // first-index tie-break does not depend on the order - and writes the pose.  `rows` != null: the same five numbers as floats
 // ([B][5]: index, prob, cos, sin, angle - the rows the data-parallel gather moves) instead of the ccvpe_pose records.
-static constexpr int PP_CHUNKS = 64;
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* heat, const float* ori, int n, PoseOut* out, float* rows, float* part, unsigned* tickets) {
     __shared__ float sv[4];
     __shared__ int si[4];
     __shared__ unsigned flag;
     const int b = blockIdx.y, c = blockIdx.x;
     const float* h = heat + (size_t)b * n;
-    const int lo = (int)((long long)n * c / PP_CHUNKS) & ~3, hi = c + 1 == PP_CHUNKS ? n : (int)((long long)n * (c + 1) / PP_CHUNKS) & ~3;
+    const int lo = (int)((long long)n * c / TAIL_CHUNKS) & ~3, hi = c + 1 == TAIL_CHUNKS ? n : (int)((long long)n * (c + 1) / TAIL_CHUNKS) & ~3;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     auto take = [&](float v, int i) { if (v > best) { best = v; bi = i; } };   // strictly greater keeps the first index per thread
@@ -179,34 +178,11 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* heat, con
     } else {
         for (int j = lo + threadIdx.x; j < hi; j += 256) take(h[j], j);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float v2 = __shfl_xor(best, off);
-        const int i2 = __shfl_xor(bi, off);
-        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        st_sc1(part + ((size_t)b * PP_CHUNKS + c) * 2, best);
-        st_sc1(part + ((size_t)b * PP_CHUNKS + c) * 2 + 1, __int_as_float(bi));
-    }
-    if (!ticket_arrive(tickets + b, 1u, (unsigned)PP_CHUNKS, &flag)) return;
+    argmax_wave(best, bi);
+    argmax_publish(best, bi, sv, si, part + ((size_t)b * TAIL_CHUNKS + c) * 2);
+    if (!ticket_arrive(tickets + b, 1u, (unsigned)TAIL_CHUNKS, &flag)) return;
     if (threadIdx.x < 64) {
-        best = -INFINITY; bi = 0x7fffffff;
-        for (int k = threadIdx.x; k < PP_CHUNKS; k += 64) {
-            const float v2 = ld_sc1(part + ((size_t)b * PP_CHUNKS + k) * 2);
-            const int i2 = __float_as_int(ld_sc1(part + ((size_t)b * PP_CHUNKS + k) * 2 + 1));
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float v2 = __shfl_xor(best, off);
-            const int i2 = __shfl_xor(bi, off);
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
+        argmax_from_pairs(part + (size_t)b * TAIL_CHUNKS * 2, best, bi);
         if (threadIdx.x == 0) {
             // no value above -inf anywhere (all NaN, all -inf, a mix): nothing was taken and bi is still the sentinel.  The sample has no
             // posterior: index -1, prob NaN, the orientation of pixel 0.  The clamp keeps the reads inside ori regardless.
@@ -229,14 +205,14 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* heat, con
     }
 }
 
-// scratch = [PP_MAX_BATCH ticket counters][B x PP_CHUNKS (max, index) pairs]; the counters are zero before the first launch and every launch
+// scratch = [PP_MAX_BATCH ticket counters][B x TAIL_CHUNKS (max, index) pairs]; the counters are zero before the first launch and every launch
 // leaves them at zero (a larger buffer serves a smaller batch: the counters do not move)
-size_t postprocess_scratch_bytes(int B) { return ((size_t)PP_MAX_BATCH + (size_t)B * PP_CHUNKS * 2) * sizeof(float); }
+size_t postprocess_scratch_bytes(int B) { return ((size_t)PP_MAX_BATCH + (size_t)B * TAIL_CHUNKS * 2) * sizeof(float); }
 
 void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseOut* out, float* rows, void* scratch, hipStream_t s) {
     unsigned* tickets = reinterpret_cast<unsigned*>(scratch);
     float* part = reinterpret_cast<float*>(scratch) + PP_MAX_BATCH;
-    CCVPE_LAUNCH(postprocess_kernel, dim3(PP_CHUNKS, B), dim3(256), 0, s, heat, ori, n, out, rows, part, tickets);
+    CCVPE_LAUNCH(postprocess_kernel, dim3(TAIL_CHUNKS, B), dim3(256), 0, s, heat, ori, n, out, rows, part, tickets);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -248,15 +224,14 @@ void launch_postprocess(const float* heat, const float* ori, int B, int n, PoseO
 // runs the window pass around the argmax with all its threads (six sums of at most 65 x 65 values, reduced the same way) and thread 0
 // writes the row.  Every order is fixed: the same map gives the same bits whoever arrives last.
 // ------------------------------------------------------------------------------------------------
-static constexpr int SM_HW = 512;                   // map side (CCVPE_OUT_HW)
 static constexpr int SM_SUMS = 7, SM_WIN = 6;       // sums per map, per window (no entropy term)
-static_assert(SM_SUMS <= SUMMARY_PART && PP_CHUNKS == 64, "one lane of the last arriver's first wave per chunk");
+static_assert(SM_SUMS <= SUMMARY_PART && TAIL_CHUNKS == 64, "one lane of the last arriver's first wave per chunk");
 
 // h at index i into a[0 .. n): S0, Sx, Sy, Sxx, Sxy, Syy and, n == 7, S(h ln h) (h == 0 adds 0).  h * x and h * y are exact in float64,
 // h * x * x below 2^42 as well: every fused multiply-add rounds once, like the add alone
 template <int n>
 __device__ __forceinline__ void summ_take(double (&a)[n], float h, int i) {
-    const double hd = (double)h, x = (double)(i & (SM_HW - 1)), y = (double)(i >> 9);
+    const double hd = (double)h, x = (double)(i & (TAIL_HW - 1)), y = (double)(i >> 9);
     const double hx = hd * x, hy = hd * y;
     a[0] += hd; a[1] += hx; a[2] += hy;
     a[3] = fma(hx, x, a[3]); a[4] = fma(hx, y, a[4]); a[5] = fma(hy, y, a[5]);
@@ -273,36 +248,24 @@ __device__ __forceinline__ void summ_publish(const double (&a)[SM_SUMS], double*
 // All 256 threads of a sample's last arriver, behind ticket_arrive and a barrier that made (bi, best) uniform.  part: the sample's
 // [64][SUMMARY_PART] hand-off; h_at(i): the map's value at index i in [0, 512 * 512), the expression the sums were taken of; lds:
 // 4 * SM_SUMS doubles nobody else touches; ok: the sample has a posterior (else the row is (-1, NaN, NaN ...)).  The window loads
-// go out SM_UB per thread at a time: r = 8 is one trip to memory, r = 32 three.
-static constexpr int SM_UB = 6;
+// go out WINDOW_UB per thread at a time.
 template <class HAt>
 __device__ __forceinline__ void summ_finish(const double* part, int bi, float best, bool ok, int r, HAt h_at, double* lds, float* row) {
     double g[SM_SUMS];
-    if (threadIdx.x < 64) {
-#pragma unroll
-        for (int k = 0; k < SM_SUMS; ++k) g[k] = ld_sc1(part + threadIdx.x * SUMMARY_PART + k);
-#pragma unroll
-        for (int k = 0; k < SM_SUMS; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) g[k] += __shfl_xor(g[k], off);
-        }
-    }
-    const int xs = bi & (SM_HW - 1), ys = bi >> 9;
-    const int x0 = max(xs - r, 0), x1 = min(xs + r, SM_HW - 1), y0 = max(ys - r, 0), y1 = min(ys + r, SM_HW - 1);
-    const int ww = x1 - x0 + 1, cells = ww * (y1 - y0 + 1);
+    sums_from_chunks(part, SUMMARY_PART, g);
+    const Window win = window_around(bi, r);
+    const int cells = win.cells;
     double w[SM_WIN] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i0 = threadIdx.x; i0 < cells; i0 += 256 * SM_UB) {
-        float hv[SM_UB];
-        int at[SM_UB];
+    for (int i0 = threadIdx.x; i0 < cells; i0 += 256 * WINDOW_UB) {
+        float hv[WINDOW_UB];
+        int at[WINDOW_UB];
 #pragma unroll
-        for (int u = 0; u < SM_UB; ++u) {
-            const int i = i0 + u * 256;
-            const int ly = i / ww;
-            at[u] = i < cells ? (y0 + ly) * SM_HW + x0 + (i - ly * ww) : bi;   // (past the window: a read inside the map that adds 0)
+        for (int u = 0; u < WINDOW_UB; ++u) {
+            at[u] = win.at(i0 + u * 256, bi);
             hv[u] = h_at(at[u]);
         }
 #pragma unroll
-        for (int u = 0; u < SM_UB; ++u) summ_take(w, i0 + u * 256 < cells ? hv[u] : 0.f, at[u]);
+        for (int u = 0; u < WINDOW_UB; ++u) summ_take(w, i0 + u * 256 < cells ? hv[u] : 0.f, at[u]);
     }
     summ_wave_to_lds(w, lds);
     __syncthreads();
@@ -330,7 +293,7 @@ __device__ __forceinline__ void summ_finish(const double* part, int bi, float be
 
 // ------------------------------------------------------------------------------------------------
 // Pose plans (ccvpe_localize): postprocess_kernel's argmax over a heatmap that is never stored.  Chunk c of sample b is postprocess_kernel's
-// chunk c (4096 values); its values are recomputed from the logits as __expf(v - m) * inv with softmax_final_kernel's (m, inv), i.e. the
+// chunk c (4096 values); its values are recomputed from the logits by posterior_value (tail_shared.h) with softmax_final_kernel's (m, inv), i.e. the
 // bits that kernel would store, so index and prob are those ccvpe_postprocess_rows reads from the heatmap, ties included (strictly greater
 // within a thread, lowest index on ties across threads and chunks).  Every thread's index starts at the first position it scans, so the
 // result is a position of the chunk whatever the values are.
@@ -342,7 +305,7 @@ __device__ __forceinline__ void summ_finish(const double* part, int bi, float be
 // posterior to its own chunk: all zeros.
 // SUMM (ccvpe_*_summary): the summary row of that map, from the values in registers - the chunk's seven float64 sums go
 // to the last arriver beside its (max, index) pair, and the last arriver, the argmax in hand, recomputes the window around it with
-// take()'s expression (summ_finish).  A sample without a finite posterior: (-1, NaN, NaN ...), with or without a prior.
+// posterior_value (summ_finish).  A sample without a finite posterior: (-1, NaN, NaN ...), with or without a prior.
 // ------------------------------------------------------------------------------------------------
 template <bool PRIOR, bool POST = false, bool SUMM = false>
 __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams p) {
@@ -356,24 +319,16 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
     softmax_stats(p.partial, b, p.chunks, gm, gs);
     const int per = p.n / p.chunks;                   // 4096: a multiple of 4 x 256
     const int lo = c * per;
-    const float4* src = reinterpret_cast<const float4*>(p.logits + (size_t)b * p.n + lo);
+    const float* lg = p.logits + (size_t)b * p.n;
+    const float* lp = PRIOR ? p.prior + (size_t)b * p.prior_stride : nullptr;
     float4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = src[threadIdx.x + u * 256];   // (per / 4 = 1024 float4 per chunk: four per thread, one trip)
-    if constexpr (PRIOR) {
-        const float4* lp = reinterpret_cast<const float4*>(p.prior + (size_t)b * p.prior_stride + lo);
-        float4 q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = lp[threadIdx.x + u * 256];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { v[u].x += q[u].x; v[u].y += q[u].y; v[u].z += q[u].z; v[u].w += q[u].w; }
-    }
+    load_chunk<PRIOR>(lg, lp, lo, v);                 // (per / 4 = 1024 float4 per chunk: four per thread, one trip)
     __syncthreads();
     const float m = gm, inv = gs;
     if (p.stats && c == 0 && threadIdx.x == 0) { p.stats[b * 2 + 0] = m; p.stats[b * 2 + 1] = inv; }   // (read by a later launch)
     float best = -INFINITY;
     int bi = lo + 4 * (int)threadIdx.x;
-    auto take = [&](float x, int i) { const float h = __expf(x - m) * inv; if (h > best) { best = h; bi = i; } };
+    auto take = [&](float x, int i) { const float h = posterior_value(x, m, inv); if (h > best) { best = h; bi = i; } };
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int e = lo + (threadIdx.x + u * 256) * 4;
@@ -387,8 +342,9 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
         // but tests/test_isa_hazard.py reads a store's first operand as its data; a buffer store names its data first.
         const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, SUMM ? per * (int)sizeof(float) : 0, 0x00020000);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {   // take()'s expression: the bits rows[b][1] carries at the argmax
-            const float4 h = make_float4(__expf(v[u].x - m) * inv, __expf(v[u].y - m) * inv, __expf(v[u].z - m) * inv, __expf(v[u].w - m) * inv);
+        for (int u = 0; u < 4; ++u) {   // take()'s values: the bits rows[b][1] carries at the argmax
+            const float4 h = make_float4(posterior_value(v[u].x, m, inv), posterior_value(v[u].y, m, inv), posterior_value(v[u].z, m, inv),
+                                         posterior_value(v[u].w, m, inv));
             if constexpr (SUMM) {
                 const tk_f32x4 o = fin ? tk_f32x4{h.x, h.y, h.z, h.w} : tk_f32x4{0.f, 0.f, 0.f, 0.f};
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tk_u32x4, o), prs, (threadIdx.x + u * 256) * 16u, 0, 0);
@@ -399,45 +355,24 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
     }
     if constexpr (SUMM) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {   // take()'s expression again: the values of the map
+        for (int u = 0; u < 4; ++u) {   // take()'s values again: the values of the map
             const int e = lo + (threadIdx.x + u * 256) * 4;
-            summ_take(acc, __expf(v[u].x - m) * inv, e); summ_take(acc, __expf(v[u].y - m) * inv, e + 1);
-            summ_take(acc, __expf(v[u].z - m) * inv, e + 2); summ_take(acc, __expf(v[u].w - m) * inv, e + 3);
+            summ_take(acc, posterior_value(v[u].x, m, inv), e); summ_take(acc, posterior_value(v[u].y, m, inv), e + 1);
+            summ_take(acc, posterior_value(v[u].z, m, inv), e + 2); summ_take(acc, posterior_value(v[u].w, m, inv), e + 3);
         }
         summ_wave_to_lds(acc, sd);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float v2 = __shfl_xor(best, off);
-        const int i2 = __shfl_xor(bi, off);
-        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2, best);
-        st_sc1(p.pairs + ((size_t)b * p.chunks + c) * 2 + 1, __int_as_float(bi));
-        if constexpr (SUMM) {
+    argmax_wave(best, bi);
+    argmax_publish(best, bi, sv, si, p.pairs + ((size_t)b * p.chunks + c) * 2);
+    if constexpr (SUMM) {
+        if (threadIdx.x == 0) {
             summ_from_lds(acc, sd);
             summ_publish(acc, p.summ_part + ((size_t)b * p.chunks + c) * SUMMARY_PART);
         }
     }
     if (!ticket_arrive(p.tickets + b, 1u, (unsigned)p.chunks, &flag)) return;
     if (threadIdx.x < 64) {
-        best = -INFINITY; bi = 0;
-        for (int k = threadIdx.x; k < p.chunks; k += 64) {
-            const float v2 = ld_sc1(p.pairs + ((size_t)b * p.chunks + k) * 2);
-            const int i2 = __float_as_int(ld_sc1(p.pairs + ((size_t)b * p.chunks + k) * 2 + 1));
-            if (k == threadIdx.x || v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float v2 = __shfl_xor(best, off);
-            const int i2 = __shfl_xor(bi, off);
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
+        argmax_from_pairs(p.pairs + (size_t)b * p.chunks * 2, best, bi);
         if constexpr (SUMM) {
             if (threadIdx.x == 0) { sv[0] = best; si[0] = bi; }
         } else if (threadIdx.x == 0) {
@@ -457,12 +392,10 @@ __global__ __launch_bounds__(256) void pose_argmax_kernel(const PoseArgmaxParams
             p.rows[b * 5 + 0] = ok ? (float)bi : -1.f;
             p.rows[b * 5 + 1] = ok ? best : NAN;
         }
-        const float* lg = p.logits + (size_t)b * p.n;
-        const float* lp = PRIOR ? p.prior + (size_t)b * p.prior_stride : nullptr;
         auto h_at = [&](int i) {
             float x = lg[i];
             if constexpr (PRIOR) x += lp[i];
-            return __expf(x - m) * inv;
+            return posterior_value(x, m, inv);
         };
         summ_finish(p.summ_part + (size_t)b * p.chunks * SUMMARY_PART, bi, best, ok, p.summary_r, h_at, sd, p.summary + (size_t)b * SUMMARY_COLS);
     }
@@ -491,7 +424,7 @@ __global__ __launch_bounds__(256) void belief_summary_kernel(const BeliefSummary
     __shared__ int si[4];
     __shared__ unsigned flag;
     __shared__ double sd[4 * SM_SUMS];
-    constexpr int n = SM_HW * SM_HW, per = n / PP_CHUNKS;   // 4096: a multiple of 4 x 256
+    constexpr int n = TAIL_HW * TAIL_HW, per = n / TAIL_CHUNKS;   // 4096: a multiple of 4 x 256
     const int b = blockIdx.y, c = blockIdx.x, lo = c * per;
     const float* h = p.belief + (size_t)b * n;
     double acc[SM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -518,44 +451,27 @@ __global__ __launch_bounds__(256) void belief_summary_kernel(const BeliefSummary
         for (int u = 0; u < per / 256; ++u) take(v[u], lo + threadIdx.x + u * 256);
     }
     summ_wave_to_lds(acc, sd);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float v2 = __shfl_xor(best, off);
-        const int i2 = __shfl_xor(bi, off);
-        if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-    }
-    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    argmax_wave(best, bi);
+    argmax_publish(best, bi, sv, si, p.pairs + ((size_t)b * TAIL_CHUNKS + c) * 2);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        st_sc1(p.pairs + ((size_t)b * PP_CHUNKS + c) * 2, best);
-        st_sc1(p.pairs + ((size_t)b * PP_CHUNKS + c) * 2 + 1, __int_as_float(bi));
         summ_from_lds(acc, sd);
-        summ_publish(acc, p.summ_part + ((size_t)b * PP_CHUNKS + c) * SUMMARY_PART);
+        summ_publish(acc, p.summ_part + ((size_t)b * TAIL_CHUNKS + c) * SUMMARY_PART);
     }
-    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)PP_CHUNKS, &flag)) return;
+    if (!ticket_arrive(p.tickets + b, 1u, (unsigned)TAIL_CHUNKS, &flag)) return;
     if (threadIdx.x < 64) {
-        best = ld_sc1(p.pairs + ((size_t)b * PP_CHUNKS + threadIdx.x) * 2);
-        bi = __float_as_int(ld_sc1(p.pairs + ((size_t)b * PP_CHUNKS + threadIdx.x) * 2 + 1));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float v2 = __shfl_xor(best, off);
-            const int i2 = __shfl_xor(bi, off);
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
+        argmax_from_pairs(p.pairs + (size_t)b * TAIL_CHUNKS * 2, best, bi);
         if (threadIdx.x == 0) { sv[0] = best; si[0] = bi; }
     }
     __syncthreads();
     best = sv[0];
     bi = min(max(si[0], 0), n - 1);   // (a position of the map by construction; the clamp keeps the window reads inside it regardless)
     if (best == -INFINITY) best = h[bi];   // nothing was taken (no value above -inf): column 1 is the map's value at the index, like any other row's
-    summ_finish(p.summ_part + (size_t)b * PP_CHUNKS * SUMMARY_PART, bi, best, true, p.r, [&](int i) { return h[i]; }, sd,
+    summ_finish(p.summ_part + (size_t)b * TAIL_CHUNKS * SUMMARY_PART, bi, best, true, p.r, [&](int i) { return h[i]; }, sd,
                 p.summary + (size_t)b * SUMMARY_COLS);
 }
 
 void launch_belief_summary(const BeliefSummaryParams& p, hipStream_t s) {
-    CCVPE_LAUNCH(belief_summary_kernel, dim3(PP_CHUNKS, p.B), dim3(256), 0, s, p);
+    CCVPE_LAUNCH(belief_summary_kernel, dim3(TAIL_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -644,12 +560,11 @@ void launch_pose_gather(const float* ori, const int* index, int B, int n, float*
 // 64-bit keys (value bits << 32 | ~index: value descending, index ascending) with a bitonic sort in LDS and hands its best K to the
 // sample's last arriver (ticket.h), which sorts the 64 K candidates the same way and writes index[b][k] and rows[b][k][0..1].  A slot
 // without a peak gets index -1 and the row (-1, 0, 0, 0, 0); the orientation launches behind skip it.
-// PRIOR (logits path only): the values are __expf((l + prior) - m) * inv with softmax_partial_kernel<true>'s statistics;
+// PRIOR (logits path only): the values are posterior_value(l + prior) with softmax_partial_kernel<true>'s statistics;
 // a sample whose (m, inv) is not finite has no peak at all.
 // ------------------------------------------------------------------------------------------------
-static constexpr int TK_HW = 512;                  // map side (CCVPE_OUT_HW)
 static constexpr int TK_T = 64;                    // tile side
-static constexpr int TK_TILES = (TK_HW / TK_T) * (TK_HW / TK_T);   // 64 per sample
+static constexpr int TK_TILES = (TAIL_HW / TK_T) * (TAIL_HW / TK_T);   // 64 per sample
 static_assert(TK_T * TK_T * (4 + 5) >= TK_TILES * TOPK_MAX_K * 8, "the sort buffer aliases the smallest staging area");
 
 __host__ __device__ constexpr int topk_halo(int r) { return TK_T + 2 * r; }
@@ -675,7 +590,7 @@ __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     __shared__ float gm, gs;
     __shared__ unsigned cnt, flag;
-    constexpr int HW = TK_HW, n = HW * HW;
+    constexpr int HW = TAIL_HW, n = HW * HW;
     const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
     const int r = p.r, S = topk_halo(r);
     const int Y0 = (t / (HW / TK_T)) * TK_T, X0 = (t % (HW / TK_T)) * TK_T;
@@ -685,7 +600,7 @@ __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
     unsigned long long* sk = reinterpret_cast<unsigned long long*>(tk_smem);
     float m = 0.f, inv = 0.f;
     if (LOGITS) {
-        softmax_stats(p.partial, b, 64, gm, gs);   // (the 64 chunks of the pose plans' softmax.partial launch)
+        softmax_stats(p.partial, b, TAIL_CHUNKS, gm, gs);   // (the chunks of the pose plans' softmax.partial launch)
         __syncthreads();
         m = gm; inv = gs;
     }
@@ -699,8 +614,8 @@ __global__ __launch_bounds__(256) void topk_peaks_kernel(const TopkParams p) {
         unsigned u = 0u;
         if ((unsigned)y < (unsigned)HW && (unsigned)x < (unsigned)HW) {
             float h = src[y * HW + x];
-            if constexpr (PRIOR) h = __expf((h + lpb[y * HW + x]) - m) * inv;
-            else if (LOGITS) h = __expf(h - m) * inv;
+            if constexpr (PRIOR) h = posterior_value(h + lpb[y * HW + x], m, inv);
+            else if (LOGITS) h = posterior_value(h, m, inv);
             u = h > 0.f && finite_stats ? __float_as_uint(h) : 0u;
         }
         in[i] = u;

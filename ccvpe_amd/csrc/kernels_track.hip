@@ -18,29 +18,25 @@
 // y pass out of that, one float4 of output per thread.  LDS: 4 * (S * 32 + S * P + 2 * (2r + 8)) bytes, P = S or S + 2: 14.0 KB at
 // r = 6, 50.6 KB at r = 32 - three workgroups per CU at the largest radius.  Every global read is bounds-checked against the grid, and
 // the integer part of the shift is clamped before it is converted, so no input value moves a read outside the tensors.
-#include "kernels.h"
+#include "track_blur.h"
 
 namespace ccvpe {
 
-static constexpr int TP_HW = 512;                  // map side (CCVPE_OUT_HW)
-static constexpr int TP_T = 32;                    // tile side
-static constexpr int TP_TILES = (TP_HW / TP_T) * (TP_HW / TP_T);   // 256 per query: one per CU at batch 1
-
-__host__ __device__ constexpr int track_side(int r) { return TP_T + 2 * r + 1; }
+__host__ __device__ constexpr int track_side(int r) { return TRACK_T + 2 * r + 1; }
 // row pitch of the staged source: S is odd; P = 1 (mod 4) keeps the x pass (8 lanes per row, 4 columns apart) free of bank conflicts
 __host__ __device__ constexpr int track_pitch(int r) { return (track_side(r) & 3) == 1 ? track_side(r) : track_side(r) + 2; }
 // merged weights of one pass, zero-padded by 3 on both sides for the x pass' four outputs per thread
 __host__ __device__ constexpr int track_wlen(int r) { return 2 * r + 2 + 6; }
-static size_t track_lds_bytes(int r) { return sizeof(float) * ((size_t)track_side(r) * TP_T + 2 * track_wlen(r) + (size_t)track_side(r) * track_pitch(r)); }
+static size_t track_lds_bytes(int r) { return sizeof(float) * ((size_t)track_side(r) * TRACK_T + 2 * track_wlen(r) + (size_t)track_side(r) * track_pitch(r)); }
 
 __global__ __launch_bounds__(256) void track_predict_kernel(const TrackPredictParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tp_smem[];
-    constexpr int HW = TP_HW, n = HW * HW;
+    constexpr int HW = TAIL_HW, n = HW * HW;
     const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
     const int r = p.radius, S = track_side(r), P = track_pitch(r), WL = track_wlen(r);
-    const int Y0 = (t / (HW / TP_T)) * TP_T, X0 = (t % (HW / TP_T)) * TP_T;
+    const int Y0 = (t / (HW / TRACK_T)) * TRACK_T, X0 = (t % (HW / TRACK_T)) * TRACK_T;
     float* mid = reinterpret_cast<float*>(tp_smem);   // [S][32] x-pass result (16-byte aligned rows)
-    float* wx = mid + S * TP_T;                      // [WL] merged weights along x, wx[3 + k] = u[k]
+    float* wx = mid + S * TRACK_T;                      // [WL] merged weights along x, wx[3 + k] = u[k]
     float* wy = wx + WL;                             // [WL] along y
     float* src = wy + WL;                            // [S][P] staged source
     const float dx = p.shift[b * 2 + 0], dy = p.shift[b * 2 + 1];
@@ -74,41 +70,14 @@ __global__ __launch_bounds__(256) void track_predict_kernel(const TrackPredictPa
         }
     }
     __syncthreads();
-    // x pass: task = (row, 4 adjacent columns); source column x4 + c feeds output i with weight u[c - i]
-    for (int i = tid; i < S * (TP_T / 4); i += 256) {
-        const int ly = i >> 3, x4 = (i & 7) * 4;
-        const float* row = src + ly * P + x4;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        float w1 = 0.f, w2 = 0.f, w3 = 0.f;          // u[c - 1], u[c - 2], u[c - 3]
-        for (int c = 0; c <= 2 * r + 4; ++c) {
-            const float v = row[c], w0 = wx[3 + c];
-            a0 = fmaf(w0, v, a0); a1 = fmaf(w1, v, a1); a2 = fmaf(w2, v, a2); a3 = fmaf(w3, v, a3);
-            w3 = w2; w2 = w1; w1 = w0;
-        }
-        *reinterpret_cast<float4*>(mid + ly * TP_T + x4) = make_float4(a0, a1, a2, a3);
-    }
-    __syncthreads();
-    // y pass: thread = (output row, 4 adjacent columns)
-    {
-        const int y = tid >> 3, x4 = (tid & 7) * 4;
-        const float4* col = reinterpret_cast<const float4*>(mid + y * TP_T + x4);
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k <= 2 * r + 1; ++k) {
-            const float4 v = col[k * (TP_T / 4)];
-            const float w = wy[3 + k];
-            a.x = fmaf(w, v.x, a.x); a.y = fmaf(w, v.y, a.y); a.z = fmaf(w, v.z, a.z); a.w = fmaf(w, v.w, a.w);
-        }
-        const float fl = p.floor[b];
-        float4* dst = reinterpret_cast<float4*>(p.log_prior + (size_t)b * n + (size_t)(Y0 + y) * HW + X0 + x4);
-        *dst = make_float4(logf(a.x + fl), logf(a.y + fl), logf(a.z + fl), logf(a.w + fl));
-    }
+    track_blur_store<1>(src, S, P, mid, wx, wy, r, p.floor, p.log_prior, b, Y0, X0);
 }
 
 void launch_track_predict(const TrackPredictParams& p, hipStream_t s) {
     const size_t lds = track_lds_bytes(p.radius);
     static LdsAttr attr;
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(track_predict_kernel), lds);
-    CCVPE_LAUNCH(track_predict_kernel, dim3(TP_TILES, p.B), dim3(256), lds, s, p);
+    CCVPE_LAUNCH(track_predict_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
 }
 
 }  // namespace ccvpe

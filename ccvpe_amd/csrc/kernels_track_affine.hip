@@ -21,29 +21,25 @@
 // 4 * (S * 32 + S * (S + 1) + 2r + 7) bytes: 13.6 KB at r = 6, 49.8 KB at r = 32 - three workgroups per CU at the largest radius.  Every
 // global read is bounds-checked against the grid, and the integer parts are clamped (NaN included) before they are converted, so no
 // matrix moves a read outside the tensors.
-#include "kernels.h"
+#include "track_blur.h"
 
 namespace ccvpe {
 
-static constexpr int TA_HW = 512;                  // map side (CCVPE_OUT_HW)
-static constexpr int TA_T = 32;                    // tile side
-static constexpr int TA_TILES = (TA_HW / TA_T) * (TA_HW / TA_T);   // 256 per query: one per CU at batch 1
-
-__host__ __device__ constexpr int affine_side(int r) { return TA_T + 2 * r; }
+__host__ __device__ constexpr int affine_side(int r) { return TRACK_T + 2 * r; }
 // row pitch of the samples: S is even; an odd pitch puts the x pass' 32 lanes (4 rows, 8 lanes per row, 4 columns apart) on 32 banks
 __host__ __device__ constexpr int affine_pitch(int r) { return affine_side(r) + 1; }
 // two-sided weights, zero-padded by 3 on both sides for the x pass' four outputs per thread
 __host__ __device__ constexpr int affine_wlen(int r) { return 2 * r + 1 + 6; }
-static size_t affine_lds_bytes(int r) { return sizeof(float) * ((size_t)affine_side(r) * TA_T + affine_wlen(r) + (size_t)affine_side(r) * affine_pitch(r)); }
+static size_t affine_lds_bytes(int r) { return sizeof(float) * ((size_t)affine_side(r) * TRACK_T + affine_wlen(r) + (size_t)affine_side(r) * affine_pitch(r)); }
 
 __global__ __launch_bounds__(256) void track_predict_affine_kernel(const TrackPredictAffineParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ta_smem[];
-    constexpr int HW = TA_HW, n = HW * HW;
+    constexpr int HW = TAIL_HW, n = HW * HW;
     const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
     const int r = p.radius, S = affine_side(r), P = affine_pitch(r), WL = affine_wlen(r);
-    const int Y0 = (t / (HW / TA_T)) * TA_T, X0 = (t % (HW / TA_T)) * TA_T;
+    const int Y0 = (t / (HW / TRACK_T)) * TRACK_T, X0 = (t % (HW / TRACK_T)) * TRACK_T;
     float* mid = reinterpret_cast<float*>(ta_smem);   // [S][32] x-pass result (16-byte aligned rows)
-    float* wt = mid + S * TA_T;                      // [WL] wt[3 + k] = t[|k - r|], k = 0 .. 2r
+    float* wt = mid + S * TRACK_T;                      // [WL] wt[3 + k] = t[|k - r|], k = 0 .. 2r
     float* src = wt + WL;                            // [S][P] samples s
     if (tid < WL) {
         const int k = tid - 3;
@@ -76,41 +72,14 @@ __global__ __launch_bounds__(256) void track_predict_affine_kernel(const TrackPr
         if (lx >= S) { lx -= S; ++ly; }
     }
     __syncthreads();
-    // x pass: task = (row, 4 adjacent columns); sample column x4 + c feeds output i with weight t[|c - i - r|]
-    for (int i = tid; i < S * (TA_T / 4); i += 256) {
-        const int row_i = i >> 3, x4 = (i & 7) * 4;
-        const float* row = src + row_i * P + x4;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        float w1 = 0.f, w2 = 0.f, w3 = 0.f;          // weights of outputs 1..3 for this column: wt[3 + c - 1], [.. - 2], [.. - 3]
-        for (int c = 0; c <= 2 * r + 3; ++c) {
-            const float v = row[c], w0 = wt[3 + c];
-            a0 = fmaf(w0, v, a0); a1 = fmaf(w1, v, a1); a2 = fmaf(w2, v, a2); a3 = fmaf(w3, v, a3);
-            w3 = w2; w2 = w1; w1 = w0;
-        }
-        *reinterpret_cast<float4*>(mid + row_i * TA_T + x4) = make_float4(a0, a1, a2, a3);
-    }
-    __syncthreads();
-    // y pass: thread = (output row, 4 adjacent columns)
-    {
-        const int y = tid >> 3, x4 = (tid & 7) * 4;
-        const float4* col = reinterpret_cast<const float4*>(mid + y * TA_T + x4);
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k <= 2 * r; ++k) {
-            const float4 v = col[k * (TA_T / 4)];
-            const float w = wt[3 + k];
-            a.x = fmaf(w, v.x, a.x); a.y = fmaf(w, v.y, a.y); a.z = fmaf(w, v.z, a.z); a.w = fmaf(w, v.w, a.w);
-        }
-        const float fl = p.floor[b];
-        float4* dst = reinterpret_cast<float4*>(p.log_prior + (size_t)b * n + (size_t)(Y0 + y) * HW + X0 + x4);
-        *dst = make_float4(logf(a.x + fl), logf(a.y + fl), logf(a.z + fl), logf(a.w + fl));
-    }
+    track_blur_store<0>(src, S, P, mid, wt, wt, r, p.floor, p.log_prior, b, Y0, X0);
 }
 
 void launch_track_predict_affine(const TrackPredictAffineParams& p, hipStream_t s) {
     const size_t lds = affine_lds_bytes(p.radius);
     static LdsAttr attr;
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(track_predict_affine_kernel), lds);
-    CCVPE_LAUNCH(track_predict_affine_kernel, dim3(TA_TILES, p.B), dim3(256), lds, s, p);
+    CCVPE_LAUNCH(track_predict_affine_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
 }
 
 }  // namespace ccvpe

@@ -85,6 +85,43 @@ def test_environment_is_read_only_by_read_switches():
     assert not offenders, "getenv outside read_switches():\n" + "\n".join(offenders)
 
 
+def test_pose_tail_has_one_definition():
+    """The output side's forms promise each other's bits (the recomputed posterior against the stored heatmap, logits forms against
+    network forms, ties and NaN alike), so what they must agree on is written once: the (value, first index) tie-break and the
+    posterior expression `__expf(x - m) * inv` occur in tail_shared.h alone, and ccvpe_api.hip fills no tail kernel's parameters
+    itself - it issues the tail through ccvpe_plan.hip's issue_* functions like the plans.  The one exception is the stored-heatmap
+    top-K of ccvpe_postprocess_topk, which has no softmax and reads no logits."""
+    csrc = os.path.join(ROOT, "ccvpe_amd", "csrc")
+
+    def code(f):
+        return re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())
+
+    tie = re.compile(r"(\w+)\s*>\s*(\w+)\s*\|\|\s*\(\s*\1\s*==\s*\2\s*&&\s*\w+\s*<\s*\w+\s*\)")
+    post = re.compile(r"__expf\s*\([^;]*?-\s*m\s*\)\s*\*\s*inv\b")
+    sources = ["kernels_tail.hip", "kernels_heading.hip", "kernels_hprior.hip", "tail_shared.h"]
+    sources += sorted(f for f in os.listdir(csrc) if f.startswith(("kernels_track", "track_")) and f.endswith((".hip", ".h")))
+    assert len(sources) > 4, "the track kernels' files"
+    for f in sources:
+        text = code(f)
+        if f == "kernels_tail.hip":   # region_reduce_kernel's pair reduction (float64 joint probabilities, an eligibility flag) is another merge
+            m = re.search(r"void region_reduce_kernel\(.*?^\}\n", text, flags=re.S | re.M)
+            assert m
+            text = text[:m.start()] + text[m.end():]
+        want = 1 if f == "tail_shared.h" else 0
+        assert len(tie.findall(text)) == want, f"{f}: the tie-break comparison is argmax_merge (tail_shared.h)"
+        assert len(post.findall(text)) == want, f"{f}: the posterior expression is posterior_value (tail_shared.h)"
+    api = code("ccvpe_api.hip")
+    for name in ("PoseArgmaxParams", "HeadingParams", "SoftmaxParams"):
+        assert not re.search(r"\b%s\b" % name, api), f"ccvpe_api.hip fills a {name} of its own"
+    inits = [m.start() for m in re.finditer(r"\bTopkParams\b", api)]
+    assert len(inits) == 1, "ccvpe_api.hip: one TopkParams, the stored-heatmap form's"
+    fn = api.rfind("\nint ccvpe_", 0, inits[0])
+    assert api[fn:].startswith("\nint ccvpe_postprocess_topk("), api[fn:fn + 60]
+    plan = code("ccvpe_plan.hip")
+    for fn_name in ("issue_softmax_partial", "issue_pose_argmax", "issue_topk_peaks", "issue_pose_heading"):
+        assert len(re.findall(r"^void %s\(" % fn_name, plan, flags=re.M)) == 1 and re.search(r"\b%s\(" % fn_name, api), fn_name
+
+
 def test_conv_hook_descriptor_refusals(built_library):
     """ccvpe_op_conv2d_ex refuses a bad descriptor before it touches the device: the pointers below are never dereferenced."""
     lib = _lib.load()
