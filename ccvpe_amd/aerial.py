@@ -391,6 +391,65 @@ def summary_to_metres(summary, metres_per_px):
     return out
 
 
+# ---- credible regions -------------------------------------------------------------------------------------------
+
+# the columns of model.belief_credible's / localize_credible's cred rows (include/ccvpe.h): four per query, then three per level
+CREDIBLE_HEAD_FIELDS = ("mass", "positive_cells", "probe_mass_above", "probe_rank")
+CREDIBLE_LEVEL_FIELDS = ("threshold", "cells", "mass_share")
+
+
+def _credible_cols(cred):
+    n = cred.shape[-1]
+    if n < 7 or (n - len(CREDIBLE_HEAD_FIELDS)) % len(CREDIBLE_LEVEL_FIELDS) != 0:
+        raise ValueError(f"cred must be [..., 4 + 3 L] with L >= 1, got {tuple(cred.shape)}")
+    return (n - len(CREDIBLE_HEAD_FIELDS)) // len(CREDIBLE_LEVEL_FIELDS)
+
+
+def credible_to_metres(cred, metres_per_px):
+    """cred rows [..., 4 + 3 L] (a tensor or an array) with every level's area in square metres: metres_per_px is the ground size
+    of one cell of the 512 grid, a number or one per row ([B], as summary_to_metres takes it).  The "cells" column of every level
+    scales by its square; every other column - the counts of the head among them - is unchanged."""
+    import torch
+    if isinstance(cred, torch.Tensor):
+        out = cred.clone()
+        f = torch.as_tensor(metres_per_px, dtype=out.dtype, device=out.device)
+    else:
+        out = np.array(cred, dtype=np.float64 if np.asarray(cred).dtype == np.float64 else np.float32)
+        f = np.asarray(metres_per_px, dtype=out.dtype)
+    L = _credible_cols(out)
+    if f.ndim > 0:
+        f = f.reshape(tuple(f.shape) + (1,))
+    cols = [5 + 3 * j for j in range(L)]
+    out[..., cols] = out[..., cols] * (f * f)
+    return out
+
+
+def credible_contains(cred, levels) -> np.ndarray:
+    """Whether each query's probe cell lies in the region of each level: bool [..., L] from cred rows [..., 4 + 3 L'] of a call with
+    a probe and any levels p - the rule above < T(p) of include/ccvpe.h, evaluated in float64 from the columns "mass" and
+    "probe_mass_above": T = ceil(p Q), raised to 1 and capped at Q, Q = mass * 2^44.  The columns are float32 roundings of Q and of
+    above / Q, so a probe within 2^-23 of a level's boundary may fall on either side; the device's own rule, from the exact
+    integers, is the level map.  False where the probe columns are NaN (no probe, a bad index, an empty map)."""
+    c = np.asarray(cred.detach().cpu() if hasattr(cred, "detach") else cred, dtype=np.float64)
+    _credible_cols(c)
+    p = np.atleast_1d(np.asarray(levels, dtype=np.float32)).astype(np.float64)
+    if p.ndim != 1 or not (np.isfinite(p) & (p > 0) & (p <= 1)).all():
+        raise ValueError(f"levels must be numbers in (0, 1], got {p.tolist()}")
+    Q = c[..., 0:1] * 2.0 ** 44
+    above = c[..., 2:3] * Q
+    T = np.minimum(np.maximum(np.ceil(p * Q), 1.0), Q)
+    with np.errstate(invalid="ignore"):
+        return (above < T) & (Q > 0)
+
+
+def _with_credible(model, belief, out, levels):
+    """what a tracker step returns, with belief_credible's cred of the stored belief appended when levels are given"""
+    if levels is None:
+        return out
+    cred = model.belief_credible(belief, levels)
+    return (out if isinstance(out, tuple) else (out,)) + (cred,)
+
+
 # ---- heading posterior (DESIGN.md 4.13) ------------------------------------------------------------------------------------------
 
 # the 12 columns of model.localize_heading's heading rows, in order (include/ccvpe.h): angles in degrees [0, 360)
@@ -518,7 +577,7 @@ class Tracker:
         self.hist = None
 
     def step(self, model, grd, cache, tile_index, origins, motion_map_px, taps, floor, summary_radius=None, heading_bins=None,
-             heading_turn_deg=None, heading_taps=None, heading_floor=None):
+             heading_turn_deg=None, heading_taps=None, heading_floor=None, credible_levels=None):
         """One frame of B parallel streams.  cache / tile_index: as model.localize_cached; origins [T,2]: the crop origin of every
         cached tile (oxford_tiles' "origin"; one per query when tile_index is None); motion_map_px [B,2] or [2]: the motion since
         the last step in map pixels (ignored by the first step); taps, floor: as model.track_predict.  Returns the rows [B,5];
@@ -529,7 +588,9 @@ class Tracker:
         summary_radius, or 8 without one.  With heading_turn_deg (a number or [B]: the heading change since the last step, positive
         when the heading angle grows), heading_taps and heading_floor (as model.heading_predict; they require heading_bins) the
         heading is filtered too: the tracker keeps the last hist, and every step after the first runs model.heading_predict on it
-        and takes the result as the heading prior of model.localize_heading_prior_cached.  Returns are unchanged."""
+        and takes the result as the heading prior of model.localize_heading_prior_cached.  Returns are unchanged.
+        With credible_levels (1..8 levels in (0, 1]) the step runs model.belief_credible on the belief it has just stored and appends
+        cred [B, 4 + 3 L] (CREDIBLE_HEAD_FIELDS, CREDIBLE_LEVEL_FIELDS) to what it returns; nothing else changes."""
         filt = _heading_filter_args(heading_bins, heading_turn_deg, heading_taps, heading_floor)
         org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
         B = grd.shape[0]
@@ -563,8 +624,10 @@ class Tracker:
         self.origin = now.copy()
         self.hist = heading[1] if filt else None
         if heading is None:
-            return rows if summary is None else (rows, summary)
-        return ((rows,) if summary is None else (rows, summary)) + tuple(heading)
+            out = rows if summary is None else (rows, summary)
+        else:
+            out = ((rows,) if summary is None else (rows, summary)) + tuple(heading)
+        return _with_credible(model, self.belief, out, credible_levels)
 
 
 # ---- tracking across rotated or rescaled frames -----------------------------------------------------------------
@@ -696,7 +759,7 @@ class AffineTracker:
         self.hist = None
 
     def step(self, model, grd, sat, matrix, taps, floor, summary_radius=None, heading_bins=None, cache=None, tile_index=None,
-             heading_turn_deg=None, heading_taps=None, heading_floor=None):
+             heading_turn_deg=None, heading_taps=None, heading_floor=None, credible_levels=None):
         """One frame of B parallel streams.  sat: this frame's aerial images [B,3,512,512], or None with cache / tile_index as
         model.localize_cached; matrix [B,6] or [6]: this frame's pixel index -> the position in the LAST frame's grid it shows
         (rigid_matrix, kitti_track_matrix; ignored by the first step); taps, floor: as model.track_predict.  Returns what
@@ -705,7 +768,7 @@ class AffineTracker:
         forms beside a cache.  heading_turn_deg, heading_taps, heading_floor: the heading filter of Tracker.step (the updates are
         then model.localize_heading_prior / _cached).  The orientation field is expressed in each frame's own grid, so here the turn
         must include the rotation between the two grids: the change of the heading angle as THIS frame's grid measures it against
-        the last frame's, not the vehicle's turn alone."""
+        the last frame's, not the vehicle's turn alone.  credible_levels: as Tracker.step - cred of the stored belief, appended."""
         filt = _heading_filter_args(heading_bins, heading_turn_deg, heading_taps, heading_floor)
         if (sat is None) == (cache is None):
             raise ValueError("give this frame's aerial side as sat or as cache, one of the two")
@@ -751,5 +814,7 @@ class AffineTracker:
                                                                        tile_index=tile_index)
         self.hist = heading[1] if filt else None
         if heading is None:
-            return rows if summary is None else (rows, summary)
-        return ((rows,) if summary is None else (rows, summary)) + tuple(heading)
+            out = rows if summary is None else (rows, summary)
+        else:
+            out = ((rows,) if summary is None else (rows, summary)) + tuple(heading)
+        return _with_credible(model, self.belief, out, credible_levels)

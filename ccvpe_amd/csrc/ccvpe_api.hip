@@ -520,7 +520,8 @@ static int ensure_scratch(ccvpe_handle_s::Scratch& buf, int batch, size_t (*byte
 // counters]; the argmax form's (max, index) hand-off pairs use the start of the key area.  Every area is a multiple of 8 bytes long.
 static size_t prior_scratch_bytes(int B) {
     return topk_scratch_bytes(B) + (size_t)B * TAIL_CHUNKS * 2 * sizeof(float) + (size_t)B * TAIL_CHUNKS * SUMMARY_PART * sizeof(double) +
-           (size_t)B * TAIL_CHUNKS * HEADING_PART * sizeof(double) + (size_t)B * HEADING_MAX_BINS * sizeof(unsigned long long);
+           (size_t)B * TAIL_CHUNKS * HEADING_PART * sizeof(double) + (size_t)B * HEADING_MAX_BINS * sizeof(unsigned long long) +
+           (credible_zero_words(B) + credible_state_words(B)) * sizeof(unsigned);   // (the credible forms: at most CRED_SLICE queries' worth)
 }
 // ... as the tail's working memory over the forward outputs the caller holds.  pose.argmax and pose.heading share the one ticket
 // range: they run in order on one stream, and each leaves its counters at zero
@@ -535,6 +536,10 @@ static TailBuffers scratch_buffers(const ccvpe_handle_s::Scratch& buf, const flo
     w.summ_part = reinterpret_cast<double*>(w.partial + (size_t)buf.batch * TAIL_CHUNKS * 2);   // (read by the summary forms alone)
     w.head_part = w.summ_part + (size_t)buf.batch * TAIL_CHUNKS * SUMMARY_PART;               // (these two by the heading form alone)
     w.bins = reinterpret_cast<unsigned long long*>(w.head_part + (size_t)buf.batch * TAIL_CHUNKS * HEADING_PART);
+    // the credible forms (the prior scratch alone reaches this far): histograms and probe sums, zero between launches, then the states
+    w.cred_tickets = w.tickets;
+    w.cred_zero = w.bins + (size_t)buf.batch * HEADING_MAX_BINS;
+    w.cred_state = reinterpret_cast<unsigned*>(w.cred_zero) + credible_zero_words(buf.batch);
     return w;
 }
 
@@ -885,6 +890,7 @@ static int run_logits_tail(ccvpe_handle h, const float* logits, const float* ori
         launch_pose_gather(ori, w.index, batch, n, t.rows, s);
     }
     if (t.heading) issue_pose_heading(w, t, batch, s);   // (behind pose.argmax on the same stream: its counters are back at zero, its index is written)
+    if (t.cred) issue_pose_credible(w, t, nullptr, batch, s);   // (likewise: the partials of softmax.partial are the map's statistics)
     return 0;
 }
 
@@ -1271,6 +1277,125 @@ int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int3
     p.B = batch; p.nb = nb;
     launch_heading_predict(p, (hipStream_t)stream);
     return launch_status("heading_predict launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Credible regions: the radix select of kernels_credible.hip over a stored map (ccvpe_belief_credible, on the prior
+// scratch), behind the logits tail on the prior scratch (ccvpe_postprocess_credible), or as pose.credible behind pose.argmax in
+// plans of their own (PlanKey::credible; every other launch keeps the name and tuning entry of the argmax pose plan).
+// ------------------------------------------------------------------------------------------------
+// the levels: host memory, read here and carried by value from here on
+static int check_credible_levels(const float* levels, int32_t n_levels) {
+    if (n_levels < 1 || n_levels > CRED_MAX_LEVELS) return ccvpe_fail(CCVPE_EINVAL, "n_levels must be in 1 .. %d, got %d", CRED_MAX_LEVELS, n_levels);
+    for (int32_t j = 0; j < n_levels; ++j)
+        if (!(std::isfinite(levels[j]) && levels[j] > 0.f && levels[j] <= 1.f))
+            return ccvpe_fail(CCVPE_EINVAL, "levels[%d] = %g is not a finite level in (0, 1]", j, (double)levels[j]);
+    return 0;
+}
+// cred and level_map against each other and against every other buffer of the call (null entries: absent)
+struct CredOther { const char* name; const void* ptr; };
+static int check_credible_alias(const void* cred, const void* level_map, std::initializer_list<CredOther> others) {
+    if (level_map && level_map == cred) return ccvpe_fail(CCVPE_EINVAL, "level_map must not alias cred");
+    for (const CredOther& o : others) {
+        if (o.ptr && o.ptr == cred) return ccvpe_fail(CCVPE_EINVAL, "cred must not alias %s", o.name);
+        if (o.ptr && level_map && o.ptr == level_map) return ccvpe_fail(CCVPE_EINVAL, "level_map must not alias %s", o.name);
+    }
+    return 0;
+}
+static void credible_call(TailCall& t, const float* levels, int32_t n_levels, const int32_t* probe, float* cred, uint8_t* level_map) {
+    t.cred = cred; t.cred_levels = n_levels; t.cred_probe = probe; t.cred_map = level_map;
+    for (int32_t j = 0; j < n_levels; ++j) t.cred_level[j] = levels[j];
+}
+// what the forms with rows share behind their own pointers: the levels, the prior's stride, the optional posterior's aliasing
+static int check_credible_tail(const float* levels, int32_t n_levels, const float* log_prior, int64_t prior_stride) {
+    if (int rc = check_credible_levels(levels, n_levels)) return rc;
+    if (log_prior) if (int rc = check_prior_stride(prior_stride)) return rc;
+    return 0;
+}
+
+int ccvpe_belief_credible(ccvpe_handle h, const float* belief, int32_t batch, const float* levels, int32_t n_levels, const int32_t* probe,
+                          float* cred, uint8_t* level_map, void* stream) {
+    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
+    if (!levels) return ccvpe_fail(CCVPE_EINVAL, "null levels");
+    if (!cred) return ccvpe_fail(CCVPE_EINVAL, "null cred");
+    if (int rc = check_credible_levels(levels, n_levels)) return rc;
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (((uintptr_t)belief & 3) != 0) return ccvpe_fail(CCVPE_EINVAL, "belief must be 4-byte aligned");
+    if (int rc = check_credible_alias(cred, level_map, {{"belief", belief}, {"probe", probe}})) return rc;
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->prior_scratch, batch, prior_scratch_bytes, "prior post-processing scratch")) return rc;
+    const TailBuffers w = scratch_buffers(h->prior_scratch, nullptr, nullptr);
+    TailCall t;
+    credible_call(t, levels, n_levels, probe, cred, level_map);
+    issue_pose_credible(w, t, belief, batch, (hipStream_t)stream);
+    return launch_status("belief_credible launch");
+}
+
+int ccvpe_postprocess_credible(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                               int64_t prior_stride, const float* levels, int32_t n_levels, const int32_t* probe, float* rows, float* cred,
+                               uint8_t* level_map, float* posterior, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (!levels) return ccvpe_fail(CCVPE_EINVAL, "null levels");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!cred) return ccvpe_fail(CCVPE_EINVAL, "null cred");
+    if (int rc = check_credible_tail(levels, n_levels, log_prior, prior_stride)) return rc;
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (int rc = check_credible_alias(cred, level_map, {{"logits", logits}, {"ori", ori}, {"log_prior", log_prior}, {"probe", probe}, {"rows", rows},
+                                                        {"posterior", posterior}})) return rc;
+    if (posterior && log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    if (posterior && posterior == rows) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias rows");
+    if (posterior && posterior == logits) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias logits");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    TailCall t;
+    t.rows = rows; t.log_prior = log_prior; t.prior_stride = log_prior ? prior_stride : 0; t.posterior = posterior;
+    credible_call(t, levels, n_levels, probe, cred, level_map);
+    if (int rc = run_logits_tail(h, logits, ori, batch, t, (hipStream_t)stream)) return rc;
+    return launch_status("postprocess_credible launch");
+}
+
+int ccvpe_localize_credible(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                            const float* log_prior, int64_t prior_stride, const float* levels, int32_t n_levels, const int32_t* probe,
+                            float* rows, float* cred, uint8_t* level_map, float* posterior, void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!sat) return ccvpe_fail(CCVPE_EINVAL, "null sat");
+    if (!levels) return ccvpe_fail(CCVPE_EINVAL, "null levels");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!cred) return ccvpe_fail(CCVPE_EINVAL, "null cred");
+    if (int rc = check_credible_tail(levels, n_levels, log_prior, prior_stride)) return rc;
+    if (int rc = check_credible_alias(cred, level_map, {{"grd", grd}, {"sat", sat}, {"log_prior", log_prior}, {"probe", probe}, {"rows", rows},
+                                                        {"posterior", posterior}})) return rc;
+    if (posterior && log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    if (posterior && posterior == rows) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias rows");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.sat = sat; fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
+    credible_call(fc.tail, levels, n_levels, probe, cred, level_map);
+    return run_forward(h, fc);
+}
+
+int ccvpe_localize_credible_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache, int32_t n_tiles,
+                                           const int32_t* tile_index, int32_t batch, const float* log_prior, int64_t prior_stride,
+                                           const float* levels, int32_t n_levels, const int32_t* probe, float* rows, float* cred,
+                                           uint8_t* level_map, float* posterior, void* stream) {
+    if (!grd) return ccvpe_fail(CCVPE_EINVAL, "null grd");
+    if (!cache) return ccvpe_fail(CCVPE_EINVAL, "null cache");
+    if (!levels) return ccvpe_fail(CCVPE_EINVAL, "null levels");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!cred) return ccvpe_fail(CCVPE_EINVAL, "null cred");
+    if (int rc = check_credible_tail(levels, n_levels, log_prior, prior_stride)) return rc;
+    if (int rc = check_credible_alias(cred, level_map, {{"grd", grd}, {"cache", cache}, {"log_prior", log_prior}, {"probe", probe}, {"rows", rows},
+                                                        {"posterior", posterior}})) return rc;
+    if (int rc = check_cached_args(grd, cache, n_tiles, tile_index, batch, rows)) return rc;
+    if (posterior && log_prior && (const float*)log_prior == posterior) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias log_prior");
+    if (posterior && posterior == rows) return ccvpe_fail(CCVPE_EINVAL, "posterior must not alias rows");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    ForwardCall fc = forward_call(grd, grd_h, grd_w, batch, stream);
+    fc.cache = (const float*)cache; fc.tile_index = tile_index; fc.n_tiles = n_tiles;
+    fc.tail.rows = rows; fc.tail.log_prior = log_prior; fc.tail.prior_stride = log_prior ? prior_stride : 0; fc.tail.posterior = posterior;
+    credible_call(fc.tail, levels, n_levels, probe, cred, level_map);
+    return run_forward(h, fc);
 }
 
 int ccvpe_preprocess(const uint8_t* hwc, int32_t batch, int32_t H, int32_t W, const int32_t* shift, int32_t crop_w,

@@ -267,6 +267,11 @@ struct TailCall {
     int heading_bins = 0, heading_r = 0;   // ... the bin count 4..360 and the window radius 0..32
     const float* hprior_table = nullptr;   // heading plans, optional (ccvpe_localize_heading_prior*): the heading prior's tables,
     int hprior_stride = 0, hprior_nb = 0;  //   the floats between two queries' tables (0: one for all) and the table's bins 4..360
+    float* cred = nullptr;             // optional [batch][4 + 3 cred_levels] credible rows (ccvpe_*_credible); selects the credible
+    int cred_levels = 0;               //   plans; with it the levels 1..8, by value as they travel to the launches,
+    float cred_level[CRED_MAX_LEVELS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int32_t* cred_probe = nullptr;       //   the optional probe cell of each query [batch] and
+    unsigned char* cred_map = nullptr;         //   the optional level maps [batch][512*512]
     // the view of the micro-batch that starts at query `done`: every per-query buffer advanced by its own row size
     TailCall at(int done) const {
         const size_t d = (size_t)done, npx = (size_t)CCVPE_OUT_HW * CCVPE_OUT_HW;
@@ -278,6 +283,9 @@ struct TailCall {
         if (summary) t.summary += d * SUMMARY_COLS;
         if (heading) { t.heading += d * HEADING_COLS; t.hist += d * heading_bins; }
         if (hprior_table) t.hprior_table += d * hprior_stride;
+        if (cred) t.cred += d * (4 + 3 * cred_levels);
+        if (cred_probe) t.cred_probe += d;
+        if (cred_map) t.cred_map += d * npx;
         return t;
     }
 };
@@ -295,11 +303,15 @@ struct TailBuffers {
     unsigned long long* bins = nullptr;   //   [B][HEADING_MAX_BINS], zero between launches (pose.heading)
     unsigned* tickets = nullptr;       // [B] counters of pose.argmax or topk.peaks ...
     unsigned* head_tickets = nullptr;  // ... and of pose.heading (the same range where both run in order on one stream)
+    unsigned* cred_tickets = nullptr;  // ... and of pose.credible, with
+    void* cred_zero = nullptr;         //   its histograms and probe sums (credible_zero_words: zero between launches) and
+    void* cred_state = nullptr;        //   the states its passes hand on (credible_state_words)
 };
 void issue_softmax_partial(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
 void issue_pose_argmax(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
 void issue_topk_peaks(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
 void issue_pose_heading(const TailBuffers& w, const TailCall& t, int B, hipStream_t s);
+void issue_pose_credible(const TailBuffers& w, const TailCall& t, const float* belief, int B, hipStream_t s);   // belief: a stored map instead of w.logits
 
 struct Ctx {
     float* arena = nullptr;
@@ -346,9 +358,11 @@ struct PlanKey {
                                   // decoders (ccvpe_localize_heading*); combines with summary
     bool hprior = false;          // heading plans: the combined prior map `comb` in the workspace, written by pose.hprior from the orientation
                                   // field, read by the tail in place of the caller's prior (ccvpe_localize_heading_prior*); needs heading
+    bool credible = false;        // argmax pose plans: the pose.credible launches behind pose.argmax, over the logits the workspace still holds
+                                  // (ccvpe_localize_credible*); combines with none of topk, summary, heading
     bool operator==(const PlanKey& o) const {
         return B == o.B && gh == o.gh && gw == o.gw && mode == o.mode && pose == o.pose && topk == o.topk && summary == o.summary &&
-               heading == o.heading && hprior == o.hprior;
+               heading == o.heading && hprior == o.hprior && credible == o.credible;
     }
 };
 
@@ -372,6 +386,7 @@ struct ForwardCall {
         key.summary = tail.rows && tail.summary;
         key.heading = tail.rows && tail.heading;
         key.hprior = key.heading && tail.hprior_table;
+        key.credible = tail.rows && tail.cred;
         return key;
     }
 };

@@ -357,6 +357,19 @@ void issue_pose_heading(const TailBuffers& w, const TailCall& t, int B, hipStrea
     launch_heading_reduce(p, s);
 }
 
+// Credible regions of the map pose.argmax describes - the logits (+ prior) with the partials of softmax.partial, an
+// earlier launch - or, belief set, of a stored map: CRED_PASSES launches and one more with a level map, per CRED_SLICE queries
+void issue_pose_credible(const TailBuffers& w, const TailCall& t, const float* belief, int B, hipStream_t s) {
+    CredibleParams p{};
+    p.belief = belief;
+    if (!belief) { p.logits = w.logits; p.partial = w.partial; p.prior = t.log_prior; p.prior_stride = t.prior_stride; }
+    p.probe = t.cred_probe; p.B = B; p.n_levels = t.cred_levels;
+    for (int j = 0; j < CRED_MAX_LEVELS; ++j) p.level[j] = t.cred_level[j];
+    credible_scratch(p, B, w.cred_zero, w.cred_state);
+    p.tickets = w.cred_tickets; p.cred = t.cred; p.level_map = t.cred_map;
+    launch_credible(p, s);
+}
+
 // Pose plans (pose = true, ccvpe_localize): the launches of the full (mode 0) or cached (mode 2) plan up to and including the level-2
 // decoders, under the same names - so the same tuning-table entries - and a tail that writes only the [B][5] result rows of
 // ccvpe_postprocess_rows: no matching-score stacks (the match kernels skip the ms store), the logits in the workspace, the first softmax
@@ -375,6 +388,9 @@ void issue_pose_heading(const TailBuffers& w, const TailCall& t, int B, hipStrea
 // Heading-prior plans (hprior = true as well, ccvpe_localize_heading_prior*): the heading plan plus the workspace map `comb`
 // and pose.hprior, which writes it from the orientation field, the call's heading table and its position prior; softmax.partial,
 // pose.argmax and pose.heading read `comb` in place of the caller's prior, so they are added behind the field's launch.
+// Credible plans (credible = true, ccvpe_localize_credible*): the argmax pose plan with pose.credible - the radix
+// select's launches - behind pose.argmax on its stream, reading the logits the workspace still holds; the histograms live beside the
+// counters (zero between launches), the passes' states in the workspace.
 // Pair plans (mode 4, pose, ccvpe_localize_region): the cached pose plan with the ground side from a ground cache as well - the ground
 // encoder, grd.heads and grd.desc give way to grd.cached_desc, a gather of each pair's query row (Ctx::query_index); the aerial
 // launches gather each pair's tile (Ctx::tile_index).  Every other launch keeps the cached pose plan's name and tuning entry.
@@ -386,6 +402,9 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
     pl.key.summary = pose && !key.topk && key.summary;
     pl.key.heading = key.heading;
     pl.key.hprior = key.hprior;
+    pl.key.credible = key.credible;
+    if (key.credible && (!pose || key.topk || key.summary || key.heading || mode == 4))
+        return ccvpe_fail(CCVPE_EINVAL, "credible plans are plain argmax pose plans (no top-K, no summary, no heading, no pairs)");
     if (key.heading && (!pose || key.topk || mode == 4)) return ccvpe_fail(CCVPE_EINVAL, "heading plans are argmax pose plans (no top-K, no pairs)");
     if (key.hprior && !key.heading) return ccvpe_fail(CCVPE_EINVAL, "heading-prior plans are heading plans");
     if (mode == 1) return build_aerial_plan(h, pl, B);
@@ -749,13 +768,16 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         Tensor part, keys;    // the softmax partials (read again by pose.heading); the (max, index) pairs or the top-K keys
         Tensor index;         // [B] argmax (int32), read by the orientation side; top-K: [B][K] (-1: no peak)
         Tensor spart, hpart;  // the float64 hand-offs of the summary and the heading sums
+        Tensor cstate;        // the states of pose.credible's passes
         size_t toff = 0, htoff = 0, boff = 0;   // ticket ranges: pose.argmax or topk.peaks, pose.heading, its fixed-point histograms
+        size_t ctoff = 0, czoff = 0;            // ... pose.credible and its histograms
         TailBuffers at(const Ctx& c) const {
             auto ptr = [&](const Tensor& t) { return t.id < 0 ? nullptr : c.ptr(t); };
             TailBuffers w;
             w.logits = ptr(logits); w.ori = ptr(ori); w.partial = ptr(part); w.keys = ptr(keys); w.index = reinterpret_cast<int*>(ptr(index));
             w.summ_part = reinterpret_cast<double*>(ptr(spart)); w.head_part = reinterpret_cast<double*>(ptr(hpart));
             w.tickets = c.tickets + toff; w.head_tickets = c.tickets + htoff; w.bins = reinterpret_cast<unsigned long long*>(c.tickets + boff);
+            w.cred_tickets = c.tickets + ctoff; w.cred_zero = c.tickets + czoff; w.cred_state = ptr(cstate);
             return w;
         }
     } tt;
@@ -799,6 +821,13 @@ int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key) {
         if (summ) am_uses.push_back(tt.spart);
         if (hprior) am_uses.push_back(comb);
         if (!topk) pl.add("pose.argmax", am_uses, [=](const Ctx& c) { issue_pose_argmax(wt.at(c), call_of(c), B, c.stream); }, 0, 4.0 * B * 262144.0);
+        if (pl.key.credible) {
+            tt.cstate = pl.alloc(1, 1, 1, (int)credible_state_words(B));
+            tt.ctoff = pl.alloc_tickets((size_t)B); tt.czoff = pl.alloc_tickets(credible_zero_words(B));
+            const TailTensors wc = tt;
+            pl.add("pose.credible", {tt.logits, tt.part, tt.cstate}, [=](const Ctx& c) { issue_pose_credible(wc.at(c), call_of(c), nullptr, B, c.stream); },
+                   0, 4.0 * B * 262144.0 * (CRED_PASSES + 1));
+        }
     };
     if (pose && !hprior) add_tail();
     if (!pose) {

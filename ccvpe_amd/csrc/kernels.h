@@ -486,6 +486,42 @@ struct HeadingParams {
 };
 void launch_heading_reduce(const HeadingParams& p, hipStream_t s);
 
+// Credible regions (kernels_credible.hip; the definition is pinned in include/ccvpe.h): a radix select on the keys of a
+// 512 x 512 map - the stored one, or pose_argmax_kernel's recomputed bits from logits (+ prior) and the softmax partials.  Per pass a grid
+// (64 chunks, B) with a last arriver per query; CRED_PASSES launches and, with a level map, one more.  Integer adds only.
+static constexpr int CRED_MAX_LEVELS = 8, CRED_DIGITS = 256, CRED_PASSES = 4, CRED_SLICE = 256;
+struct CredState {             // per query: what a pass's last arriver leaves for the next launch
+    unsigned long long Q;                         // the map's total mass (pass 0)
+    unsigned long long T[CRED_MAX_LEVELS];        // the levels' thresholds T(p) (pass 0)
+    unsigned long long above[CRED_MAX_LEVELS];    // mass and ...
+    unsigned cabove[CRED_MAX_LEVELS];             // ... count of the keys above the level's prefix
+    unsigned prefix[CRED_MAX_LEVELS];             // the digits fixed so far, in place; after the last pass k*
+    unsigned group[CRED_MAX_LEVELS];              // the first level with the same prefix: its histogram row serves this level too
+    unsigned alive, pad;                          // Q > 0
+};
+static_assert(sizeof(CredState) % 8 == 0, "an array of states keeps its 64-bit fields aligned");
+struct CredibleParams {
+    const float* belief;       // [B][512*512] stored map, 4-byte aligned (16-byte aligned maps are read as float4), or null: recompute from
+    const float* logits;       //   [B][512*512] logits,
+    const float* partial;      //   [B][64][2] softmax partials (of logits + prior when there is one) and
+    const float* prior;        //   the optional log-prior as PoseArgmaxParams::prior
+    long long prior_stride;
+    const int* probe;          // optional [B] cell per query; an index outside the map is never dereferenced
+    int B, n_levels;           // n_levels 1 .. CRED_MAX_LEVELS
+    float level[CRED_MAX_LEVELS];   // the levels, by value
+    unsigned long long* hmass; // [min(B, CRED_SLICE)][8][256] the queries' histograms, ...
+    unsigned* hcnt;            // ... their counts and ...
+    unsigned long long* pacc;  // ... [..][2] the probe's sums: zero before and after every launch, like ...
+    unsigned* tickets;         // ... the [B] counters
+    CredState* state;          // [min(B, CRED_SLICE)]
+    float* cred;               // [B][4 + 3 n_levels]
+    unsigned char* level_map;  // optional [B][512*512]
+};
+size_t credible_zero_words(int B);    // 32-bit words of the zeroed region for B queries (8-byte aligned start) ...
+size_t credible_state_words(int B);   // ... and of the states
+void credible_scratch(CredibleParams& p, int B, void* zeroed, void* state);   // hmass, hcnt, pacc and state over those two regions
+void launch_credible(const CredibleParams& p, hipStream_t s);   // CRED_PASSES launches (+ 1 with a level map) per CRED_SLICE queries
+
 // Top-K peaks (ccvpe_postprocess_topk / ccvpe_localize_topk).  Grid (64 tiles of 64 x 64, B): peaks of the heatmap
 // under a Chebyshev radius r (value descending, index ascending), the best k per tile handed to the sample's last arriver (ticket),
 // which writes index[b][k] (-1: no peak) and rows[b][k][0..1] - the whole row (-1, 0, 0, 0, 0) for a slot without a peak.

@@ -255,7 +255,7 @@ class _CVMBase(nn.Module):
         return out, (logits, heat, ori, *ms)
 
     def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False, summary=False,
-              heading=0):
+              heading=0, alloc=None):
         """The skeleton forward and the pose forms share: validate and normalise grd and sat - or, sat=None, the cache and tile_index of a
         cached form -, ensure the handle, allocate the results, call ccvpe_<name> under the inputs' device on its current stream, check
         the return code, sync the tuning table.  args(B) holds the method's own argument checks, run after those of the inputs, and
@@ -265,7 +265,8 @@ class _CVMBase(nn.Module):
         take a nullable posterior behind it) and the posterior [B, 512, 512] behind them if asked.  heading = a bin count: the heading
         forms, whose C functions take heading [B, 12] and hist [B, bins] behind rows, then a nullable summary and a nullable posterior.
         Cached forms: ccvpe_<name> takes a nullable tile_index if the name ends in _indexed; the older forms have two entry points each,
-        ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it."""
+        ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it.  alloc(B, dev) -> (results,
+        C arguments): a form with results of its own (the credible forms), returned as they are."""
         if sat is not None:
             grd, sat = self._prepare(grd, sat)
         else:
@@ -292,6 +293,8 @@ class _CVMBase(nn.Module):
             if outputs:
                 out, res = self._alloc_outputs(B, dev)
                 ptrs = (C.byref(out),)
+            elif alloc is not None:
+                res, ptrs = alloc(B, dev)
             else:
                 res, ptrs = self._alloc_rows(B, dev, k, heading, summary, posterior)
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
@@ -300,7 +303,7 @@ class _CVMBase(nn.Module):
                                                        *extra, *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
         self._tuning_sync()
-        return res if outputs or posterior or summary or heading else res[0]
+        return res if outputs or posterior or summary or heading or alloc is not None else res[0]
 
     @staticmethod
     def _alloc_rows(B: int, dev, k: int, heading: int, summary: bool, posterior: bool):
@@ -601,7 +604,7 @@ class _CVMBase(nn.Module):
         return self._call("localize_prior_cached_indexed", grd, cache=cache, tile_index=tile_index,
                           args=lambda B: self._prior_args(log_prior, B, k, radius), k=k)
 
-    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False, heading=0):
+    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False, heading=0, alloc=None):
         """postprocess_prior, track_update_logits and postprocess_summary: validate and normalise the forward outputs the caller holds,
         check the prior with args(B) and take k (both as _call's), allocate rows (and the summary, the posterior) and call ccvpe_<name>."""
         if self.training:
@@ -619,13 +622,13 @@ class _CVMBase(nn.Module):
         dev = logits.device
         self._ensure_handle(dev)
         with torch.cuda.device(dev):
-            res, ptrs = self._alloc_rows(B, dev, k, heading, summary, posterior)
+            res, ptrs = alloc(B, dev) if alloc is not None else self._alloc_rows(B, dev, k, heading, summary, posterior)
             extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
             stream = torch.cuda.current_stream(dev).cuda_stream
             rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, *extra,
                                                        *ptrs, C.c_void_p(stream))
         _lib.check(rc, "ccvpe_" + name)
-        return res if posterior or summary or heading else res[0]
+        return res if posterior or summary or heading or alloc is not None else res[0]
 
     def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
                           ) -> torch.Tensor:
@@ -872,6 +875,111 @@ class _CVMBase(nn.Module):
                                                   C.c_void_p(out.data_ptr()), C.c_void_p(stream))
         _lib.check(rc, "ccvpe_belief_summary")
         return out
+
+    # ---- credible regions -------------------------------------------------------
+    @staticmethod
+    def _credible_levels(levels) -> np.ndarray:
+        """levels of the credible forms -> contiguous host float32 [L], 1 <= L <= 8, each finite and in (0, 1]; any order, repeats allowed"""
+        lv = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float32)))
+        if lv.ndim != 1 or not 1 <= lv.size <= 8:
+            raise ValueError(f"levels must hold 1..8 numbers, got shape {lv.shape}")
+        if not (np.isfinite(lv) & (lv > 0) & (lv <= 1)).all():
+            raise ValueError(f"every level must be finite and in (0, 1], got {lv.tolist()}")
+        return lv
+
+    @staticmethod
+    def _credible_probe(probe, B: int, dev) -> Optional[torch.Tensor]:
+        """probe of the credible forms -> None or an int32 tensor [B] on dev: one cell index per query, any value (an index outside
+        the map gives NaN and is never dereferenced)"""
+        if probe is None:
+            return None
+        t = probe if isinstance(probe, torch.Tensor) else torch.as_tensor(np.asarray(probe, dtype=np.int64))
+        if t.dim() != 1 or t.shape[0] != B or t.is_floating_point():
+            raise ValueError(f"probe must hold one integer cell index per query ([{B}]), got {tuple(t.shape)} {t.dtype}")
+        return t.detach().clamp(-1, 1 << 30).to(device=dev, dtype=torch.int32).contiguous()
+
+    @staticmethod
+    def _credible_alloc(L: int, level_map: bool, posterior: Optional[bool]):
+        """alloc of _call / _logits_call for a credible form: rows [B, 5] (posterior is None: the stored-map form, which has neither
+        rows nor a posterior), cred [B, 4 + 3 L], then the optional level map [B, 512, 512] uint8 and posterior [B, 512, 512]"""
+        def alloc(B, dev):
+            res = () if posterior is None else (torch.empty((B, 5), dtype=torch.float32, device=dev),)
+            res += (torch.empty((B, 4 + 3 * L), dtype=torch.float32, device=dev),)
+            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
+            for want, dtype in ((level_map, torch.uint8),) + (() if posterior is None else ((posterior, torch.float32),)):
+                t = torch.empty((B,) + spec.OUT_HW, dtype=dtype, device=dev) if want else None
+                res += (t,) if want else ()
+                ptrs += (C.c_void_p(t.data_ptr()) if want else None,)
+            return res, ptrs
+        return alloc
+
+    def _credible_args(self, log_prior, B: int, lv: np.ndarray, probe, dev):
+        return self._track_prior(log_prior, B) + (lv.ctypes.data_as(C.c_void_p), int(lv.size), self._credible_probe(probe, B, dev))
+
+    def belief_credible(self, belief: torch.Tensor, levels, probe=None, level_map: bool = False):
+        """Credible regions of stored maps: cred [B, 4 + 3 L] for the L levels (each in (0, 1]; any order) - per query the columns
+        aerial.CREDIBLE_HEAD_FIELDS (total mass, positive cells, and for the probe cell the mass share and count of the cells strictly
+        above it), then aerial.CREDIBLE_LEVEL_FIELDS per level: the threshold value, the region's cells and its share of the mass.
+        The region of a level is the smallest set of whole value classes holding that share (include/ccvpe.h has the definition).
+        belief as belief_summary takes it; probe: one cell index per query (a tensor or a sequence) or None; level_map=True also
+        returns a uint8 map [B, 512, 512] of the number of levels whose region holds each cell: (cred, level_map).  An all-zero
+        map gives the level columns (NaN, 0, NaN) (ccvpe_belief_credible)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        if not isinstance(belief, torch.Tensor):
+            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
+        shape = tuple(belief.shape)
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
+                                                                                       and shape[2:] == spec.OUT_HW):
+            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
+        if belief.dtype != torch.float32:
+            raise ValueError(f"belief must be float32, got {belief.dtype}")
+        if not belief.is_contiguous():
+            raise ValueError("belief must be contiguous")
+        if shape[0] > 4096:
+            raise ValueError(f"belief holds {shape[0]} maps, at most 4096 per call")
+        lv = self._credible_levels(levels)
+        if not belief.is_cuda:
+            raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+        dev = belief.device
+        pr = self._credible_probe(probe, shape[0], dev)
+        self._ensure_handle(dev)
+        with torch.cuda.device(dev):
+            res, ptrs = self._credible_alloc(int(lv.size), level_map, None)(shape[0], dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().ccvpe_belief_credible(self._handle, C.c_void_p(belief.detach().data_ptr()), shape[0], lv.ctypes.data_as(C.c_void_p),
+                                                   int(lv.size), C.c_void_p(pr.data_ptr()) if pr is not None else None, *ptrs,
+                                                   C.c_void_p(stream))
+        _lib.check(rc, "ccvpe_belief_credible")
+        return res if level_map else res[0]
+
+    def localize_credible(self, grd: torch.Tensor, sat: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
+                          level_map: bool = False, posterior: bool = False):
+        """The pose and the credible regions of its posterior: (rows [B, 5], cred [B, 4 + 3 L]), then the level map and the posterior
+        if asked.  rows and posterior are track_update(grd, sat, log_prior)'s; cred and the level map are belief_credible's on that
+        posterior, bit for bit, whether or not it is returned (ccvpe_localize_credible)."""
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        lv = self._credible_levels(levels)
+        own = self._credible_args(log_prior, grd.shape[0], lv, probe, grd.device)   # (before the inputs' checks)
+        return self._call("localize_credible", grd, sat, args=lambda B: own, alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
+
+    def localize_credible_cached(self, grd: torch.Tensor, cache: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
+                                 level_map: bool = False, posterior: bool = False, tile_index=None):
+        """localize_credible with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
+        (ccvpe_localize_credible_cached_indexed)."""
+        lv = self._credible_levels(levels)
+        return self._call("localize_credible_cached_indexed", grd, cache=cache, tile_index=tile_index,
+                          args=lambda B: self._credible_args(log_prior, B, lv, probe, grd.device),
+                          alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
+
+    def postprocess_credible(self, logits: torch.Tensor, ori: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
+                             level_map: bool = False, posterior: bool = False):
+        """localize_credible from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
+        ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_credible)."""
+        lv = self._credible_levels(levels)
+        return self._logits_call("postprocess_credible", logits, ori, lambda B: self._credible_args(log_prior, B, lv, probe, logits.device),
+                                 alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
 
     # ---- heading posterior (DESIGN.md 4.13) ------------------------------------------------------
     @classmethod

@@ -503,6 +503,61 @@ int ccvpe_localize_heading_prior_cached_indexed(ccvpe_handle h, const float* grd
 int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int32_t nb, const float* turn_deg, const float* taps,
                           int32_t taps_stride, int32_t radius, const float* floor, float* out, void* stream);
 
+/* Credible regions: the smallest set of cells holding a share of the posterior (the highest-density region of a histogram
+ * posterior).  Per query, over the n = 512 * 512 cells of a float32 map h - ccvpe_belief_credible: the map given; the other forms:
+ * the posterior h' of the prior forms, the map ccvpe_track_update* stores (all zero for a query without a finite posterior):
+ *   key    k_i = the uint32 bit pattern of h_i when h_i > 0, else 0.  +inf is a value; NaN, zero and negative values have key 0.
+ *          Positive floats order as their bit patterns do.
+ *   mass   q_i = (uint64) floorf(fminf(h_i, 1.f) * 2^44) when h_i > 0, else 0: an exact scaling and one truncation.  A value above
+ *          1 is outside the contract: it is ordered by its value and weighs 1.  A cell below 2^-44 has a key and no mass.
+ *   total  Q = sum q_i, an exact uint64 (n * 2^44 = 2^62).  G(k) = sum of q_i over k_i >= k, C(k) = count of k_i >= k.
+ *   level  p, a float32 in (0, 1]: T = (uint64) ceil((double)p * (double)Q), raised to 1 and capped at Q.  k* = the largest key
+ *          present in the map with G(k*) >= T; the region is { i : k_i >= k* } - closed under ties, the smallest union of whole
+ *          value classes that holds at least the share p.  It exists whenever Q > 0.
+ *   probe  optional, one cell index per query (DEVICE int32 [batch], NULL: none): above = sum of q_i over k_i > k_probe,
+ *          rank = count of k_i > k_probe.  The cell lies in the region of level p exactly when above < T(p).  An index outside
+ *          [0, n) gives NaN for both and nothing is read there (the rule of gt_index in ccvpe_eval_metrics).
+ * `cred` is float32 DEVICE memory [batch][4 + 3 * n_levels]:
+ *     0        (float)((double)Q * 2^-44)
+ *     1        cells with h > 0
+ *     2        probe: (float)((double)above / (double)Q); NaN without a probe, with a bad index, or when Q == 0
+ *     3        probe: rank; NaN without a probe or with a bad index
+ *     4 + 3j   level j: the threshold value, the float whose bits are k*
+ *     5 + 3j   level j: C(k*), the region's area in cells (exact, at most 2^18)
+ *     6 + 3j   level j: (float)((double)G(k*) / (double)Q), at least p up to that one rounding
+ * Q == 0: the level columns are (NaN, 0, NaN).  `level_map` (optional, NULL: none) is uint8 DEVICE memory [batch][n]: cell i holds
+ * the number of requested levels whose region contains it - with ascending levels a contour map, a value >= n_levels - j marks
+ * the region of level j; all zero when Q == 0.  `levels` is HOST float32 [n_levels], 1 <= n_levels <= 8, each finite and in
+ * (0, 1], any order, repeats allowed; they travel in the launch arguments (no copy to the device, no synchronisation, the array
+ * may be reused when the call returns).  Every number is an integer or one correctly rounded float64 operation on integers: the
+ * same inputs give the same bits in every form, on every run.
+ *   ccvpe_belief_credible: a stored map (4-byte aligned; 16-byte aligned maps are read as float4).  4 launches, 5 with a
+ *     level_map, per 256 queries of the batch.
+ *   ccvpe_postprocess_credible: rows and the optional posterior of ccvpe_track_update_logits, cred and level_map of
+ *     ccvpe_belief_credible on that posterior, bit for bit, whether or not it is stored.  The launches of
+ *     ccvpe_track_update_logits plus those of ccvpe_belief_credible.
+ *   ccvpe_localize_credible, ccvpe_localize_credible_cached_indexed (tile_index may be NULL): the same for
+ *     ccvpe_track_update / ccvpe_track_update_cached_indexed; plans of their own, the argmax pose plan with the credible launches
+ *     (4, 5 with a level_map) behind pose.argmax.
+ * log_prior, probe, level_map and posterior may be NULL.  CCVPE_EINVAL, nothing launched, checked before the handle is used: a
+ * null pointer other than those, n_levels outside 1..8, a level that is not finite or not in (0, 1], a bad prior_stride beside a
+ * prior, batch outside 1..4096 (stored-map and logits forms), a misaligned belief, cred or level_map equal to each other or to
+ * any input or other output; then the checks of the matching ccvpe_track_update form.  CCVPE_ESTATE on a debug handle for the two
+ * network forms.  The stored-map and logits forms share the scratch of ccvpe_postprocess_prior: one call in flight per handle. */
+#define CCVPE_CREDIBLE_MAX_LEVELS 8
+int ccvpe_belief_credible(ccvpe_handle h, const float* belief, int32_t batch, const float* levels, int32_t n_levels,
+                          const int32_t* probe, float* cred, uint8_t* level_map, void* stream);
+int ccvpe_postprocess_credible(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* log_prior,
+                               int64_t prior_stride, const float* levels, int32_t n_levels, const int32_t* probe, float* rows,
+                               float* cred, uint8_t* level_map, float* posterior, void* stream);
+int ccvpe_localize_credible(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const float* sat, int32_t batch,
+                            const float* log_prior, int64_t prior_stride, const float* levels, int32_t n_levels,
+                            const int32_t* probe, float* rows, float* cred, uint8_t* level_map, float* posterior, void* stream);
+int ccvpe_localize_credible_cached_indexed(ccvpe_handle h, const float* grd, int32_t grd_h, int32_t grd_w, const void* cache,
+                                           int32_t n_tiles, const int32_t* tile_index, int32_t batch, const float* log_prior,
+                                           int64_t prior_stride, const float* levels, int32_t n_levels, const int32_t* probe,
+                                           float* rows, float* cred, uint8_t* level_map, float* posterior, void* stream);
+
 /* Input pre-processing on device (reference train_VIGOR.py:57-70 ToTensor + Normalize, datasets.py:118
  * torch.roll(grd, shift, dims=2), train_VIGOR.py:272-273 FoV crop): uint8 HWC images [B,H,W,3] (decoded and
  * resized on the host) -> float32 NCHW [B,3,H,crop_w] with out[..., x] = norm(in[..., (x - shift[b]) mod W, :]).
