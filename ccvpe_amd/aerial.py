@@ -442,12 +442,13 @@ def credible_contains(cred, levels) -> np.ndarray:
         return (above < T) & (Q > 0)
 
 
-def _with_credible(model, belief, out, levels):
-    """what a tracker step returns, with belief_credible's cred of the stored belief appended when levels are given"""
-    if levels is None:
-        return out
-    cred = model.belief_credible(belief, levels)
-    return (out if isinstance(out, tuple) else (out,)) + (cred,)
+def _step_result(model, rows, summary, heading, belief, levels):
+    """what a tracker step returns: rows alone, or (rows, summary if any, heading and hist if any, belief_credible's cred of the
+    stored belief if levels are given)"""
+    out = (rows,) + (() if summary is None else (summary,)) + (() if heading is None else tuple(heading))
+    if levels is not None:
+        out += (model.belief_credible(belief, levels),)
+    return out[0] if len(out) == 1 else out
 
 
 # ---- heading posterior (DESIGN.md 4.13) ------------------------------------------------------------------------------------------
@@ -561,6 +562,30 @@ def _heading_table(model, hist, B: int, heading_bins, turn_deg, taps, floor):
     return model.heading_predict(hist, turn_deg, taps, floor)
 
 
+def _update(model, grd, sat, cache, tile_index, prior, table, summary_radius, heading_bins):
+    """The update half of both trackers' steps -> (rows, summary or None, (heading, hist) or None, belief).  The aerial side is sat, or
+    (sat is None) cache and tile_index; prior: the predicted position prior or None; table: the predicted heading prior or None.
+    The family follows from what the step returns: heading_bins -> the heading forms (under the table: the heading-prior forms),
+    else summary_radius -> the summary forms, else the update forms; all of them give the same rows and belief."""
+    cached = sat is None
+    side = (cache,) if cached else (sat,)
+    kw = {"tile_index": tile_index} if cached else {}
+    if heading_bins is not None:
+        kw.update(radius=8 if summary_radius is None else summary_radius, bins=heading_bins, summary=summary_radius is not None,
+                  posterior=True)
+        if table is not None:
+            res = (model.localize_heading_prior_cached if cached else model.localize_heading_prior)(grd, *side, table, prior, **kw)
+        else:
+            res = (model.localize_heading_cached if cached else model.localize_heading)(grd, *side, prior, **kw)
+        return res[0], (res[3] if summary_radius is not None else None), res[1:3], res[-1]
+    if summary_radius is not None:
+        fn = model.localize_summary_cached if cached else model.localize_summary
+        rows, summary, belief = fn(grd, *side, prior, radius=summary_radius, posterior=True, **kw)
+        return rows, summary, None, belief
+    rows, belief = (model.track_update_cached if cached else model.track_update)(grd, *side, prior, **kw)
+    return rows, None, None, belief
+
+
 class Tracker:
     """A histogram filter over the Oxford windows, host side: holds the posterior map of the last frame (a device tensor
     [B,512,512]) and the window origin it lives in.  step() = model.track_predict (the last posterior moved into this frame's
@@ -602,32 +627,11 @@ class Tracker:
             if self.belief.shape[0] != B:
                 raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
             prior = model.track_predict(self.belief, oxford_track_shift(self.origin, now, motion_map_px), taps, floor)
-        summary = None
-        heading = None
         table = _heading_table(model, self.hist, B, heading_bins, heading_turn_deg, heading_taps, heading_floor) if filt else None
-        if table is not None:
-            res = model.localize_heading_prior_cached(grd, cache, table, prior, radius=8 if summary_radius is None else summary_radius,
-                                                      bins=heading_bins, summary=summary_radius is not None, posterior=True,
-                                                      tile_index=tile_index)
-            rows, heading, self.belief = res[0], res[1:3], res[-1]
-            summary = res[3] if summary_radius is not None else None
-        elif heading_bins is not None:
-            res = model.localize_heading_cached(grd, cache, prior, radius=8 if summary_radius is None else summary_radius, bins=heading_bins,
-                                                summary=summary_radius is not None, posterior=True, tile_index=tile_index)
-            rows, heading, self.belief = res[0], res[1:3], res[-1]
-            summary = res[3] if summary_radius is not None else None
-        elif summary_radius is None:
-            rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
-        else:
-            rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
-                                                                       tile_index=tile_index)
+        rows, summary, heading, self.belief = _update(model, grd, None, cache, tile_index, prior, table, summary_radius, heading_bins)
         self.origin = now.copy()
         self.hist = heading[1] if filt else None
-        if heading is None:
-            out = rows if summary is None else (rows, summary)
-        else:
-            out = ((rows,) if summary is None else (rows, summary)) + tuple(heading)
-        return _with_credible(model, self.belief, out, credible_levels)
+        return _step_result(model, rows, summary, heading, self.belief, credible_levels)
 
 
 # ---- tracking across rotated or rescaled frames -----------------------------------------------------------------
@@ -780,41 +784,7 @@ class AffineTracker:
             if self.belief.shape[0] != B:
                 raise ValueError(f"the tracker holds {self.belief.shape[0]} streams, this step has {B}")
             prior = model.track_predict_affine(self.belief, matrix, taps, floor)
-        radius = 8 if summary_radius is None else summary_radius
-        summary = None
-        heading = None
         table = _heading_table(model, self.hist, B, heading_bins, heading_turn_deg, heading_taps, heading_floor) if filt else None
-        if table is not None:
-            if cache is None:
-                res = model.localize_heading_prior(grd, sat, table, prior, radius=radius, bins=heading_bins,
-                                                   summary=summary_radius is not None, posterior=True)
-            else:
-                res = model.localize_heading_prior_cached(grd, cache, table, prior, radius=radius, bins=heading_bins,
-                                                          summary=summary_radius is not None, posterior=True, tile_index=tile_index)
-            rows, heading, self.belief = res[0], res[1:3], res[-1]
-            summary = res[3] if summary_radius is not None else None
-        elif heading_bins is not None:
-            if cache is None:
-                res = model.localize_heading(grd, sat, prior, radius=radius, bins=heading_bins, summary=summary_radius is not None,
-                                             posterior=True)
-            else:
-                res = model.localize_heading_cached(grd, cache, prior, radius=radius, bins=heading_bins,
-                                                    summary=summary_radius is not None, posterior=True, tile_index=tile_index)
-            rows, heading, self.belief = res[0], res[1:3], res[-1]
-            summary = res[3] if summary_radius is not None else None
-        elif summary_radius is None:
-            if cache is None:
-                rows, self.belief = model.track_update(grd, sat, prior)
-            else:
-                rows, self.belief = model.track_update_cached(grd, cache, prior, tile_index=tile_index)
-        elif cache is None:
-            rows, summary, self.belief = model.localize_summary(grd, sat, prior, radius=summary_radius, posterior=True)
-        else:
-            rows, summary, self.belief = model.localize_summary_cached(grd, cache, prior, radius=summary_radius, posterior=True,
-                                                                       tile_index=tile_index)
+        rows, summary, heading, self.belief = _update(model, grd, sat, cache, tile_index, prior, table, summary_radius, heading_bins)
         self.hist = heading[1] if filt else None
-        if heading is None:
-            out = rows if summary is None else (rows, summary)
-        else:
-            out = ((rows,) if summary is None else (rows, summary)) + tuple(heading)
-        return _with_credible(model, self.belief, out, credible_levels)
+        return _step_result(model, rows, summary, heading, self.belief, credible_levels)

@@ -12,6 +12,7 @@ Inference only: no autograd through the HIP path, `eval()` mode required, GPU re
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Dict, Optional, Tuple
 
@@ -70,6 +71,168 @@ class _EfficientNetParams(_Params):
 
 def _double_conv(cin: int, mid: int, cout: int) -> nn.Sequential:
     return nn.Sequential(nn.Conv2d(cin, mid, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(mid, cout, 3, padding=1))
+
+
+# ---------------------------------------------------------------------------------------------
+# the two descriptions a call into the library is built from: where its inputs come from, what it returns
+# ---------------------------------------------------------------------------------------------
+def _foreign(extra, dev) -> bool:
+    """whether a tensor among a form's own arguments (a prior, a table) lives on another device than the inputs"""
+    return any(isinstance(a, torch.Tensor) and a.device != dev for a in extra)
+
+
+class _Layout(tuple):
+    """What a call returns: its result slots in the order of the C arguments, each (shape after B, dtype, wanted).  A slot that is not
+    wanted - an optional output nobody asked for - is not allocated and goes to the library as a null pointer."""
+
+    def alloc(self, B: int, dev):
+        res, ptrs = [], []
+        for tail, dtype, wanted in self:       # (a plain loop and plain addresses: a one-launch call is mostly this host time)
+            if wanted:
+                res.append(torch.empty((B,) + tail, dtype=dtype, device=dev))
+                ptrs.append(res[-1].data_ptr())
+            else:
+                ptrs.append(None)
+        return res, ptrs
+
+
+class _NineOutputs:
+    """forward's results behind _Layout's interface: the nine tensors, handed over as one ccvpe_outputs struct"""
+
+    def __init__(self, model):
+        self.model = model
+
+    def alloc(self, B: int, dev):
+        out, res = self.model._alloc_outputs(B, dev)
+        return res, (C.byref(out),)
+
+
+def _slot(*tail, dtype=torch.float32, wanted=True):
+    return tail, dtype, bool(wanted)
+
+
+_MAP = _slot(*spec.OUT_HW)
+_ROWS = _Layout((_slot(5),))                       # the argmax forms
+_ROWS_MAP = _Layout((_slot(5), _MAP))              # the update forms: rows and their posterior
+_ONE_MAP = _Layout((_MAP,))
+_SUMMARY = _Layout((_slot(16),))
+_POSE_INT = _Layout((_slot(5, dtype=torch.int32),))   # postprocess: the rows as the kernel's integer / float bit patterns
+
+
+# the layouts that depend on a method's arguments are kept (the last 64 combinations each): a call looks its layout up
+@functools.lru_cache(maxsize=64)
+def _rows_layout(k: int) -> _Layout:
+    return _ROWS if k == 0 else _Layout((_slot(k, 5),))
+
+
+@functools.lru_cache(maxsize=64)
+def _row_layout(n: int) -> _Layout:
+    return _Layout((_slot(n),))
+
+
+@functools.lru_cache(maxsize=64)
+def _summary_layout(posterior: bool) -> _Layout:
+    return _Layout((_slot(5), _slot(16), _slot(*spec.OUT_HW, wanted=posterior)))
+
+
+@functools.lru_cache(maxsize=64)
+def _heading_layout(bins: int, summary: bool, posterior: bool) -> _Layout:
+    return _Layout((_slot(5), _slot(12), _slot(bins), _slot(16, wanted=summary), _slot(*spec.OUT_HW, wanted=posterior)))
+
+
+@functools.lru_cache(maxsize=64)
+def _credible_layout(L: int, level_map: bool, posterior: Optional[bool]) -> _Layout:
+    """rows [B, 5] (posterior is None: the stored-map form, which has neither rows nor a posterior), cred [B, 4 + 3 L], then the
+    optional level map [B, 512, 512] uint8 and posterior"""
+    cred = (_slot(4 + 3 * L), _slot(*spec.OUT_HW, dtype=torch.uint8, wanted=level_map))
+    return _Layout(cred if posterior is None else (_slot(5),) + cred + (_slot(*spec.OUT_HW, wanted=posterior),))
+
+
+class _Images:
+    """Input side (grd, sat).  A side checks and normalises its tensors in two steps, check() before the form's own arguments are
+    looked at and bind() after, exactly where each check has always stood; t is the tensor that gives B and the device; names picks
+    the side's entry of a family's C names; sync: whether the call may have measured a plan (the network runs)."""
+    names, sync = 0, True
+
+    def __init__(self, grd, sat):
+        self.t, self.sat = grd, sat
+
+    def check(self, m) -> int:
+        self.t, self.sat = m._prepare(self.t, self.sat)
+        return self.t.shape[0]
+
+    def bind(self, m, name: str, extra):
+        g = self.t
+        if _foreign(extra, g.device):
+            raise ValueError("log_prior must be on the inputs' device")
+        return name, (g, g.shape[2], g.shape[3], self.sat)
+
+
+class _Cached:
+    """Input side (grd, cache, tile_index).  ccvpe_<name> takes n_tiles and a nullable tile_index if the name ends in _indexed; the older
+    forms have two entry points each, ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it."""
+    names, sync = 1, True
+
+    def __init__(self, grd, cache, tile_index):
+        self.t, self.cache, self.tile_index = grd, cache, tile_index
+
+    def check(self, m) -> int:
+        m._require_eval()
+        g = self.t
+        self.idx = m._host_tile_index(self.tile_index, g)
+        if not g.is_cuda or g.dim() != 4 or g.shape[1] != 3:
+            raise ValueError("grd must be a cuda tensor [B,3,H,W]")
+        return g.shape[0]
+
+    def bind(self, m, name: str, extra):
+        if _foreign(extra, self.t.device):
+            raise ValueError("log_prior must be on the inputs' device")
+        g = self.t = self.t.detach().to(torch.float32).contiguous()
+        m._ensure_handle(g.device)
+        idx = self.idx
+        n_tiles = m._cache_tiles(self.cache, g.shape[0], idx)
+        src = (g, g.shape[2], g.shape[3], self.cache.data_ptr())
+        if name.endswith("_indexed") or idx is not None:
+            name = name if name.endswith("_indexed") else name + "_indexed"
+            src += (n_tiles, idx.ctypes.data_as(C.c_void_p) if idx is not None else None)
+        return name, src
+
+
+class _Held:
+    """Input side (logits, ori): forward outputs the caller holds.  No network runs, so no plan is built."""
+    names, sync = 2, False
+
+    def __init__(self, logits, ori):
+        self.t, self.ori = logits, ori
+
+    def check(self, m) -> int:
+        m._require_eval()
+        logits, ori = self.t, self.ori
+        B = logits.shape[0] if logits.dim() > 0 else 0
+        if logits.numel() != B * m.PRIOR_MAP or ori.numel() != B * 2 * m.PRIOR_MAP or B == 0:
+            raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
+        return B
+
+    def bind(self, m, name: str, extra):
+        logits, ori = self.t, self.ori
+        if not (logits.is_cuda and ori.is_cuda):
+            raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
+        if logits.device != ori.device or _foreign(extra, logits.device):
+            raise ValueError("logits, ori and log_prior must be on one device")
+        self.t = logits.detach().to(torch.float32).contiguous()
+        ori = ori.detach().to(torch.float32).contiguous()
+        m._ensure_handle(self.t.device)
+        return name, (self.t, ori)
+
+
+class _Family:
+    """One definition of a family of forms: names = the C names (after ccvpe_) of its image, cached and held-outputs form (None: the
+    family has no such form); args(model, B, t, *a) (t: the side's tensor, for a form that needs its device) checks the methods' own arguments a and returns (the C arguments between batch
+    and the results, the _Layout); own_first = the sides (their `names`) on which args runs before the inputs' checks - on the
+    others it runs after them.  That precedence is behaviour the methods have always had."""
+
+    def __init__(self, names, args, own_first=()):
+        self.names, self.args, self.own_first = names, args, own_first
 
 
 class _CVMBase(nn.Module):
@@ -254,87 +417,51 @@ class _CVMBase(nn.Module):
             out.matching_score[k] = ms[k].data_ptr()
         return out, (logits, heat, ori, *ms)
 
-    def _call(self, name: str, grd, sat=None, cache=None, tile_index=None, args=lambda B: (), k=0, outputs=False, posterior=False, summary=False,
-              heading=0, alloc=None):
-        """The skeleton forward and the pose forms share: validate and normalise grd and sat - or, sat=None, the cache and tile_index of a
-        cached form -, ensure the handle, allocate the results, call ccvpe_<name> under the inputs' device on its current stream, check
-        the return code, sync the tuning table.  args(B) holds the method's own argument checks, run after those of the inputs, and
-        returns the C arguments between batch and the results; a tensor among them, the log_prior, must be on the inputs' device and is
-        passed by pointer, None as a null pointer.  Returns the nine outputs (outputs=True) or rows [B, 5] (k = 0, the argmax forms) /
-        [B, k, 5] (k as the method received it: args has checked it), with the summary [B, 16] (the summary forms, whose C functions
-        take a nullable posterior behind it) and the posterior [B, 512, 512] behind them if asked.  heading = a bin count: the heading
-        forms, whose C functions take heading [B, 12] and hist [B, bins] behind rows, then a nullable summary and a nullable posterior.
-        Cached forms: ccvpe_<name> takes a nullable tile_index if the name ends in _indexed; the older forms have two entry points each,
-        ccvpe_<name> without tile_index (it enforces B <= micro_batch) and ccvpe_<name>_indexed with it.  alloc(B, dev) -> (results,
-        C arguments): a form with results of its own (the credible forms), returned as they are."""
-        if sat is not None:
-            grd, sat = self._prepare(grd, sat)
-        else:
-            if self.training:
-                raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-            idx = self._host_tile_index(tile_index, grd)
-            if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
-                raise ValueError("grd must be a cuda tensor [B,3,H,W]")
-        extra, k = args(grd.shape[0]), int(k)
-        if any(isinstance(a, torch.Tensor) and a.device != grd.device for a in extra):
-            raise ValueError("log_prior must be on the inputs' device")
-        if sat is not None:
-            src = (C.c_void_p(sat.data_ptr()),)
-        else:
-            grd = grd.detach().to(torch.float32).contiguous()
-            self._ensure_handle(grd.device)
-            n_tiles = self._cache_tiles(cache, grd.shape[0], idx)
-            src = (C.c_void_p(cache.data_ptr()),)
-            if name.endswith("_indexed") or idx is not None:
-                name = name if name.endswith("_indexed") else name + "_indexed"
-                src += (n_tiles, idx.ctypes.data_as(C.c_void_p) if idx is not None else None)
-        B, dev = grd.shape[0], grd.device
-        with torch.cuda.device(dev):
-            if outputs:
-                out, res = self._alloc_outputs(B, dev)
-                ptrs = (C.byref(out),)
-            elif alloc is not None:
-                res, ptrs = alloc(B, dev)
-            else:
-                res, ptrs = self._alloc_rows(B, dev, k, heading, summary, posterior)
-            extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(grd.data_ptr()), grd.shape[2], grd.shape[3], *src, B,
-                                                       *extra, *ptrs, C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_" + name)
-        self._tuning_sync()
-        return res if outputs or posterior or summary or heading or alloc is not None else res[0]
+    def _require_eval(self) -> None:
+        if self.training:
+            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
 
-    @staticmethod
-    def _alloc_rows(B: int, dev, k: int, heading: int, summary: bool, posterior: bool):
-        """The results of a pose form and their C arguments: rows [B, 5] or [B, k, 5], then - heading forms - heading [B, 12] and hist
-        [B, heading], then the summary [B, 16] and the posterior [B, 512, 512] if asked.  The summary and heading forms take a null
-        pointer for an optional output that was not asked for."""
-        res = (torch.empty((B, 5) if k == 0 else (B, k, 5), dtype=torch.float32, device=dev),)
-        if heading:
-            res += (torch.empty((B, 12), dtype=torch.float32, device=dev), torch.empty((B, heading), dtype=torch.float32, device=dev))
-        ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
-        opt = ()
-        if summary:
-            opt += (torch.empty((B, 16), dtype=torch.float32, device=dev),)
-        elif heading:
-            ptrs += (None,)
-        if posterior:
-            opt += (torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev),)
-        ptrs += tuple(C.c_void_p(t.data_ptr()) for t in opt)
-        if (summary or heading) and not posterior:
-            ptrs += (None,)
-        return res + opt, ptrs
+    def _launch(self, name: str, dev, B: int, cargs, layout, sync: bool = False):
+        """Every call with results enters the library here, behind its checks and _ensure_handle: allocate the layout's tensors, call
+        ccvpe_<name>(handle, *cargs, *result pointers, stream) under dev on its current stream, check the return code, sync the tuning
+        table if the call may have built a plan.  cargs: tensors go by address (the bindings declare every pointer a void pointer, which
+        takes an integer), None as a null pointer.  Returns the results in the layout's order: a tuple, or the tensor itself when
+        there is one."""
+        name = "ccvpe_" + name
+        with torch.cuda.device(dev):
+            res, ptrs = layout.alloc(B, dev)
+            cargs = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in cargs]
+            rc = getattr(_lib.load(), name)(self._handle, *cargs, *ptrs, torch.cuda.current_stream(dev).cuda_stream)
+        if rc != _lib.OK:
+            _lib.check(rc, name)
+        if sync:
+            self._tuning_sync()
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def _run(self, family: _Family, side, *a):
+        """The skeleton of forward and every pose form: the side checks its inputs, the family its own arguments a - before them on the
+        sides the family names in own_first, else after -, the side normalises its tensors and ensures the handle, and the call goes
+        out through _launch with the C arguments (side's, batch, family's)."""
+        own = side.names in family.own_first
+        if own:
+            self._require_eval()
+            made = family.args(self, side.t.shape[0], side.t, *a)   # (before the inputs' checks)
+        B = side.check(self)
+        extra, layout = made if own else family.args(self, B, side.t, *a)
+        name, src = side.bind(self, family.names[side.names], extra)
+        return self._launch(name, side.t.device, B, src + (B,) + tuple(extra), layout, side.sync)
+
+    _FORWARD = _Family(("forward", "forward_cached", None), lambda self, B, t: ((), _NineOutputs(self)))
+    _LOCALIZE = _Family(("localize", "localize_cached", None), lambda self, B, t: ((), _ROWS))
 
     def forward(self, grd: torch.Tensor, sat: torch.Tensor):
-        return self._call("forward", grd, sat, outputs=True)
+        return self._run(self._FORWARD, _Images(grd, sat))
 
     # ---- aerial-side caching for streaming (SURVEY 8f row 4) -------------------------------
     def encode_aerial(self, sat: torch.Tensor) -> torch.Tensor:
         """Encode aerial images once; the returned device buffer feeds forward_cached() for any number of
         ground frames that share the tile (Oxford RobotCar reuses tiles, datasets.py:306-317)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         if not sat.is_cuda or sat.dim() != 4 or tuple(sat.shape[1:]) != (3,) + spec.SAT_HW:
             raise ValueError("sat must be a cuda tensor [B,3,512,512]")
         return self._encode("aerial", sat)
@@ -393,14 +520,13 @@ class _CVMBase(nn.Module):
         """forward(grd, sat) with the aerial side taken from encode_aerial(sat).  tile_index (host ints [B], optional): query b
         reads tile tile_index[b] of a cache encode_aerial wrote for any number of tiles up to the micro-batch, and B may then
         be any size (ccvpe_forward_cached_indexed)."""
-        return self._call("forward_cached", grd, cache=cache, tile_index=tile_index, outputs=True)
+        return self._run(self._FORWARD, _Cached(grd, cache, tile_index))
 
     # ---- one ground encoding against several aerial tiles ---------------------------------------
     def encode_ground(self, grd: torch.Tensor) -> torch.Tensor:
         """Encode ground images once: the returned device buffer (float32 [B * Ltot], the descriptor vector of each image, layout in
         include/ccvpe.h) feeds localize_region, which pairs each image with several aerial tiles (ccvpe_encode_ground)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         if not grd.is_cuda or grd.dim() != 4 or grd.shape[1] != 3:
             raise ValueError("grd must be a cuda tensor [B,3,H,W]")
         self._ensure_handle(grd.device)
@@ -465,8 +591,7 @@ class _CVMBase(nn.Module):
     def _region(self, ground_cache, sat_cache, tiles, pair_log_prior=_NO_PRIOR) -> Dict[str, object]:
         """localize_region and, with a pair_log_prior, localize_region_prior."""
         prior = pair_log_prior is not self._NO_PRIOR
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         offsets, flat = self._host_region_tiles(tiles)
         G, P = offsets.shape[0] - 1, flat.shape[0]
         if prior:
@@ -507,13 +632,13 @@ class _CVMBase(nn.Module):
         (index, prob, cos, sin, angle_deg).  Bit-identical to postprocess_rows(*forward(grd, sat)[1:3]), also for a query without a
         finite posterior (one NaN or +inf logit: the heatmap is all NaN), whose row is (-1, NaN, cos, sin, angle_deg of pixel 0) in
         both (ccvpe_localize)."""
-        return self._call("localize", grd, sat)
+        return self._run(self._LOCALIZE, _Images(grd, sat))
 
     def localize_cached(self, grd: torch.Tensor, cache: torch.Tensor, tile_index=None) -> torch.Tensor:
         """localize(grd, sat) with the aerial side taken from encode_aerial(sat): float32 [B, 5] rows (index, prob, cos, sin,
         angle_deg), the postprocess_rows layout (ccvpe_localize_cached).  tile_index: as forward_cached
         (ccvpe_localize_cached_indexed)."""
-        return self._call("localize_cached", grd, cache=cache, tile_index=tile_index)
+        return self._run(self._LOCALIZE, _Cached(grd, cache, tile_index))
 
     # ---- several pose hypotheses per query ----------------------------------------------------
     @staticmethod
@@ -525,23 +650,27 @@ class _CVMBase(nn.Module):
             raise ValueError(f"radius must be in 0..32, got {radius}")
         return k, radius
 
+    def _topk_form(self, B: int, t, k, radius):
+        k, radius = self._topk_args(k, radius)
+        return (k, radius), _rows_layout(k)
+
+    _TOPK = _Family(("localize_topk", "localize_topk_cached", None), _topk_form)
+
     def localize_topk(self, grd: torch.Tensor, sat: torch.Tensor, k: int, radius: int) -> torch.Tensor:
         """The k strongest heatmap peaks of every query under a suppression radius, with their orientation: float32 [B, k, 5]
         on the device, rows (index, prob, cos, sin, angle_deg); (-1, 0, 0, 0, 0) past a query's last peak.  Bit-identical to
         postprocess_topk(*forward(grd, sat)[1:3], k, radius) (ccvpe_localize_topk)."""
-        return self._call("localize_topk", grd, sat, args=lambda B: self._topk_args(k, radius), k=k)
+        return self._run(self._TOPK, _Images(grd, sat), k, radius)
 
     def localize_topk_cached(self, grd: torch.Tensor, cache: torch.Tensor, k: int, radius: int, tile_index=None) -> torch.Tensor:
         """localize_topk(grd, sat, k, radius) with the aerial side taken from encode_aerial(sat): float32 [B, k, 5]
         (ccvpe_localize_topk_cached).  tile_index: as forward_cached (ccvpe_localize_topk_cached_indexed)."""
-        return self._call("localize_topk_cached", grd, cache=cache, tile_index=tile_index, args=lambda B: self._topk_args(k, radius),
-                          k=k)
+        return self._run(self._TOPK, _Cached(grd, cache, tile_index), k, radius)
 
     def postprocess_topk(self, heatmap: torch.Tensor, ori: torch.Tensor, k: int, radius: int) -> torch.Tensor:
         """postprocess_rows() generalised to the k strongest peaks under a suppression radius, on forward outputs the caller
         holds: float32 [B, k, 5] on the device (ccvpe_postprocess_topk, the definition in include/ccvpe.h)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         if not (heatmap.is_cuda and ori.is_cuda):
             raise RuntimeError("ccvpe_amd has no CPU path: heatmap and ori must live on an MI355X (cuda) device")
         k, radius = self._topk_args(k, radius)
@@ -551,12 +680,7 @@ class _CVMBase(nn.Module):
         heatmap = heatmap.detach().to(torch.float32).contiguous()
         ori = ori.detach().to(torch.float32).contiguous()
         self._ensure_handle(heatmap.device)
-        rows = torch.empty((B, k, 5), dtype=torch.float32, device=heatmap.device)
-        stream = torch.cuda.current_stream(heatmap.device).cuda_stream
-        rc = _lib.load().ccvpe_postprocess_topk(self._handle, C.c_void_p(heatmap.data_ptr()), C.c_void_p(ori.data_ptr()), B, k,
-                                                radius, C.c_void_p(rows.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_postprocess_topk")
-        return rows
+        return self._launch("postprocess_topk", heatmap.device, B, (heatmap, ori, B, k, radius), _rows_layout(k))
 
     # ---- pose with a position prior -------------------------------------------
     PRIOR_MAP = 512 * 512
@@ -588,53 +712,29 @@ class _CVMBase(nn.Module):
             raise ValueError(f"log_prior must be a cuda tensor on the inputs' device, not a {log_prior.device.type} tensor")
         return log_prior.detach(), (cls.PRIOR_MAP if n > 1 else 0), k, radius
 
+    def _prior_form(self, B: int, t, log_prior, k, radius):
+        a = self._prior_args(log_prior, B, k, radius)
+        return a, _rows_layout(a[2])
+
+    _PRIOR = _Family(("localize_prior", "localize_prior_cached_indexed", "postprocess_prior"), _prior_form, own_first=(_Images.names,))
+
     def localize_prior(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0) -> torch.Tensor:
         """localize (k = 0: rows [B, 5]) or localize_topk (k in 1..64: rows [B, k, 5]) on the posterior softmax(logits + log_prior):
         the semantics in include/ccvpe.h (ccvpe_localize_prior).  An all-zero prior gives the rows of the forms without one; a query
         without a finite posterior (a prior of -inf everywhere) has index -1."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._prior_args(log_prior, grd.shape[0], k, radius)   # (before the inputs' checks)
-        return self._call("localize_prior", grd, sat, args=lambda B: own, k=k)
+        return self._run(self._PRIOR, _Images(grd, sat), log_prior, k, radius)
 
     def localize_prior_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0,
                               tile_index=None) -> torch.Tensor:
         """localize_prior(grd, sat, log_prior, k, radius) with the aerial side taken from encode_aerial(sat); tile_index as
         forward_cached (ccvpe_localize_prior_cached_indexed)."""
-        return self._call("localize_prior_cached_indexed", grd, cache=cache, tile_index=tile_index,
-                          args=lambda B: self._prior_args(log_prior, B, k, radius), k=k)
-
-    def _logits_call(self, name: str, logits, ori, args, k=0, posterior=False, summary=False, heading=0, alloc=None):
-        """postprocess_prior, track_update_logits and postprocess_summary: validate and normalise the forward outputs the caller holds,
-        check the prior with args(B) and take k (both as _call's), allocate rows (and the summary, the posterior) and call ccvpe_<name>."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        B = logits.shape[0] if logits.dim() > 0 else 0
-        if logits.numel() != B * self.PRIOR_MAP or ori.numel() != B * 2 * self.PRIOR_MAP or B == 0:
-            raise ValueError(f"expected logits [B,512*512] and ori [B,2,512,512], got {tuple(logits.shape)} / {tuple(ori.shape)}")
-        extra, k = args(B), int(k)
-        if not (logits.is_cuda and ori.is_cuda):
-            raise RuntimeError("ccvpe_amd has no CPU path: logits and ori must live on an MI355X (cuda) device")
-        if logits.device != ori.device or any(isinstance(a, torch.Tensor) and a.device != logits.device for a in extra):
-            raise ValueError("logits, ori and log_prior must be on one device")
-        logits = logits.detach().to(torch.float32).contiguous()
-        ori = ori.detach().to(torch.float32).contiguous()
-        dev = logits.device
-        self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            res, ptrs = alloc(B, dev) if alloc is not None else self._alloc_rows(B, dev, k, heading, summary, posterior)
-            extra = tuple(C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in extra)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = getattr(_lib.load(), "ccvpe_" + name)(self._handle, C.c_void_p(logits.data_ptr()), C.c_void_p(ori.data_ptr()), B, *extra,
-                                                       *ptrs, C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_" + name)
-        return res if posterior or summary or heading or alloc is not None else res[0]
+        return self._run(self._PRIOR, _Cached(grd, cache, tile_index), log_prior, k, radius)
 
     def postprocess_prior(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: torch.Tensor, k: int = 0, radius: int = 0
                           ) -> torch.Tensor:
         """The rows of localize_prior from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori =
         forward(...)[2] ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_prior)."""
-        return self._logits_call("postprocess_prior", logits, ori, lambda B: self._prior_args(log_prior, B, k, radius), k=k)
+        return self._run(self._PRIOR, _Held(logits, ori), log_prior, k, radius)
 
     def localize_region_prior(self, ground_cache: torch.Tensor, sat_cache: torch.Tensor, tiles, pair_log_prior: torch.Tensor
                               ) -> Dict[str, object]:
@@ -654,26 +754,25 @@ class _CVMBase(nn.Module):
         lp, stride, _, _ = cls._prior_args(log_prior, B, 0, 0)
         return lp, stride
 
+    _UPDATE = _Family(("track_update", "track_update_cached_indexed", "track_update_logits"),
+                      lambda self, B, t, log_prior: (self._track_prior(log_prior, B), _ROWS_MAP), own_first=(_Images.names,))
+
     def track_update(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None):
         """The update half of a filter step: (rows [B, 5], posterior [B, 512, 512]).  rows are localize_prior(grd, sat, log_prior)'s,
         posterior is the map they are the argmax of - softmax(logits + log_prior) in the pixel order of the logits, with the bits of
         rows[b, 1] at rows[b, 0]; log_prior=None: the forward's heatmap.  A query without a finite posterior gets the row (-1, NaN, ..)
         and an all-zero map (ccvpe_track_update)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._track_prior(log_prior, grd.shape[0])   # (before the inputs' checks)
-        return self._call("track_update", grd, sat, args=lambda B: own, posterior=True)
+        return self._run(self._UPDATE, _Images(grd, sat), log_prior)
 
     def track_update_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, tile_index=None):
         """track_update(grd, sat, log_prior) with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
         (ccvpe_track_update_cached_indexed)."""
-        return self._call("track_update_cached_indexed", grd, cache=cache, tile_index=tile_index,
-                          args=lambda B: self._track_prior(log_prior, B), posterior=True)
+        return self._run(self._UPDATE, _Cached(grd, cache, tile_index), log_prior)
 
     def track_update_logits(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None):
         """track_update from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
         ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_track_update_logits)."""
-        return self._logits_call("track_update_logits", logits, ori, lambda B: self._track_prior(log_prior, B), posterior=True)
+        return self._run(self._UPDATE, _Held(logits, ori), log_prior)
 
     @staticmethod
     def _track_vec(value, what: str, shape, dev):
@@ -692,54 +791,67 @@ class _CVMBase(nn.Module):
             raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
         return t.to(dev).contiguous()
 
+    @staticmethod
+    def _stored_maps(t, what: str = "belief") -> int:
+        """A stored map argument - [B,512,512] or [B,1,512,512], float32, contiguous, at most 4096 maps - -> B.  Where it lives is
+        checked by the caller: that check stands at another place in every method."""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what} must be a float32 cuda tensor [B,512,512]")
+        shape = tuple(t.shape)
+        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
+                                                                                       and shape[2:] == spec.OUT_HW):
+            raise ValueError(f"{what} must be [B,512,512] or [B,1,512,512], got {shape}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        if shape[0] > 4096:
+            raise ValueError(f"{what} holds {shape[0]} maps, at most 4096 per call")
+        return shape[0]
+
+    @staticmethod
+    def _blur_checks(taps, floor, B: int, nb: Optional[int] = None):
+        """The taps, radius and floor checks of the predict methods, in their order -> (taps' shape, taps_stride, radius, whether floor
+        is one number; per-query floors are the library's to read).  nb: heading_predict's bin count, which bounds the radius as well
+        and has its own sentence for it."""
+        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
+        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
+            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
+        radius = int(tshape[-1]) - 1
+        if nb is None and radius > 32:
+            raise ValueError(f"taps give radius {radius}, must be in 0..32")
+        if nb is not None and (radius > 32 or 2 * radius + 1 > nb):
+            raise ValueError(f"taps give radius {radius}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
+        number = np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor)
+        if number and not float(floor) >= 0.0:
+            raise ValueError(f"floor must be >= 0, got {floor}")
+        return tshape, (radius + 1) if len(tshape) == 2 else 0, radius, number
+
+    @classmethod
+    def _per_query(cls, value, number: bool, what: str, B: int, dev):
+        """a number or [B] -> float32 [B] on dev"""
+        if number:
+            return torch.full((B,), float(value), dtype=torch.float32, device=dev)
+        return cls._track_vec(value, what, (B,), dev)
+
     def track_predict(self, belief: torch.Tensor, shift_px, taps, floor) -> torch.Tensor:
         """The predict half of a filter step: the log-prior [B, 512, 512] of the next frame from a posterior map.  belief [B,512,512]
         (track_update's map) is extended by zero, moved by shift_px [B,2] = (dx, dy) output pixels with bilinear weights, blurred
         along x and y with the one-sided taps t[0..radius] ([radius+1] for every query or [B, radius+1]; aerial.gaussian_taps), and
         the result is log(. + floor), floor a number or [B], >= 0: the definition in include/ccvpe.h (ccvpe_track_predict).  One
         launch.  shift_px, taps and floor may be host data or tensors on the belief's device."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        if not isinstance(belief, torch.Tensor):
-            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
-        shape = tuple(belief.shape)
-        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
-                                                                                       and shape[2:] == spec.OUT_HW):
-            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
-        if belief.dtype != torch.float32:
-            raise ValueError(f"belief must be float32, got {belief.dtype}")
-        if not belief.is_contiguous():
-            raise ValueError("belief must be contiguous")
-        B = shape[0]
-        if B > 4096:
-            raise ValueError(f"belief holds {B} maps, at most 4096 per call")
-        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
-        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
-            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
-        radius = int(tshape[-1]) - 1
-        if radius > 32:
-            raise ValueError(f"taps give radius {radius}, must be in 0..32")
-        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
-        if fshape == () and not float(floor) >= 0.0:
-            raise ValueError(f"floor must be >= 0, got {floor}")
+        self._require_eval()
+        B = self._stored_maps(belief)
+        tshape, stride, radius, number = self._blur_checks(taps, floor, B)
         dev = belief.device
-        host = torch.device("cpu")
         # shapes and values first (so that they are refused without a device), then the copies
-        sh = self._track_vec(shift_px, "shift_px", (B, 2), host if not belief.is_cuda else dev)
-        tp = self._track_vec(taps, "taps", tshape, host if not belief.is_cuda else dev)
-        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
-              else self._track_vec(floor, "floor", (B,), dev))
+        sh = self._track_vec(shift_px, "shift_px", (B, 2), dev)
+        tp = self._track_vec(taps, "taps", tshape, dev)
+        fl = self._per_query(floor, number, "floor", B, dev)
         if not belief.is_cuda:
             raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
         self._ensure_handle(dev)
-        out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = _lib.load().ccvpe_track_predict(self._handle, C.c_void_p(belief.data_ptr()), B, C.c_void_p(sh.data_ptr()),
-                                                 C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
-                                                 C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_track_predict")
-        return out
+        return self._launch("track_predict", dev, B, (belief, B, sh, tp, stride, radius, fl), _ONE_MAP)
 
     def track_predict_affine(self, belief: torch.Tensor, matrix, taps, floor) -> torch.Tensor:
         """track_predict under an affine map per query: output pixel index (x, y) reads the belief, extended by zero,
@@ -750,21 +862,8 @@ class _CVMBase(nn.Module):
         belief's device, which is not looked at (non-finite entries there may give NaN, never a read outside the belief).  belief,
         taps and floor as in track_predict.  One launch, always the affine kernel: (1, 0, -dx, 0, 1, -dy) is track_predict's shift
         (dx, dy), bit for bit at integer shifts."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        if not isinstance(belief, torch.Tensor):
-            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
-        shape = tuple(belief.shape)
-        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
-                                                                                       and shape[2:] == spec.OUT_HW):
-            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
-        if belief.dtype != torch.float32:
-            raise ValueError(f"belief must be float32, got {belief.dtype}")
-        if not belief.is_contiguous():
-            raise ValueError("belief must be contiguous")
-        B = shape[0]
-        if B > 4096:
-            raise ValueError(f"belief holds {B} maps, at most 4096 per call")
+        self._require_eval()
+        B = self._stored_maps(belief)
         on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
         if on_device:
             mt = matrix.detach()
@@ -776,35 +875,18 @@ class _CVMBase(nn.Module):
             raise ValueError(f"matrix must be [6] or [{B}, 6], got {tuple(mt.shape)}")
         if not on_device and not bool(torch.isfinite(mt).all()):
             raise ValueError("matrix must be finite")
-        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
-        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
-            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
-        radius = int(tshape[-1]) - 1
-        if radius > 32:
-            raise ValueError(f"taps give radius {radius}, must be in 0..32")
-        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
-        if fshape == () and not float(floor) >= 0.0:
-            raise ValueError(f"floor must be >= 0, got {floor}")
+        tshape, stride, radius, number = self._blur_checks(taps, floor, B)
         dev = belief.device
-        host = torch.device("cpu")
         # shapes and values first (so that they are refused without a device), then the copies
-        tp = self._track_vec(taps, "taps", tshape, host if not belief.is_cuda else dev)
-        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
-              else self._track_vec(floor, "floor", (B,), dev))
+        tp = self._track_vec(taps, "taps", tshape, dev)
+        fl = self._per_query(floor, number, "floor", B, dev)
         if not belief.is_cuda:
             raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
         if on_device and mt.device != dev:
             raise ValueError(f"matrix is on {mt.device}, belief on {dev}")
         mt = mt.expand(B, 6).to(dev).contiguous()
         self._ensure_handle(dev)
-        out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = _lib.load().ccvpe_track_predict_affine(self._handle, C.c_void_p(belief.data_ptr()), B, C.c_void_p(mt.data_ptr()),
-                                                        C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
-                                                        C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_track_predict_affine")
-        return out
+        return self._launch("track_predict_affine", dev, B, (belief, B, mt, tp, stride, radius, fl), _ONE_MAP)
 
     # ---- posterior summary ------------------------------------------------------
     @classmethod
@@ -816,6 +898,12 @@ class _CVMBase(nn.Module):
             raise ValueError(f"radius must be in 0..32, got {radius}")
         return cls._track_prior(log_prior, B) + (radius,)
 
+    def _summary_form(self, B: int, t, log_prior, radius, posterior):
+        return self._summary_args(log_prior, B, radius), _summary_layout(bool(posterior))
+
+    _SUMMARY_FORMS = _Family(("localize_summary", "localize_summary_cached_indexed", "postprocess_summary"), _summary_form,
+                             own_first=(_Images.names,))
+
     def localize_summary(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                          posterior: bool = False):
         """The pose and how sure it is: (rows [B, 5], summary [B, 16]), with the posterior [B, 512, 512] behind them if asked.  rows
@@ -823,44 +911,27 @@ class _CVMBase(nn.Module):
         map - argmax and its value, total mass, entropy, mean and covariance, and the mass, mean and covariance of the
         (2 radius + 1)^2 window around the argmax - in cells of the 512 grid (aerial.summary_to_metres scales them).  No launch is
         added to localize_prior's.  A query without a finite posterior has the summary (-1, NaN, NaN ...) (ccvpe_localize_summary)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._summary_args(log_prior, grd.shape[0], radius)   # (before the inputs' checks)
-        return self._call("localize_summary", grd, sat, args=lambda B: own, posterior=posterior, summary=True)
+        return self._run(self._SUMMARY_FORMS, _Images(grd, sat), log_prior, radius, posterior)
 
     def localize_summary_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                                 posterior: bool = False, tile_index=None):
         """localize_summary(grd, sat, log_prior, radius, posterior) with the aerial side taken from encode_aerial(sat); tile_index as
         forward_cached (ccvpe_localize_summary_cached_indexed)."""
-        return self._call("localize_summary_cached_indexed", grd, cache=cache, tile_index=tile_index,
-                          args=lambda B: self._summary_args(log_prior, B, radius), posterior=posterior, summary=True)
+        return self._run(self._SUMMARY_FORMS, _Cached(grd, cache, tile_index), log_prior, radius, posterior)
 
     def postprocess_summary(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                             posterior: bool = False):
         """localize_summary from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
         ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_summary)."""
-        return self._logits_call("postprocess_summary", logits, ori, lambda B: self._summary_args(log_prior, B, radius),
-                                 posterior=posterior, summary=True)
+        return self._run(self._SUMMARY_FORMS, _Held(logits, ori), log_prior, radius, posterior)
 
     def belief_summary(self, belief: torch.Tensor, radius: int = 8) -> torch.Tensor:
         """The summary [B, 16] of stored maps: belief [B,512,512] or [B,1,512,512], float32, contiguous, non-negative - a forward's
         heatmap, a tracker belief; it need not sum to 1 (column 2 is its sum).  An all-zero map gives (0, 0, 0, NaN ...); NaN never
         wins the argmax, and a map without a value above -inf gives index 0 with the map's value there.  One launch
         (ccvpe_belief_summary)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        if not isinstance(belief, torch.Tensor):
-            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
-        shape = tuple(belief.shape)
-        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
-                                                                                       and shape[2:] == spec.OUT_HW):
-            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
-        if belief.dtype != torch.float32:
-            raise ValueError(f"belief must be float32, got {belief.dtype}")
-        if not belief.is_contiguous():
-            raise ValueError("belief must be contiguous")
-        if shape[0] > 4096:
-            raise ValueError(f"belief holds {shape[0]} maps, at most 4096 per call")
+        self._require_eval()
+        B = self._stored_maps(belief)
         radius = int(radius)
         if not 0 <= radius <= 32:
             raise ValueError(f"radius must be in 0..32, got {radius}")
@@ -868,13 +939,7 @@ class _CVMBase(nn.Module):
             raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
         dev = belief.device
         self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            out = torch.empty((shape[0], 16), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().ccvpe_belief_summary(self._handle, C.c_void_p(belief.detach().data_ptr()), shape[0], radius,
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_belief_summary")
-        return out
+        return self._launch("belief_summary", dev, B, (belief, B, radius), _SUMMARY)
 
     # ---- credible regions -------------------------------------------------------
     @staticmethod
@@ -898,23 +963,14 @@ class _CVMBase(nn.Module):
             raise ValueError(f"probe must hold one integer cell index per query ([{B}]), got {tuple(t.shape)} {t.dtype}")
         return t.detach().clamp(-1, 1 << 30).to(device=dev, dtype=torch.int32).contiguous()
 
-    @staticmethod
-    def _credible_alloc(L: int, level_map: bool, posterior: Optional[bool]):
-        """alloc of _call / _logits_call for a credible form: rows [B, 5] (posterior is None: the stored-map form, which has neither
-        rows nor a posterior), cred [B, 4 + 3 L], then the optional level map [B, 512, 512] uint8 and posterior [B, 512, 512]"""
-        def alloc(B, dev):
-            res = () if posterior is None else (torch.empty((B, 5), dtype=torch.float32, device=dev),)
-            res += (torch.empty((B, 4 + 3 * L), dtype=torch.float32, device=dev),)
-            ptrs = tuple(C.c_void_p(t.data_ptr()) for t in res)
-            for want, dtype in ((level_map, torch.uint8),) + (() if posterior is None else ((posterior, torch.float32),)):
-                t = torch.empty((B,) + spec.OUT_HW, dtype=dtype, device=dev) if want else None
-                res += (t,) if want else ()
-                ptrs += (C.c_void_p(t.data_ptr()) if want else None,)
-            return res, ptrs
-        return alloc
+    def _credible_form(self, B: int, t, lv: np.ndarray, log_prior, probe, level_map, posterior):
+        """lv: the levels as _credible_levels returns them - the methods convert them before anything else is checked, the image form
+        behind its eval guard"""
+        extra = self._track_prior(log_prior, B) + (lv.ctypes.data_as(C.c_void_p), int(lv.size), self._credible_probe(probe, B, t.device))
+        return extra, _credible_layout(int(lv.size), bool(level_map), bool(posterior))
 
-    def _credible_args(self, log_prior, B: int, lv: np.ndarray, probe, dev):
-        return self._track_prior(log_prior, B) + (lv.ctypes.data_as(C.c_void_p), int(lv.size), self._credible_probe(probe, B, dev))
+    _CREDIBLE = _Family(("localize_credible", "localize_credible_cached_indexed", "postprocess_credible"), _credible_form,
+                        own_first=(_Images.names,))
 
     def belief_credible(self, belief: torch.Tensor, levels, probe=None, level_map: bool = False):
         """Credible regions of stored maps: cred [B, 4 + 3 L] for the L levels (each in (0, 1]; any order) - per query the columns
@@ -924,62 +980,37 @@ class _CVMBase(nn.Module):
         belief as belief_summary takes it; probe: one cell index per query (a tensor or a sequence) or None; level_map=True also
         returns a uint8 map [B, 512, 512] of the number of levels whose region holds each cell: (cred, level_map).  An all-zero
         map gives the level columns (NaN, 0, NaN) (ccvpe_belief_credible)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        if not isinstance(belief, torch.Tensor):
-            raise ValueError("belief must be a float32 cuda tensor [B,512,512]")
-        shape = tuple(belief.shape)
-        if not (len(shape) == 3 and shape[0] >= 1 and shape[1:] == spec.OUT_HW) and not (len(shape) == 4 and shape[0] >= 1 and shape[1] == 1
-                                                                                       and shape[2:] == spec.OUT_HW):
-            raise ValueError(f"belief must be [B,512,512] or [B,1,512,512], got {shape}")
-        if belief.dtype != torch.float32:
-            raise ValueError(f"belief must be float32, got {belief.dtype}")
-        if not belief.is_contiguous():
-            raise ValueError("belief must be contiguous")
-        if shape[0] > 4096:
-            raise ValueError(f"belief holds {shape[0]} maps, at most 4096 per call")
+        self._require_eval()
+        B = self._stored_maps(belief)
         lv = self._credible_levels(levels)
         if not belief.is_cuda:
             raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
         dev = belief.device
-        pr = self._credible_probe(probe, shape[0], dev)
+        pr = self._credible_probe(probe, B, dev)
         self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            res, ptrs = self._credible_alloc(int(lv.size), level_map, None)(shape[0], dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().ccvpe_belief_credible(self._handle, C.c_void_p(belief.detach().data_ptr()), shape[0], lv.ctypes.data_as(C.c_void_p),
-                                                   int(lv.size), C.c_void_p(pr.data_ptr()) if pr is not None else None, *ptrs,
-                                                   C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_belief_credible")
-        return res if level_map else res[0]
+        return self._launch("belief_credible", dev, B, (belief, B, lv.ctypes.data_as(C.c_void_p), int(lv.size), pr),
+                            _credible_layout(int(lv.size), bool(level_map), None))
 
     def localize_credible(self, grd: torch.Tensor, sat: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
                           level_map: bool = False, posterior: bool = False):
         """The pose and the credible regions of its posterior: (rows [B, 5], cred [B, 4 + 3 L]), then the level map and the posterior
         if asked.  rows and posterior are track_update(grd, sat, log_prior)'s; cred and the level map are belief_credible's on that
         posterior, bit for bit, whether or not it is returned (ccvpe_localize_credible)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        lv = self._credible_levels(levels)
-        own = self._credible_args(log_prior, grd.shape[0], lv, probe, grd.device)   # (before the inputs' checks)
-        return self._call("localize_credible", grd, sat, args=lambda B: own, alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
+        self._require_eval()
+        return self._run(self._CREDIBLE, _Images(grd, sat), self._credible_levels(levels), log_prior, probe, level_map, posterior)
 
     def localize_credible_cached(self, grd: torch.Tensor, cache: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
                                  level_map: bool = False, posterior: bool = False, tile_index=None):
         """localize_credible with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
         (ccvpe_localize_credible_cached_indexed)."""
-        lv = self._credible_levels(levels)
-        return self._call("localize_credible_cached_indexed", grd, cache=cache, tile_index=tile_index,
-                          args=lambda B: self._credible_args(log_prior, B, lv, probe, grd.device),
-                          alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
+        return self._run(self._CREDIBLE, _Cached(grd, cache, tile_index), self._credible_levels(levels), log_prior, probe, level_map,
+                         posterior)
 
     def postprocess_credible(self, logits: torch.Tensor, ori: torch.Tensor, levels, log_prior: Optional[torch.Tensor] = None, probe=None,
                              level_map: bool = False, posterior: bool = False):
         """localize_credible from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
         ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_credible)."""
-        lv = self._credible_levels(levels)
-        return self._logits_call("postprocess_credible", logits, ori, lambda B: self._credible_args(log_prior, B, lv, probe, logits.device),
-                                 alloc=self._credible_alloc(int(lv.size), level_map, bool(posterior)))
+        return self._run(self._CREDIBLE, _Held(logits, ori), self._credible_levels(levels), log_prior, probe, level_map, posterior)
 
     # ---- heading posterior (DESIGN.md 4.13) ------------------------------------------------------
     @classmethod
@@ -991,6 +1022,19 @@ class _CVMBase(nn.Module):
             raise ValueError(f"bins must be in 4..360, got {bins}")
         return cls._summary_args(log_prior, B, radius) + (bins,)
 
+    @classmethod
+    def _window_bins(cls, radius, bins):
+        """(radius, bins) of a heading form, checked on their own: the cached and the held-outputs form refuse them before anything
+        else - before the eval guard, too -, as they always have"""
+        return cls._heading_args(None, 1, radius, bins)[2:]
+
+    def _heading_form(self, B: int, t, log_prior, radius, bins, summary, posterior):
+        a = self._heading_args(log_prior, B, radius, bins)
+        return a, _heading_layout(a[3], bool(summary), bool(posterior))
+
+    _HEADING = _Family(("localize_heading", "localize_heading_cached_indexed", "postprocess_heading"), _heading_form,
+                       own_first=(_Images.names,))
+
     def localize_heading(self, grd: torch.Tensor, sat: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                          bins: int = 72, summary: bool = False, posterior: bool = False):
         """The pose and the heading the network believes in: (rows [B, 5], heading [B, 12], hist [B, bins]), with the summary [B, 16]
@@ -1000,25 +1044,19 @@ class _CVMBase(nn.Module):
         share, and the same over the (2 radius + 1)^2 window around the argmax.  Computes the whole orientation field and adds one
         launch to localize_prior's.  A query without a finite posterior has heading NaN with mode -1 and an all-zero hist
         (ccvpe_localize_heading)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._heading_args(log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
-        return self._call("localize_heading", grd, sat, args=lambda B: own, posterior=posterior, summary=summary, heading=own[3])
+        return self._run(self._HEADING, _Images(grd, sat), log_prior, radius, bins, summary, posterior)
 
     def localize_heading_cached(self, grd: torch.Tensor, cache: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                                 bins: int = 72, summary: bool = False, posterior: bool = False, tile_index=None):
         """localize_heading(grd, sat, log_prior, radius, bins, summary, posterior) with the aerial side taken from encode_aerial(sat);
         tile_index as forward_cached (ccvpe_localize_heading_cached_indexed)."""
-        return self._call("localize_heading_cached_indexed", grd, cache=cache, tile_index=tile_index,
-                          args=lambda B: self._heading_args(log_prior, B, radius, bins), posterior=posterior, summary=summary,
-                          heading=self._heading_args(None, 1, radius, bins)[3])
+        return self._run(self._HEADING, _Cached(grd, cache, tile_index), log_prior, *self._window_bins(radius, bins), summary, posterior)
 
     def postprocess_heading(self, logits: torch.Tensor, ori: torch.Tensor, log_prior: Optional[torch.Tensor] = None, radius: int = 8,
                             bins: int = 72, summary: bool = False, posterior: bool = False):
         """localize_heading from forward outputs the caller holds: logits = forward(...)[0] ([B, 512*512]), ori = forward(...)[2]
         ([B, 2, 512, 512]); bit-identical to the pose-only forms (ccvpe_postprocess_heading)."""
-        return self._logits_call("postprocess_heading", logits, ori, lambda B: self._heading_args(log_prior, B, radius, bins),
-                                 posterior=posterior, summary=summary, heading=self._heading_args(None, 1, radius, bins)[3])
+        return self._run(self._HEADING, _Held(logits, ori), log_prior, *self._window_bins(radius, bins), summary, posterior)
 
     # ---- heading prior (DESIGN.md 4.16) ------------------------------------------------------------
     @staticmethod
@@ -1048,14 +1086,20 @@ class _CVMBase(nn.Module):
         lp, stride, radius, bins = cls._heading_args(log_prior, B, radius, bins)
         return (lp, stride) + cls._hprior_table(table, B) + (radius, bins)
 
+    def _heading_prior_form(self, B: int, t, table, log_prior, radius, bins, summary, posterior):
+        a = self._heading_prior_args(table, log_prior, B, radius, bins)
+        return a, _heading_layout(a[6], bool(summary), bool(posterior))
+
+    _HEADING_PRIOR = _Family(("localize_heading_prior", "localize_heading_prior_cached_indexed", None), _heading_prior_form,
+                             own_first=(_Images.names, _Cached.names))   # (this family's cached form, too)
+
     def heading_prior_map(self, ori: torch.Tensor, heading_log_prior: torch.Tensor, log_prior: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The combined prior map [B, 512, 512] of a heading prior and an optional position prior, from a forward's ori
         ([B, 2, 512, 512]): per cell heading_log_prior[bin of the cell's heading], entry nb for a cell without one, plus log_prior
         there.  heading_log_prior is [nb+1] or [B, nb+1] (aerial.von_mises_heading_log_prior, heading_predict).  The map is the
         log_prior of any prior form - postprocess_prior, postprocess_summary, postprocess_heading, track_update_logits.  One launch
         (ccvpe_heading_prior_map)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         if not isinstance(ori, torch.Tensor) or ori.dim() != 4 or ori.shape[0] < 1 or tuple(ori.shape[1:]) != (2,) + spec.OUT_HW:
             raise ValueError(f"ori must be [B,2,512,512], got {tuple(ori.shape) if isinstance(ori, torch.Tensor) else type(ori)}")
         B = ori.shape[0]
@@ -1068,16 +1112,8 @@ class _CVMBase(nn.Module):
         if tb.device != ori.device or (lp is not None and lp.device != ori.device):
             raise ValueError("ori, heading_log_prior and log_prior must be on one device")
         ori = ori.detach().to(torch.float32).contiguous()
-        dev = ori.device
-        self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            out = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = _lib.load().ccvpe_heading_prior_map(self._handle, C.c_void_p(ori.data_ptr()), B,
-                                                     C.c_void_p(lp.data_ptr()) if lp is not None else None, stride,
-                                                     C.c_void_p(tb.data_ptr()), tstride, nb, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_heading_prior_map")
-        return out
+        self._ensure_handle(ori.device)
+        return self._launch("heading_prior_map", ori.device, B, (ori, B, lp, stride, tb, tstride, nb), _ONE_MAP)
 
     def localize_heading_prior(self, grd: torch.Tensor, sat: torch.Tensor, heading_log_prior: torch.Tensor,
                                log_prior: Optional[torch.Tensor] = None, radius: int = 8, bins: int = 72, summary: bool = False,
@@ -1086,21 +1122,15 @@ class _CVMBase(nn.Module):
         comb = heading_prior_map(ori, heading_log_prior, log_prior), without the detour through the full forward's outputs - bit for
         bit.  heading_log_prior [nb+1] or [B, nb+1]; nb is independent of bins.  One launch more than localize_heading; the carried
         heading belief is treated as independent of the position (ccvpe_localize_heading_prior)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._heading_prior_args(heading_log_prior, log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
-        return self._call("localize_heading_prior", grd, sat, args=lambda B: own, posterior=posterior, summary=summary, heading=own[6])
+        return self._run(self._HEADING_PRIOR, _Images(grd, sat), heading_log_prior, log_prior, radius, bins, summary, posterior)
 
     def localize_heading_prior_cached(self, grd: torch.Tensor, cache: torch.Tensor, heading_log_prior: torch.Tensor,
                                       log_prior: Optional[torch.Tensor] = None, radius: int = 8, bins: int = 72, summary: bool = False,
                                       posterior: bool = False, tile_index=None):
         """localize_heading_prior with the aerial side taken from encode_aerial(sat); tile_index as forward_cached
         (ccvpe_localize_heading_prior_cached_indexed)."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
-        own = self._heading_prior_args(heading_log_prior, log_prior, grd.shape[0], radius, bins)   # (before the inputs' checks)
-        return self._call("localize_heading_prior_cached_indexed", grd, cache=cache, tile_index=tile_index, args=lambda B: own,
-                          posterior=posterior, summary=summary, heading=own[6])
+        return self._run(self._HEADING_PRIOR, _Cached(grd, cache, tile_index), heading_log_prior, log_prior, radius, bins, summary,
+                         posterior)
 
     def heading_predict(self, hist: torch.Tensor, turn_deg, taps, floor) -> torch.Tensor:
         """The predict half of a filter step on the heading axis: the heading prior [B, nb+1] of the next frame from a hist [B, nb]
@@ -1109,8 +1139,7 @@ class _CVMBase(nn.Module):
         t[0..radius] ([radius+1] or [B, radius+1]; aerial.gaussian_taps, 2 radius + 1 <= nb), and the result is log(. + floor), floor a
         number or [B], >= 0; the last entry, for a cell without a heading, is what the average bin gets: the definition in
         include/ccvpe.h (ccvpe_heading_predict).  One launch.  turn_deg, taps and floor may be host data or tensors on hist's device."""
-        if self.training:
-            raise RuntimeError("ccvpe_amd runs the inference path only: call .eval() first")
+        self._require_eval()
         if not isinstance(hist, torch.Tensor) or hist.dim() != 2 or hist.shape[0] < 1:
             raise ValueError("hist must be a float32 cuda tensor [B, nb]")
         B, nb = int(hist.shape[0]), int(hist.shape[1])
@@ -1122,35 +1151,16 @@ class _CVMBase(nn.Module):
             raise ValueError("hist must be contiguous")
         if B > 4096:
             raise ValueError(f"hist holds {B} rows, at most 4096 per call")
-        tshape = tuple(taps.shape) if isinstance(taps, (torch.Tensor, np.ndarray)) else np.shape(taps)
-        if len(tshape) not in (1, 2) or tshape[-1] < 1 or (len(tshape) == 2 and tshape[0] != B):
-            raise ValueError(f"taps must be [radius+1] or [{B}, radius+1], got {tuple(tshape)}")
-        radius = int(tshape[-1]) - 1
-        if radius > 32 or 2 * radius + 1 > nb:
-            raise ValueError(f"taps give radius {radius}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
-        fshape = () if np.ndim(floor) == 0 and not isinstance(floor, torch.Tensor) else (B,)
-        if fshape == () and not float(floor) >= 0.0:
-            raise ValueError(f"floor must be >= 0, got {floor}")
-        scalar_turn = np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor)
+        tshape, stride, radius, number = self._blur_checks(taps, floor, B, nb)
         dev = hist.device
-        host = torch.device("cpu")
         # shapes and values first (so that they are refused without a device), then the copies
-        tp = self._track_vec(taps, "taps", tshape, host if not hist.is_cuda else dev)
-        tn = (torch.full((B,), float(turn_deg), dtype=torch.float32, device=dev) if scalar_turn
-              else self._track_vec(turn_deg, "turn_deg", (B,), dev))
-        fl = (torch.full((B,), float(floor), dtype=torch.float32, device=dev) if fshape == ()
-              else self._track_vec(floor, "floor", (B,), dev))
+        tp = self._track_vec(taps, "taps", tshape, dev)
+        tn = self._per_query(turn_deg, np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor), "turn_deg", B, dev)
+        fl = self._per_query(floor, number, "floor", B, dev)
         if not hist.is_cuda:
             raise ValueError(f"hist must be a cuda tensor, not a {hist.device.type} tensor")
         self._ensure_handle(dev)
-        out = torch.empty((B, nb + 1), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            rc = _lib.load().ccvpe_heading_predict(self._handle, C.c_void_p(hist.detach().data_ptr()), B, nb, C.c_void_p(tn.data_ptr()),
-                                                   C.c_void_p(tp.data_ptr()), (radius + 1) if len(tshape) == 2 else 0, radius,
-                                                   C.c_void_p(fl.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_heading_predict")
-        return out
+        return self._launch("heading_predict", dev, B, (hist, B, nb, tn, tp, stride, radius, fl), _row_layout(nb + 1))
 
     # ---- extras beyond the reference surface ------------------------------------------------
     def postprocess(self, heatmap: torch.Tensor, ori: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -1159,12 +1169,7 @@ class _CVMBase(nn.Module):
         +inf logit makes of the softmax, all -inf, a mix - gives index -1, prob NaN and the orientation of pixel 0."""
         B = heatmap.shape[0]
         self._ensure_handle(heatmap.device)
-        buf = torch.empty((B, 5), dtype=torch.int32, device=heatmap.device)
-        stream = torch.cuda.current_stream(heatmap.device).cuda_stream
-        rc = _lib.load().ccvpe_postprocess(self._handle, C.c_void_p(heatmap.contiguous().data_ptr()),
-                                           C.c_void_p(ori.contiguous().data_ptr()), B, C.c_void_p(buf.data_ptr()),
-                                           C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_postprocess")
+        buf = self._launch("postprocess", heatmap.device, B, (heatmap.contiguous(), ori.contiguous(), B), _POSE_INT)
         f = buf.view(torch.float32)
         return {"index": buf[:, 0].to(torch.int64), "prob": f[:, 1], "cos": f[:, 2], "sin": f[:, 3], "angle_deg": f[:, 4]}
 
@@ -1174,13 +1179,7 @@ class _CVMBase(nn.Module):
         value above -inf: (-1, NaN, cos, sin, angle_deg of pixel 0), as postprocess()."""
         B = heatmap.shape[0]
         self._ensure_handle(heatmap.device)
-        rows = torch.empty((B, 5), dtype=torch.float32, device=heatmap.device)
-        stream = torch.cuda.current_stream(heatmap.device).cuda_stream
-        rc = _lib.load().ccvpe_postprocess_rows(self._handle, C.c_void_p(heatmap.contiguous().data_ptr()),
-                                                C.c_void_p(ori.contiguous().data_ptr()), B, C.c_void_p(rows.data_ptr()),
-                                                C.c_void_p(stream))
-        _lib.check(rc, "ccvpe_postprocess_rows")
-        return rows
+        return self._launch("postprocess_rows", heatmap.device, B, (heatmap.contiguous(), ori.contiguous(), B), _ROWS)
 
     METRIC_FIELDS = ("pixel_distance", "meter_distance", "prob_at_gt", "angle_pred_deg", "angle_gt_deg", "orientation_error_deg",
                      "longitudinal_m", "lateral_m")
