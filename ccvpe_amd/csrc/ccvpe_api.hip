@@ -1033,6 +1033,32 @@ int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batc
     return launch_status("track_predict_affine launch");
 }
 
+// The backward pass over stored beliefs: three launches of kernels_track_smooth.hip on the caller's stream that hand
+// over through the caller's `work` - no plan, no tuning entry, nothing of the handle but its device, so calls on several streams of one
+// handle do not meet.
+size_t ccvpe_track_smooth_work_bytes(int32_t batch) { return batch > 0 ? track_smooth_work_bytes(batch) : 0; }
+
+int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift, const float* taps,
+                       int32_t taps_stride, int32_t radius, const float* floor, float* smoothed, float* stats, void* work, void* stream) {
+    if (!smoothed_next) return ccvpe_fail(CCVPE_EINVAL, "null smoothed_next");
+    if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, smoothed, "smoothed")) return rc;
+    if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if (smoothed == belief || (const void*)smoothed == work || smoothed == stats) return ccvpe_fail(CCVPE_EINVAL, "smoothed must not alias belief, work or stats");
+    if (stats == belief || (const void*)stats == work) return ccvpe_fail(CCVPE_EINVAL, "stats must not alias belief or work");
+    if (smoothed_next == belief) return ccvpe_fail(CCVPE_EINVAL, "smoothed_next must not alias belief");
+    if (((uintptr_t)belief | (uintptr_t)smoothed_next | (uintptr_t)smoothed | (uintptr_t)work) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "belief, smoothed_next, smoothed and work must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackSmoothParams p{};
+    p.belief = belief; p.next = smoothed_next; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
+    p.smoothed = smoothed; p.stats = stats; p.work = (float*)work; p.B = batch;
+    launch_track_smooth(p, (hipStream_t)stream);
+    return launch_status("track_smooth launch");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Posterior summary: the argmax pose plans with the summary row as one more output of pose.argmax (plans of their own,
 // PlanKey::summary, for the float64 hand-off in the workspace; the launches, names and tuning entries of the pose plans), the logits

@@ -642,6 +642,25 @@ struct TrackPredictAffineParams {
 };
 void launch_track_predict_affine(const TrackPredictAffineParams& p, hipStream_t s);
 
+// Backward pass over stored beliefs (ccvpe_track_smooth, DESIGN.md 4.20, kernels_track_smooth.hip): per query the smoothed map of frame
+// t from its filter posterior `belief`, the smoothed map `next` of frame t + 1 and the arguments of the launch_track_predict call
+// between the two.  Three launches - grid (256 tiles, B) twice, then (64 chunks, B) - that hand over through `work` alone.
+struct TrackSmoothParams {
+    const float* belief;       // [B][512*512]
+    const float* next;         // [B][512*512]; may be `smoothed`
+    const float* shift;        // [B][2] = (dx, dy) of the predict call
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0
+    float* smoothed;           // [B][512*512]
+    float* stats;              // [B][4] = (index, prob, Z, G)
+    float* work;               // track_smooth_work_bytes(B) bytes, written before it is read: any contents
+    int B;
+};
+size_t track_smooth_work_bytes(int B);
+void launch_track_smooth(const TrackSmoothParams& p, hipStream_t s);
+
 // Heading prior (kernels_hprior.hip).  The combined prior map of a heading table T [nb + 1] (log-weights of the heading
 // bins of DESIGN.md 4.13, entry nb for a cell without a heading) and an optional position prior P: per cell
 // out = T[k] or fl32(P + T[k]), k = the cell's bin by heading_reduce_kernel's own expression, nb for an invalid cell.  One launch,

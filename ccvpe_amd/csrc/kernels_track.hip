@@ -22,13 +22,6 @@
 
 namespace ccvpe {
 
-__host__ __device__ constexpr int track_side(int r) { return TRACK_T + 2 * r + 1; }
-// row pitch of the staged source: S is odd; P = 1 (mod 4) keeps the x pass (8 lanes per row, 4 columns apart) free of bank conflicts
-__host__ __device__ constexpr int track_pitch(int r) { return (track_side(r) & 3) == 1 ? track_side(r) : track_side(r) + 2; }
-// merged weights of one pass, zero-padded by 3 on both sides for the x pass' four outputs per thread
-__host__ __device__ constexpr int track_wlen(int r) { return 2 * r + 2 + 6; }
-static size_t track_lds_bytes(int r) { return sizeof(float) * ((size_t)track_side(r) * TRACK_T + 2 * track_wlen(r) + (size_t)track_side(r) * track_pitch(r)); }
-
 __global__ __launch_bounds__(256) void track_predict_kernel(const TrackPredictParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tp_smem[];
     constexpr int HW = TAIL_HW, n = HW * HW;

@@ -370,6 +370,42 @@ int ccvpe_track_predict(ccvpe_handle h, const float* belief, int32_t batch, cons
 int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batch, const double* matrix, const float* taps,
                                int32_t taps_stride, int32_t radius, const float* floor, float* log_prior, void* stream);
 
+/* Smoothing a tracked stream: the backward half of the histogram filter.  The filter answers p(x_t | frames 1..t); one call of
+ * ccvpe_track_smooth per frame, from the last frame back, turns the stored beliefs into p(x_t | frames 1..T).  All map pointers
+ * DEVICE float32 [batch][512*512]: `belief` the filter posterior of frame t (ccvpe_track_update's map), `smoothed_next` the
+ * smoothed map of frame t + 1 (for the last frame but one: the last frame's own belief), `smoothed` out.  shift, taps,
+ * taps_stride, radius, floor: the arguments of the ccvpe_track_predict call that carried `belief` into frame t + 1.  With
+ * P(m; dx, dy) that call's c for a map m (zero extension, bilinear shift, x pass then y pass, the window only), per query
+ *     prior_i = P(belief; dx, dy)_i + floor            the bits ccvpe_track_predict takes the logf of
+ *     g_i     = s'_i > 0 ? s'_i / prior_i : 0          (s' = smoothed_next; NaN and negative s' are not taken)
+ *     G       = sum_i g_i
+ *     a_i     = fma(floor, G, P(g; -dx, -dy)_i)        P with the negated shift is the adjoint of P
+ *     w_i     = belief_i * a_i,   Z = sum_i w_i,   smoothed_i = w_i * (1 / Z)
+ * which inverts the transition T(x'|x) = u(x' - x - d) + floor of the filter's predict; Z = sum s' (1 up to rounding) when the
+ * belief has mass 1.  stats [batch][4] = (index, prob, Z, G): index the first index of the largest w, as float; prob the bits
+ * of smoothed[index].
+ *   - G == 0 (the next map has no positive cell - the zero map of a frame without a finite posterior, a broken link): the
+ *     future says nothing, smoothed is belief bit for bit, index / prob its argmax (a value is taken when it is above -inf,
+ *     NaN never wins, the first index wins ties; no taken value: -1, NaN), Z = NaN, G = 0.
+ *   - else Z not finite or Z <= 0 (a zero belief, a NaN in belief, floor = 0 and prior_i = 0 under a positive s'_i): an
+ *     all-zero map and (-1, NaN, Z, G).
+ * Queries are independent: a poisoned query changes no bit of its neighbours.  No launch reads outside its tensors whatever
+ * the inputs hold (ccvpe_track_predict's clamps and guards).  Every sum has a fixed order and nothing is accumulated
+ * atomically: the same inputs give the same bits on every call, alone as in a batch.  Relative error of smoothed against the
+ * exact recursion on the same float32 inputs: at most (16 radius + 97) * 2^-24 to first order.
+ * `work` is DEVICE memory of ccvpe_track_smooth_work_bytes(batch) bytes (pure host arithmetic; 0 for batch <= 0), 16-byte
+ * aligned, any contents: it holds g and the per-tile partial sums between the launches, and nothing in it has to survive a
+ * call.  The call allocates nothing, synchronises nothing and uses no scratch of the handle: calls on several streams of one
+ * handle may run at once when each has its own work, smoothed and stats.  `smoothed` may be `smoothed_next`: a backward sweep
+ * can run in one buffer, with the bits of the out-of-place call.  Three launches.  CCVPE_EINVAL, nothing launched, checked
+ * before the handle is used: a null pointer, radius outside 0..32, a taps_stride other than 0 or radius + 1, batch outside
+ * 1..4096, smoothed or stats equal to belief, work or each other, smoothed_next == belief, a map or work that is not 16-byte
+ * aligned (the kernels read and write the maps four cells at a time). */
+size_t ccvpe_track_smooth_work_bytes(int32_t batch);
+int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift,
+                       const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed,
+                       float* stats, void* work, void* stream);
+
 /* Posterior summary: how sure the pose is.  `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
  * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
  * ccvpe_belief_summary: the map given), in cells of the 512 grid, x = index % 512 the column, y = index / 512 the row:
