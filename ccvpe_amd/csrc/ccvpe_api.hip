@@ -1693,11 +1693,8 @@ int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
     if (!rc) rc = pack_level1_tail(&tmp, d, hwt, hbt, Cout);
     if (rc) { cleanup(); return rc; }
     if (!level1_supported(d.l1_cxp)) { cleanup(); return ccvpe_fail(CCVPE_EINVAL, "the fused level takes up to 64 input channels"); }
-    Level1Params lp{};
-    lp.x = in; lp.x_ld = d.l1_cx; lp.cx = d.l1_cx; lp.cxp = d.l1_cxp; lp.B = B; lp.H = H; lp.W = W;
-    lp.c0 = d.l1_c0; lp.ng = d.l1_ng; lp.score = d.l1_score; lp.wc = d.l1_wc; lp.ws = d.l1_ws; lp.bc = d.l1_bc; lp.wt = d.l1_wt;
-    lp.bt[0] = d.tail_b[0]; lp.bt[1] = d.tail_b[1]; lp.cout = Cout; lp.normalize = Cout == 2 ? 1 : 0;
-    lp.out = out; lp.raw = nullptr; lp.tile = tile & 0xff; lp.max_wg = tile >> 8;
+    Level1Params lp = level1_params(d, d.l1_cx, B, Cout, Cout == 2);
+    lp.x = in; lp.H = H; lp.W = W; lp.out = out; lp.raw = nullptr; lp.tile = tile & 0xff; lp.max_wg = tile >> 8;
     hipStream_t st = (hipStream_t)stream;
     launch_level1(lp, st);
     hipError_t e = hipGetLastError();

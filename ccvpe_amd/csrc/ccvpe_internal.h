@@ -662,6 +662,8 @@ ConvParams conv_params(const PackedConv& pc, const float* in, int in_ld, int B, 
 size_t cache_layout(const VariantSpec& vs, int B, size_t off[6]);
 int ground_desc_floats(const ccvpe_handle_s* h, int gh, int gw);   // Ltot of a ground image (ground cache row), < 0: bad geometry
 int build_plan(ccvpe_handle_s* h, Plan& pl, const PlanKey& key);
+// the fused last level's parameters from a decoder's composed weights, at 512 x 512; the caller adds x, out, raw, tile, max_wg
+Level1Params level1_params(const DecoderW& dw, int x_ld, int B, int cout, bool normalize);
 
 // ---- ccvpe_tune.hip ----
 int autotune_plan(ccvpe_handle_s* h, Plan& pl, const std::vector<bool>* known = nullptr);

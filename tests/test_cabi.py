@@ -122,6 +122,29 @@ def test_pose_tail_has_one_definition():
         assert len(re.findall(r"^void %s\(" % fn_name, plan, flags=re.M)) == 1 and re.search(r"\b%s\(" % fn_name, api), fn_name
 
 
+def test_plan_launches_have_one_description():
+    """build_plan is an ordered list of stages over one file-local builder, and the launches that several plan forms
+    share are described once: the Level1Params fill from a DecoderW (level1_params: the fused full-plan launch, ori1.pose / ori1.topk and
+    ccvpe_op_level1), the 3x3 eligibility flags (one setter, and the level-6 skip layer's own conditions beside it), the read of an aerial
+    cache section (gather when indexed, else scatter) and sat.descmap (the full and the aerial-encode plan).  A plan outlives its builder:
+    build_plan nests no by-reference lambda, and the builder's stages hold no lambda at all - every closure is made in a free function,
+    where there is no builder to capture."""
+    csrc = os.path.join(ROOT, "ccvpe_amd", "csrc")
+    plan = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "ccvpe_plan.hip")).read())
+    both = plan + re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "ccvpe_api.hip")).read())
+    assert len(re.findall(r"\.wc\s*=\s*\w+\.l1_wc\b", both)) == 1, "the Level1Params fill is level1_params"
+    assert re.search(r"^Level1Params level1_params\(", plan, flags=re.M) and re.search(r"\blevel1_params\(", both[len(plan):])
+    assert 1 <= len(re.findall(r"\bwino4x_ok\s*=[^=]", both)) <= 2, "the 3x3 flag setter and the level-6 skip layer's conditions"
+    assert both.count("launch_scatter_channels(c.cache_in") == 1, "one description of a cache section's read"
+    assert both.count('"sat.descmap"') == 1
+    assert not re.search(r"\bfused_done\b", both)
+    m = re.search(r"^int build_plan\(.*?^\}\n", plan, flags=re.S | re.M)
+    assert m and "[&" not in m.group(0), "build_plan nests no lambda that captures by reference"
+    assert len([ln for ln in m.group(0).splitlines() if ln.strip()]) < 60, "build_plan fits on one screen"
+    b = re.search(r"^struct PlanBuilder \{.*?^\};\n", plan, flags=re.S | re.M)
+    assert b and not re.search(r"\[[=&][^\]]*\]|\[\]\s*\(|\[this\]", b.group(0)), "a stage of the builder holds no lambda"
+
+
 def test_conv_hook_descriptor_refusals(built_library):
     """ccvpe_op_conv2d_ex refuses a bad descriptor before it touches the device: the pointers below are never dereferenced."""
     lib = _lib.load()
