@@ -1035,13 +1035,13 @@ int ccvpe_track_predict_affine(ccvpe_handle h, const float* belief, int32_t batc
 
 // The backward pass over stored beliefs: three launches of kernels_track_smooth.hip on the caller's stream that hand
 // over through the caller's `work` - no plan, no tuning entry, nothing of the handle but its device, so calls on several streams of one
-// handle do not meet.
-size_t ccvpe_track_smooth_work_bytes(int32_t batch) { return batch > 0 ? track_smooth_work_bytes(batch) : 0; }
-
-int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift, const float* taps,
-                       int32_t taps_stride, int32_t radius, const float* floor, float* smoothed, float* stats, void* work, void* stream) {
+// handle do not meet.  check_smooth_args: the arguments the two smoothers share (ccvpe_track_smooth, ccvpe_track_smooth_affine), in
+// the order ccvpe_track_smooth always had; motion is the shift or the matrix of the predict call.
+static int check_smooth_args(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const void* motion,
+                             const char* motion_name, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
+                             const float* smoothed, const float* stats, const void* work) {
     if (!smoothed_next) return ccvpe_fail(CCVPE_EINVAL, "null smoothed_next");
-    if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, smoothed, "smoothed")) return rc;
+    if (int rc = check_predict_ptrs(belief, "belief", motion, motion_name, taps, floor, smoothed, "smoothed")) return rc;
     if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
     if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
     if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
@@ -1051,12 +1051,36 @@ int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothe
     if (((uintptr_t)belief | (uintptr_t)smoothed_next | (uintptr_t)smoothed | (uintptr_t)work) & 15)
         return ccvpe_fail(CCVPE_EINVAL, "belief, smoothed_next, smoothed and work must be 16-byte aligned");
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return 0;
+}
+
+size_t ccvpe_track_smooth_work_bytes(int32_t batch) { return batch > 0 ? track_smooth_work_bytes(batch) : 0; }
+
+int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift, const float* taps,
+                       int32_t taps_stride, int32_t radius, const float* floor, float* smoothed, float* stats, void* work, void* stream) {
+    if (int rc = check_smooth_args(h, belief, smoothed_next, batch, shift, "shift", taps, taps_stride, radius, floor, smoothed, stats, work)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     TrackSmoothParams p{};
     p.belief = belief; p.next = smoothed_next; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
     p.smoothed = smoothed; p.stats = stats; p.work = (float*)work; p.B = batch;
     launch_track_smooth(p, (hipStream_t)stream);
     return launch_status("track_smooth launch");
+}
+
+// The same step behind ccvpe_track_predict_affine: four launches of kernels_track_smooth_affine.hip, the last one
+// ccvpe_track_smooth's; ccvpe_track_smooth's checks in its order, a null matrix where a null shift stood.
+size_t ccvpe_track_smooth_affine_work_bytes(int32_t batch) { return batch > 0 ? track_smooth_affine_work_bytes(batch) : 0; }
+
+int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const double* matrix,
+                              const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed, float* stats,
+                              void* work, void* stream) {
+    if (int rc = check_smooth_args(h, belief, smoothed_next, batch, matrix, "matrix", taps, taps_stride, radius, floor, smoothed, stats, work)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackSmoothAffineParams p{};
+    p.belief = belief; p.next = smoothed_next; p.matrix = matrix; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
+    p.smoothed = smoothed; p.stats = stats; p.work = (float*)work; p.B = batch;
+    launch_track_smooth_affine(p, (hipStream_t)stream);
+    return launch_status("track_smooth_affine launch");
 }
 
 // ------------------------------------------------------------------------------------------------

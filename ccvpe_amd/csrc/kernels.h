@@ -660,6 +660,27 @@ struct TrackSmoothParams {
 };
 size_t track_smooth_work_bytes(int B);
 void launch_track_smooth(const TrackSmoothParams& p, hipStream_t s);
+void launch_track_smooth_scale(const TrackSmoothParams& p, hipStream_t s);   // its last launch alone (work, smoothed, stats, B are read)
+
+// The same backward step behind a launch_track_predict_affine call (ccvpe_track_smooth_affine, DESIGN.md 4.22,
+// kernels_track_smooth_affine.hip): the adjoint of the bilinear gather through `matrix` as a gather over the candidate samples of every
+// cell, in a fixed order.  Four launches - (256 tiles, B), the tiles of the grid extended by the radius, (256 tiles, B), then
+// launch_track_smooth_scale - that hand over through `work`: TrackSmoothParams' layout per query, then the blurred ratio map h.
+struct TrackSmoothAffineParams {
+    const float* belief;       // [B][512*512]
+    const float* next;         // [B][512*512]; may be `smoothed`
+    const double* matrix;      // [B][6] of the predict call: output index -> source index position
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0
+    float* smoothed;           // [B][512*512]
+    float* stats;              // [B][4] = (index, prob, Z, G)
+    float* work;               // track_smooth_affine_work_bytes(B) bytes, written before it is read: any contents
+    int B;
+};
+size_t track_smooth_affine_work_bytes(int B);
+void launch_track_smooth_affine(const TrackSmoothAffineParams& p, hipStream_t s);
 
 // Heading prior (kernels_hprior.hip).  The combined prior map of a heading table T [nb + 1] (log-weights of the heading
 // bins of DESIGN.md 4.13, entry nb for a cell without a heading) and an optional position prior P: per cell

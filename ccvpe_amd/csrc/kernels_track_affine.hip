@@ -25,13 +25,6 @@
 
 namespace ccvpe {
 
-__host__ __device__ constexpr int affine_side(int r) { return TRACK_T + 2 * r; }
-// row pitch of the samples: S is even; an odd pitch puts the x pass' 32 lanes (4 rows, 8 lanes per row, 4 columns apart) on 32 banks
-__host__ __device__ constexpr int affine_pitch(int r) { return affine_side(r) + 1; }
-// two-sided weights, zero-padded by 3 on both sides for the x pass' four outputs per thread
-__host__ __device__ constexpr int affine_wlen(int r) { return 2 * r + 1 + 6; }
-static size_t affine_lds_bytes(int r) { return sizeof(float) * ((size_t)affine_side(r) * TRACK_T + affine_wlen(r) + (size_t)affine_side(r) * affine_pitch(r)); }
-
 __global__ __launch_bounds__(256) void track_predict_affine_kernel(const TrackPredictAffineParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ta_smem[];
     constexpr int HW = TAIL_HW, n = HW * HW;

@@ -20,42 +20,11 @@
 // `smoothed` may be `smoothed_next`: s' is read by the first launch only, and every cell by the thread that later writes it.
 #include "tail_shared.h"
 #include "track_blur.h"
+#include "track_smooth_work.h"
 
 namespace ccvpe {
 
-// floats of `work` per query: the g map, then the tiles' sums of g, sums of w, maxima of w and (as bits) their first indices
-static constexpr size_t SMOOTH_WORK_FLOATS = (size_t)TAIL_HW * TAIL_HW + 4 * TRACK_TILES;
 size_t track_smooth_work_bytes(int B) { return sizeof(float) * SMOOTH_WORK_FLOATS * (size_t)B; }
-
-struct SmoothWork {
-    float* g;       // [512*512]
-    float* gsum;    // [256]
-    float* wsum;    // [256]
-    float* wmax;    // [256]
-    float* widx;    // [256] int bits
-};
-__device__ __forceinline__ SmoothWork smooth_work(float* work, int b) {
-    constexpr int n = TAIL_HW * TAIL_HW;
-    SmoothWork w;
-    w.g = work + (size_t)b * SMOOTH_WORK_FLOATS;
-    w.gsum = w.g + n;
-    w.wsum = w.gsum + TRACK_TILES;
-    w.wmax = w.wsum + TRACK_TILES;
-    w.widx = w.wmax + TRACK_TILES;
-    return w;
-}
-
-// every thread's value -> the wave's sum in all of its lanes
-__device__ __forceinline__ float smooth_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-// the first wave: the sum of a query's 256 tile partials, in all of its lanes
-__device__ __forceinline__ float smooth_sum_tiles(const float* part) {
-    const int l = threadIdx.x & 63;
-    return smooth_wave_sum(((part[l] + part[l + 64]) + part[l + 128]) + part[l + 192]);
-}
 
 __global__ __launch_bounds__(256) void track_smooth_ratio_kernel(const TrackSmoothParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sr_smem[];
@@ -181,6 +150,11 @@ void launch_track_smooth(const TrackSmoothParams& p, hipStream_t s) {
     ensure_dynamic_lds(weight_attr, reinterpret_cast<const void*>(track_smooth_weight_kernel), lds);
     CCVPE_LAUNCH(track_smooth_ratio_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
     CCVPE_LAUNCH(track_smooth_weight_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
+    launch_track_smooth_scale(p, s);
+}
+
+// the last launch alone: the affine smoother (kernels_track_smooth_affine.hip) ends with it, on the same work layout
+void launch_track_smooth_scale(const TrackSmoothParams& p, hipStream_t s) {
     CCVPE_LAUNCH(track_smooth_scale_kernel, dim3(SMOOTH_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 

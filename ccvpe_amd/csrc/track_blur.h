@@ -1,7 +1,8 @@
 // The blur passes and the log store track_predict_kernel (kernels_track.hip) and track_predict_affine_kernel (kernels_track_affine.hip)
 // share: one definition, so that the affine kernel at an integer translation gives track_predict_kernel's bits.  The
 // smoother (kernels_track_smooth.hip) runs the same passes on its two maps, so its motion model is the filter's bit
-// for bit.  The files that include this are built with -fno-slp-vectorize (ccvpe_amd/build.py).
+// for bit; the affine smoother (kernels_track_smooth_affine.hip) runs them behind the affine kernel's sampling and on
+// its ratio map.  The files that include this are built with -fno-slp-vectorize (ccvpe_amd/build.py).
 #pragma once
 #include "kernels.h"
 
@@ -17,6 +18,14 @@ __host__ __device__ constexpr int track_pitch(int r) { return (track_side(r) & 3
 // merged weights of one pass, zero-padded by 3 on both sides for the x pass' four outputs per thread
 __host__ __device__ constexpr int track_wlen(int r) { return 2 * r + 2 + 6; }
 static size_t track_lds_bytes(int r) { return sizeof(float) * ((size_t)track_side(r) * TRACK_T + 2 * track_wlen(r) + (size_t)track_side(r) * track_pitch(r)); }
+
+// ---- a tile's source without a merged shift: the LDS layout of track_predict_affine_kernel and of the affine smoother's blur phases ----
+__host__ __device__ constexpr int affine_side(int r) { return TRACK_T + 2 * r; }
+// row pitch of the samples: S is even; an odd pitch puts the x pass' 32 lanes (4 rows, 8 lanes per row, 4 columns apart) on 32 banks
+__host__ __device__ constexpr int affine_pitch(int r) { return affine_side(r) + 1; }
+// two-sided weights, zero-padded by 3 on both sides for the x pass' four outputs per thread
+__host__ __device__ constexpr int affine_wlen(int r) { return 2 * r + 1 + 6; }
+static size_t affine_lds_bytes(int r) { return sizeof(float) * ((size_t)affine_side(r) * TRACK_T + affine_wlen(r) + (size_t)affine_side(r) * affine_pitch(r)); }
 
 // The LDS of a shifted tile, carved out of track_lds_bytes(r) bytes (16-byte aligned)
 struct TrackTile {

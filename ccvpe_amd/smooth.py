@@ -9,9 +9,14 @@ where it has no prior yet and a distractor wins.
         rows = tracker.step(model, grd, cache, tile_index, origins, motion_map_px, taps, floor)
     maps, stats = smooth.smooth_stream(model, tracker.log)      # maps[t] [B,512,512], stats [T,B,4] (SMOOTH_FIELDS)
 
-track_smooth is one backward step (ccvpe_track_smooth, include/ccvpe.h: the definition, the degenerate rules, the error bound).  Out
-of scope: aerial.AffineTracker (the adjoint of a bilinear gather through a matrix is a scatter, not a predict call with the inverse
-matrix), the heading belief (hist is not smoothed), the MAP trajectory, pose rows with orientation at the smoothed cell.
+track_smooth is one backward step (ccvpe_track_smooth, include/ccvpe.h: the definition, the degenerate rules, the error bound).
+
+Streams of aerial.AffineTracker - frames whose grids turn or change scale, KITTI's heading-up tiles - have the same three pieces
+(DESIGN.md 4.22): RecordingAffineTracker, smooth_stream_affine and track_smooth_affine (ccvpe_track_smooth_affine), whose adjoint of
+the bilinear gather through the matrix is a gather over every cell's candidate samples in a fixed order, within the reach
+affine_reach measures.
+
+Out of scope: the heading belief (hist is not smoothed), the MAP trajectory, pose rows with orientation at the smoothed cell.
 """
 from __future__ import annotations
 
@@ -28,16 +33,31 @@ SMOOTH_FIELDS = ("index", "prob", "evidence", "future")
 class _SmoothResults:
     """track_smooth's results behind models._Layout's interface: the smoothed map - `out` when the caller gave one - and stats, then the
     work buffer as the last pointer before the stream (torch's allocator keeps its memory for this stream's launches after the tensor
-    is dropped)."""
+    is dropped).  work_bytes: the library's size function of the entry point."""
 
-    def __init__(self, out):
+    def __init__(self, out, work_bytes: str = "ccvpe_track_smooth_work_bytes"):
         self.out = out
+        self.work_bytes = work_bytes
 
     def alloc(self, B: int, dev):
         smoothed = self.out if self.out is not None else torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
         stats = torch.empty((B, len(SMOOTH_FIELDS)), dtype=torch.float32, device=dev)
-        work = torch.empty(_lib.load().ccvpe_track_smooth_work_bytes(B), dtype=torch.uint8, device=dev)
+        work = torch.empty(getattr(_lib.load(), self.work_bytes)(B), dtype=torch.uint8, device=dev)
         return [smoothed, stats], [smoothed.data_ptr(), stats.data_ptr(), work.data_ptr()]
+
+
+def _check_placement(model, belief, smoothed_next, out, B: int) -> None:
+    """where the maps of a backward step live, and the out tensor: the last checks of track_smooth, in its order"""
+    dev = belief.device
+    if not belief.is_cuda:
+        raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+    if smoothed_next.device != dev:
+        raise ValueError(f"smoothed_next is on {smoothed_next.device}, belief on {dev}")
+    if out is not None:
+        if model._stored_maps(out, "out") != B or out.device != dev:
+            raise ValueError(f"out must hold {B} maps on {dev}")
+        if out.data_ptr() == belief.data_ptr():
+            raise ValueError("out must not be belief")
 
 
 def track_smooth(model, belief, smoothed_next, shift_px, taps, floor, out=None):
@@ -58,17 +78,76 @@ def track_smooth(model, belief, smoothed_next, shift_px, taps, floor, out=None):
     sh = model._track_vec(shift_px, "shift_px", (B, 2), dev)
     tp = model._track_vec(taps, "taps", tshape, dev)
     fl = model._per_query(floor, number, "floor", B, dev)
-    if not belief.is_cuda:
-        raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
-    if smoothed_next.device != dev:
-        raise ValueError(f"smoothed_next is on {smoothed_next.device}, belief on {dev}")
-    if out is not None:
-        if model._stored_maps(out, "out") != B or out.device != dev:
-            raise ValueError(f"out must hold {B} maps on {dev}")
-        if out.data_ptr() == belief.data_ptr():
-            raise ValueError("out must not be belief")
+    _check_placement(model, belief, smoothed_next, out, B)
     model._ensure_handle(dev)
     return model._launch("track_smooth", dev, B, (belief, smoothed_next, B, sh, tp, stride, radius, fl), _SmoothResults(out))
+
+
+def affine_reach(matrix):
+    """(hx, hy) of an affine map [6] or [B,6] (model.track_predict_affine's matrix): the half extents, in pixels of the predict's
+    output grid, of the box of sample positions that can touch one source cell - hx = |N00| + |N01|, hy = |N10| + |N11| with N the
+    inverse of [[m0, m1], [m3, m4]], in float64 as ccvpe_track_smooth_affine computes them.  Numbers for [6], arrays [B] for [B,6];
+    inf or NaN for a singular matrix.  track_smooth_affine supports a link when |m0 m4 - m1 m3|, rounded to float32, is finite and
+    non-zero and both are <= 3."""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.ndim not in (1, 2) or m.shape[-1] != 6:
+        raise ValueError(f"matrix must be [6] or [B,6], got {m.shape}")
+    m0, m1, _, m3, m4, _ = np.moveaxis(m, -1, 0)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = m0 * m4 - m1 * m3
+        hx, hy = np.abs(m4 / d) + np.abs(-m1 / d), np.abs(-m3 / d) + np.abs(m0 / d)
+    return (float(hx), float(hy)) if m.ndim == 1 else (hx, hy)
+
+
+def _within_reach(matrix) -> np.ndarray:
+    """the reach rule of ccvpe_track_smooth_affine per row of a host matrix [.., 6] -> bool [..]"""
+    m = np.asarray(matrix, dtype=np.float64)
+    hx, hy = affine_reach(m)
+    with np.errstate(over="ignore", invalid="ignore"):
+        det = np.abs(m[..., 0] * m[..., 4] - m[..., 1] * m[..., 3]).astype(np.float32)
+        return np.isfinite(det) & (det != 0) & (np.asarray(hx) <= 3.0) & (np.asarray(hy) <= 3.0)
+
+
+def track_smooth_affine(model, belief, smoothed_next, matrix, taps, floor, out=None):
+    """track_smooth for a link made by model.track_predict_affine: matrix ([B,6] or [6]), taps, floor are that call's arguments, checked
+    as that method checks them and in its order, smoothed_next like belief and directly after it; everything else - the results,
+    stats, the degenerate rules, out - is track_smooth's (ccvpe_track_smooth_affine, include/ccvpe.h: the definition, the reach rule,
+    the error bound).  A host matrix beyond reach (affine_reach) is refused with ValueError; a float64 tensor on the belief's device
+    is not looked at, and the kernel's rule applies: a query beyond reach is a broken link - smoothed is belief bit for bit, stats
+    (belief's argmax, its value, NaN, 0).  Four launches; the work buffer is allocated here, per call."""
+    model._require_eval()
+    B = model._stored_maps(belief)
+    if model._stored_maps(smoothed_next, "smoothed_next") != B:
+        raise ValueError(f"smoothed_next holds {smoothed_next.shape[0]} maps, belief {B}")
+    on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
+    if on_device:
+        mt = matrix.detach()
+        if mt.dtype != torch.float64:
+            raise ValueError(f"matrix on the device must be float64, got {mt.dtype}")
+    else:
+        mt = torch.as_tensor(np.asarray(matrix.detach() if isinstance(matrix, torch.Tensor) else matrix, dtype=np.float64))
+    if tuple(mt.shape) not in ((6,), (B, 6)):
+        raise ValueError(f"matrix must be [6] or [{B}, 6], got {tuple(mt.shape)}")
+    if not on_device:
+        if not bool(torch.isfinite(mt).all()):
+            raise ValueError("matrix must be finite")
+        ok = np.atleast_1d(_within_reach(mt.numpy()))
+        if not ok.all():
+            q = int(np.argmin(ok))
+            hx, hy = affine_reach(mt.numpy().reshape(-1, 6)[q])
+            raise ValueError(f"matrix {q} is beyond the smoother's reach: a determinant that is finite and non-zero in float32 and "
+                             f"half extents <= 3 are needed, got (hx, hy) = ({hx:.4g}, {hy:.4g})")
+    tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+    dev = belief.device
+    tp = model._track_vec(taps, "taps", tshape, dev)
+    fl = model._per_query(floor, number, "floor", B, dev)
+    _check_placement(model, belief, smoothed_next, out, B)
+    if on_device and mt.device != dev:
+        raise ValueError(f"matrix is on {mt.device}, belief on {dev}")
+    mt = mt.expand(B, 6).to(dev).contiguous()
+    model._ensure_handle(dev)
+    return model._launch("track_smooth_affine", dev, B, (belief, smoothed_next, B, mt, tp, stride, radius, fl),
+                         _SmoothResults(out, "ccvpe_track_smooth_affine_work_bytes"))
 
 
 class RecordingTracker(aerial.Tracker):
@@ -105,23 +184,63 @@ def smooth_stream(model, log, in_place: bool = False):
     takes entry t + 1's shift, taps and floor.  in_place: the sweep runs in one running buffer (out=smoothed_next) and each frame's
     map is copied out of it; the bits are the same.  A zero belief in the log (a frame without a finite posterior) needs no special
     case here: the rules of track_smooth restart the sweep behind it."""
+    return _sweep(model, log, in_place, lambda *a, **kw: track_smooth(*a, **kw), lambda B: [[0.0, 0.0]] * B, "shift")
+
+
+def _sweep(model, log, in_place: bool, step, still, what: str):
+    """The backward sweep of smooth_stream and smooth_stream_affine over T entries (belief, motion, taps, floor).  step: the backward
+    step of the log's tracker (track_smooth's signature); still(B): the motion that moves nothing, for the last frame's call against
+    a zero next map; what: the motion's name in the refusal of an entry without one."""
     T = len(log)
     if T == 0:
         raise ValueError("the log is empty")
     last = log[-1][0]
     B = last.shape[0]
     maps, stats = [None] * T, [None] * T
-    _, stats[-1] = track_smooth(model, last, torch.zeros_like(last), [[0.0, 0.0]] * B, [1.0], 0.0)
+    _, stats[-1] = step(model, last, torch.zeros_like(last), still(B), [1.0], 0.0)
     maps[-1] = last
     run = last.clone() if in_place else last
     for t in range(T - 2, -1, -1):
-        _, shift, taps, floor = log[t + 1]
-        if shift is None:
-            raise ValueError(f"log entry {t + 1} has no shift: a stream's first frame can only stand first")
+        _, motion, taps, floor = log[t + 1]
+        if motion is None:
+            raise ValueError(f"log entry {t + 1} has no {what}: a stream's first frame can only stand first")
         if in_place:
-            _, stats[t] = track_smooth(model, log[t][0], run, shift, taps, floor, out=run)
+            _, stats[t] = step(model, log[t][0], run, motion, taps, floor, out=run)
             maps[t] = run.clone()
         else:
-            run, stats[t] = track_smooth(model, log[t][0], run, shift, taps, floor)
+            run, stats[t] = step(model, log[t][0], run, motion, taps, floor)
             maps[t] = run
     return maps, torch.stack(stats)
+
+
+class RecordingAffineTracker(aerial.AffineTracker):
+    """aerial.AffineTracker that keeps what a backward sweep needs, as RecordingTracker does for aerial.Tracker: step() is the parent's
+    - the same arguments, the same returns, the same rows and beliefs bit for bit - and appends (belief, matrix, taps, floor) to
+    self.log: the posterior the step stored and the arguments of the model.track_predict_affine call that led into this frame (matrix
+    None for the first frame of a stream, which has no such call).  A host matrix is kept as a float64 copy, a device tensor as it is;
+    the beliefs are the tensors the update returned.  reset() clears the log."""
+
+    def __init__(self):
+        super().__init__()
+        self.log = []
+
+    def reset(self) -> None:
+        super().reset()
+        self.log = []
+
+    def step(self, model, grd, sat, matrix, taps, floor, *args, **kwargs):
+        kept = None
+        if self.belief is not None:
+            on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
+            kept = matrix if on_device else np.array(matrix, dtype=np.float64)
+        res = super().step(model, grd, sat, matrix, taps, floor, *args, **kwargs)
+        self.log.append((self.belief, kept, taps, floor))
+        return res
+
+
+def smooth_stream_affine(model, log, in_place: bool = False):
+    """smooth_stream over a RecordingAffineTracker's log (T entries (belief, matrix, taps, floor)): frame t takes entry t + 1's matrix,
+    taps and floor through track_smooth_affine; the last frame's stats row comes from a call with a zero next map and the identity
+    matrix.  A link beyond the smoother's reach is refused when its matrix is host data, and is a broken link (the sweep restarts
+    behind it) when it is a device tensor."""
+    return _sweep(model, log, in_place, lambda *a, **kw: track_smooth_affine(*a, **kw), lambda B: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], "matrix")

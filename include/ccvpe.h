@@ -405,6 +405,42 @@ size_t ccvpe_track_smooth_work_bytes(int32_t batch);
 int ccvpe_track_smooth(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift,
                        const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed,
                        float* stats, void* work, void* stream);
+/* ccvpe_track_smooth for a stream tracked through ccvpe_track_predict_affine (KITTI's heading-up tiles): matrix, DEVICE float64
+ * [batch][6], taps, taps_stride, radius, floor are the arguments of the ccvpe_track_predict_affine call that carried `belief` into
+ * frame t + 1; every other argument is ccvpe_track_smooth's.  For a plane position y = (yx, yy) (integers, also outside the window)
+ * take (sx, sy), ix, iy, fx, fy and det exactly as ccvpe_track_predict_affine computes them - the coordinates as float64 fma, floor,
+ * the fraction rounded once to float32, det = (float)|m0 m4 - m1 m3| - and let wgt(y, x) be the float32 bilinear weight the sample
+ * at y gives source cell x = (i, j): wx_a * wy_b with a = i - ix, b = j - iy both in {0, 1}, wx_0 = 1.f - fx, wx_1 = fx, likewise
+ * along y; 0 when x is not one of the four cells.  Per query
+ *     prior_i = Paff(belief; M)_i + floor              the bits ccvpe_track_predict_affine takes the logf of
+ *     g_i     = s'_i > 0 ? s'_i / prior_i : 0
+ *     G       = sum_i g_i
+ *     h(y)    = (g, zero-extended, convolved with t[|k|] along x, then y)(y)   for y in [-radius, 511 + radius]^2, 0 beyond
+ *     A(x)    = sum over y, rows ascending, then columns ascending, of det * (wy_b * (wx_a * h(y)))
+ *               only terms with wx_a * wy_b > 0 enter the sum
+ *     a_x     = fma(floor, G, A(x))
+ *     w = belief * a,  Z = sum w,  smoothed = w * (1 / Z),  stats = (index, prob, Z, G)       as ccvpe_track_smooth
+ * which inverts the transition T(x'|x) = det sum_y u(x' - y) wgt(y, x) + floor of that predict (u the separable tap kernel): the
+ * blur is symmetric and moves to the g side, the adjoint of the resampling is taken on h.  That adjoint is a scatter; it is
+ * computed as a gather - every cell walks the integer positions of the bounding box of the preimage of the open square
+ * (i - 1, i + 1) x (j - 1, j + 1) under M and rejects those whose sample does not touch it - so nothing is accumulated
+ * atomically and the same inputs give the same bits on every call, alone as in a batch.
+ * Reach: with N the float64 inverse of [[m0, m1], [m3, m4]], hx = |N00| + |N01| and hy = |N10| + |N11|, a query is supported when
+ * det is finite and non-zero and hx <= 3 and hy <= 3 (NaN fails): every rotation at scale >= 0.4715, every scale >= 0.5 at any
+ * angle.  An unsupported link is a broken link: g = 0, so G = 0 and ccvpe_track_smooth's first rule holds - smoothed is belief
+ * bit for bit, stats (argmax of belief, its value, NaN, 0).  det = 0 falls under this: that predict's prior is flat.  The other
+ * degenerate rules, the independence of queries and the guards of every read are ccvpe_track_smooth's and
+ * ccvpe_track_predict_affine's.  Relative error of smoothed against the exact recursion on the same float32 inputs and the same
+ * float32 fractions: at most (16 radius + 141) * 2^-24 to first order - the count for ceil(2 hx) ceil(2 hy) <= 36 samples touching
+ * one cell; DESIGN.md 4.22 has the table - when the coordinate arithmetic is exact in float64 (entries on a 2^-20 grid); otherwise
+ * ccvpe_track_predict_affine's absolute term enters prior.
+ * `work`: ccvpe_track_smooth_affine_work_bytes(batch) bytes (pure host arithmetic; 0 for batch <= 0), 16-byte aligned, any
+ * contents: ccvpe_track_smooth's buffer, then h [576][576] per query.  Four launches, the last one ccvpe_track_smooth's.
+ * CCVPE_EINVAL as ccvpe_track_smooth (a null matrix for a null shift). */
+size_t ccvpe_track_smooth_affine_work_bytes(int32_t batch);
+int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const double* matrix,
+                              const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed,
+                              float* stats, void* work, void* stream);
 
 /* Posterior summary: how sure the pose is.  `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
  * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
