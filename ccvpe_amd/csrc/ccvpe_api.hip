@@ -1083,6 +1083,64 @@ int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* 
     return launch_status("track_smooth_affine launch");
 }
 
+// The MAP trajectory: two launches of kernels_track_viterbi.hip per frame of the forward sweep, one per backtracked
+// link, on the caller's stream; like the smoother, nothing of the handle but its device.
+size_t ccvpe_track_viterbi_work_bytes(int32_t batch) { return batch > 0 ? track_viterbi_work_bytes(batch) : 0; }
+
+int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev, const float* prev_stats,
+                        int32_t batch, const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
+                        float* score, float* stats, void* work, void* stream) {
+    if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
+    const int given = (belief_prev != nullptr) + (score_prev != nullptr) + (prev_stats != nullptr) + (shift != nullptr);
+    if (given != 0 && given != 4)
+        return ccvpe_fail(CCVPE_EINVAL, "belief_prev, score_prev, prev_stats and shift must be all null (a stream's first frame) or all given");
+    const bool first = given == 0;
+    if (!first) {
+        if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, score, "score")) return rc;
+    }
+    if (!score) return ccvpe_fail(CCVPE_EINVAL, "null score");
+    if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (!first) {
+        if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    }
+    if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
+    if (score == belief || score == belief_prev || score == score_prev || score == prev_stats)
+        return ccvpe_fail(CCVPE_EINVAL, "score must not alias belief, belief_prev, score_prev or prev_stats");
+    if ((const void*)score == work || score == stats || (const void*)stats == work) return ccvpe_fail(CCVPE_EINVAL, "score, stats and work must not alias each other");
+    if (stats == belief || stats == belief_prev || stats == score_prev || stats == prev_stats)
+        return ccvpe_fail(CCVPE_EINVAL, "stats must not alias belief, belief_prev, score_prev or prev_stats");
+    if (((uintptr_t)belief | (uintptr_t)belief_prev | (uintptr_t)score_prev | (uintptr_t)score | (uintptr_t)work) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "belief, belief_prev, score_prev, score and work must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackViterbiParams p{};
+    p.belief = belief; p.belief_prev = belief_prev; p.score_prev = score_prev; p.prev_stats = prev_stats; p.shift = shift;
+    if (!first) { p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor; }
+    p.score = score; p.stats = stats; p.work = (float*)work; p.B = batch;
+    launch_track_viterbi(p, (hipStream_t)stream);
+    return launch_status("track_viterbi launch");
+}
+
+int ccvpe_track_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
+                             const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor, int32_t* back,
+                             void* stream) {
+    if (int rc = check_predict_ptrs(score_prev, "score_prev", shift, "shift", taps, floor, back, "back")) return rc;
+    if (!prev_stats) return ccvpe_fail(CCVPE_EINVAL, "null prev_stats");
+    if (!cell) return ccvpe_fail(CCVPE_EINVAL, "null cell");
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if ((const void*)back == score_prev || (const void*)back == prev_stats || back == cell)
+        return ccvpe_fail(CCVPE_EINVAL, "back must not alias score_prev, prev_stats or cell");
+    if ((uintptr_t)score_prev & 15) return ccvpe_fail(CCVPE_EINVAL, "score_prev must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackViterbiBackParams p{};
+    p.score_prev = score_prev; p.prev_stats = prev_stats; p.cell = cell; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride;
+    p.radius = radius; p.floor = floor; p.back = back; p.B = batch;
+    launch_track_viterbi_back(p, (hipStream_t)stream);
+    return launch_status("track_viterbi_back launch");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Posterior summary: the argmax pose plans with the summary row as one more output of pose.argmax (plans of their own,
 // PlanKey::summary, for the float64 hand-off in the workspace; the launches, names and tuning entries of the pose plans), the logits

@@ -682,6 +682,45 @@ struct TrackSmoothAffineParams {
 size_t track_smooth_affine_work_bytes(int B);
 void launch_track_smooth_affine(const TrackSmoothAffineParams& p, hipStream_t s);
 
+// MAP trajectory of a tracked stream (ccvpe_track_viterbi, DESIGN.md 4.23, kernels_track_viterbi.hip): per query the max-product score
+// map of frame t from its filter posterior `belief`, the posterior `belief_prev` and the score map `score_prev` of frame t - 1 and the
+// arguments of the launch_track_predict call between the two.  belief_prev, score_prev, prev_stats and shift all null: the first frame
+// of a stream, score = belief.  Two launches - grid (256 tiles, B), then (64 chunks, B) - that hand over through `work` alone.
+struct TrackViterbiParams {
+    const float* belief;       // [B][512*512]
+    const float* belief_prev;  // [B][512*512] or null
+    const float* score_prev;   // [B][512*512] or null
+    const float* prev_stats;   // [B][4], the stats of the call that made score_prev, or null
+    const float* shift;        // [B][2] = (dx, dy) of the predict call, or null
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0
+    float* score;              // [B][512*512], aliasing no input map
+    float* stats;              // [B][4] = (index, peak, exponent, restarted)
+    float* work;               // track_viterbi_work_bytes(B) bytes, written before it is read: any contents
+    int B;
+};
+size_t track_viterbi_work_bytes(int B);
+void launch_track_viterbi(const TrackViterbiParams& p, hipStream_t s);
+
+// One link of the backtrack (ccvpe_track_viterbi_back): per query the cell of frame t - 1 that the path's `cell` of frame t came from
+// and the link's kind, from the score map of frame t - 1 and the arguments of the predict call between the two.  One launch, grid (B).
+enum ViterbiLink { VITERBI_LINK_MOVE = 0, VITERBI_LINK_JUMP = 1, VITERBI_LINK_START = 2 };
+struct TrackViterbiBackParams {
+    const float* score_prev;   // [B][512*512]
+    const float* prev_stats;   // [B][4]
+    const int* cell;           // [B]; outside [0, 512*512): the backtrack starts here
+    const float* shift;        // [B][2]
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;
+    const float* floor;        // [B]
+    int* back;                 // [B][2] = (previous cell or -1, ViterbiLink)
+    int B;
+};
+void launch_track_viterbi_back(const TrackViterbiBackParams& p, hipStream_t s);
+
 // Heading prior (kernels_hprior.hip).  The combined prior map of a heading table T [nb + 1] (log-weights of the heading
 // bins of DESIGN.md 4.13, entry nb for a cell without a heading) and an optional position prior P: per cell
 // out = T[k] or fl32(P + T[k]), k = the cell's bin by heading_reduce_kernel's own expression, nb for an invalid cell.  One launch,

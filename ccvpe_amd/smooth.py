@@ -16,7 +16,8 @@ Streams of aerial.AffineTracker - frames whose grids turn or change scale, KITTI
 the bilinear gather through the matrix is a gather over every cell's candidate samples in a fixed order, within the reach
 affine_reach measures.
 
-Out of scope: the heading belief (hist is not smoothed), the MAP trajectory, pose rows with orientation at the smoothed cell.
+Out of scope: the heading belief (hist is not smoothed), pose rows with orientation at the smoothed cell.  The MAP trajectory - one
+consistent sequence of cells instead of T marginals - is ccvpe_amd.viterbi's, over the same log.
 """
 from __future__ import annotations
 

@@ -1,0 +1,155 @@
+"""The MAP trajectory of a tracked stream: the one most probable sequence of cells under the histogram filter of
+aerial.Tracker.
+
+The filter gives p(x_t | frames 1..t), smooth.smooth_stream p(x_t | frames 1..T); the argmaxes of T marginals are not a path - with
+two plausible modes consecutive argmaxes can sit hundreds of pixels apart.  The path maximises over cells and link kinds jointly:
+every link is a move under the filter's motion kernel or a jump under its relocalisation floor, and the links' kinds are part of the
+result.
+
+    tracker = smooth.RecordingTracker()
+    for frame in stream:
+        rows = tracker.step(model, grd, cache, tile_index, origins, motion_map_px, taps, floor)
+    cells, links, stats, scores = viterbi.map_path(model, tracker.log)      # cells, links [T,B] int32; stats [T,B,4] (VITERBI_FIELDS)
+
+track_viterbi is one step of the forward sweep and track_viterbi_back one link of the backtrack (ccvpe_track_viterbi,
+ccvpe_track_viterbi_back, include/ccvpe.h: the definition, the restart and degenerate rules, the error bounds).
+
+Out of scope: streams of aerial.AffineTracker (the maximum over a bilinear resampling through a matrix is not separable), the heading
+belief, orientation at the path's cells, fusing the scale launch into the next step.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, spec
+
+# columns of stats: the first index of the largest score, the score there (in [1, 2)), the exponent e the frame's products were scaled
+# by (w = score * 2^e), and 1 where the frame starts a segment (a stream's first frame, a frame behind one without a finite posterior)
+VITERBI_FIELDS = ("index", "peak", "exponent", "restarted")
+LINK_MOVE, LINK_JUMP, LINK_START = 0, 1, 2
+
+
+class _ViterbiResults:
+    """track_viterbi's results behind models._Layout's interface: the score map - `out` when the caller gave one - and stats, then the
+    work buffer as the last pointer before the stream."""
+
+    def __init__(self, out):
+        self.out = out
+
+    def alloc(self, B: int, dev):
+        score = self.out if self.out is not None else torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
+        stats = torch.empty((B, len(VITERBI_FIELDS)), dtype=torch.float32, device=dev)
+        work = torch.empty(_lib.load().ccvpe_track_viterbi_work_bytes(B), dtype=torch.uint8, device=dev)
+        return [score, stats], [score.data_ptr(), stats.data_ptr(), work.data_ptr()]
+
+
+class _BackResults:
+    def alloc(self, B: int, dev):
+        back = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        return [back], [back.data_ptr()]
+
+
+def _prev_stats(prev_stats, B: int):
+    if not isinstance(prev_stats, torch.Tensor) or tuple(prev_stats.shape) != (B, len(VITERBI_FIELDS)) or prev_stats.dtype != torch.float32:
+        raise ValueError(f"prev_stats must be a float32 tensor [{B}, 4]: the stats of the call that made score_prev")
+    return prev_stats.detach().contiguous()
+
+
+def _same_device(dev, ref: str, **tensors) -> None:
+    for name, t in tensors.items():
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, {ref} on {dev}")
+
+
+def track_viterbi(model, belief, belief_prev=None, score_prev=None, prev_stats=None, shift_px=None, taps=None, floor=None, out=None):
+    """One step of the forward sweep: (score [B,512,512], stats [B,4]) of frame t from belief [B,512,512], the filter posterior of frame
+    t (track_update's map), belief_prev, that of frame t - 1, score_prev and prev_stats, this function's results for frame t - 1, and
+    shift_px, taps, floor, the arguments of the model.track_predict call that carried belief_prev into frame t - checked as that method
+    checks them and in its order, belief_prev and score_prev like belief and directly after it.  belief alone: the first frame of a
+    stream, score is belief (cells that are not > 0 as 0) scaled to a peak in [1, 2).  stats: VITERBI_FIELDS.  A frame behind one
+    without a positive score restarts (restarted = 1, score the frame's likelihood); a frame whose largest product is not positive and
+    finite gives a zero map and (-1, NaN, NaN, restarted).  out: the tensor that receives the score map; it must be none of the input
+    maps.  Two launches; the work buffer is allocated here, per call."""
+    model._require_eval()
+    B = model._stored_maps(belief)
+    given = [a is not None for a in (belief_prev, score_prev, prev_stats, shift_px)]
+    if any(given) and not all(given):
+        raise ValueError("belief_prev, score_prev, prev_stats and shift_px go together: all of them, or none for a stream's first frame")
+    first = not any(given)
+    dev = belief.device
+    if first:
+        cargs = (belief, None, None, None, B, None, None, 0, 0, None)
+    else:
+        for name, t in (("belief_prev", belief_prev), ("score_prev", score_prev)):
+            if model._stored_maps(t, name) != B:
+                raise ValueError(f"{name} holds {t.shape[0]} maps, belief {B}")
+        ps = _prev_stats(prev_stats, B)
+        if taps is None or floor is None:
+            raise ValueError("taps and floor of the predict call are needed behind a stream's first frame")
+        tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+        sh = model._track_vec(shift_px, "shift_px", (B, 2), dev)
+        tp = model._track_vec(taps, "taps", tshape, dev)
+        fl = model._per_query(floor, number, "floor", B, dev)
+        cargs = (belief, belief_prev, score_prev, ps, B, sh, tp, stride, radius, fl)
+    if not belief.is_cuda:
+        raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+    if not first:
+        _same_device(dev, "belief", belief_prev=belief_prev, score_prev=score_prev, prev_stats=ps)
+    if out is not None:
+        if model._stored_maps(out, "out") != B or out.device != dev:
+            raise ValueError(f"out must hold {B} maps on {dev}")
+        if any(t is not None and out.data_ptr() == t.data_ptr() for t in (belief, belief_prev, score_prev)):
+            raise ValueError("out must be none of the input maps: the step reads their halos")
+    model._ensure_handle(dev)
+    return model._launch("track_viterbi", dev, B, cargs, _ViterbiResults(out))
+
+
+def track_viterbi_back(model, score_prev, prev_stats, cell, shift_px, taps, floor):
+    """One link of the backtrack: back [B,2] int32 = (previous cell, kind) from score_prev and prev_stats, track_viterbi's results for
+    frame t - 1, cell [B] int32 on their device, the path's cell at frame t, and the arguments of the model.track_predict call between
+    the two frames.  kind: LINK_MOVE (the best of the cell's window of source cells), LINK_JUMP (the frame's argmax, through the floor)
+    or LINK_START (cell outside the grid: the previous frame's argmax, or -1 where it has none - the end of a backtrack or the frame
+    behind a broken one).  One launch; nothing synchronises."""
+    model._require_eval()
+    B = model._stored_maps(score_prev, "score_prev")
+    ps = _prev_stats(prev_stats, B)
+    if not isinstance(cell, torch.Tensor) or tuple(cell.shape) != (B,) or cell.dtype != torch.int32:
+        raise ValueError(f"cell must be an int32 tensor [{B}]")
+    tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+    dev = score_prev.device
+    sh = model._track_vec(shift_px, "shift_px", (B, 2), dev)
+    tp = model._track_vec(taps, "taps", tshape, dev)
+    fl = model._per_query(floor, number, "floor", B, dev)
+    if not score_prev.is_cuda:
+        raise ValueError(f"score_prev must be a cuda tensor, not a {score_prev.device.type} tensor")
+    _same_device(dev, "score_prev", prev_stats=ps, cell=cell)
+    model._ensure_handle(dev)
+    return model._launch("track_viterbi_back", dev, B, (score_prev, ps, cell.contiguous(), B, sh, tp, stride, radius, fl), _BackResults())
+
+
+def map_path(model, log):
+    """The MAP trajectory over a smooth.RecordingTracker's log (T entries (belief, shift, taps, floor)) -> (cells [T,B] int32, links
+    [T,B] int32, stats [T,B,4], scores): cells[t] the path's cell at frame t (-1 for a frame without a finite posterior), links[t] the
+    kind of the link from frame t - 1 into frame t (links[0] = LINK_START), stats and scores (a list of T maps [B,512,512]) the
+    forward sweep's.  T track_viterbi calls, frame t with entry t - 1's belief and entry t's shift, taps and floor; then T - 1
+    track_viterbi_back calls from the last frame back.  The last frame's cell is its own argmax, stats[T - 1]'s index - a cell of -1
+    there starts the backtrack one frame earlier, as behind any broken frame.  Indices stay on the device and nothing synchronises.  A
+    zero belief in the log needs no special case: the rules of the two calls end one segment and start the next."""
+    T = len(log)
+    if T == 0:
+        raise ValueError("the log is empty")
+    scores, stats = [None] * T, [None] * T
+    scores[0], stats[0] = track_viterbi(model, log[0][0])
+    for t in range(1, T):
+        belief, shift, taps, floor = log[t]
+        if shift is None:
+            raise ValueError(f"log entry {t} has no shift: a stream's first frame can only stand first")
+        scores[t], stats[t] = track_viterbi(model, belief, log[t - 1][0], scores[t - 1], stats[t - 1], shift, taps, floor)
+    cells, links = [None] * T, [None] * T
+    cells[-1] = stats[-1][:, 0].to(torch.int32)
+    for t in range(T - 1, 0, -1):
+        _, shift, taps, floor = log[t]
+        back = track_viterbi_back(model, scores[t - 1], stats[t - 1], cells[t], shift, taps, floor)
+        cells[t - 1], links[t] = back[:, 0].contiguous(), back[:, 1]
+    links[0] = torch.full_like(cells[0], LINK_START)
+    return torch.stack(cells), torch.stack(links), torch.stack(stats), scores

@@ -442,7 +442,65 @@ int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* 
                               const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed,
                               float* stats, void* work, void* stream);
 
-/* Posterior summary: how sure the pose is.  `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
+/* The MAP trajectory of a tracked stream: the one most probable sequence of cells, which the argmaxes of T marginals are not.
+ * The model is the filter's own mixture transition read as a latent choice per link: a link is a MOVE, with the merged kernel u
+ * of ccvpe_track_predict, or a JUMP, with its floor; the path maximises over cells and link kinds jointly, which is
+ * max(max_x u delta, floor max delta) and separable.  One call of ccvpe_track_viterbi per frame, from the first frame on, builds
+ * the max-product score maps; one call of ccvpe_track_viterbi_back per link, from the last frame back, reads the path off them.
+ * All maps DEVICE float32 [batch][512*512], n = 512*512: `belief` (b) the filter posterior of frame t (ccvpe_track_update's map),
+ * `belief_prev` (b-) that of frame t - 1, `score_prev` (v-) the score map of frame t - 1 and `prev_stats` [batch][4] the stats of
+ * the call that made it, `score` out.  shift (dx, dy), taps, taps_stride, radius, floor: the arguments of the ccvpe_track_predict
+ * call that carried b- into frame t.  Along each axis, as that call splits a shift d: the integer part i = floor(d) clamped to
+ * +-2048, the fraction f = d - floor(d), and the merged weights u[k] = fmaf(f, t[|k - r|], (1.f - f) * t[|k - 1 - r|]), k = 0 ..
+ * 2r + 1 (a tap index above r reads 0); weight k belongs to source column x' - ix - r - 1 + k of target column x', likewise for
+ * rows.  Per query, fl() one float32 rounding:
+ *     prior_i = P(b-; dx, dy)_i + floor          the bits ccvpe_track_predict takes the logf of (ccvpe_track_smooth's prior)
+ *     lik_i   = b_i > 0 ? b_i / prior_i : 0      the frame's likelihood up to a constant; NaN and negative b are not taken
+ *     j       = (int) prev_stats[0] when 0 <= prev_stats[0] < n, else none;   peak = v-[j]
+ *     win_i   = max over ky of fl(uy[ky] * max over kx of fl(ux[kx] * v-(source cell)))      v- zero-extended; each max taken
+ *               as `c > acc ? c : acc` from acc = 0, so NaN and negatives never enter
+ *     m_i     = max(win_i, fl(floor * peak))     move or jump (the jump enters when it is strictly larger)
+ *     w_i     = fl(lik_i * m_i);  a w_i that is not > 0 (NaN included) counts and is stored as 0
+ *     W       = max_i w_i at its first index i*;  e = the integer with W * 2^-e in [1, 2)
+ *     score_i = ldexpf(w_i, -e)                  exact unless the result is subnormal
+ *     stats   = (i*, score[i*], e, restarted)    float32 [4]
+ *   - First frame: belief_prev, score_prev, prev_stats and shift all NULL.  w_i = b_i for b_i > 0, else 0; taps, taps_stride,
+ *     radius and floor are not looked at and may be NULL or 0; restarted = 1.
+ *   - Restart: j is none, or peak is not > 0 (the zero map behind a frame without a finite posterior).  m_i = 1, so w = lik, and
+ *     restarted = 1; otherwise restarted = 0.
+ *   - Degenerate: W is not > 0 or not finite.  An all-zero map and stats (-1, NaN, NaN, restarted).
+ * The recursion has no sum of its own: the one blur is prior's, everything else is one float32 product and an exact maximum, and
+ * the normalisation is by a power of two, so the frame-to-frame comparisons do not depend on it.  Relative error against a
+ * float64 evaluation on the same float32 inputs, first order, u = 2^-24: lik (4 radius + 14) u, each merged weight 2 u, win 6 u,
+ * the jump 1 u, w (4 radius + 21) u; the scaling adds none.  Queries are independent; no launch reads outside its tensors
+ * whatever the inputs hold (ccvpe_track_predict's clamps and guards, and a guarded j); the same inputs give the same bits on
+ * every call, alone as in a batch.  `work`: ccvpe_track_viterbi_work_bytes(batch) bytes of DEVICE memory (pure host arithmetic;
+ * 0 for batch <= 0), 16-byte aligned, any contents: the 256 tile maxima per query between the two launches.  Two launches, in
+ * the first-frame form as well.  The call allocates nothing, synchronises nothing and uses no scratch of the handle.
+ * CCVPE_EINVAL, nothing launched, checked before the handle is used: a null belief, score, stats or work; a mix of NULL and
+ * non-NULL among belief_prev, score_prev, prev_stats and shift; outside the first-frame form a null taps or floor, radius
+ * outside 0..32, a taps_stride other than 0 or radius + 1; batch outside 1..4096; score or stats equal to an input, to work or
+ * to each other (the step reads halos of its inputs: it cannot run in place); a map or work that is not 16-byte aligned.
+ *
+ * Backtrack of one link: `cell` DEVICE int32 [batch], the path's cell at frame t; back DEVICE int32 [batch][2] out =
+ * (previous cell, kind), kind MOVE = 0, JUMP = 1, START = 2; score_prev, prev_stats and the predict arguments as above.
+ *   - cell outside [0, n): (j or -1, START) - the end of a backtrack, or the frame behind a broken one.
+ *   - otherwise j none: (-1, START).
+ *   - otherwise the window candidates are the (2 radius + 2)^2 source cells of `cell` that lie inside the grid, each with the
+ *     value fl(uy * fl(ux * v-)); the largest wins, the smallest source index on ties, NaN never; jump = fl(floor * v-[j]).
+ *     Neither the best window value nor jump > 0: (j, START).  jump strictly larger than the best window value: (j, JUMP).
+ *     Otherwise (best source cell, MOVE).
+ * One launch, one workgroup per query, every read guarded.  CCVPE_EINVAL as above: a null pointer, the radius, taps_stride and
+ * batch rules, back equal to an input, a score_prev that is not 16-byte aligned. */
+size_t ccvpe_track_viterbi_work_bytes(int32_t batch);
+int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev,
+                        const float* prev_stats, int32_t batch, const float* shift, const float* taps, int32_t taps_stride,
+                        int32_t radius, const float* floor, float* score, float* stats, void* work, void* stream);
+int ccvpe_track_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
+                             const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
+                             int32_t* back, void* stream);
+
+/* Posterior summary: how sure the pose is. `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
  * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
  * ccvpe_belief_summary: the map given), in cells of the 512 grid, x = index % 512 the column, y = index / 512 the row:
  *     0        argmax index as float: the first maximal index, NaN never wins, always a position inside the map
