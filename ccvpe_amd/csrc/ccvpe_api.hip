@@ -1087,21 +1087,23 @@ int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* 
 // link, on the caller's stream; like the smoother, nothing of the handle but its device.
 size_t ccvpe_track_viterbi_work_bytes(int32_t batch) { return batch > 0 ? track_viterbi_work_bytes(batch) : 0; }
 
-int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev, const float* prev_stats,
-                        int32_t batch, const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
-                        float* score, float* stats, void* work, void* stream) {
+// check_viterbi_args: the arguments the two steps share (ccvpe_track_viterbi, ccvpe_track_viterbi_affine), in the order
+// ccvpe_track_viterbi always had; motion is the shift or the matrix of the predict call.  first: the first-frame form.
+static int check_viterbi_args(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev, const float* prev_stats,
+                              int32_t batch, const void* motion, const char* motion_name, const float* taps, int32_t taps_stride,
+                              int32_t radius, const float* floor, const float* score, const float* stats, const void* work, bool* first) {
     if (!belief) return ccvpe_fail(CCVPE_EINVAL, "null belief");
-    const int given = (belief_prev != nullptr) + (score_prev != nullptr) + (prev_stats != nullptr) + (shift != nullptr);
+    const int given = (belief_prev != nullptr) + (score_prev != nullptr) + (prev_stats != nullptr) + (motion != nullptr);
     if (given != 0 && given != 4)
-        return ccvpe_fail(CCVPE_EINVAL, "belief_prev, score_prev, prev_stats and shift must be all null (a stream's first frame) or all given");
-    const bool first = given == 0;
-    if (!first) {
-        if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, score, "score")) return rc;
+        return ccvpe_fail(CCVPE_EINVAL, "belief_prev, score_prev, prev_stats and %s must be all null (a stream's first frame) or all given", motion_name);
+    *first = given == 0;
+    if (!*first) {
+        if (int rc = check_predict_ptrs(belief, "belief", motion, motion_name, taps, floor, score, "score")) return rc;
     }
     if (!score) return ccvpe_fail(CCVPE_EINVAL, "null score");
     if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
     if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
-    if (!first) {
+    if (!*first) {
         if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
     }
     if (batch <= 0 || batch > PP_MAX_BATCH) return ccvpe_fail(CCVPE_EINVAL, "batch must be in 1 .. %d, got %d", PP_MAX_BATCH, batch);
@@ -1113,6 +1115,29 @@ int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief
     if (((uintptr_t)belief | (uintptr_t)belief_prev | (uintptr_t)score_prev | (uintptr_t)score | (uintptr_t)work) & 15)
         return ccvpe_fail(CCVPE_EINVAL, "belief, belief_prev, score_prev, score and work must be 16-byte aligned");
     if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return 0;
+}
+// the arguments the two backtracks share, likewise
+static int check_viterbi_back_args(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
+                                   const void* motion, const char* motion_name, const float* taps, int32_t taps_stride, int32_t radius,
+                                   const float* floor, const int32_t* back) {
+    if (int rc = check_predict_ptrs(score_prev, "score_prev", motion, motion_name, taps, floor, back, "back")) return rc;
+    if (!prev_stats) return ccvpe_fail(CCVPE_EINVAL, "null prev_stats");
+    if (!cell) return ccvpe_fail(CCVPE_EINVAL, "null cell");
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if ((const void*)back == score_prev || (const void*)back == prev_stats || back == cell)
+        return ccvpe_fail(CCVPE_EINVAL, "back must not alias score_prev, prev_stats or cell");
+    if ((uintptr_t)score_prev & 15) return ccvpe_fail(CCVPE_EINVAL, "score_prev must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    return 0;
+}
+
+int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev, const float* prev_stats,
+                        int32_t batch, const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
+                        float* score, float* stats, void* work, void* stream) {
+    bool first;
+    if (int rc = check_viterbi_args(h, belief, belief_prev, score_prev, prev_stats, batch, shift, "shift", taps, taps_stride, radius, floor,
+                                    score, stats, work, &first)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     TrackViterbiParams p{};
     p.belief = belief; p.belief_prev = belief_prev; p.score_prev = score_prev; p.prev_stats = prev_stats; p.shift = shift;
@@ -1125,20 +1150,42 @@ int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief
 int ccvpe_track_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
                              const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor, int32_t* back,
                              void* stream) {
-    if (int rc = check_predict_ptrs(score_prev, "score_prev", shift, "shift", taps, floor, back, "back")) return rc;
-    if (!prev_stats) return ccvpe_fail(CCVPE_EINVAL, "null prev_stats");
-    if (!cell) return ccvpe_fail(CCVPE_EINVAL, "null cell");
-    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
-    if ((const void*)back == score_prev || (const void*)back == prev_stats || back == cell)
-        return ccvpe_fail(CCVPE_EINVAL, "back must not alias score_prev, prev_stats or cell");
-    if ((uintptr_t)score_prev & 15) return ccvpe_fail(CCVPE_EINVAL, "score_prev must be 16-byte aligned");
-    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    if (int rc = check_viterbi_back_args(h, score_prev, prev_stats, cell, batch, shift, "shift", taps, taps_stride, radius, floor, back)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device));
     TrackViterbiBackParams p{};
     p.score_prev = score_prev; p.prev_stats = prev_stats; p.cell = cell; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride;
     p.radius = radius; p.floor = floor; p.back = back; p.B = batch;
     launch_track_viterbi_back(p, (hipStream_t)stream);
     return launch_status("track_viterbi_back launch");
+}
+
+// The same two calls behind ccvpe_track_predict_affine: the checks of the translation entry points in their order, a
+// null matrix where a null shift stood; the first-frame form is ccvpe_track_viterbi's two launches.
+int ccvpe_track_viterbi_affine(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev,
+                               const float* prev_stats, int32_t batch, const double* matrix, const float* taps, int32_t taps_stride,
+                               int32_t radius, const float* floor, float* score, float* stats, void* work, void* stream) {
+    bool first;
+    if (int rc = check_viterbi_args(h, belief, belief_prev, score_prev, prev_stats, batch, matrix, "matrix", taps, taps_stride, radius, floor,
+                                    score, stats, work, &first)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackViterbiAffineParams p{};
+    p.belief = belief; p.belief_prev = belief_prev; p.score_prev = score_prev; p.prev_stats = prev_stats; p.matrix = matrix;
+    if (!first) { p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor; }
+    p.score = score; p.stats = stats; p.work = (float*)work; p.B = batch;
+    launch_track_viterbi_affine(p, (hipStream_t)stream);
+    return launch_status("track_viterbi_affine launch");
+}
+
+int ccvpe_track_viterbi_back_affine(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
+                                    const double* matrix, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
+                                    int32_t* back, void* stream) {
+    if (int rc = check_viterbi_back_args(h, score_prev, prev_stats, cell, batch, matrix, "matrix", taps, taps_stride, radius, floor, back)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackViterbiBackAffineParams p{};
+    p.score_prev = score_prev; p.prev_stats = prev_stats; p.cell = cell; p.matrix = matrix; p.taps = taps; p.taps_stride = taps_stride;
+    p.radius = radius; p.floor = floor; p.back = back; p.B = batch;
+    launch_track_viterbi_back_affine(p, (hipStream_t)stream);
+    return launch_status("track_viterbi_back_affine launch");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -720,6 +720,44 @@ struct TrackViterbiBackParams {
     int B;
 };
 void launch_track_viterbi_back(const TrackViterbiBackParams& p, hipStream_t s);
+void launch_track_viterbi_scale(const TrackViterbiParams& p, hipStream_t s);   // its last launch alone (work, score, stats, B, and for
+                                                                               // `restarted` belief_prev, score_prev, prev_stats are read)
+
+// The same two calls behind a launch_track_predict_affine call (ccvpe_track_viterbi_affine, ccvpe_track_viterbi_back_affine, DESIGN.md
+// 4.24, kernels_track_viterbi_affine.hip): the move is read as a latent choice of the sample position the blur reads and of the one of
+// its four bilinear taps that carried the mass, so a link's maximum is a four-tap max-gather through `matrix` followed by the max passes
+// over the 2r + 1 symmetric taps.  Two launches - grid (256 tiles, B), then launch_track_viterbi_scale - through TrackViterbiParams'
+// work; belief_prev null (with score_prev, prev_stats, matrix): launch_track_viterbi's first-frame form itself.
+struct TrackViterbiAffineParams {
+    const float* belief;       // [B][512*512]
+    const float* belief_prev;  // [B][512*512] or null
+    const float* score_prev;   // [B][512*512] or null
+    const float* prev_stats;   // [B][4] or null
+    const double* matrix;      // [B][6] of the predict call: output index -> source index position, or null
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0
+    float* score;              // [B][512*512], aliasing no input map
+    float* stats;              // [B][4] = (index, peak, exponent, restarted)
+    float* work;               // track_viterbi_work_bytes(B) bytes
+    int B;
+};
+void launch_track_viterbi_affine(const TrackViterbiAffineParams& p, hipStream_t s);
+
+struct TrackViterbiBackAffineParams {
+    const float* score_prev;   // [B][512*512]
+    const float* prev_stats;   // [B][4]
+    const int* cell;           // [B]; outside [0, 512*512): the backtrack starts here
+    const double* matrix;      // [B][6]
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;
+    const float* floor;        // [B]
+    int* back;                 // [B][2] = (previous cell or -1, ViterbiLink)
+    int B;
+};
+void launch_track_viterbi_back_affine(const TrackViterbiBackAffineParams& p, hipStream_t s);
 
 // Heading prior (kernels_hprior.hip).  The combined prior map of a heading table T [nb + 1] (log-weights of the heading
 // bins of DESIGN.md 4.13, entry nb for a cell without a heading) and an optional position prior P: per cell

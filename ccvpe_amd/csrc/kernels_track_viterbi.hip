@@ -24,16 +24,7 @@
 
 namespace ccvpe {
 
-static constexpr int VITERBI_WORK_FLOATS = 2 * TRACK_TILES;   // per query: the tiles' largest w [256], its first index [256] (int bits)
-
 size_t track_viterbi_work_bytes(int B) { return sizeof(float) * VITERBI_WORK_FLOATS * (size_t)B; }
-
-// j = (int) prev_stats[0] when that is a cell index, else -1 (NaN fails both comparisons)
-__device__ __forceinline__ int viterbi_prev_index(const float* prev_stats, int b) {
-    const float s = prev_stats[(size_t)b * 4];
-    return s >= 0.f && s < (float)(TAIL_HW * TAIL_HW) ? (int)s : -1;
-}
-__device__ __forceinline__ float viterbi_clean(float w) { return w > 0.f ? w : 0.f; }
 
 __global__ __launch_bounds__(256) void track_viterbi_step_kernel(const TrackViterbiParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vs_smem[];
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(256) void track_viterbi_step_kernel(const TrackVite
             __syncthreads();                    // the y pass has read mid and wy
             track_stage_shifted(tile, p.score_prev, p.shift, 1.f, p.taps, p.taps_stride, b, r, Y0, X0);
             __syncthreads();
-            const float4 win = track_maxmul_passes(tile.src, tile.S, tile.P, tile.mid, tile.wx, tile.wy, r);
+            const float4 win = track_maxmul_passes<1>(tile.src, tile.S, tile.P, tile.mid, tile.wx, tile.wy, r);
             const float jump = fl * peak;
             w.x = w.x * (jump > win.x ? jump : win.x);
             w.y = w.y * (jump > win.y ? jump : win.y);
@@ -140,6 +131,10 @@ void launch_track_viterbi(const TrackViterbiParams& p, hipStream_t s) {
     static LdsAttr step_attr;
     ensure_dynamic_lds(step_attr, reinterpret_cast<const void*>(track_viterbi_step_kernel), lds);
     CCVPE_LAUNCH(track_viterbi_step_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
+    launch_track_viterbi_scale(p, s);
+}
+
+void launch_track_viterbi_scale(const TrackViterbiParams& p, hipStream_t s) {
     CCVPE_LAUNCH(track_viterbi_scale_kernel, dim3(VITERBI_CHUNKS, p.B), dim3(256), 0, s, p);
 }
 

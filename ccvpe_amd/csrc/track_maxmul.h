@@ -9,10 +9,23 @@ namespace ccvpe {
 
 __device__ __forceinline__ float maxmul_take(float acc, float c) { return c > acc ? c : acc; }
 
-// A workgroup of 256 threads behind the barrier that completed track_stage_shifted (src [S][P], wx[3 + k], wy[3 + k], k = 0 .. 2r + 1,
+// What the step kernels of the two motion models share (kernels_track_viterbi.hip, kernels_track_viterbi_affine.hip): the hand-off to
+// track_viterbi_scale_kernel, the guarded previous index and the cleaned product.
+static constexpr int VITERBI_WORK_FLOATS = 2 * TRACK_TILES;   // per query: the tiles' largest w [256], its first index [256] (int bits)
+
+// j = (int) prev_stats[0] when that is a cell index, else -1 (NaN fails both comparisons)
+__device__ __forceinline__ int viterbi_prev_index(const float* prev_stats, int b) {
+    const float s = prev_stats[(size_t)b * 4];
+    return s >= 0.f && s < (float)(TAIL_HW * TAIL_HW) ? (int)s : -1;
+}
+__device__ __forceinline__ float viterbi_clean(float w) { return w > 0.f ? w : 0.f; }
+
+// A workgroup of 256 threads behind the barrier that completed its staged source (src [S][P], wx[3 + k], wy[3 + k], k = 0 .. 2r + MERGED,
 // zero-padded by 3 on both sides): thread tid gets, for row tid >> 3, columns (tid & 7) * 4 .. + 3 of the tile,
 //     max over ky of fl(wy[ky] * max over kx of fl(wx[kx] * src))
-// x pass out of src into mid [S][32], y pass out of that, as track_blur_tile<1> walks them.
+// x pass out of src into mid [S][32], y pass out of that, as track_blur_tile<MERGED> walks them: MERGED = 1 behind track_stage_shifted
+// (2r + 2 merged weights), MERGED = 0 behind the affine sampling (the 2r + 1 symmetric taps, kernels_track_viterbi_affine.hip).
+template <int MERGED>
 __device__ __forceinline__ float4 track_maxmul_passes(const float* src, int S, int P, float* mid, const float* wx, const float* wy, int r) {
     const int tid = threadIdx.x;
     // x pass: task = (row, 4 adjacent columns); source column x4 + c is candidate c - i of output i, with weight wx[3 + c - i]
@@ -21,7 +34,7 @@ __device__ __forceinline__ float4 track_maxmul_passes(const float* src, int S, i
         const float* row = src + ly * P + x4;
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
         float w1 = 0.f, w2 = 0.f, w3 = 0.f;
-        for (int c = 0; c <= 2 * r + 1 + 3; ++c) {
+        for (int c = 0; c <= 2 * r + MERGED + 3; ++c) {
             const float v = row[c], w0 = wx[3 + c];
             a0 = maxmul_take(a0, w0 * v); a1 = maxmul_take(a1, w1 * v); a2 = maxmul_take(a2, w2 * v); a3 = maxmul_take(a3, w3 * v);
             w3 = w2; w2 = w1; w1 = w0;
@@ -33,7 +46,7 @@ __device__ __forceinline__ float4 track_maxmul_passes(const float* src, int S, i
     const int y = tid >> 3, x4 = (tid & 7) * 4;
     const float4* col = reinterpret_cast<const float4*>(mid + y * TRACK_T + x4);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k <= 2 * r + 1; ++k) {
+    for (int k = 0; k <= 2 * r + MERGED; ++k) {
         const float4 v = col[k * (TRACK_T / 4)];
         const float w = wy[3 + k];
         a.x = maxmul_take(a.x, w * v.x); a.y = maxmul_take(a.y, w * v.y); a.z = maxmul_take(a.z, w * v.z); a.w = maxmul_take(a.w, w * v.w);

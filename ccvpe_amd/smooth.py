@@ -17,7 +17,8 @@ the bilinear gather through the matrix is a gather over every cell's candidate s
 affine_reach measures.
 
 Out of scope: the heading belief (hist is not smoothed), pose rows with orientation at the smoothed cell.  The MAP trajectory - one
-consistent sequence of cells instead of T marginals - is ccvpe_amd.viterbi's, over the same log.
+consistent sequence of cells instead of T marginals - is ccvpe_amd.viterbi's, over the same logs: map_path and, for a
+RecordingAffineTracker's, map_path_affine.
 """
 from __future__ import annotations
 
@@ -109,6 +110,31 @@ def _within_reach(matrix) -> np.ndarray:
         return np.isfinite(det) & (det != 0) & (np.asarray(hx) <= 3.0) & (np.asarray(hy) <= 3.0)
 
 
+def _matrix_checked(matrix, B: int):
+    """model.track_predict_affine's checks of its matrix, in its order, for the calls that take that call's arguments (track_smooth_affine,
+    viterbi.track_viterbi_affine) -> (tensor [6] or [B,6], on_device): host data as a float64 host tensor, finite; a device tensor
+    float64 and not looked at."""
+    on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
+    if on_device:
+        mt = matrix.detach()
+        if mt.dtype != torch.float64:
+            raise ValueError(f"matrix on the device must be float64, got {mt.dtype}")
+    else:
+        mt = torch.as_tensor(np.asarray(matrix.detach() if isinstance(matrix, torch.Tensor) else matrix, dtype=np.float64))
+    if tuple(mt.shape) not in ((6,), (B, 6)):
+        raise ValueError(f"matrix must be [6] or [{B}, 6], got {tuple(mt.shape)}")
+    if not on_device and not bool(torch.isfinite(mt).all()):
+        raise ValueError("matrix must be finite")
+    return mt, on_device
+
+
+def _matrix_placed(mt, on_device: bool, B: int, dev, ref: str = "belief"):
+    """the checked matrix as the library reads it: [B,6] float64 on dev, the device of the map `ref`; a device tensor must be there"""
+    if on_device and mt.device != dev:
+        raise ValueError(f"matrix is on {mt.device}, {ref} on {dev}")
+    return mt.expand(B, 6).to(dev).contiguous()
+
+
 def track_smooth_affine(model, belief, smoothed_next, matrix, taps, floor, out=None):
     """track_smooth for a link made by model.track_predict_affine: matrix ([B,6] or [6]), taps, floor are that call's arguments, checked
     as that method checks them and in its order, smoothed_next like belief and directly after it; everything else - the results,
@@ -120,18 +146,8 @@ def track_smooth_affine(model, belief, smoothed_next, matrix, taps, floor, out=N
     B = model._stored_maps(belief)
     if model._stored_maps(smoothed_next, "smoothed_next") != B:
         raise ValueError(f"smoothed_next holds {smoothed_next.shape[0]} maps, belief {B}")
-    on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
-    if on_device:
-        mt = matrix.detach()
-        if mt.dtype != torch.float64:
-            raise ValueError(f"matrix on the device must be float64, got {mt.dtype}")
-    else:
-        mt = torch.as_tensor(np.asarray(matrix.detach() if isinstance(matrix, torch.Tensor) else matrix, dtype=np.float64))
-    if tuple(mt.shape) not in ((6,), (B, 6)):
-        raise ValueError(f"matrix must be [6] or [{B}, 6], got {tuple(mt.shape)}")
+    mt, on_device = _matrix_checked(matrix, B)
     if not on_device:
-        if not bool(torch.isfinite(mt).all()):
-            raise ValueError("matrix must be finite")
         ok = np.atleast_1d(_within_reach(mt.numpy()))
         if not ok.all():
             q = int(np.argmin(ok))
@@ -143,9 +159,7 @@ def track_smooth_affine(model, belief, smoothed_next, matrix, taps, floor, out=N
     tp = model._track_vec(taps, "taps", tshape, dev)
     fl = model._per_query(floor, number, "floor", B, dev)
     _check_placement(model, belief, smoothed_next, out, B)
-    if on_device and mt.device != dev:
-        raise ValueError(f"matrix is on {mt.device}, belief on {dev}")
-    mt = mt.expand(B, 6).to(dev).contiguous()
+    mt = _matrix_placed(mt, on_device, B, dev)
     model._ensure_handle(dev)
     return model._launch("track_smooth_affine", dev, B, (belief, smoothed_next, B, mt, tp, stride, radius, fl),
                          _SmoothResults(out, "ccvpe_track_smooth_affine_work_bytes"))

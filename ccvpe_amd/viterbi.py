@@ -14,14 +14,23 @@ result.
 track_viterbi is one step of the forward sweep and track_viterbi_back one link of the backtrack (ccvpe_track_viterbi,
 ccvpe_track_viterbi_back, include/ccvpe.h: the definition, the restart and degenerate rules, the error bounds).
 
-Out of scope: streams of aerial.AffineTracker (the maximum over a bilinear resampling through a matrix is not separable), the heading
-belief, orientation at the path's cells, fusing the scale launch into the next step.
+Streams of aerial.AffineTracker - frames that turn or change scale, KITTI's heading-up tiles - have the same three pieces (DESIGN.md
+4.24): map_path_affine over a smooth.RecordingAffineTracker's log, track_viterbi_affine and track_viterbi_back_affine
+(ccvpe_track_viterbi_affine, ccvpe_track_viterbi_back_affine).  The maximum over the exact transition - a sum over the samples that
+touch a cell - is not separable; the affine move is read as one more latent choice instead, of the sample position the blur reads and
+of the one of its four bilinear taps that carried the mass.  That link weight T_aug satisfies T_aug <= T <= N T_aug with N =
+ceil(2 hx) ceil(2 hy) of smooth.affine_reach (9 for a rotation at scale 1; the largest ratio seen is 3.9), and T_aug = T at integer
+translations: the path is the MAP path of a model whose moves are weighed at most N times lighter against the floor than the
+filter's, and it never takes a link the filter rules out.
+
+Out of scope: the exact (summed-over-samples) transition as the link weight, the sample position of a link, the heading belief,
+orientation at the path's cells, fusing the scale launch into the next step.
 """
 from __future__ import annotations
 
 import torch
 
-from . import _lib, spec
+from . import _lib, smooth, spec
 
 # columns of stats: the first index of the largest score, the score there (in [1, 2)), the exponent e the frame's products were scaled
 # by (w = score * 2^e), and 1 where the frame starts a segment (a stream's first frame, a frame behind one without a finite posterior)
@@ -61,6 +70,15 @@ def _same_device(dev, ref: str, **tensors) -> None:
             raise ValueError(f"{name} is on {t.device}, {ref} on {dev}")
 
 
+def _check_out(model, out, B: int, dev, maps) -> None:
+    """the out tensor of a step: the last check of track_viterbi and track_viterbi_affine"""
+    if out is not None:
+        if model._stored_maps(out, "out") != B or out.device != dev:
+            raise ValueError(f"out must hold {B} maps on {dev}")
+        if any(t is not None and out.data_ptr() == t.data_ptr() for t in maps):
+            raise ValueError("out must be none of the input maps: the step reads their halos")
+
+
 def track_viterbi(model, belief, belief_prev=None, score_prev=None, prev_stats=None, shift_px=None, taps=None, floor=None, out=None):
     """One step of the forward sweep: (score [B,512,512], stats [B,4]) of frame t from belief [B,512,512], the filter posterior of frame
     t (track_update's map), belief_prev, that of frame t - 1, score_prev and prev_stats, this function's results for frame t - 1, and
@@ -95,11 +113,7 @@ def track_viterbi(model, belief, belief_prev=None, score_prev=None, prev_stats=N
         raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
     if not first:
         _same_device(dev, "belief", belief_prev=belief_prev, score_prev=score_prev, prev_stats=ps)
-    if out is not None:
-        if model._stored_maps(out, "out") != B or out.device != dev:
-            raise ValueError(f"out must hold {B} maps on {dev}")
-        if any(t is not None and out.data_ptr() == t.data_ptr() for t in (belief, belief_prev, score_prev)):
-            raise ValueError("out must be none of the input maps: the step reads their halos")
+    _check_out(model, out, B, dev, (belief, belief_prev, score_prev))
     model._ensure_handle(dev)
     return model._launch("track_viterbi", dev, B, cargs, _ViterbiResults(out))
 
@@ -135,21 +149,95 @@ def map_path(model, log):
     track_viterbi_back calls from the last frame back.  The last frame's cell is its own argmax, stats[T - 1]'s index - a cell of -1
     there starts the backtrack one frame earlier, as behind any broken frame.  Indices stay on the device and nothing synchronises.  A
     zero belief in the log needs no special case: the rules of the two calls end one segment and start the next."""
+    return _sweep(model, log, lambda *a: track_viterbi(*a), lambda *a: track_viterbi_back(*a), "shift")
+
+
+def _sweep(model, log, step, back_step, what: str):
+    """The forward sweep and the backtrack of map_path and map_path_affine over T entries (belief, motion, taps, floor).  step,
+    back_step: the two calls of the log's tracker (track_viterbi's and track_viterbi_back's signatures); what: the motion's name in the
+    refusal of an entry without one."""
     T = len(log)
     if T == 0:
         raise ValueError("the log is empty")
     scores, stats = [None] * T, [None] * T
-    scores[0], stats[0] = track_viterbi(model, log[0][0])
+    scores[0], stats[0] = step(model, log[0][0])
     for t in range(1, T):
-        belief, shift, taps, floor = log[t]
-        if shift is None:
-            raise ValueError(f"log entry {t} has no shift: a stream's first frame can only stand first")
-        scores[t], stats[t] = track_viterbi(model, belief, log[t - 1][0], scores[t - 1], stats[t - 1], shift, taps, floor)
+        belief, motion, taps, floor = log[t]
+        if motion is None:
+            raise ValueError(f"log entry {t} has no {what}: a stream's first frame can only stand first")
+        scores[t], stats[t] = step(model, belief, log[t - 1][0], scores[t - 1], stats[t - 1], motion, taps, floor)
     cells, links = [None] * T, [None] * T
     cells[-1] = stats[-1][:, 0].to(torch.int32)
     for t in range(T - 1, 0, -1):
-        _, shift, taps, floor = log[t]
-        back = track_viterbi_back(model, scores[t - 1], stats[t - 1], cells[t], shift, taps, floor)
+        _, motion, taps, floor = log[t]
+        back = back_step(model, scores[t - 1], stats[t - 1], cells[t], motion, taps, floor)
         cells[t - 1], links[t] = back[:, 0].contiguous(), back[:, 1]
     links[0] = torch.full_like(cells[0], LINK_START)
     return torch.stack(cells), torch.stack(links), torch.stack(stats), scores
+
+
+def track_viterbi_affine(model, belief, belief_prev=None, score_prev=None, prev_stats=None, matrix=None, taps=None, floor=None, out=None):
+    """track_viterbi for a link made by model.track_predict_affine: matrix ([B,6] or [6]), taps, floor are that call's arguments, checked
+    as that method checks them and in its order - host data must be finite, a float64 tensor on the belief's device is not looked at -
+    behind belief_prev, score_prev and prev_stats; everything else - the results, stats, the first-frame form (belief alone), the
+    restart and degenerate rules, out - is track_viterbi's (ccvpe_track_viterbi_affine, include/ccvpe.h: the definition, the error
+    bound).  No matrix is refused for its reach: the recursion only gathers, and a matrix that is singular or moves everything off the
+    grid leaves the floor as the only link.  Two launches; the work buffer is allocated here, per call."""
+    model._require_eval()
+    B = model._stored_maps(belief)
+    given = [a is not None for a in (belief_prev, score_prev, prev_stats, matrix)]
+    if any(given) and not all(given):
+        raise ValueError("belief_prev, score_prev, prev_stats and matrix go together: all of them, or none for a stream's first frame")
+    first = not any(given)
+    dev = belief.device
+    if first:
+        cargs = (belief, None, None, None, B, None, None, 0, 0, None)
+    else:
+        for name, t in (("belief_prev", belief_prev), ("score_prev", score_prev)):
+            if model._stored_maps(t, name) != B:
+                raise ValueError(f"{name} holds {t.shape[0]} maps, belief {B}")
+        ps = _prev_stats(prev_stats, B)
+        if taps is None or floor is None:
+            raise ValueError("taps and floor of the predict call are needed behind a stream's first frame")
+        mt, on_device = smooth._matrix_checked(matrix, B)
+        tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+        tp = model._track_vec(taps, "taps", tshape, dev)
+        fl = model._per_query(floor, number, "floor", B, dev)
+    if not belief.is_cuda:
+        raise ValueError(f"belief must be a cuda tensor, not a {belief.device.type} tensor")
+    if not first:
+        _same_device(dev, "belief", belief_prev=belief_prev, score_prev=score_prev, prev_stats=ps)
+        cargs = (belief, belief_prev, score_prev, ps, B, smooth._matrix_placed(mt, on_device, B, dev), tp, stride, radius, fl)
+    _check_out(model, out, B, dev, (belief, belief_prev, score_prev))
+    model._ensure_handle(dev)
+    return model._launch("track_viterbi_affine", dev, B, cargs, _ViterbiResults(out))
+
+
+def track_viterbi_back_affine(model, score_prev, prev_stats, cell, matrix, taps, floor):
+    """track_viterbi_back for a link made by model.track_predict_affine: back [B,2] int32 = (previous cell, kind), the arguments and the
+    kinds track_viterbi_back's with that call's matrix for its shift, checked as in track_viterbi_affine.  A MOVE's candidates are the
+    4 (2 radius + 1)^2 pairs of a sample position in the cell's window and one of its four taps; the largest wins, the smallest
+    source cell on ties.  One launch; nothing synchronises."""
+    model._require_eval()
+    B = model._stored_maps(score_prev, "score_prev")
+    ps = _prev_stats(prev_stats, B)
+    if not isinstance(cell, torch.Tensor) or tuple(cell.shape) != (B,) or cell.dtype != torch.int32:
+        raise ValueError(f"cell must be an int32 tensor [{B}]")
+    mt, on_device = smooth._matrix_checked(matrix, B)
+    tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+    dev = score_prev.device
+    tp = model._track_vec(taps, "taps", tshape, dev)
+    fl = model._per_query(floor, number, "floor", B, dev)
+    if not score_prev.is_cuda:
+        raise ValueError(f"score_prev must be a cuda tensor, not a {score_prev.device.type} tensor")
+    _same_device(dev, "score_prev", prev_stats=ps, cell=cell)
+    mt = smooth._matrix_placed(mt, on_device, B, dev, "score_prev")
+    model._ensure_handle(dev)
+    return model._launch("track_viterbi_back_affine", dev, B, (score_prev, ps, cell.contiguous(), B, mt, tp, stride, radius, fl), _BackResults())
+
+
+def map_path_affine(model, log):
+    """map_path over a smooth.RecordingAffineTracker's log (T entries (belief, matrix, taps, floor)): the same return tuple and rules,
+    frame t through track_viterbi_affine with entry t - 1's belief and entry t's matrix, taps and floor, the links through
+    track_viterbi_back_affine."""
+    return _sweep(model, log, lambda *a: track_viterbi_affine(*a), lambda *a: track_viterbi_back_affine(*a), "matrix")

@@ -499,6 +499,50 @@ int ccvpe_track_viterbi(ccvpe_handle h, const float* belief, const float* belief
 int ccvpe_track_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, int32_t batch,
                              const float* shift, const float* taps, int32_t taps_stride, int32_t radius, const float* floor,
                              int32_t* back, void* stream);
+/* The same two calls for a stream tracked through ccvpe_track_predict_affine (KITTI's heading-up tiles): matrix, DEVICE float64
+ * [batch][6], taps, taps_stride, radius, floor are the arguments of the ccvpe_track_predict_affine call that carried b- into frame
+ * t; b, b-, v-, prev_stats, j, peak and every other argument are ccvpe_track_viterbi's.  The maximum over the exact transition
+ * T(x'|x) = det sum_y u(x' - y) wgt(y, x) + floor is not separable; the affine move is read as one more latent choice instead - of
+ * the sample position y the blur reads, and of the one of that sample's four bilinear taps that carried the mass - as "move or
+ * floor" already is.  For an integer plane position y (also outside the window) take (sx, sy), ix, iy, fx, fy and det exactly as
+ * ccvpe_track_predict_affine computes them - the coordinates as float64 fma, then floor, the integer parts clamped to +-2048, the
+ * fractions rounded once to float32, det = (float)|m0 m4 - m1 m3|; the four taps are (a, b) in {0, 1}^2 with source cell
+ * (ix + a, iy + b) and weights wx_0 = 1.f - fx, wx_1 = fx, likewise along y; v- is zero-extended.  Per query, fl() one float32
+ * rounding:
+ *     prior_i = Paff(b-; M)_i + floor              the bits ccvpe_track_predict_affine takes the logf of
+ *     lik_i   = b_i > 0 ? b_i / prior_i : 0
+ *     cand(y, a, b) = fl(det * fl(wy_b * fl(wx_a * v-(ix + a, iy + b))))
+ *     q(y)    = max over the four taps of cand     each max as `c > acc ? c : acc` from acc = 0
+ *     win_i   = max over ky of fl(t[|ky - r|] * max over kx of fl(t[|kx - r|] * q(x' - r + kx, y' - r + ky))),   kx, ky = 0 .. 2r
+ *     m_i     = max(win_i, fl(floor * peak))       the jump enters when it is strictly larger
+ *     w, W, e, score, stats                        exactly ccvpe_track_viterbi's lines
+ * The first-frame form (belief_prev, score_prev, prev_stats and matrix all NULL), the restart and the degenerate rules are
+ * ccvpe_track_viterbi's, word for word; the first-frame form runs that call's two launches.  There is no reach rule: the recursion
+ * only gathers.  det = 0, or a matrix that moves everything off the grid, gives win = 0, so every surviving link is a JUMP through
+ * the floor; that follows from the definition and is no special case.  The matrix (1, 0, -dx, 0, 1, -dy) with integer dx, dy gives
+ * ccvpe_track_viterbi's bits, score, stats and back.  The link weight of this model, T_aug(x'|x) = max over (y, tap) reaching x of
+ * det u(x' - y) w_tap(y), satisfies T_aug <= T <= N T_aug with N = ceil(2 hx) ceil(2 hy) (hx, hy of ccvpe_track_smooth_affine: the
+ * number of samples that can touch one cell), is positive wherever T is, and equals T at integer translations.
+ * Backtrack of one link: the cell and j rules are ccvpe_track_viterbi_back's.  Otherwise the candidates are the 4 (2 radius + 1)^2
+ * pairs of a sample position of the cell's window and one of its taps whose source cell lies inside the grid, each weighed
+ * fl(t_y * fl(t_x * cand)); the largest wins, on ties the smallest source cell index, whatever sample it came through, NaN never;
+ * jump and START / JUMP / MOVE as in ccvpe_track_viterbi_back.  Rounding is monotone and all factors are non-negative, so "max, then
+ * multiply" in the step and "multiply, then max" in the backtrack pick the same value: a MOVE's candidate carries the bits of win.
+ * Relative error against a float64 evaluation on the same float32 inputs, fractions and det, first order, u = 2^-24: lik
+ * (4 radius + 14) u (ccvpe_track_predict_affine's (4 radius + 12) u on its sum, the floor add, the division), cand 5 u (1 - fx,
+ * 1 - fy, three products), win 7 u, the jump 1 u, w (4 radius + 22) u; the scaling adds none.  Purely relative when the coordinate
+ * arithmetic is exact in float64 (entries on a 2^-20 grid); otherwise ccvpe_track_predict_affine's absolute term enters prior.
+ * Queries are independent; every read is guarded and clamped as in ccvpe_track_predict_affine; the same inputs give the same bits
+ * on every call, alone as in a batch.  `work`: ccvpe_track_viterbi_work_bytes(batch) bytes.  Two launches per step, one per link;
+ * nothing is allocated or synchronised, no scratch of the handle.  CCVPE_EINVAL as the two calls above, a null matrix standing where
+ * a null shift stood. */
+int ccvpe_track_viterbi_affine(ccvpe_handle h, const float* belief, const float* belief_prev, const float* score_prev,
+                               const float* prev_stats, int32_t batch, const double* matrix, const float* taps,
+                               int32_t taps_stride, int32_t radius, const float* floor, float* score, float* stats, void* work,
+                               void* stream);
+int ccvpe_track_viterbi_back_affine(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell,
+                                    int32_t batch, const double* matrix, const float* taps, int32_t taps_stride, int32_t radius,
+                                    const float* floor, int32_t* back, void* stream);
 
 /* Posterior summary: how sure the pose is. `summary` is float32 DEVICE memory [batch][16], one row per query, a function of the
  * float32 map h the same call would store as its posterior (h' of the definition above; log_prior NULL: ccvpe_forward's heatmap;
