@@ -99,6 +99,9 @@ SYMBOLS = [
     ("ccvpe_track_smooth_affine_work_bytes", C.c_size_t, [C.c_int32]),
     ("ccvpe_track_smooth_affine", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ccvpe_track_link_work_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("ccvpe_track_link", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ccvpe_track_viterbi_work_bytes", C.c_size_t, [C.c_int32]),
     ("ccvpe_track_viterbi", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1083,6 +1083,35 @@ int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* 
     return launch_status("track_smooth_affine launch");
 }
 
+// Link statistics of a smoothed stream: four launches, the first one ccvpe_track_smooth's, on the caller's stream; like
+// the smoother, nothing of the handle but its device.  Nothing is written to a map, so smoothed_next may be belief.
+size_t ccvpe_track_link_work_bytes(int32_t batch, int32_t radius) {
+    return batch > 0 && radius >= 0 && radius <= TRACK_MAX_R ? track_link_work_bytes(batch, radius) : 0;
+}
+
+int ccvpe_track_link(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift, const float* taps,
+                     int32_t taps_stride, int32_t radius, const float* floor, float* moves, float* stats, void* work, void* stream) {
+    if (!smoothed_next) return ccvpe_fail(CCVPE_EINVAL, "null smoothed_next");
+    if (int rc = check_predict_ptrs(belief, "belief", shift, "shift", taps, floor, moves, "moves")) return rc;
+    if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    const void* in[] = {belief, smoothed_next, shift, taps, floor};
+    for (const void* q : in)
+        if (moves == q || stats == q || work == q) return ccvpe_fail(CCVPE_EINVAL, "moves, stats and work must not alias an input");
+    if (moves == stats || (const void*)moves == work || (const void*)stats == work)
+        return ccvpe_fail(CCVPE_EINVAL, "moves, stats and work must not alias each other");
+    if (((uintptr_t)belief | (uintptr_t)smoothed_next | (uintptr_t)work) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "belief, smoothed_next and work must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackLinkParams p{};
+    p.belief = belief; p.next = smoothed_next; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.floor = floor;
+    p.moves = moves; p.stats = stats; p.work = (float*)work; p.B = batch;
+    launch_track_link(p, (hipStream_t)stream);
+    return launch_status("track_link launch");
+}
+
 // The MAP trajectory: two launches of kernels_track_viterbi.hip per frame of the forward sweep, one per backtracked
 // link, on the caller's stream; like the smoother, nothing of the handle but its device.
 size_t ccvpe_track_viterbi_work_bytes(int32_t batch) { return batch > 0 ? track_viterbi_work_bytes(batch) : 0; }

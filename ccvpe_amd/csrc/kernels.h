@@ -661,6 +661,27 @@ struct TrackSmoothParams {
 size_t track_smooth_work_bytes(int B);
 void launch_track_smooth(const TrackSmoothParams& p, hipStream_t s);
 void launch_track_smooth_scale(const TrackSmoothParams& p, hipStream_t s);   // its last launch alone (work, smoothed, stats, B are read)
+void launch_track_smooth_ratio(const TrackSmoothParams& p, hipStream_t s);   // its first launch alone (smoothed and stats are not read)
+
+// Link statistics of a smoothed stream (ccvpe_track_link, DESIGN.md 4.25, kernels_track_link.hip): per query the posterior mass of
+// every integer displacement the predict call between frames t and t + 1 can move a cell by, and of a jump through its floor, from the
+// filter posterior `belief` of frame t, the smoothed map `next` of frame t + 1 and that call's arguments.  Four launches -
+// launch_track_smooth_ratio, grid (256 tiles, B), (ceil((2r + 2)^2 / 256), B), (B) - that hand over through `work` alone.
+struct TrackLinkParams {
+    const float* belief;       // [B][512*512]
+    const float* next;         // [B][512*512]; may be `belief`
+    const float* shift;        // [B][2] = (dx, dy) of the predict call
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* floor;        // [B] >= 0
+    float* moves;              // [B][2r + 2][2r + 2]: row ky, column kx is the displacement (ix + r + 1 - kx, iy + r + 1 - ky)
+    float* stats;              // [B][4] = (Z, G, J, M)
+    float* work;               // track_link_work_bytes(B, radius) bytes, written before it is read: any contents
+    int B;
+};
+size_t track_link_work_bytes(int B, int radius);
+void launch_track_link(const TrackLinkParams& p, hipStream_t s);
 
 // The same backward step behind a launch_track_predict_affine call (ccvpe_track_smooth_affine, DESIGN.md 4.22,
 // kernels_track_smooth_affine.hip): the adjoint of the bilinear gather through `matrix` as a gather over the candidate samples of every

@@ -145,12 +145,19 @@ __global__ __launch_bounds__(256) void track_smooth_scale_kernel(const TrackSmoo
 
 void launch_track_smooth(const TrackSmoothParams& p, hipStream_t s) {
     const size_t lds = track_lds_bytes(p.radius);
-    static LdsAttr ratio_attr, weight_attr;
-    ensure_dynamic_lds(ratio_attr, reinterpret_cast<const void*>(track_smooth_ratio_kernel), lds);
+    static LdsAttr weight_attr;
     ensure_dynamic_lds(weight_attr, reinterpret_cast<const void*>(track_smooth_weight_kernel), lds);
-    CCVPE_LAUNCH(track_smooth_ratio_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
+    launch_track_smooth_ratio(p, s);
     CCVPE_LAUNCH(track_smooth_weight_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
     launch_track_smooth_scale(p, s);
+}
+
+// the first launch alone: the link statistics (kernels_track_link.hip) start with it, so their g and G are the smoother's bits
+void launch_track_smooth_ratio(const TrackSmoothParams& p, hipStream_t s) {
+    const size_t lds = track_lds_bytes(p.radius);
+    static LdsAttr ratio_attr;
+    ensure_dynamic_lds(ratio_attr, reinterpret_cast<const void*>(track_smooth_ratio_kernel), lds);
+    CCVPE_LAUNCH(track_smooth_ratio_kernel, dim3(TRACK_TILES, p.B), dim3(256), lds, s, p);
 }
 
 // the last launch alone: the affine smoother (kernels_track_smooth_affine.hip) ends with it, on the same work layout

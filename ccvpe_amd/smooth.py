@@ -19,6 +19,7 @@ affine_reach measures.
 Out of scope: the heading belief (hist is not smoothed), pose rows with orientation at the smoothed cell.  The MAP trajectory - one
 consistent sequence of cells instead of T marginals - is ccvpe_amd.viterbi's, over the same logs: map_path and, for a
 RecordingAffineTracker's, map_path_affine.
+What a stream says about taps, floor and the odometry - the pairwise posterior of every link - is ccvpe_amd.motion's.
 """
 from __future__ import annotations
 

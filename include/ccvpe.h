@@ -442,6 +442,45 @@ int ccvpe_track_smooth_affine(ccvpe_handle h, const float* belief, const float* 
                               const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* smoothed,
                               float* stats, void* work, void* stream);
 
+/* Link statistics of a smoothed stream: what the stream itself says about the motion model of its tracker.  The transition of the
+ * filter's hidden Markov model between frames t and t + 1 is T(x'|x) = u(x' - x - d) + floor; its pairwise posterior
+ * p(x_t = x, x_t+1 = x' | frames 1..T) = b(x) T(x'|x) g(x') / Z, with g = s' / prior the ratio ccvpe_track_smooth forms, summed
+ * over all pairs with one displacement x' - x, is the expected count of that transition - the E-step of Baum-Welch for `taps`,
+ * `floor` and a bias of `shift`.  Arguments: ccvpe_track_smooth's - `belief` b, the filter posterior of frame t, `smoothed_next`
+ * s', the smoothed map of frame t + 1, and shift, taps, taps_stride, radius, floor of the ccvpe_track_predict call that carried b
+ * into frame t + 1.  Along each axis i = floor(d) clamped to +-2048 and f = d - floor(d), as that call splits a shift, and the
+ * merged weights are u[k] = fmaf(f, t[|k - r|], (1.f - f) * t[|k - 1 - r|]), k = 0 .. 2r + 1 (t[j] = 0 for j > r); weight k
+ * belongs to source column x' - ix - r - 1 + k of target column x'.  Per query, with K = 2 radius + 2,
+ *     prior, g, G     exactly ccvpe_track_smooth's (the bits of its first launch)
+ *     Sb              = sum_i b_i
+ *     D[ky][kx]       = sum over the cells (y', x') of the window of
+ *                       g(y', x') * b(y' - iy - r - 1 + ky, x' - ix - r - 1 + kx)             b zero-extended; ky, kx = 0 .. K - 1
+ *     moves[ky][kx]   = fl(fl(uy[ky] * ux[kx]) * D[ky][kx])
+ *     M = sum moves,  J = fl(fl(floor * G) * Sb),  Z = M + J
+ * moves [batch][K][K] and stats [batch][4] = (Z, G, J, M), DEVICE float32, out.  moves[ky][kx] / Z is the posterior probability
+ * that the link was a move under the motion kernel by the integer displacement x' - x = (ix + r + 1 - kx, iy + r + 1 - ky), J / Z
+ * that it was a jump through the floor; Z is ccvpe_track_smooth's Z (sum s' over the taken cells) up to rounding.
+ * There is no degenerate branch: every output is what the arithmetic gives.  A next map without a positive cell gives G = 0, zero
+ * moves and Z = 0; a NaN in b gives that query NaN.  A link is usable when Z is finite and > 0.
+ * Queries are independent: a poisoned query changes no bit of its neighbours.  No launch reads outside its tensors whatever the
+ * inputs hold (ccvpe_track_predict's clamp and guards).  Every sum has a fixed order (kernels_track_link.hip lists them) and
+ * nothing is accumulated atomically: the same inputs give the same bits on every call, alone as in a batch.
+ * Relative error against the exact sums on the same float32 inputs, first order, every term non-negative, u = 2^-24: g
+ * (4 radius + 14) u (ccvpe_track_smooth); a tile's D 37 u more (32 fused multiply-adds, 5 adds over the rows); an offset's 256 tile
+ * sums 65 u; the two weights 2 u each, their product and the product with D 1 u each: moves (4 radius + 122) u.  M 26 u more (17 adds
+ * in a thread, 6 over the wave, 3 over the waves): (4 radius + 148) u.  G (4 radius + 35) u and Sb 21 u (ccvpe_track_smooth's
+ * orders), two products: J (4 radius + 58) u.  Z one add on the larger of the two: (4 radius + 149) u.
+ * `work` is DEVICE memory of ccvpe_track_link_work_bytes(batch, radius) bytes (pure host arithmetic; 0 for batch <= 0 or radius
+ * outside 0..32), 16-byte aligned, any contents: ccvpe_track_smooth's buffer for the batch, then 256 K K floats per query.  The
+ * call allocates nothing, synchronises nothing and uses no scratch of the handle.  Four launches, the first one
+ * ccvpe_track_smooth's.  CCVPE_EINVAL, nothing launched, checked before the handle is used: a null pointer, radius outside 0..32,
+ * a taps_stride other than 0 or radius + 1, batch outside 1..4096, moves, stats or work equal to an input or to each other, a map
+ * or work that is not 16-byte aligned.  smoothed_next == belief is allowed (nothing is written to a map). */
+size_t ccvpe_track_link_work_bytes(int32_t batch, int32_t radius);
+int ccvpe_track_link(ccvpe_handle h, const float* belief, const float* smoothed_next, int32_t batch, const float* shift,
+                     const float* taps, int32_t taps_stride, int32_t radius, const float* floor, float* moves,
+                     float* stats, void* work, void* stream);
+
 /* The MAP trajectory of a tracked stream: the one most probable sequence of cells, which the argmaxes of T marginals are not.
  * The model is the filter's own mixture transition read as a latent choice per link: a link is a MOVE, with the merged kernel u
  * of ccvpe_track_predict, or a JUMP, with its floor; the path maximises over cells and link kinds jointly, which is
