@@ -43,6 +43,7 @@ Switches read_switches() {
     if (const char* e = getenv("CCVPE_FUSE_L1")) s.fuse_level1 = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_L1_TILE")) s.l1_tile = std::atoi(e);
     if (const char* e = getenv("CCVPE_COMPOSE_L6")) s.compose_l6 = std::atoi(e);
+    if (const char* e = getenv("CCVPE_SPLIT_L6")) s.split_l6 = std::atoi(e);
     if (const char* e = getenv("CCVPE_WINOGRAD")) s.wino = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_GRAPH")) s.graph_mode = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_STREAMS")) s.two_streams = std::atoi(e) >= 2;
@@ -388,6 +389,8 @@ static int issue_forward(ccvpe_handle h, Plan* pl, Ctx& c, const ForwardCall& fc
                 if (t->wino_f == 4) issued = 2.0 * mn_pad * 2.25 * ((op.conv_cin + 3) / 4 * 4);   // 36 products per 4x4 tile; k-steps of 4 channels, all-zero ones skipped
                 else if (t->wino_f == 2) issued = 2.0 * mn_pad * 4.0 * op.conv_cin;
                 else issued = 2.0 * mn_pad * op.gemm_kpad * (t->family == TILE_BF16X3 ? 3.0 : 1.0);
+            } else if (op.form) {
+                nm += std::string("|") + op.form;
             }
             h->prof.push_back({nm, ms, op.flops, op.bytes, issued});
         }

@@ -124,6 +124,10 @@ struct Switches {
     // CCVPE_COMPOSE_L6: unset = fp32 plans of at least LEVEL6_AUTO_MIN_BATCH samples run decoder level 6 composed, 0 = never
     // (deconv, conv_a and its reduction as before), 1 = every fp32 plan, as F(4x4,2x2); 2 = every fp32 plan, as F(2x2,2x2) (for A/B runs)
     std::optional<int> compose_l6;
+    // CCVPE_SPLIT_L6: conv6.2 and the skip half of conv6.0 in split Winograd form on the grouped GEMM (transform, GEMM,
+    // inverse transform) where the composed level 6 runs.  unset = plans of at least LEVEL6_SPLIT_MIN_BATCH samples, 0 = never (the tiled
+    // launches and their reductions), 1 = every plan that runs the composed level 6; 2 / 3 = as 1, conv6.2 only / the skip half only
+    std::optional<int> split_l6;
     // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
     // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
     bool wino = true;
@@ -229,13 +233,19 @@ struct Level6W {
     float* bc = nullptr;          // [9][N]
     PackedConv skip;              // conv6.0's skip half (columns 1024 .. 1344) as a 3x3 convolution of its own, zero bias
     int K = 0, Kc = 0, N = 0, Npad = 0;
+    // split form (Split6Params; ensure_level6_split): G g G^T of conv6.2 and of the skip half, [36][Npad][Kc] each, rounded once
+    float* wb = nullptr;
+    float* ws = nullptr;
 };
 static constexpr int LEVEL6_AUTO_MIN_BATCH = 8;   // the smallest batch at which the composed path measured faster (8, 16, 32 tried)
+static constexpr int LEVEL6_SPLIT_MIN_BATCH = 8;  // ... and the split form of conv6.2 / the skip half (8, 16, 32 tried)
+enum { SPLIT6_CONV_B = 1, SPLIT6_SKIP = 2 };      // Plan::l6_split
 struct ccvpe_handle_s;
 struct DecoderW;
 // sizes of a decoder's composed level 6 from its packed descriptors (no device work); != 0: these weights cannot be composed
 int level6_shape(const ccvpe_handle_s* h, const DecoderW& d, const struct DecLevel& l, int& K, int& Kc, int& N, int& Npad);
 int ensure_level6(ccvpe_handle_s* h, int wm);   // 0, or an error code; wm = 4 or 2
+int ensure_level6_split(ccvpe_handle_s* h);     // after ensure_level6: the split-form weights of both decoders; 0, or an error code
 void release_level6(ccvpe_handle_s* h);
 // the fused level's weights from the reference's layouts (ccvpe_weights.hip; the plan and ccvpe_op_level1 share them)
 int compose_level1(ccvpe_handle_s* h, DecoderW& d, const std::vector<float>& w, const std::vector<float>& b, const std::vector<float>& wa,
@@ -398,6 +408,7 @@ struct Op {
     double flops = 0, bytes = 0;
     // implicit-GEMM launches: tile id the launch uses (0 = heuristic) - set by Plan::autotune
     std::shared_ptr<int> tile;
+    const char* form = nullptr;   // a launch that is not a tiled GEMM but runs one's arithmetic: the tile part of its profile row ("name|form")
     int gemm_m = 0, gemm_n = 0, gemm_kpad = 0;
     int conv_cin = 0;             // 3x3 layers: input channels (issued-FLOP accounting of the Winograd tiles)
     bool bf16x3_only = false;     // the launch reads a pre-split bf16 tensor: exact-fp32 tiles cannot serve it
@@ -438,6 +449,7 @@ struct Plan {
     unsigned* tickets = nullptr;
     size_t alloc_tickets(size_t n) { const size_t o = ticket_words; ticket_words += (n + 15) & ~(size_t)15; return o; }
     int l6_wm = 0;                // composed level 6: the Winograd form its launches run (0: the three launches); get_plan derives the weights
+    int l6_split = 0;             // SPLIT6_* bits: the level-6 layers that run in split form (get_plan derives their weights)
     bool tiles_checked = false;   // the first issue compared every tiled launch with its plan entry (ccvpe_api.hip: check_issued_tile)
     // Two-stream execution: the aerial encoder and the orientation decoder are issued on a second stream, so the
     // ramp-up / drain of the ~330 short kernels of one chain is filled by the other chain.  Dependencies come from
@@ -624,6 +636,8 @@ struct ccvpe_handle_s {
     int l6_wm = 0;                // the Winograd form l6 was derived for (0: not derived)
     std::vector<void*> l6_allocs;
     bool l6_failed = false;       // the derivation failed once (out of memory): plans under the automatic rule keep the three launches
+    bool l6_split = false;        // l6[.].wb / ws are derived (ensure_level6_split)
+    bool l6_split_failed = false; // ... failed once: plans under the automatic rule keep the tiled launches
     std::vector<std::unique_ptr<Plan>> plans;
     Plan* last_plan = nullptr;    // plan of the most recent forward (ccvpe_debug_dump_plan)
     float* snap[2] = {nullptr, nullptr};   // CCVPE_DIAG_SNAP: the named launch's tensors before / after it

@@ -452,7 +452,32 @@ static void add_descmap(ccvpe_handle_s* h, Plan& pl, int B, Tensor x, Tensor dma
 // Level 6 composed (kernels_level6.hip): the Winograd form (0: the three launches), the sizes of the localisation and
 // the orientation decoder's composed launches, and sat_block15's dense tensor [B, 16, 16, 320] - the level-6 concat buffers are then
 // never written
-struct Level6Form { int wm = 0; Level6Params p[2] = {}; Tensor skip15; };
+struct Level6Form {
+    int wm = 0; Level6Params p[2] = {}; Tensor skip15;
+    // split form of conv6.2 and of conv6.0's skip half (SPLIT6_* bits; Split6Params, kernels_level6.hip): the sizes per decoder
+    int split = 0; Split6Params sb[2] = {}, ss[2] = {};
+};
+
+// A 3x3 layer of the 16 x 16 map in split form: transform, the grouped GEMM over 36 positions, inverse transform (+ bias, ReLU) into
+// `out` - three launches, tag.{layer}_transform, tag.conv_{layer} (the GEMM keeps the layer's launch name) and tag.{layer}_inverse; `wc`
+// and `bias` point into the handle's weights, filled before the plan first runs and read at launch
+static void plan_split6(Plan& pl, const Split6Params& sp, float* const* wc, float* const* bias, bool relu, Tensor in, Tensor out, const std::string& tag,
+                        const std::string& layer) {
+    Tensor V = pl.alloc(36, 1, sp.R, sp.Kc), Mp = pl.alloc(36, 1, sp.R, sp.N);
+    pl.add(tag + "." + layer + "_transform", {in, V}, [=](const Ctx& c) {
+        Split6Params q = sp; q.x = c.ptr(in); q.v = c.ptr(V);
+        launch_split6_transform(q, c.stream);
+    }, 0.0, 4.0 * ((double)in.numel() + (double)V.numel()));
+    pl.add(tag + ".conv_" + layer, {V, Mp}, [=](const Ctx& c) {
+        Split6Params q = sp; q.v = c.ptr(V); q.wc = *wc; q.mp = c.ptr(Mp);
+        launch_level6_gemm(split6_gemm_params(q), c.stream);
+    }, 2.0 * 36 * sp.R * (double)sp.N * sp.Kc, 4.0 * ((double)V.numel() + 36.0 * sp.Npad * sp.Kc + (double)Mp.numel()));
+    pl.ops.back().form = "conv_wino4_split";   // an F(4x4,3x3) layer like the tile it replaces: profile rows (and what reads them) say so
+    pl.add(tag + "." + layer + "_inverse", {Mp, out}, [=](const Ctx& c) {
+        Split6Params q = sp; q.mp = c.ptr(Mp); q.bias = bias ? *bias : nullptr; q.relu = relu ? 1 : 0; q.out = c.ptr(out);
+        launch_split6_inverse(q, c.stream);
+    }, 0.0, 4.0 * ((double)Mp.numel() + (double)out.numel()));
+}
 
 // Composed level 6 of decoder `dw` into `mid`: transform, grouped GEMM, the skip half as a 3x3 convolution of its own (a tiled
 // launch: the tuner picks its tile and split), combine (output transform + skip half + border-case bias + ReLU)
@@ -472,14 +497,20 @@ static void plan_level6_composed(ccvpe_handle_s* h, Plan& pl, int B, const Level
         Level6Params q = lp; q.v = c.ptr(V); q.wc = w6->wc; q.mp = c.ptr(Mp);
         launch_level6_gemm(q, c.stream);
     }, 2.0 * G * lp.R * (double)lp.N * lp.Kc, 4.0 * ((double)V.numel() + (double)G * lp.Npad * lp.Kc + (double)Mp.numel()));
-    // the skip layer's GEMM shape is known now (N, 9 taps of l.skip channels)
-    const PackedConv* pc = &w6->skip;
-    pl.add_conv(tag + ".conv_skip", {s15, sk}, B * hout * hout, lp.N, round_up(9 * l.skip, 32), [=](const Ctx& c, int tile) {
-        ConvParams p = conv_params(*pc, c.ptr(s15), s15.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_NONE);
-        p.dst[0] = c.dst(sk); p.ndst = 1;
-        c.launch_conv(p, tile);
-    }, 2.0 * B * hout * hout * 9.0 * s15.C * l.mid, 4.0 * B * hout * hout * ((double)s15.C + l.mid));
-    set_skip6_flags(h, pl.ops.back(), s15.C, l.skip, lp.N);
+    if (l6.split & SPLIT6_SKIP) {   // the skip half in split form: no bias, no activation, into the same dense tensor
+        Split6Params sp = l6.ss[&dw == &h->ori ? 1 : 0];
+        sp.x_ld = s15.C;
+        plan_split6(pl, sp, &w6->ws, nullptr, false, s15, sk, tag, "skip");
+    } else {
+        // the skip layer's GEMM shape is known now (N, 9 taps of l.skip channels)
+        const PackedConv* pc = &w6->skip;
+        pl.add_conv(tag + ".conv_skip", {s15, sk}, B * hout * hout, lp.N, round_up(9 * l.skip, 32), [=](const Ctx& c, int tile) {
+            ConvParams p = conv_params(*pc, c.ptr(s15), s15.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_NONE);
+            p.dst[0] = c.dst(sk); p.ndst = 1;
+            c.launch_conv(p, tile);
+        }, 2.0 * B * hout * hout * 9.0 * s15.C * l.mid, 4.0 * B * hout * hout * ((double)s15.C + l.mid));
+        set_skip6_flags(h, pl.ops.back(), s15.C, l.skip, lp.N);
+    }
     pl.add(tag + ".l6_combine", {Mp, sk, mid}, [=](const Ctx& c) {
         Level6Params q = lp; q.mp = c.ptr(Mp); q.skip = c.ptr(sk); q.bc = w6->bc; q.out = c.ptr(mid);
         launch_level6_combine(q, c.stream);
@@ -521,6 +552,11 @@ static Tensor plan_level(ccvpe_handle_s* h, Plan& pl, int B, const Level6Form& l
     if (j == 5) return mid;
     Tensor o = pl.alloc(B, hout, hout, l.out);
     const PackedConv* pc = &dw.convb[j];
+    if (j == 0 && l6.wm && (l6.split & SPLIT6_CONV_B)) {   // conv6.2 in split form: + bias, into conv_b's tensor
+        const int d = &dw == &h->ori ? 1 : 0;
+        plan_split6(pl, l6.sb[d], &h->l6[d].wb, &pc->bias, false, mid, o, tag, "b");
+        return o;
+    }
     pl.add_conv(tag + ".conv_b", {mid, o}, B * hout * hout, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {
         ConvParams p = conv_params(*pc, c.ptr(mid), mid.C, B, hout, hout, hout, hout, 1, 1, 1, ACT_NONE);
         p.in_split = mid.split; p.in_plane_bytes = (unsigned)(mid.numel() * 2);
@@ -876,7 +912,7 @@ struct PlanBuilder {
             bool ok = true;
             for (int d = 0; d < 2; ++d) {
                 Level6Params& q = l6.p[d];
-                q.wm = l6.wm; q.B = B;
+                q.wm = l6.wm; q.B = B; q.groups = 4 * level6_positions(l6.wm);
                 ok = ok && level6_shape(h, d ? h->ori : h->loc, d ? vs.ori[0] : vs.loc[0], q.K, q.Kc, q.N, q.Npad) == 0;
                 q.R = level6_rows(B, l6.wm, &q.bm);
                 ok = ok && level6_supported(q) && q.K == (d ? rpad + D : loc_in[0].C);
@@ -884,7 +920,31 @@ struct PlanBuilder {
             if (!ok && forced) return ccvpe_fail(CCVPE_ESTATE, "composed level 6: the packed weights do not fit the plan's level-6 inputs");
             if (!ok) l6.wm = 0;
         }
+        // conv6.2 and the skip half in split form (CCVPE_SPLIT_L6): only beside the composed level 6 - the skip half is a layer of its
+        // own only there; a layer whose sizes the kernels do not take keeps its tiled launch
+        if (l6.wm) {
+            const int both = SPLIT6_CONV_B | SPLIT6_SKIP, sw = h->sw.split_l6 ? *h->sw.split_l6 : -1;
+            const int want = sw >= 0 ? (sw == 1 ? both : sw == 2 ? SPLIT6_CONV_B : sw == 3 ? SPLIT6_SKIP : 0)
+                             : (B >= LEVEL6_SPLIT_MIN_BATCH && !h->l6_split_failed) ? both : 0;
+            for (int bit : {SPLIT6_CONV_B, SPLIT6_SKIP}) {
+                if (!(want & bit)) continue;
+                bool ok = true;
+                for (int d = 0; d < 2; ++d) {
+                    const DecLevel& l = d ? vs.ori[0] : vs.loc[0];
+                    Split6Params& q = bit == SPLIT6_CONV_B ? l6.sb[d] : l6.ss[d];
+                    q = Split6Params{};
+                    q.B = B; q.C = bit == SPLIT6_CONV_B ? l.mid : l.skip; q.Kc = round_up(q.C, 32);
+                    q.N = bit == SPLIT6_CONV_B ? l.out : l.mid; q.Npad = round_up(q.N, 128);
+                    q.R = split6_rows(B, &q.bm);
+                    q.x_ld = q.C; q.x_coff = 0; q.out_ld = q.N; q.out_coff = 0;   // dense tensors on both sides
+                    const PackedConv& pc = bit == SPLIT6_CONV_B ? (d ? h->ori : h->loc).convb[0] : (d ? h->ori : h->loc).conva[0];
+                    ok = ok && split6_supported(q) && pc.w != nullptr && (bit == SPLIT6_CONV_B ? pc.N == q.N && pc.cinp == q.C : l6.p[d].N == q.N);
+                }
+                if (ok) l6.split |= bit;
+            }
+        }
         pl.l6_wm = l6.wm;
+        pl.l6_split = l6.split;
         ori_in6 = pl.alloc(B, 8, 8, rpad + D);
         pl.taps["ori_in6"] = {ori_in6, 0, ori_in6.C};   // (read by debug handles only, like every tap: [rfull scores | pad to rpad | D])
         return 0;

@@ -214,6 +214,14 @@ int get_plan(ccvpe_handle_s* h, const PlanKey& key, Plan** out) {
         pl = std::make_unique<Plan>();
         if ((rc = build_plan(h, *pl, key))) return rc;
     }
+    // ... and the split-form weights of conv6.2 and the skip half, under the same rule: the plan then keeps the tiled launches
+    if (pl->l6_split && (rc = ensure_level6_split(h)) != 0) {
+        if (h->sw.split_l6) return rc;
+        (void)hipGetLastError();
+        h->l6_split_failed = true;
+        pl = std::make_unique<Plan>();
+        if ((rc = build_plan(h, *pl, key))) return rc;
+    }
     if (pl->total > h->arena_floats) {
         // growing the arena is the only synchronising step; it happens on the first call per shape
         HIPCHK(hipDeviceSynchronize());

@@ -3,6 +3,7 @@
 // F(2x2) / F(4x4) weight transforms in double precision), and the packed-weight cache.
 #include "ccvpe_internal.h"
 
+#include <thread>
 #include <unistd.h>
 
 // ---- expected state_dict layout -----------------------------------------------------------------
@@ -358,6 +359,7 @@ void release_level6(ccvpe_handle_s* h) {
     h->l6_allocs.clear();
     h->l6[0] = Level6W{}; h->l6[1] = Level6W{};
     h->l6_wm = 0;
+    h->l6_split = false;
 }
 
 int level6_shape(const ccvpe_handle_s* h, const DecoderW& d, const DecLevel& l, int& K, int& Kc, int& N, int& Npad) {
@@ -452,6 +454,57 @@ int ensure_level6(ccvpe_handle_s* h, int wm) {
     return 0;
 }
 
+// Split-form weights of a packed 3x3 layer (N outputs, cin inputs, pack_conv's K order): [36][Npad][Kc], position xi = 6 r + q holds
+// (G g G^T)[r][q] of every (output, input) pair - conv_wino4_pack's double-precision transform, rounded once - as K-contiguous rows of the
+// grouped GEMM's weight operand; rows N .. Npad and columns cin .. Kc are zeros.  The buffer joins h->l6_allocs.
+static int derive_split6(ccvpe_handle_s* h, const PackedConv& pc, int cin, float** out) {
+    const int N = pc.N, Npad = round_up(N, 128), Kc = round_up(cin, 32);
+    std::vector<float> w((size_t)round_up(N, conv_igemm_npad()) * pc.Kpad);
+    HIPCHK(hipMemcpy(w.data(), pc.w, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t per = (size_t)Npad * Kc;
+    std::vector<float> u(36 * per, 0.f);
+    auto work = [&](int n_lo, int n_hi) {
+        for (int n = n_lo; n < n_hi; ++n)
+            for (int c = 0; c < cin; ++c) {
+                double g[3][3], t[36];
+                for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = (double)w[(size_t)n * pc.Kpad + conv_igemm_k_index(cin, 9, k, c)];
+                conv_wino4_filter(g, t);
+                for (int xi = 0; xi < 36; ++xi) u[xi * per + (size_t)n * Kc + c] = (float)t[xi];
+            }
+    };
+    const int nthreads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t) th.emplace_back(work, (int)((long long)N * t / nthreads), (int)((long long)N * (t + 1) / nthreads));
+    for (auto& x : th) x.join();
+    void* d = nullptr;
+    HIPCHK(hipMalloc(&d, u.size() * sizeof(float)));
+    h->l6_allocs.push_back(d);
+    HIPCHK(hipMemcpy(d, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice));
+    *out = (float*)d;
+    return 0;
+}
+
+int ensure_level6_split(ccvpe_handle_s* h) {
+    if (h->l6_split) return 0;
+    if (!h->l6_wm) return ccvpe_fail(CCVPE_ESTATE, "the split form of level 6 needs the composed level 6");
+    const size_t keep = h->l6_allocs.size();
+    int rc = 0;
+    for (int d = 0; d < 2 && !rc; ++d) {
+        const DecoderW& dw = d ? h->ori : h->loc;
+        const DecLevel& l = d ? h->vs.ori[0] : h->vs.loc[0];
+        rc = derive_split6(h, dw.convb[0], l.mid, &h->l6[d].wb);
+        if (!rc) rc = derive_split6(h, h->l6[d].skip, l.skip, &h->l6[d].ws);
+    }
+    if (rc) {   // the composed weights stay
+        for (size_t i = keep; i < h->l6_allocs.size(); ++i) (void)hipFree(h->l6_allocs[i]);
+        h->l6_allocs.resize(keep);
+        h->l6[0].wb = h->l6[0].ws = h->l6[1].wb = h->l6[1].ws = nullptr;
+        return rc;
+    }
+    h->l6_split = true;
+    return 0;
+}
+
 // ---- packed-weight cache --------------------------------------------------------------------------
 // ccvpe_finalize_weights folds BatchNorm, repacks ~60 M parameters into the kernels' layouts and runs the Winograd weight
 // transforms in double precision: seconds per handle.  Its result is a set of device buffers plus plain-data descriptor
@@ -513,6 +566,7 @@ int ccvpe_finalize_weights(ccvpe_handle h) {
     // drop previous device copies (re-finalize after a new load_state_dict)
     release_level6(h);
     h->l6_failed = false;
+    h->l6_split_failed = false;
     for (void* p : h->dev_allocs) (void)hipFree(p);
     h->dev_allocs.clear();
     h->dev_alloc_bytes.clear();
@@ -618,6 +672,7 @@ int ccvpe_load_packed(ccvpe_handle h, const char* path) {
     if (hd.n_allocs == 0 || hd.n_allocs > 100000 || hd.n_relocs > 100000) return bad("implausible buffer / relocation counts");
     release_level6(h);
     h->l6_failed = false;
+    h->l6_split_failed = false;
     for (void* p : h->dev_allocs) (void)hipFree(p);
     h->dev_allocs.clear(); h->dev_alloc_bytes.clear(); h->plans.clear(); h->last_plan = nullptr; h->finalized = false;
     bool ok = true;

@@ -365,6 +365,7 @@ struct Level6Params {
     int K, Kc;                 // floats per input pixel (score pad + descriptor channels, multiple of 4); K rounded up to 32
     int N, Npad;               // conv6.0's output channels (multiple of 4); rows of a weight panel (N rounded up to 128, zero rows)
     int R, bm;                 // rows of a group = level6_rows(B, wm, &bm): B (8 / wm)^2 tiles, zero rows up to the GEMM's tile height bm
+    int groups;                // groups of the GEMM launch: 4 P composed, 36 for a split-form 3x3 layer (Split6Params)
     const float* x;            // NHWC [B, 8, 8, K]
     float* v;                  // [4 P][R][Kc] transformed input
     const float* wc;           // [4 P][Npad][Kc] composed weights in the Winograd domain
@@ -392,6 +393,32 @@ struct Level6ComposeParams {
     float* wc;                 // [4 P][Npad][Kc], rows N .. Npad zero before the launch
 };
 void launch_level6_compose(const Level6ComposeParams& p, hipStream_t s);
+
+// A 3x3 layer (pad 1) on the 16 x 16 level-6 map in split Winograd form F(4x4,3x3), on the same grouped GEMM:
+//   split6_transform   x -> V[36 positions][R rows = tiles of all samples][Kc]          (B^T d B, kernels_wino4.hip's matrices)
+//   level6_gemm        M'[xi] = V[xi] . Wc[xi]^T, 36 groups (split6_gemm_params)
+//   split6_inverse     A^T M' A per (tile, 4 channels) (+ bias, ReLU) -> the layer's output pixels
+struct Split6Params {
+    int B, C, Kc;              // samples; input channels (multiple of 4); C rounded up to 32 (zero channels)
+    int N, Npad;               // output channels (multiple of 4); rows of a weight panel (N rounded up to 128)
+    int R, bm;                 // rows of a position = split6_rows(B, &bm): 16 B tiles, zero rows up to the GEMM's tile height bm
+    const float* x;            // NHWC [B, 16, 16, .]: pixel (b, y, x), channel c at x[((b * 16 + y) * 16 + x) * x_ld + x_coff + c]
+    int x_ld, x_coff;          // (multiples of 4)
+    float* v;                  // [36][R][Kc]
+    const float* wc;           // [36][Npad][Kc]: G g G^T per (output, input) channel, xi = 6 r + q (split6_pack_weights)
+    float* mp;                 // [36][R][N]
+    const float* bias;         // [N], or null: no bias
+    int relu;
+    float* out;                // NHWC, out[((b * 16 + y) * 16 + x) * out_ld + out_coff + n]
+    int out_ld, out_coff;      // (multiples of 4)
+};
+int split6_rows(int B, int* bm_out);
+bool split6_supported(const Split6Params& p);   // sizes only (pointers are not looked at)
+Level6Params split6_gemm_params(const Split6Params& p);
+void launch_split6_transform(const Split6Params& p, hipStream_t s);
+void launch_split6_inverse(const Split6Params& p, hipStream_t s);
+// F(4x4,3x3) filter transform of one (output, input) channel pair in double: u[6 r + q] = (G g G^T)[r][q] (kernels_wino4.hip)
+void conv_wino4_filter(const double g[3][3], double u[36]);
 
 // the angle of the test loops (train_VIGOR.py:307-311) in the fp32 form the post-processing kernels write
 __device__ __forceinline__ float pose_angle_deg(float cs, float sn) {

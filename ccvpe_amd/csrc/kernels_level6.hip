@@ -14,6 +14,8 @@
 // M and the transform matrices are compile-time parameters (Wino<M>): F(4x4,2x2), 25 positions, 1.5625 K N products per output pixel of
 // a class; F(2x2,2x2), 9 positions, 2.25 K N, four times the rows per group and 0.36 of the weight bytes.
 // The weights come from level6_compose (fp64, once per handle): see ensure_level6 (ccvpe_weights.hip).
+// The level's two remaining 3x3 layers, conv6.2 and conv6.0's skip half, run on the same GEMM in split form F(4x4,3x3): split6_transform,
+// level6_gemm over 36 groups, split6_inverse (Split6Params, below the combine kernel).
 #include "igemm_common.h"
 
 namespace ccvpe {
@@ -288,10 +290,157 @@ __global__ __launch_bounds__(64) void level6_combine_kernel(const Level6Params p
         }
 }
 
+// ---- a 3x3 layer on the 16 x 16 map in split form (Split6Params) ---------------------------------------------------------------------
+// F(4x4,3x3), points 0, +-1, +-2, inf: the B^T and A^T of kernels_wino4.hip (w4_bt, w4_at), so conv_wino4_filter's G g G^T are its
+// weights.  tests/split_wino_ref.py restates the three matrices; tests/test_level6_split_cpu.py checks them.
+struct Wino43 {
+    static __host__ __device__ constexpr float bt(int u, int i) {
+        constexpr float t[6][6] = {{4, 0, -5, 0, 1, 0}, {0, -4, -4, 1, 1, 0}, {0, 4, -4, -1, 1, 0}, {0, -2, -1, 2, 1, 0}, {0, 2, -1, -2, 1, 0}, {0, 4, 0, -5, 0, 1}};
+        return t[u][i];
+    }
+    static __host__ __device__ constexpr float at(int i, int u) {
+        constexpr float t[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
+        return t[i][u];
+    }
+};
+
+// The tile height of the 36-group launches: at least eight row blocks per position where the rows allow it.  With 128-row tiles batch 32
+// is 720 workgroups, 2.8 per CU at two resident: 87 TFLOP/s against 104 - 108 with 64-row tiles (1440); at batch 8 and 16 the 32-row
+// tiles measured fastest (profiles/level6_split_trace_b32_fp32.md).  The composed launch keeps level6_rows.
+int split6_rows(int B, int* bm_out) {
+    const int rows = 16 * B;
+    const int bm = rows >= 1024 ? 128 : rows >= 512 ? 64 : 32;
+    if (bm_out) *bm_out = bm;
+    return (rows + bm - 1) / bm * bm;
+}
+
+// One thread = 4 channels of one tile (row = 16 b + 4 ty + tx; threads run over (row, channel quad), quads fastest).  The tile's 6 x 6
+// window starts at pixel (4 ty - 1, 4 tx - 1); pixels outside the map are zeros (pad 1).  Rows past the last tile and channels C .. Kc
+// are written as zeros: the GEMM reads them unguarded.
+__global__ __launch_bounds__(128) void split6_transform_kernel(const Split6Params p) {
+    using W = Wino43;
+    const int k4n = p.Kc >> 2;
+    const int idx = blockIdx.x * 128 + threadIdx.x;
+    if (idx >= p.R * k4n) return;
+    const int row = idx / k4n, k = (idx - row * k4n) * 4;
+    const int b = row >> 4, t = row & 15;
+    const int y0 = 4 * (t >> 2) - 1, x0 = 4 * (t & 3) - 1;
+    const bool live = b < p.B && k < p.C;
+    f32x4 d[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int y = y0 + i, x = x0 + j;
+            d[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (live && (unsigned)y < 16u && (unsigned)x < 16u)
+                d[i][j] = *reinterpret_cast<const f32x4*>(p.x + ((size_t)(b * 16 + y) * 16 + x) * p.x_ld + p.x_coff + k);
+        }
+    f32x4 c[6][6];   // B^T d
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+                if (W::bt(u, i) != 0.f) s += W::bt(u, i) * d[i][j];
+            c[u][j] = s;
+        }
+    float* dst = p.v + (size_t)row * p.Kc + k;
+    const size_t gstride = (size_t)p.R * p.Kc;
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+        for (int v = 0; v < 6; ++v) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                if (W::bt(v, j) != 0.f) s += W::bt(v, j) * c[u][j];
+            *reinterpret_cast<f32x4*>(dst + (size_t)(u * 6 + v) * gstride) = s;
+            // two wait states behind every 16-byte store, as in level6_transform_kernel
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_nop 1");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+}
+
+// One thread = 4 output channels of one tile: Y = A^T M' A, then per output pixel (4 ty + i, 4 tx + j): + bias, ReLU, one 16-byte store.
+// The same order for every pixel, no atomics: the same bits in every run.
+__global__ __launch_bounds__(64) void split6_inverse_kernel(const Split6Params p) {
+    using W = Wino43;
+    const int n4n = p.N >> 2;
+    const int idx = blockIdx.x * 64 + threadIdx.x;
+    if (idx >= 16 * p.B * n4n) return;
+    const int row = idx / n4n, n = (idx - row * n4n) * 4;
+    const int b = row >> 4, t = row & 15, ty = t >> 2, tx = t & 3;
+    const float* src = p.mp + (size_t)row * p.N + n;
+    const size_t gstride = (size_t)p.R * p.N;
+    f32x4 m[6][6];
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+        for (int v = 0; v < 6; ++v) m[u][v] = *reinterpret_cast<const f32x4*>(src + (size_t)(u * 6 + v) * gstride);
+    f32x4 c[4][6];   // A^T M'
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int v = 0; v < 6; ++v) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+                if (W::at(i, u) != 0.f) s += W::at(i, u) * m[u][v];
+            c[i][v] = s;
+        }
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + n);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int v = 0; v < 6; ++v)
+                if (W::at(j, v) != 0.f) s += W::at(j, v) * c[i][v];
+            s += bias;
+            if (p.relu) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) s[q] = fmaxf(s[q], 0.f);
+            }
+            *reinterpret_cast<f32x4*>(p.out + ((size_t)(b * 16 + 4 * ty + i) * 16 + 4 * tx + j) * p.out_ld + p.out_coff + n) = s;
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_nop 1");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+}
+
+bool split6_supported(const Split6Params& p) {
+    int bm = 0;
+    return p.B > 0 && p.B <= (1 << 20) && p.C > 0 && p.C % 4 == 0 && p.Kc % BK == 0 && p.Kc >= p.C && p.N > 0 && p.N % 4 == 0 && p.Npad % 128 == 0 &&
+           p.Npad >= p.N && p.R == split6_rows(p.B, &bm) && p.bm == bm && p.x_ld % 4 == 0 && p.x_coff % 4 == 0 && p.x_coff + p.C <= p.x_ld &&
+           p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && p.out_coff + p.N <= p.out_ld && (long long)p.R * (p.Kc / 4) < (1ll << 31) &&
+           (long long)36 * (p.R / p.bm) * (p.Npad / 128) < (1ll << 31);
+}
+
+Level6Params split6_gemm_params(const Split6Params& p) {
+    Level6Params q{};
+    q.wm = 4; q.B = p.B; q.K = p.C; q.Kc = p.Kc; q.N = p.N; q.Npad = p.Npad; q.R = p.R; q.bm = p.bm; q.groups = 36;
+    q.v = p.v; q.wc = p.wc; q.mp = p.mp;
+    return q;
+}
+
+void launch_split6_transform(const Split6Params& p, hipStream_t s) {
+    CCVPE_LAUNCH(split6_transform_kernel, dim3((unsigned)((p.R * (p.Kc / 4) + 127) / 128)), dim3(128), 0, s, p);
+}
+
+void launch_split6_inverse(const Split6Params& p, hipStream_t s) {
+    CCVPE_LAUNCH(split6_inverse_kernel, dim3((unsigned)((16 * p.B * (p.N / 4) + 63) / 64)), dim3(64), 0, s, p);
+}
+
 // ---- launchers --------------------------------------------------------------------------------------------------------------------
 bool level6_supported(const Level6Params& p) {
     int bm = 0;
-    return (p.wm == 4 || p.wm == 2) && p.B > 0 && p.K > 0 && p.K % 4 == 0 && p.Kc % BK == 0 && p.Kc >= p.K && p.N > 0 && p.N % 4 == 0 &&
+    return (p.wm == 4 || p.wm == 2) && p.groups == 4 * level6_positions(p.wm) && p.B > 0 && p.K > 0 && p.K % 4 == 0 && p.Kc % BK == 0 && p.Kc >= p.K && p.N > 0 && p.N % 4 == 0 &&
            p.Npad % 128 == 0 && p.Npad >= p.N && p.R == level6_rows(p.B, p.wm, &bm) && p.bm == bm;
 }
 
@@ -307,7 +456,7 @@ static void launch_gemm_t(const Level6Params& p, hipStream_t s) {
     static LdsAttr attr;
     auto kern = level6_gemm_kernel<BM, WGM, WGN>;
     ensure_dynamic_lds(attr, reinterpret_cast<const void*>(kern), lds);
-    const int blocks = 4 * level6_positions(p.wm) * (p.R / BM) * (p.Npad / 128);
+    const int blocks = p.groups * (p.R / BM) * (p.Npad / 128);
     CCVPE_LAUNCH(kern, dim3(blocks), dim3(256), lds, s, p);
 }
 void launch_level6_gemm(const Level6Params& p, hipStream_t s) {

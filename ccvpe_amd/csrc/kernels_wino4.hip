@@ -443,28 +443,32 @@ bool conv_wino4_supported(const ConvParams& p) {
 // Host-side weight transform: U = G g G^T (6 x 6) per (cout, cin) in double precision, stored as the B-fragment layout
 //   [k-step = cin/4][xi/4][n16][lane = (cin%4)*16 + cout%16][xi%4]       (1024 B per (k-step, quad, n16 slice))
 // with K padded to a multiple of 16 channels (zero weights).  `get(n, tap, c)` returns the 3x3 weight (tap = ky*3 + kx).
-size_t conv_wino4_pack(int N, int cin, const std::function<float(int, int, int)>& get, std::vector<float>& out) {
+void conv_wino4_filter(const double g[3][3], double u[36]) {
     static const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
+    double tmp[6][3];
+    for (int r = 0; r < 6; ++r)
+        for (int j = 0; j < 3; ++j) tmp[r][j] = G[r][0] * g[0][j] + G[r][1] * g[1][j] + G[r][2] * g[2][j];
+    for (int r = 0; r < 6; ++r)
+        for (int q = 0; q < 6; ++q) u[r * 6 + q] = tmp[r][0] * G[q][0] + tmp[r][1] * G[q][1] + tmp[r][2] * G[q][2];
+}
+
+size_t conv_wino4_pack(int N, int cin, const std::function<float(int, int, int)>& get, std::vector<float>& out) {
     const int n16 = (N + 15) / 16;
     const int ksteps = ((cin + 15) / 16) * 4;
     out.assign((size_t)ksteps * 9 * n16 * 256, 0.f);
     auto work = [&](int n_lo, int n_hi) {
         for (int n = n_lo; n < n_hi; ++n)
             for (int c = 0; c < cin; ++c) {
-                double g[3][3], tmp[6][3];
+                double g[3][3], u[36];
                 for (int i = 0; i < 3; ++i)
                     for (int j = 0; j < 3; ++j) g[i][j] = (double)get(n, i * 3 + j, c);
-                for (int r = 0; r < 6; ++r)
-                    for (int j = 0; j < 3; ++j) tmp[r][j] = G[r][0] * g[0][j] + G[r][1] * g[1][j] + G[r][2] * g[2][j];
+                conv_wino4_filter(g, u);
                 const int ks = c / 4, k = c % 4;
-                for (int r = 0; r < 6; ++r)
-                    for (int q = 0; q < 6; ++q) {
-                        const double uv = tmp[r][0] * G[q][0] + tmp[r][1] * G[q][1] + tmp[r][2] * G[q][2];
-                        const int xi = r * 6 + q;
-                        const size_t idx = ((((size_t)ks * 9 + xi / 4) * n16 + n / 16) * 64 + k * 16 + (n % 16)) * 4 + (xi & 3);
-                        out[idx] = (float)uv;
-                    }
+                for (int xi = 0; xi < 36; ++xi) {
+                    const size_t idx = ((((size_t)ks * 9 + xi / 4) * n16 + n / 16) * 64 + k * 16 + (n % 16)) * 4 + (xi & 3);
+                    out[idx] = (float)u[xi];
+                }
             }
     };
     const int nthreads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
