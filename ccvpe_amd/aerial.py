@@ -788,3 +788,119 @@ class AffineTracker:
         rows, summary, heading, self.belief = _update(model, grd, sat, cache, tile_index, prior, table, summary_radius, heading_bins)
         self.hist = heading[1] if filt else None
         return _step_result(model, rows, summary, heading, self.belief, credible_levels)
+
+
+# ---- joint position-heading filter --------------------------------------------------------------------------------
+
+# the 5 columns of model.track_joint_update_logits' rows, in order (include/ccvpe.h): the marginal's first argmax cell, the marginal
+# there, the first argmax heading bin at that cell, the largest logit, the normaliser Z
+JOINT_FIELDS = ("index", "prob", "heading_bin", "logit_max", "norm")
+
+
+def heading_emission(kappa, bins: int, none=None) -> np.ndarray:
+    """The emission table of model.track_joint_update_logits from the concentration of the orientation field's error: float32
+    [bins+1] (kappa a number) or [B, bins+1] (kappa [B]).  Entry j < bins is the von Mises kernel exp(kappa cos(j w)), w = 360 / bins,
+    on the bin offsets, normalised to sum 1 over the bins (float64, rounded once): the weight of a heading j bins ahead of the bin of
+    the cell's own orientation, symmetric on the circle.  The last entry, the weight of any heading at a cell without an
+    orientation, is `none` or by default 1 / bins - what a flat kernel gives a bin.  kappa >= 0 is about 1 / sigma^2 in radians;
+    kappa = 0 is the uniform table."""
+    bins = int(bins)
+    if not 4 <= bins <= 72:
+        raise ValueError(f"bins must be in 4..72, got {bins}")
+    scalar = np.ndim(kappa) == 0
+    kap = np.asarray(kappa, dtype=np.float64).reshape(-1, 1)
+    if not (np.isfinite(kap).all() and (kap >= 0).all()):
+        raise ValueError("kappa must be finite and >= 0")
+    last = 1.0 / bins if none is None else float(none)
+    if not (np.isfinite(last) and last >= 0.0):
+        raise ValueError(f"none must be finite and >= 0, got {none}")
+    off = np.arange(bins, dtype=np.float64) * (2.0 * np.pi / bins)
+    body = np.exp(kap * (np.cos(off)[None, :] - 1.0))              # (the common factor exp(-kappa) cancels: no overflow)
+    body /= body.sum(axis=1, keepdims=True)
+    out = np.concatenate([body, np.full((body.shape[0], 1), last)], axis=1).astype(np.float32)
+    return out[0] if scalar else out
+
+
+def joint_shift_table(forward_px, left_px, bins: int, zero_deg: float = 0.0, clockwise: bool = False, common_px=None) -> np.ndarray:
+    """The shift table of model.track_joint_predict from a body-frame motion: float64 [B, bins, 2] = (dx, dy) in image pixels (x right,
+    y down) for a vehicle whose heading is the centre of each bin (heading_bin_centres) and which moved forward_px ahead and left_px
+    to its left (numbers or [B], output pixels).  A heading label a stands for the image direction at zero_deg + a degrees, or
+    zero_deg - a with clockwise, measured counter-clockwise on the screen from the x axis (90 = up): the orientation labels of
+    kitti_ground_truth are (zero_deg=0, clockwise=False) - 90 is up on the heading-up tile -, those of oxford_ground_truth
+    (zero_deg=90, clockwise=True) - 0 is north, which is up.  common_px ([2] or [B,2]) is added to every bin: the shift a window
+    change causes (oxford_track_shift with the motion left out)."""
+    centres = heading_bin_centres(bins)
+    if int(bins) > 72:
+        raise ValueError(f"bins must be in 4..72, got {bins}")
+    fw = np.asarray(forward_px, dtype=np.float64).reshape(-1)
+    lf = np.asarray(left_px, dtype=np.float64).reshape(-1)
+    cm = np.zeros((1, 2)) if common_px is None else np.asarray(common_px, dtype=np.float64).reshape(-1, 2)
+    B = max(fw.shape[0], lf.shape[0], cm.shape[0])
+    for what, v in (("forward_px", fw), ("left_px", lf), ("common_px", cm)):
+        if v.shape[0] not in (1, B):
+            raise ValueError(f"{what} must hold 1 or {B} rows, got {v.shape[0]}")
+        if not np.isfinite(v).all():
+            raise ValueError(f"{what} must be finite")
+    if not np.isfinite(zero_deg):
+        raise ValueError("zero_deg must be finite")
+    phi = np.radians(float(zero_deg) + (-centres if clockwise else centres))       # the image direction of every bin centre
+    ahead = np.stack([np.cos(phi), -np.sin(phi)], axis=1)                           # (x right, y down)
+    left = np.stack([-np.sin(phi), -np.cos(phi)], axis=1)                           # 90 degrees counter-clockwise of it on the screen
+    return fw[:, None, None] * ahead[None] + lf[:, None, None] * left[None] + cm[:, None, :] + np.zeros((B, 1, 1))
+
+
+class JointTracker:
+    """A histogram filter over (heading bin, cell), host side: holds the joint posterior of the last frame (a device tensor
+    [B,nb,512,512]) and, for windows that move, the window origins it lives in.  step() = the forward, model.track_joint_predict
+    (every heading bin moved by the body-frame odometry as that heading sees it, the bins turned, both blurred, floored) and
+    model.track_joint_update_logits; the first step has no prior."""
+
+    def __init__(self):
+        self.joint = None     # joint posterior of the last frame, or None before the first step
+        self.origin = None    # [B,2] int64 window origin (x0, y0) of each query's maps, or None without origins
+
+    def reset(self) -> None:
+        self.joint = None
+        self.origin = None
+
+    def step(self, model, grd, emission, forward_px, left_px, turn_deg, taps, heading_taps, floor, cache=None, tile_index=None, sat=None,
+             origins=None, zero_deg: float = 0.0, clockwise: bool = False, summary_radius=None, credible_levels=None):
+        """One frame of B parallel streams.  The aerial side is cache / tile_index (model.forward_cached) or sat (model.forward).
+        emission [nb+1] or [B,nb+1]: heading_emission; forward_px, left_px (numbers or [B], output pixels) and turn_deg (a number or
+        [B], the change of the heading label): the body-frame motion since the last step, ignored by the first; zero_deg, clockwise:
+        what the dataset's heading labels mean on the image (joint_shift_table); taps, heading_taps, floor: as
+        model.track_joint_predict.  origins [T,2]: the crop origin of every cached tile as in Tracker.step, for windows that move
+        (Oxford); None: every frame shares one grid.  Returns (rows [B,5], marginal [B,512,512], hist [B,nb]); with summary_radius
+        model.belief_summary of the marginal is appended, with credible_levels model.belief_credible of it."""
+        if (sat is None) == (cache is None):
+            raise ValueError("give this frame's aerial side as sat or as cache, one of the two")
+        if sat is not None and tile_index is not None:
+            raise ValueError("tile_index belongs to a cache")
+        B = grd.shape[0]
+        nb = int(np.shape(emission)[-1]) - 1
+        now = None
+        if origins is not None:
+            org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+            now = org if tile_index is None else org[np.asarray(tile_index, dtype=np.int64)]
+            if now.shape[0] != B:
+                raise ValueError(f"origins must name one window per query: {B} expected, got {now.shape[0]}")
+        out = model.forward(grd, sat) if cache is None else model.forward_cached(grd, cache, tile_index=tile_index)
+        logits, ori = out[0], out[2]
+        prior = None
+        if self.joint is not None:
+            if tuple(self.joint.shape[:2]) != (B, nb):
+                raise ValueError(f"the tracker holds a joint of shape {tuple(self.joint.shape[:2])}, this step has {B} streams of {nb} bins")
+            if (now is None) != (self.origin is None):
+                raise ValueError("origins must be given on every step of a stream or on none")
+            common = None if now is None else oxford_track_shift(self.origin, now, np.zeros(2))
+            table = joint_shift_table(forward_px, left_px, nb, zero_deg, clockwise, common)
+            prior = model.track_joint_predict(self.joint, np.broadcast_to(table, (B, nb, 2)), taps, floor, turn_deg, heading_taps)
+        # in place: the prior is this step's alone
+        rows, self.joint, marginal, hist = model.track_joint_update_logits(logits, ori, emission, prior, out=prior)
+        self.origin = None if now is None else now.copy()
+        res = (rows, marginal, hist)
+        if summary_radius is not None:
+            res += (model.belief_summary(marginal, summary_radius),)
+        if credible_levels is not None:
+            res += (model.belief_credible(marginal, credible_levels),)
+        return res

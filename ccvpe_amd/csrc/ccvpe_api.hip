@@ -154,7 +154,7 @@ int ccvpe_destroy(ccvpe_handle h) {
     for (void* p : h->dev_allocs) (void)hipFree(p);
     release_level6(h);
     if (h->arena) (void)hipFree(h->arena);
-    for (auto* buf : {&h->post_scratch, &h->topk_scratch, &h->prior_scratch}) if (buf->ptr) (void)hipFree(buf->ptr);
+    for (auto* buf : {&h->post_scratch, &h->topk_scratch, &h->prior_scratch, &h->joint_scratch}) if (buf->ptr) (void)hipFree(buf->ptr);
     h->plans.clear();
     for (int k = 0; k < 2; ++k) if (h->snap[k]) (void)hipFree(h->snap[k]);
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
@@ -1464,6 +1464,84 @@ int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int3
     p.B = batch; p.nb = nb;
     launch_heading_predict(p, (hipStream_t)stream);
     return launch_status("heading_predict launch");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Joint position-heading filter: a histogram filter over (heading bin, cell), kernels_track_joint.hip.  Predict: two
+// launches on the caller's stream that hand over through the caller's `work`; nothing of the handle but its device.  Update: four
+// launches over forward outputs the caller holds, through the handle's joint scratch.  No plan, no tuning entry.
+// ------------------------------------------------------------------------------------------------
+static int check_joint_shape(int32_t batch, int32_t nb) {
+    if (nb < JOINT_MIN_BINS || nb > JOINT_MAX_BINS) return ccvpe_fail(CCVPE_EINVAL, "nb must be in %d .. %d, got %d", JOINT_MIN_BINS, JOINT_MAX_BINS, nb);
+    if (batch <= 0 || (int64_t)batch * nb > JOINT_MAX_SLICES)
+        return ccvpe_fail(CCVPE_EINVAL, "batch must be >= 1 with batch * nb <= %d, got batch %d, nb %d", JOINT_MAX_SLICES, batch, nb);
+    return 0;
+}
+
+size_t ccvpe_track_joint_work_bytes(int32_t batch, int32_t nb) {
+    return batch > 0 && nb >= JOINT_MIN_BINS && nb <= JOINT_MAX_BINS && (int64_t)batch * nb <= JOINT_MAX_SLICES ? track_joint_work_bytes(batch, nb) : 0;
+}
+
+int ccvpe_track_joint_predict(ccvpe_handle h, const float* joint, int32_t batch, int32_t nb, const float* shift, const float* taps,
+                              int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps, int32_t htaps_stride,
+                              int32_t hradius, const float* floor, void* work, float* prior, void* stream) {
+    if (int rc = check_predict_ptrs(joint, "joint", shift, "shift", taps, floor, prior, "prior")) return rc;
+    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+    if (!htaps) return ccvpe_fail(CCVPE_EINVAL, "null htaps");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if (hradius < 0 || hradius > TRACK_MAX_R || 2 * hradius + 1 > nb)
+        return ccvpe_fail(CCVPE_EINVAL, "hradius must be in 0 .. %d with 2 hradius + 1 <= nb = %d, got %d", TRACK_MAX_R, nb, hradius);
+    if (htaps_stride != 0 && htaps_stride != hradius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "htaps_stride must be 0 (one set of taps) or hradius + 1 = %d (one per query), got %d", hradius + 1,
+                          htaps_stride);
+    if (prior == joint || (const void*)prior == work || (const void*)joint == work)
+        return ccvpe_fail(CCVPE_EINVAL, "joint, work and prior must not alias each other");
+    if (((uintptr_t)joint | (uintptr_t)work | (uintptr_t)prior) & 15) return ccvpe_fail(CCVPE_EINVAL, "joint, work and prior must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackJointPredictParams p{};
+    p.joint = joint; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.turn_deg = turn_deg; p.htaps = htaps;
+    p.htaps_stride = htaps_stride; p.hradius = hradius; p.floor = floor; p.work = (float*)work; p.prior = prior; p.B = batch; p.nb = nb;
+    launch_track_joint_predict(p, (hipStream_t)stream);
+    return launch_status("track_joint_predict launch");
+}
+
+int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* prior,
+                                    const float* emission, int32_t emission_stride, int32_t nb, float* rows, float* joint_out,
+                                    float* marginal, float* hist, void* stream) {
+    if (!logits) return ccvpe_fail(CCVPE_EINVAL, "null logits");
+    if (!ori) return ccvpe_fail(CCVPE_EINVAL, "null ori");
+    if (!emission) return ccvpe_fail(CCVPE_EINVAL, "null emission");
+    if (!rows) return ccvpe_fail(CCVPE_EINVAL, "null rows");
+    if (!joint_out) return ccvpe_fail(CCVPE_EINVAL, "null joint_out");
+    if (!marginal) return ccvpe_fail(CCVPE_EINVAL, "null marginal");
+    if (!hist) return ccvpe_fail(CCVPE_EINVAL, "null hist");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (emission_stride != 0 && emission_stride != nb + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "emission_stride must be 0 (one table) or nb + 1 = %d (one per query), got %d", nb + 1, emission_stride);
+    const void* in[] = {logits, ori, emission};
+    const void* out[] = {rows, joint_out, marginal, hist};
+    for (const void* o : out) {
+        for (const void* q : in)
+            if (o == q) return ccvpe_fail(CCVPE_EINVAL, "rows, joint_out, marginal and hist must not alias logits, ori or emission");
+        if (o != joint_out && o == prior) return ccvpe_fail(CCVPE_EINVAL, "rows, marginal and hist must not alias prior");
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (out[i] == out[j]) return ccvpe_fail(CCVPE_EINVAL, "rows, joint_out, marginal and hist must not alias each other");
+    if (((uintptr_t)logits | (uintptr_t)ori | (uintptr_t)prior | (uintptr_t)joint_out | (uintptr_t)marginal) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "logits, ori, prior, joint_out and marginal must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (int rc = ensure_scratch(h->joint_scratch, batch, track_joint_scratch_bytes, "joint filter scratch")) return rc;
+    TrackJointUpdateParams p{};
+    p.logits = logits; p.ori = ori; p.prior = prior; p.emission = emission; p.emission_stride = emission_stride; p.rows = rows;
+    p.joint_out = joint_out; p.marginal = marginal; p.hist = hist; p.B = batch; p.nb = nb;
+    track_joint_scratch(h->joint_scratch.ptr, h->joint_scratch.batch, p);
+    launch_track_joint_update(p, (hipStream_t)stream);
+    return launch_status("track_joint_update_logits launch");
 }
 
 // ------------------------------------------------------------------------------------------------

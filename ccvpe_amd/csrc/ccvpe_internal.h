@@ -649,7 +649,7 @@ struct ccvpe_handle_s {
     int tuned_plans = 0;          // plans this handle has (partly) tuned by measurement (ccvpe_tuning_generation)
     float* arena = nullptr;
     size_t arena_floats = 0;
-    // Growable scratch of the three post-processing families (ensure_scratch, ccvpe_api.hip).  One buffer each: the families may be in
+    // Growable scratch of the four post-processing families (ensure_scratch, ccvpe_api.hip).  One buffer each: the families may be in
     // flight on different streams of one handle at once, and every buffer carries its own ticket counters.
     struct Scratch { void* ptr = nullptr; int batch = 0; };
     Scratch post_scratch;         // launch_postprocess: partial pairs and ticket counters
@@ -657,6 +657,7 @@ struct ccvpe_handle_s {
     Scratch prior_scratch;        // ccvpe_postprocess_prior, ccvpe_track_update_logits, ccvpe_postprocess_summary, ccvpe_belief_summary: the
                                   // top-K scratch plus softmax partials plus the summary's float64 hand-off plus, for ccvpe_postprocess_heading,
                                   // the heading sums' hand-off and the queries' fixed-point histograms
+    Scratch joint_scratch;        // ccvpe_track_joint_update_logits: softmax partials and the chunks' hand-offs (track_joint_scratch_bytes)
     // profiling rows of the last ccvpe_profile_forward
     struct Row { std::string name; float ms; double flops, bytes, issued; };
     std::vector<Row> prof;

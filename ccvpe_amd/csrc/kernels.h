@@ -838,6 +838,53 @@ struct HeadingPredictParams {
 };
 void launch_heading_predict(const HeadingPredictParams& p, hipStream_t s);
 
+// Joint position-heading filter (ccvpe_track_joint_*, DESIGN.md 4.26, kernels_track_joint.hip): the state is one [512][512] map per
+// heading bin of DESIGN.md 4.13, joint [B][nb][512*512], linear and non-negative.  Predict: launch_track_predict's c of every slice
+// under its own shift into `work` - grid (256 tiles, B * nb) - then per cell the turn and the blur on the circle of bins, plus the
+// floor - grid (1024 groups of 256 cells, B).  Two launches.
+static constexpr int JOINT_MIN_BINS = HEADING_MIN_BINS, JOINT_MAX_BINS = 72, JOINT_MAX_SLICES = 32768, JOINT_COLS = 5;
+struct TrackJointPredictParams {
+    const float* joint;        // [B][nb][512*512]
+    const float* shift;        // [B][nb][2] = (dx, dy) in output pixels of every SOURCE bin
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* turn_deg;     // [B]
+    const float* htaps;        // [hradius + 1] one-sided weights on the circle, one set (htaps_stride 0) or one per query (hradius + 1)
+    int htaps_stride;
+    int hradius;               // 0 .. TRACK_MAX_R, 2 hradius + 1 <= nb
+    const float* floor;        // [B] >= 0
+    float* work;               // track_joint_work_bytes(B, nb) bytes, written before it is read: any contents
+    float* prior;              // [B][nb][512*512], not aliasing joint or work
+    int B, nb;
+};
+size_t track_joint_work_bytes(int B, int nb);
+void launch_track_joint_predict(const TrackJointPredictParams& p, hipStream_t s);
+
+// Update: U(k, i) = (__expf(l_i - m) * E(k | i)) * prior(k, i), Z its float64 sum, J' = U * (float)(1 / Z) with the marginal over the
+// bins, the mass per bin and a row per query.  Four launches, grid (64 chunks, B) three times and (B): softmax_partial_kernel for m;
+// the sum (the prior read once, nothing of the joint written); the store (U recomputed, the prior read again, J' written once);
+// the finish.  The hand-offs are launch boundaries; every sum has one order.
+struct TrackJointUpdateParams {
+    const float* logits;       // [B][512*512]
+    const float* ori;          // [B][2][512*512]
+    const float* prior;        // [B][nb][512*512] or null (1 everywhere); may be joint_out
+    const float* emission;     // [nb + 1] non-negative weights, one table (emission_stride 0) or one per query (nb + 1)
+    int emission_stride;
+    float* rows;               // [B][JOINT_COLS]
+    float* joint_out;          // [B][nb][512*512]
+    float* marginal;           // [B][512*512]
+    float* hist;               // [B][nb]
+    float* partial;            // scratch [B][64][2] softmax partials
+    float* pairs;              // scratch [B][64][2] (max, first index) of the marginal per chunk
+    double* zpart;             // scratch [B][64] the chunks' sums of U
+    double* hpart;             // scratch [B][JOINT_MAX_BINS][64] the chunks' sums of J' per bin
+    int B, nb;
+};
+size_t track_joint_scratch_bytes(int B);   // partial, pairs, zpart, hpart of B queries, in TrackJointUpdateParams' order from the back
+void track_joint_scratch(void* scratch, int cap, TrackJointUpdateParams& p);   // ... carved out of a buffer of `cap` queries
+void launch_track_joint_update(const TrackJointUpdateParams& p, hipStream_t s);
+
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call
 size_t postprocess_scratch_bytes(int B);            // partial (max, index) pairs + one ticket counter per sample (the counters zero before the first launch)

@@ -96,6 +96,19 @@ class _Layout(tuple):
         return res, ptrs
 
 
+class _JointResults:
+    """The joint filter's results behind _Layout's interface: its slots, with given[i] - a tensor the caller passed as out= - standing
+    in for slot i instead of a new one (None: a new one)."""
+
+    def __init__(self, slots, given):
+        self.slots, self.given = slots, given
+
+    def alloc(self, B: int, dev):
+        res = [self.given.get(i) if self.given.get(i) is not None else torch.empty((B,) + tail, dtype=dtype, device=dev)
+               for i, (tail, dtype, _) in enumerate(self.slots)]
+        return res, [t.data_ptr() for t in res]
+
+
 class _NineOutputs:
     """forward's results behind _Layout's interface: the nine tensors, handed over as one ccvpe_outputs struct"""
 
@@ -235,7 +248,117 @@ class _Family:
         self.names, self.args, self.own_first = names, args, own_first
 
 
-class _CVMBase(nn.Module):
+class _JointFilter:
+    """The joint position-heading filter's two methods, mixed into _CVMBase: a filter over (heading bin, cell) beside
+    the position forms, with a state layout, results and a work buffer of its own."""
+
+    @staticmethod
+    def _joint_maps(t, what: str, nb: Optional[int] = None, B: Optional[int] = None):
+        """A joint state argument - [B, nb, 512, 512], float32, contiguous, nb in 4..72, B * nb <= 32768 - -> (B, nb); with nb and B
+        given it must have exactly that shape.  Where it lives is checked by the caller."""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what} must be a float32 cuda tensor [B,nb,512,512]")
+        shape = tuple(t.shape)
+        if len(shape) != 4 or shape[0] < 1 or shape[2:] != spec.OUT_HW:
+            raise ValueError(f"{what} must be [B,nb,512,512], got {shape}")
+        if nb is not None and shape[:2] != (B, nb):
+            raise ValueError(f"{what} must be [{B},{nb},512,512], got {shape}")
+        if not 4 <= shape[1] <= 72:
+            raise ValueError(f"{what} must hold nb in 4..72 heading bins, got {shape[1]}")
+        if shape[0] * shape[1] > 32768:
+            raise ValueError(f"{what} holds {shape[0] * shape[1]} maps, at most 32768 per call")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        return shape[0], shape[1]
+
+    def _joint_work(self, dev, nbytes: int) -> torch.Tensor:
+        """the predict's work buffer: one per (device, current stream) - calls on two streams of one model never share one, calls on
+        one stream are ordered by it -, grown to the largest size asked for"""
+        cache = self.__dict__.setdefault("_joint_work_cache", {})
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        buf = cache.get(key)
+        if buf is None or buf.numel() < nbytes:
+            cache.pop(key, None)
+            buf = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return buf
+
+    def track_joint_predict(self, joint: torch.Tensor, shift_px, taps, floor, turn_deg, heading_taps, out: Optional[torch.Tensor] = None
+                            ) -> torch.Tensor:
+        """The predict half of a joint filter step: the prior [B, nb, 512, 512] of the next frame from a joint posterior [B, nb, 512,
+        512] (track_joint_update_logits' joint).  The map of every SOURCE heading bin k is moved by shift_px[b, k] = (dx, dy) output
+        pixels (aerial.joint_shift_table) and blurred with taps as track_predict does; the bins are then turned by turn_deg (a number
+        or [B], positive when the heading angle grows) with linear weights, blurred on the circle with heading_taps ([rh+1] or
+        [B, rh+1], 2 rh + 1 <= nb), and floor (a number or [B], >= 0) is added: linear values, the definition in include/ccvpe.h
+        (ccvpe_track_joint_predict).  Two launches.  out: a [B, nb, 512, 512] tensor to write into, not the joint.  The small
+        arguments may be host data or tensors on the joint's device; the work buffer is kept by the model, one per stream."""
+        self._require_eval()
+        B, nb = self._joint_maps(joint, "joint")
+        tshape, stride, radius, number = self._blur_checks(taps, floor, B)
+        hshape = tuple(heading_taps.shape) if isinstance(heading_taps, (torch.Tensor, np.ndarray)) else np.shape(heading_taps)
+        if len(hshape) not in (1, 2) or hshape[-1] < 1 or (len(hshape) == 2 and hshape[0] != B):
+            raise ValueError(f"heading_taps must be [rh+1] or [{B}, rh+1], got {tuple(hshape)}")
+        rh = int(hshape[-1]) - 1
+        if rh > 32 or 2 * rh + 1 > nb:
+            raise ValueError(f"heading_taps give radius {rh}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
+        if out is not None:
+            self._joint_maps(out, "out", nb, B)
+            if out.data_ptr() == joint.data_ptr():
+                raise ValueError("out must not be the joint")
+        dev = joint.device
+        # shapes and values first (so that they are refused without a device), then the copies
+        sh = self._track_vec(shift_px, "shift_px", (B, nb, 2), dev)
+        tp = self._track_vec(taps, "taps", tshape, dev)
+        ht = self._track_vec(heading_taps, "heading_taps", hshape, dev)
+        tn = self._per_query(turn_deg, np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor), "turn_deg", B, dev)
+        fl = self._per_query(floor, number, "floor", B, dev)
+        if not joint.is_cuda:
+            raise ValueError(f"joint must be a cuda tensor, not a {joint.device.type} tensor")
+        if out is not None and out.device != dev:
+            raise ValueError(f"out is on {out.device}, joint on {dev}")
+        self._ensure_handle(dev)
+        work = self._joint_work(dev, _lib.load().ccvpe_track_joint_work_bytes(B, nb))
+        return self._launch("track_joint_predict", dev, B,
+                            (joint, B, nb, sh, tp, stride, radius, tn, ht, (rh + 1) if len(hshape) == 2 else 0, rh, fl, work),
+                            _JointResults((_slot(nb, *spec.OUT_HW),), {0: out}))
+
+    def track_joint_update_logits(self, logits: torch.Tensor, ori: torch.Tensor, emission, prior: Optional[torch.Tensor] = None,
+                                  out: Optional[torch.Tensor] = None):
+        """The update half of a joint filter step, from forward outputs the caller holds (logits [B, 512*512], ori [B, 2, 512, 512]):
+        (rows [B, 5], joint [B, nb, 512, 512], marginal [B, 512, 512], hist [B, nb]).  emission is [nb+1] or [B, nb+1] non-negative
+        weights (aerial.heading_emission): entry j < nb weighs a heading j bins ahead of the cell's own, entry nb any heading at a
+        cell without one.  prior: track_joint_predict's, or None for the first frame.  joint = logit weight x emission x prior over
+        its float64 sum; marginal its sum over the bins - a belief map for belief_summary and belief_credible -, hist its sum over
+        the cells, rows aerial.JOINT_FIELDS.  A query without a finite posterior gets the row (-1, NaN, -1, m, Z) and zeros.  out: a
+        [B, nb, 512, 512] tensor to write the joint into; it may be the prior (ccvpe_track_joint_update_logits)."""
+        self._require_eval()
+        side = _Held(logits, ori)
+        B = side.check(self)
+        on_device = isinstance(emission, torch.Tensor) and emission.device.type != "cpu"
+        eshape = tuple(emission.shape) if isinstance(emission, (torch.Tensor, np.ndarray)) else np.shape(emission)
+        if len(eshape) not in (1, 2) or (len(eshape) == 2 and eshape[0] != B):
+            raise ValueError(f"emission must be [nb+1] or [{B}, nb+1], got {tuple(eshape)}")
+        nb = int(eshape[-1]) - 1
+        if not 4 <= nb <= 72:
+            raise ValueError(f"emission must hold nb + 1 entries with nb in 4..72, got {eshape[-1]}")
+        if B * nb > 32768:
+            raise ValueError(f"{B} queries of {nb} bins are {B * nb} maps, at most 32768 per call")
+        if not on_device:
+            ev = np.asarray(emission.detach() if isinstance(emission, torch.Tensor) else emission, dtype=np.float64)
+            if not (ev >= 0.0).all():
+                raise ValueError("emission must be non-negative (and not NaN)")
+        for t, what in ((prior, "prior"), (out, "out")):
+            if t is not None:
+                self._joint_maps(t, what, nb, B)
+        dev = logits.device
+        _, (lg, fo) = side.bind(self, "track_joint_update_logits", tuple(t for t in (prior, out) if t is not None))
+        em = self._track_vec(emission, "emission", eshape, dev)
+        return self._launch("track_joint_update_logits", dev, B, (lg, fo, B, prior, em, (nb + 1) if len(eshape) == 2 else 0, nb),
+                            _JointResults((_slot(5), _slot(nb, *spec.OUT_HW), _MAP, _slot(nb)), {1: out}))
+
+
+class _CVMBase(_JointFilter, nn.Module):
     _variant: str = ""
 
     def __init__(self, device, circular_padding: bool = False, ori_noise: Optional[float] = None,

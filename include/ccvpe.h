@@ -716,6 +716,69 @@ int ccvpe_localize_heading_prior_cached_indexed(ccvpe_handle h, const float* grd
 int ccvpe_heading_predict(ccvpe_handle h, const float* hist, int32_t batch, int32_t nb, const float* turn_deg, const float* taps,
                           int32_t taps_stride, int32_t radius, const float* floor, float* out, void* stream);
 
+/* Joint position-heading filter: a histogram filter over (heading bin k, cell i), which drops the approximation above.  The state
+ * `joint` is float32 DEVICE memory [batch][nb][512*512]: one 512 x 512 map per heading bin in the pixel order of every other map,
+ * bin k covering [k w, (k + 1) w) degrees, w = 360 / nb - hist's binning.  Values are linear (not logarithms) and non-negative.
+ * nb in 4..72, batch >= 1, batch * nb <= 32768; every map pointer 16-byte aligned.  One step per frame =
+ * ccvpe_track_joint_predict + ccvpe_track_joint_update_logits.
+ *
+ * Predict.  The motion model is x' = x + shift[heading], heading' = heading + turn, both halves blurred.  All pointers DEVICE:
+ * shift [batch][nb][2] float32 = (dx, dy) in output pixels of every SOURCE heading bin (the kernel knows no angle convention: the
+ * table carries it); taps, taps_stride, radius 0..32: the one-sided xy blur of ccvpe_track_predict; turn_deg [batch] (positive:
+ * the heading angle grows); htaps the one-sided heading blur th[0..hradius], htaps_stride 0 or hradius + 1, hradius 0..32 with
+ * 2 hradius + 1 <= nb; floor [batch] >= 0; work: ccvpe_track_joint_work_bytes(batch, nb) bytes, any contents; prior
+ * [batch][nb][512*512] out, not aliasing joint or work.  Per query
+ *     A(k', .)   = the map c of ccvpe_track_predict for the belief joint[k'], the shift shift[k'] and taps - the same arithmetic
+ *     u          = k - turn_deg / w  (float64),  i0 = floor(u),  f = (float)(u - i0)
+ *     g(k, i)    = (1 - f) A(i0 mod nb, i) + f A((i0 + 1) mod nb, i)         f == 0 weighs the one source bin with exactly 1
+ *     C(k, i)    = sum over j = -hradius..hradius of th[|j|] g((k - j) mod nb, i)
+ *     prior(k,i) = C(k, i) + floor
+ * k is an integer, so i0 - k and f are those of k = 0 for every k, and the kernel takes them there: o = floor(-turn_deg / w),
+ * f = (float)(-turn_deg / w - o).  The linear weights are folded into 2 hradius + 2 merged weights
+ * M[d] = fmaf(f, th[|d - 1|], (1 - f) * th[|d|]), d = -hradius..hradius + 1 (th = 0 outside 0..hradius), and
+ * C(k, i) = the fused multiply-adds M[d] * A((k + o + d) mod nb, i) in ascending d from a zero accumulator.  Every term is
+ * non-negative, so the error is relative: prior is within (4 radius + 2 hradius + 18) * 2^-24 of the exact value on the same
+ * float32 inputs - ccvpe_track_predict's (4 radius + 12), three roundings in a merged weight, 2 hradius + 2 fused multiply-adds
+ * and the floor's add (first order; f as the kernel takes it).  Mass that leaves a map's window is lost; floor stands for it.
+ * Non-finite shifts or turns may give NaN, but no launch reads outside its tensors whatever the inputs hold: the xy pass clamps and
+ * guards as ccvpe_track_predict, the integer part of the turn is clamped to +-2^30 before it is converted and reduced modulo nb.
+ * Two launches on the caller's stream; nothing of the handle but its device.
+ *
+ * Update, on ccvpe_forward's outputs logits [batch][512*512] and ori [batch][2][512*512], read as p(frame | position) and
+ * p(heading | position).  prior [batch][nb][512*512] or NULL (the first frame: 1 everywhere).  emission: a table e of nb + 1
+ * non-negative float32 weights, emission_stride 0 (one table) or nb + 1 (one per query): e[j], j < nb, weighs a heading j bins
+ * ahead of the cell's own bin on the circle, e[nb] any heading at a cell without a valid orientation (valid and bin: the
+ * definition of hist).  Per query
+ *     m        = max l_i,  w_i = __expf(l_i - m)                            the statistics of the softmax above
+ *     E(k | i) = valid(c_i, s_i) ? e[(k - bin_nb(c_i, s_i)) mod nb] : e[nb]
+ *     U(k, i)  = (w_i * E(k | i)) * prior(k, i)                             float32 products, in this order
+ *     Z        = sum over k, i of U                                         float64, fixed order
+ *     J'(k, i) = U(k, i) * (float)(1 / Z)
+ * joint_out [batch][nb][512*512] receives J'; it may be prior (in place).  marginal [batch][512*512] = the sum over k of J'(k, i)
+ * in ascending k, float32: an ordinary belief map, to which ccvpe_belief_summary and ccvpe_belief_credible apply as they stand.
+ * hist [batch][nb] = the sum over i of J'(k, i), a float64 sum in fixed order rounded once.  rows [batch][CCVPE_JOINT_COLS]:
+ *   0 the first argmax cell of marginal, as float   1 marginal there   2 the first argmax bin of J'(., cell)   3 m   4 (float)Z
+ * A query without a finite joint posterior - NaN or +inf in its logits, Z zero or not finite, or a positive Z so small (below
+ * 2^-128) that (float)(1 / Z) is not finite - gets the row (-1, NaN, -1, m, Z)
+ * and all-zero joint_out, marginal and hist, so that with a positive floor the next predict is flat and the stream starts over;
+ * its batch neighbours keep their bits.  No float atomics: the same inputs give the same bits.  Four launches (the statistics,
+ * the sum, the store, the finish); the joint moves through memory three times - prior read twice, J' written once.  The
+ * handle's joint scratch grows with the largest batch seen; update calls on one handle run one at a time.  The predict's `work`
+ * is the caller's: two predict calls in flight at once (two streams) need a work buffer each.
+ * CCVPE_EINVAL, nothing launched, checked before the handle is used: a null pointer (prior of the update excepted), nb, radius,
+ * hradius or the batch out of range, a bad taps_stride, htaps_stride or emission_stride, prior / joint / work of the predict
+ * aliasing each other, an output of the update aliasing an input or another output (joint_out == prior excepted), a map
+ * pointer that is not 16-byte aligned. */
+#define CCVPE_JOINT_COLS 5
+#define CCVPE_JOINT_MAX_BINS 72
+size_t ccvpe_track_joint_work_bytes(int32_t batch, int32_t nb);
+int ccvpe_track_joint_predict(ccvpe_handle h, const float* joint, int32_t batch, int32_t nb, const float* shift, const float* taps,
+                              int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps, int32_t htaps_stride,
+                              int32_t hradius, const float* floor, void* work, float* prior, void* stream);
+int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* prior,
+                                    const float* emission, int32_t emission_stride, int32_t nb, float* rows, float* joint_out,
+                                    float* marginal, float* hist, void* stream);
+
 /* Credible regions: the smallest set of cells holding a share of the posterior (the highest-density region of a histogram
  * posterior).  Per query, over the n = 512 * 512 cells of a float32 map h - ccvpe_belief_credible: the map given; the other forms:
  * the posterior h' of the prior forms, the map ccvpe_track_update* stores (all zero for a query without a finite posterior):
