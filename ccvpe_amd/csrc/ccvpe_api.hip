@@ -1544,6 +1544,55 @@ int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const f
     return launch_status("track_joint_update_logits launch");
 }
 
+// The backward step of the joint filter: five launches of kernels_track_joint.hip's first kernel and
+// kernels_track_joint_smooth.hip on the caller's stream that hand over through the caller's `work` - nothing of the handle but its
+// device, so calls on several streams of one handle do not meet.
+size_t ccvpe_track_joint_smooth_work_bytes(int32_t batch, int32_t nb) {
+    return batch > 0 && nb >= JOINT_MIN_BINS && nb <= JOINT_MAX_BINS && (int64_t)batch * nb <= JOINT_MAX_SLICES ? track_joint_smooth_work_bytes(batch, nb) : 0;
+}
+
+int ccvpe_track_joint_smooth(ccvpe_handle h, const float* joint, const float* smoothed_next, int32_t batch, int32_t nb, const float* shift,
+                             const float* taps, int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps,
+                             int32_t htaps_stride, int32_t hradius, const float* floor, void* work, float* smoothed, float* marginal,
+                             float* hist, float* stats, void* stream) {
+    if (int rc = check_predict_ptrs(joint, "joint", shift, "shift", taps, floor, smoothed, "smoothed")) return rc;
+    if (!smoothed_next) return ccvpe_fail(CCVPE_EINVAL, "null smoothed_next");
+    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+    if (!htaps) return ccvpe_fail(CCVPE_EINVAL, "null htaps");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (!marginal) return ccvpe_fail(CCVPE_EINVAL, "null marginal");
+    if (!hist) return ccvpe_fail(CCVPE_EINVAL, "null hist");
+    if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if (hradius < 0 || hradius > TRACK_MAX_R || 2 * hradius + 1 > nb)
+        return ccvpe_fail(CCVPE_EINVAL, "hradius must be in 0 .. %d with 2 hradius + 1 <= nb = %d, got %d", TRACK_MAX_R, nb, hradius);
+    if (htaps_stride != 0 && htaps_stride != hradius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "htaps_stride must be 0 (one set of taps) or hradius + 1 = %d (one per query), got %d", hradius + 1,
+                          htaps_stride);
+    const void* in[] = {joint, smoothed_next, shift, taps, turn_deg, htaps, floor, work};
+    const void* out[] = {smoothed, marginal, hist, stats};
+    for (const void* o : out)
+        for (const void* q : in)
+            if (o == q && !(o == smoothed && q == smoothed_next))
+                return ccvpe_fail(CCVPE_EINVAL, "smoothed, marginal, hist and stats must not alias an input or work (smoothed == smoothed_next excepted)");
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (out[i] == out[j]) return ccvpe_fail(CCVPE_EINVAL, "smoothed, marginal, hist and stats must not alias each other");
+    if (smoothed_next == joint || (const void*)joint == work || (const void*)smoothed_next == work)
+        return ccvpe_fail(CCVPE_EINVAL, "joint, smoothed_next and work must not alias each other");
+    if (((uintptr_t)joint | (uintptr_t)smoothed_next | (uintptr_t)work | (uintptr_t)smoothed | (uintptr_t)marginal) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "joint, smoothed_next, work, smoothed and marginal must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackJointSmoothParams p{};
+    p.joint = joint; p.next = smoothed_next; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius;
+    p.turn_deg = turn_deg; p.htaps = htaps; p.htaps_stride = htaps_stride; p.hradius = hradius; p.floor = floor; p.work = (float*)work;
+    p.smoothed = smoothed; p.marginal = marginal; p.hist = hist; p.stats = stats; p.B = batch; p.nb = nb;
+    launch_track_joint_smooth(p, (hipStream_t)stream);
+    return launch_status("track_joint_smooth launch");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Credible regions: the radix select of kernels_credible.hip over a stored map (ccvpe_belief_credible, on the prior
 // scratch), behind the logits tail on the prior scratch (ccvpe_postprocess_credible), or as pose.credible behind pose.argmax in

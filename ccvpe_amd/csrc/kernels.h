@@ -885,6 +885,37 @@ size_t track_joint_scratch_bytes(int B);   // partial, pairs, zpart, hpart of B 
 void track_joint_scratch(void* scratch, int cap, TrackJointUpdateParams& p);   // ... carved out of a buffer of `cap` queries
 void launch_track_joint_update(const TrackJointUpdateParams& p, hipStream_t s);
 
+// The first launch of the predict alone: the backward step (kernels_track_joint_smooth.hip) starts with it, so its A is the predict's
+// bits.  p.prior is not used.
+void launch_track_joint_xy(const TrackJointPredictParams& p, hipStream_t s);
+
+// The backward step of the joint filter (ccvpe_track_joint_smooth, DESIGN.md 4.27, kernels_track_joint_smooth.hip): the smoothed joint
+// of frame t from the stored filter joint J, the smoothed joint s' of frame t + 1 and the arguments of the predict that carried J
+// into frame t + 1.  Five launches - launch_track_joint_xy, the ratio (1024 groups, B), the weight (256 tiles, B * nb), the scale
+// (64 chunks, B), the finish (B) - that hand over through `work`: one joint-sized buffer (A, then h over it), then the partial sums.
+struct TrackJointSmoothParams {
+    const float* joint;        // [B][nb][512*512] J
+    const float* next;         // [B][nb][512*512] s'; may be smoothed
+    const float* shift;        // as TrackJointPredictParams, from here ...
+    const float* taps;
+    int taps_stride;
+    int radius;
+    const float* turn_deg;
+    const float* htaps;
+    int htaps_stride;
+    int hradius;
+    const float* floor;        // ... to here
+    float* work;               // track_joint_smooth_work_bytes(B, nb) bytes, written before it is read: any contents
+    float* smoothed;           // [B][nb][512*512]
+    float* marginal;           // [B][512*512]
+    float* hist;               // [B][nb]
+    float* stats;              // [B][JOINT_SMOOTH_COLS] = (index, prob, bin, Z, G)
+    int B, nb;
+};
+static constexpr int JOINT_SMOOTH_COLS = 5;
+size_t track_joint_smooth_work_bytes(int B, int nb);
+void launch_track_joint_smooth(const TrackJointSmoothParams& p, hipStream_t s);
+
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call
 size_t postprocess_scratch_bytes(int B);            // partial (max, index) pairs + one ticket counter per sample (the counters zero before the first launch)

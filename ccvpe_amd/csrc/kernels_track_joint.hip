@@ -116,6 +116,13 @@ void launch_track_joint_predict(const TrackJointPredictParams& p, hipStream_t s)
     CCVPE_LAUNCH(track_joint_mix_kernel, dim3(JOINT_MIX_GROUPS, p.B), dim3(256), mix_lds, s, p);
 }
 
+void launch_track_joint_xy(const TrackJointPredictParams& p, hipStream_t s) {
+    const size_t lds = track_lds_bytes(p.radius);
+    static LdsAttr xy_attr;
+    ensure_dynamic_lds(xy_attr, reinterpret_cast<const void*>(track_joint_xy_kernel), lds);
+    CCVPE_LAUNCH(track_joint_xy_kernel, dim3(TRACK_TILES, p.B * p.nb), dim3(256), lds, s, p);
+}
+
 // ---- update ----------------------------------------------------------------------------------------------------------------------
 
 size_t track_joint_scratch_bytes(int B) {

@@ -20,6 +20,10 @@ Out of scope: the heading belief (hist is not smoothed), pose rows with orientat
 consistent sequence of cells instead of T marginals - is ccvpe_amd.viterbi's, over the same logs: map_path and, for a
 RecordingAffineTracker's, map_path_affine.
 What a stream says about taps, floor and the odometry - the pairwise posterior of every link - is ccvpe_amd.motion's.
+
+Streams of aerial.JointTracker - the filter over (heading bin, cell) - have the same three pieces:
+RecordingJointTracker, smooth_joint_stream and track_joint_smooth (ccvpe_track_joint_smooth), which give p(cell, heading bin | frames
+1..T) with its marginal map, heading histogram and a stats row per frame.
 """
 from __future__ import annotations
 
@@ -31,6 +35,11 @@ from . import _lib, aerial, spec
 # columns of stats: the first index of the largest smoothed cell, the map's value there, Z = sum_i belief_i a_i - the evidence the
 # later frames give this belief, sum s' (about 1) when the belief has mass 1 - and G = sum_i s'_i / prior_i, the future's total weight
 SMOOTH_FIELDS = ("index", "prob", "evidence", "future")
+
+
+# columns of track_joint_smooth's stats: the first argmax cell of the smoothed marginal, the marginal there, the first argmax heading bin
+# of the smoothed joint at that cell, Z and G as above
+JOINT_SMOOTH_FIELDS = ("index", "prob", "bin", "evidence", "future")
 
 
 class _SmoothResults:
@@ -260,3 +269,136 @@ def smooth_stream_affine(model, log, in_place: bool = False):
     matrix.  A link beyond the smoother's reach is refused when its matrix is host data, and is a broken link (the sweep restarts
     behind it) when it is a device tensor."""
     return _sweep(model, log, in_place, lambda *a, **kw: track_smooth_affine(*a, **kw), lambda B: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0], "matrix")
+
+
+# ---- the joint position-heading filter's backward half (DESIGN.md 4.27) ---------------------------------------------------------------
+
+class _JointSmoothResults:
+    """track_joint_smooth's results behind models._Layout's interface: the work buffer as the last pointer before the results (torch's
+    allocator keeps its memory for this stream's launches after the tensor is dropped), then smoothed - `out` when the caller gave one
+    -, marginal, hist and stats."""
+
+    def __init__(self, nb: int, out):
+        self.nb, self.out = nb, out
+
+    def alloc(self, B: int, dev):
+        nb = self.nb
+        work = torch.empty(_lib.load().ccvpe_track_joint_smooth_work_bytes(B, nb), dtype=torch.uint8, device=dev)
+        smoothed = self.out if self.out is not None else torch.empty((B, nb) + spec.OUT_HW, dtype=torch.float32, device=dev)
+        marginal = torch.empty((B,) + spec.OUT_HW, dtype=torch.float32, device=dev)
+        hist = torch.empty((B, nb), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, len(JOINT_SMOOTH_FIELDS)), dtype=torch.float32, device=dev)
+        res = [smoothed, marginal, hist, stats]
+        return res, [work.data_ptr()] + [t.data_ptr() for t in res]
+
+
+def track_joint_smooth(model, joint, smoothed_next, shift_px, taps, floor, turn_deg, heading_taps, out=None):
+    """One backward step of the joint filter: (smoothed [B,nb,512,512], marginal [B,512,512], hist [B,nb], stats [B,5]) of frame t from
+    joint [B,nb,512,512], the filter joint of frame t (track_joint_update_logits' joint), smoothed_next, the smoothed joint of frame
+    t + 1 (for the last frame but one: the last frame's joint), and shift_px, taps, floor, turn_deg, heading_taps, the arguments of
+    the model.track_joint_predict call that carried joint into frame t + 1 - checked as that method checks them and in its order,
+    smoothed_next like joint and directly after it.  stats: JOINT_SMOOTH_FIELDS.  A next joint without a positive value says nothing:
+    smoothed is joint bit for bit and stats (its marginal's argmax, the value, the best bin, NaN, 0); a joint the recursion cannot
+    weigh (all zero, a NaN) gives zeros and (-1, NaN, -1, Z, G).  out: the tensor that receives the smoothed joint (same shape,
+    float32, contiguous, on joint's device), not the joint; out=smoothed_next is the in-place form of a backward sweep, with the bits
+    of the out-of-place call.  Five launches (ccvpe_track_joint_smooth, include/ccvpe.h: the definition, the rules, the error bound);
+    the work buffer - one more joint - is allocated here, per call."""
+    model._require_eval()
+    B, nb = model._joint_maps(joint, "joint")
+    model._joint_maps(smoothed_next, "smoothed_next", nb, B)
+    tshape, stride, radius, number = model._blur_checks(taps, floor, B)
+    hshape = tuple(heading_taps.shape) if isinstance(heading_taps, (torch.Tensor, np.ndarray)) else np.shape(heading_taps)
+    if len(hshape) not in (1, 2) or hshape[-1] < 1 or (len(hshape) == 2 and hshape[0] != B):
+        raise ValueError(f"heading_taps must be [rh+1] or [{B}, rh+1], got {tuple(hshape)}")
+    rh = int(hshape[-1]) - 1
+    if rh > 32 or 2 * rh + 1 > nb:
+        raise ValueError(f"heading_taps give radius {rh}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
+    if out is not None:
+        model._joint_maps(out, "out", nb, B)
+        if out.data_ptr() == joint.data_ptr():
+            raise ValueError("out must not be the joint")
+    if smoothed_next.data_ptr() == joint.data_ptr():
+        raise ValueError("smoothed_next must not be the joint")
+    dev = joint.device
+    sh = model._track_vec(shift_px, "shift_px", (B, nb, 2), dev)
+    tp = model._track_vec(taps, "taps", tshape, dev)
+    ht = model._track_vec(heading_taps, "heading_taps", hshape, dev)
+    tn = model._per_query(turn_deg, np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor), "turn_deg", B, dev)
+    fl = model._per_query(floor, number, "floor", B, dev)
+    if not joint.is_cuda:
+        raise ValueError(f"joint must be a cuda tensor, not a {joint.device.type} tensor")
+    if smoothed_next.device != dev:
+        raise ValueError(f"smoothed_next is on {smoothed_next.device}, joint on {dev}")
+    if out is not None and out.device != dev:
+        raise ValueError(f"out is on {out.device}, joint on {dev}")
+    model._ensure_handle(dev)
+    return model._launch("track_joint_smooth", dev, B,
+                         (joint, smoothed_next, B, nb, sh, tp, stride, radius, tn, ht, (rh + 1) if len(hshape) == 2 else 0, rh, fl),
+                         _JointSmoothResults(nb, out))
+
+
+class RecordingJointTracker(aerial.JointTracker):
+    """aerial.JointTracker that keeps what a backward sweep needs: step() is the parent's - the same arguments, the same returns, the
+    same rows and joints bit for bit - and appends (joint, table, taps, floor, turn_deg, heading_taps) to self.log, one entry per
+    frame: the joint the step stored and the arguments of the model.track_joint_predict call that led into this frame (table, the
+    shift table [B,nb,2] recomputed with the parent's own calls; None for the first frame of a stream, which has no such call).  The
+    joints are the tensors the update returned, not copies: every call into the library allocates its results anew, so nothing writes
+    to them again.  Memory: a stored joint is 1 MB per stream and heading bin, so a log of T frames holds T * B * nb MB on the device
+    (T = 100, B = 1, nb = 36: 3.6 GB).  reset() clears the log."""
+
+    def __init__(self):
+        super().__init__()
+        self.log = []
+
+    def reset(self) -> None:
+        super().reset()
+        self.log = []
+
+    def step(self, model, grd, emission, forward_px, left_px, turn_deg, taps, heading_taps, floor, cache=None, tile_index=None, sat=None,
+             origins=None, zero_deg: float = 0.0, clockwise: bool = False, summary_radius=None, credible_levels=None):
+        had, before = self.joint is not None, self.origin
+        res = super().step(model, grd, emission, forward_px, left_px, turn_deg, taps, heading_taps, floor, cache=cache, tile_index=tile_index,
+                           sat=sat, origins=origins, zero_deg=zero_deg, clockwise=clockwise, summary_radius=summary_radius,
+                           credible_levels=credible_levels)
+        table = None
+        if had:
+            # the table the parent's predict just got, by the parent's own calls (self.origin is this frame's window now)
+            B, nb = self.joint.shape[:2]
+            common = None if self.origin is None else aerial.oxford_track_shift(before, self.origin, np.zeros(2))
+            table = np.broadcast_to(aerial.joint_shift_table(forward_px, left_px, nb, zero_deg, clockwise, common), (B, nb, 2)).copy()
+        self.log.append((self.joint, table, taps, floor, turn_deg, heading_taps))
+        return res
+
+
+def smooth_joint_stream(model, log, in_place: bool = False, keep_joint: bool = False):
+    """The backward sweep over a RecordingJointTracker's log (T entries (joint, table, taps, floor, turn_deg, heading_taps)) ->
+    (marginals [T,B,512,512], hists [T,B,nb], stats [T,B,5] (JOINT_SMOOTH_FIELDS)); with keep_joint a list of the T smoothed joints
+    [B,nb,512,512] is appended (T * B * nb MB more).  marginals[t] = p(cell | frames 1..T), hists[t] = p(heading bin | frames 1..T).
+    The last frame goes through a call with a zero next joint - the rule of a future that says nothing: its own joint, marginal, hist
+    and argmax, NaN, 0.  Frame t takes entry t + 1's motion.  in_place: the sweep runs in one running buffer (out=smoothed_next); the
+    bits are the same.  A zero joint in the log (a frame without a finite posterior) needs no special case here: the rules of
+    track_joint_smooth restart the sweep behind it."""
+    T = len(log)
+    if T == 0:
+        raise ValueError("the log is empty")
+    last = log[-1][0]
+    B, nb = last.shape[:2]
+    run = torch.zeros_like(last)
+    marginals, hists, stats, joints = [None] * T, [None] * T, [None] * T, [None] * T
+    for t in range(T - 1, -1, -1):
+        if t == T - 1:
+            motion = (np.zeros((B, nb, 2)), [1.0], 0.0, 0.0, [1.0])
+        else:
+            motion = log[t + 1][1:]
+            if motion[0] is None:
+                raise ValueError(f"log entry {t + 1} has no shift table: a stream's first frame can only stand first")
+        table, taps, floor, turn_deg, heading_taps = motion
+        if in_place:
+            _, marginals[t], hists[t], stats[t] = track_joint_smooth(model, log[t][0], run, table, taps, floor, turn_deg, heading_taps, out=run)
+            if keep_joint:
+                joints[t] = run.clone()
+        else:
+            run, marginals[t], hists[t], stats[t] = track_joint_smooth(model, log[t][0], run, table, taps, floor, turn_deg, heading_taps)
+            joints[t] = run if keep_joint else None
+    res = (torch.stack(marginals), torch.stack(hists), torch.stack(stats))
+    return res + (joints,) if keep_joint else res

@@ -779,6 +779,52 @@ int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const f
                                     const float* emission, int32_t emission_stride, int32_t nb, float* rows, float* joint_out,
                                     float* marginal, float* hist, void* stream);
 
+/* Smoothing a joint stream: the backward half of the joint filter.  One call per frame, from the last frame back, turns the stored
+ * joints into p(cell, heading bin | frames 1..T).  `joint` J is the stored filter joint of frame t (ccvpe_track_joint_update_logits'
+ * joint_out), `smoothed_next` s' the smoothed joint of frame t + 1 (for the last frame but one: the last frame's own J), both DEVICE
+ * float32 [batch][nb][512*512]; shift, taps, taps_stride, radius, turn_deg, htaps, htaps_stride, hradius, floor: the arguments of the
+ * ccvpe_track_joint_predict call that carried J into frame t + 1, with its ranges.  With P(m; d), o, f and M[d] as above, per query
+ *     A(k')      = P(J[k']; shift[k'])                                   the predict's first launch, unchanged
+ *     prior(k,i) = (fmaf chain of M[d] A((k + o + d) mod nb, i), ascending d) + floor     the bits the predict stores
+ *     g(k,i)     = s'(k,i) > 0 ? s'(k,i) / prior(k,i) : 0                NaN and negative s' are not taken
+ *     G          = sum over k, i of g                                    float64, one fixed order
+ *     h(k',i)    = sum over d = -hradius..hradius+1, ascending, of fmaf(M[d], g((k' - o - d) mod nb, i), h)
+ *     a(k',i)    = fmaf(floor, (float)G, P(h[k']; -shift[k'])_i)
+ *     w(k',i)    = J(k',i) * a(k',i);   Z = float64 sum of w, fixed order
+ *     s(k',i)    = w(k',i) * (float)(1 / Z)
+ * For a J of mass 1 the predict is prior = T J with T((k,x) | (k',x')) = sum over d with (k + o + d) mod nb == k' of
+ * M[d] u_k'(x - x' - shift[k']) + floor, and the recursion is s = J . (T^t g), g = s' / prior.  The adjoint of the circle mix sends
+ * g(k) to every k' = (k + o + d) mod nb with weight M[d] - the line for h, which runs the other way round the circle and covers
+ * 2 hradius + 2 > nb, where two d meet in one bin; the adjoint of P(.; shift[k']) is P(.; -shift[k']) (taps and tent are even) with
+ * each SOURCE bin's own shift; the floor's is floor * G.  Z = sum g prior = sum s' over the taken cells: 1 up to rounding.
+ * Outputs: smoothed [batch][nb][512*512] = s; marginal [batch][512*512] = the sum over k of s(k, i), ascending k, float32; hist
+ * [batch][nb] = the float64 sum over i of s(k, i), rounded once; stats [batch][CCVPE_JOINT_SMOOTH_COLS] = (index, prob, bin,
+ * (float)Z, (float)G): index the first argmax cell of marginal, prob marginal there (its stored bits), bin the first argmax of
+ * s(., index).
+ *   - G == 0 (s' has no positive value - the zero joint of a frame without a finite posterior, the call for the last frame): the
+ *     future says nothing; s is J bit for bit, marginal, hist, index, prob, bin are those of J (a value is taken when it is above
+ *     -inf, NaN never wins, the first index wins ties; no taken value: -1, NaN, -1), Z = NaN, G = 0.
+ *   - else Z not finite, Z <= 0, or positive but without a finite (float)(1 / Z) (a zero J, a NaN in J, floor = 0 and a prior of 0
+ *     under a positive s'): zeros everywhere and (-1, NaN, -1, Z, G).
+ * Queries are independent: a poisoned query changes no bit of its neighbours.  No input value moves a read outside a tensor (the
+ * predict's clamps of the shift and of the turn's integer part).  Every sum has a fixed order and nothing is accumulated atomically:
+ * the same inputs give the same bits, alone as in a batch.  Relative error of smoothed against the exact recursion on the same
+ * float32 inputs: (16 radius + 8 hradius + 78) * 2^-24 to first order, marginal nb more, hist 1 more.
+ * `work`: DEVICE memory of ccvpe_track_joint_smooth_work_bytes(batch, nb) bytes (pure host arithmetic; 0 outside the ranges), 16-byte
+ * aligned, any contents: one joint-sized buffer (A, then h) and the partial sums; nothing in it has to survive a call.  The call
+ * allocates nothing, synchronises nothing and uses no scratch of the handle: calls on several streams of one handle may run at once
+ * when each has its own work and outputs.  `smoothed` may be `smoothed_next`: a backward sweep runs in one buffer, with the bits of
+ * the out-of-place call.  Five launches; the joint moves through memory ten times (2 + 3 + 3 + 2).  CCVPE_EINVAL, nothing launched,
+ * checked before the handle is used: a null pointer, nb, radius, hradius or the batch out of range, a bad taps_stride or
+ * htaps_stride, an output equal to an input, to work or to another output (smoothed == smoothed_next excepted), joint, smoothed_next
+ * and work equal to each other, a map or work that is not 16-byte aligned. */
+#define CCVPE_JOINT_SMOOTH_COLS 5
+size_t ccvpe_track_joint_smooth_work_bytes(int32_t batch, int32_t nb);
+int ccvpe_track_joint_smooth(ccvpe_handle h, const float* joint, const float* smoothed_next, int32_t batch, int32_t nb, const float* shift,
+                             const float* taps, int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps,
+                             int32_t htaps_stride, int32_t hradius, const float* floor, void* work, float* smoothed, float* marginal,
+                             float* hist, float* stats, void* stream);
+
 /* Credible regions: the smallest set of cells holding a share of the posterior (the highest-density region of a histogram
  * posterior).  Per query, over the n = 512 * 512 cells of a float32 map h - ccvpe_belief_credible: the map given; the other forms:
  * the posterior h' of the prior forms, the map ccvpe_track_update* stores (all zero for a query without a finite posterior):
