@@ -183,6 +183,8 @@ SYMBOLS = [
     ("ccvpe_op_conv2d_ex", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ccvpe_op_level1", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("ccvpe_op_deconv_k2s2", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     ("ccvpe_op_pose_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 ]
 
@@ -393,6 +395,26 @@ def op_level1(x_nhwc, wd, bd, wa, ba, wt, bt, score=False, tile=1, max_wg=0):
                              Cout, tile | (max_wg << 8), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
     check(rc, "ccvpe_op_level1")
     return out, rc
+
+
+def op_deconv_k2s2(x_nhwc, w, bias, dst, coff=0, cw=None):
+    """Kernel-level hook: deconv_k2s2_kernel on its own (ccvpe_op_deconv_k2s2).  x [B,H,W,in_ld] cuda fp32 with in_ld >= Cin, w
+    [Cin,Cout,2,2], bias [Cout] or None; the result lands in channels [coff, coff + cw) of dst [B,2H,2W,ld] (cw >= Cout, default Cout:
+    the channels past Cout are written as zeros), nothing else of dst is written.  Returns the taps a workgroup held (4 or 2)."""
+    import torch
+    lib = load()
+    x = x_nhwc.contiguous()
+    B, H, W, in_ld = x.shape
+    w = w.detach().float().contiguous()
+    Cin, Cout = w.shape[0], w.shape[1]
+    b = bias.detach().float().contiguous() if bias is not None else None
+    assert dst.is_cuda and dst.is_contiguous() and dst.dtype == torch.float32 and tuple(dst.shape[:3]) == (B, 2 * H, 2 * W), tuple(dst.shape)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    rc = lib.ccvpe_op_deconv_k2s2(C.c_void_p(x.data_ptr()), B, H, W, Cin, in_ld, C.c_void_p(w.data_ptr()),
+                                  C.c_void_p(b.data_ptr()) if b is not None else None, Cout, C.c_void_p(dst.data_ptr()), dst.shape[3], coff,
+                                  Cout if cw is None else cw, C.c_void_p(stream))
+    check(rc, "ccvpe_op_deconv_k2s2")
+    return rc
 
 
 def op_pose_rows(handle, logits, ori):

@@ -44,6 +44,7 @@ Switches read_switches() {
     if (const char* e = getenv("CCVPE_L1_TILE")) s.l1_tile = std::atoi(e);
     if (const char* e = getenv("CCVPE_COMPOSE_L6")) s.compose_l6 = std::atoi(e);
     if (const char* e = getenv("CCVPE_SPLIT_L6")) s.split_l6 = std::atoi(e);
+    if (const char* e = getenv("CCVPE_DECONV_K2S2")) s.deconv_k2s2 = std::atoi(e);
     if (const char* e = getenv("CCVPE_WINOGRAD")) s.wino = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_GRAPH")) s.graph_mode = std::atoi(e) != 0;
     if (const char* e = getenv("CCVPE_STREAMS")) s.two_streams = std::atoi(e) >= 2;
@@ -1991,6 +1992,46 @@ int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Ci
     if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "level-1 launch failed: %s", hipGetErrorString(e));
     if (e2 != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "level-1 execution failed: %s", hipGetErrorString(e2));
     return level1_tile(lp);
+}
+
+int ccvpe_op_deconv_k2s2(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t in_ld, const float* w, const float* bias, int32_t Cout,
+                         float* out, int32_t ld, int32_t coff, int32_t cw, void* stream) {
+    if (!in || !w || !out) return ccvpe_fail(CCVPE_EINVAL, "null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 8 || Cout <= 0 || cw < Cout || in_ld < Cin)
+        return ccvpe_fail(CCVPE_EINVAL, "bad transposed-conv geometry (Cin a multiple of 8, in_ld >= Cin, cw >= Cout)");
+    std::vector<float> hw((size_t)Cin * Cout * 4), b1(Cout, 0.f), hb(4 * (size_t)cw, 0.f);
+    HIPCHK(hipMemcpy(hw.data(), w, hw.size() * sizeof(float), hipMemcpyDefault));
+    if (bias) HIPCHK(hipMemcpy(b1.data(), bias, Cout * sizeof(float), hipMemcpyDefault));
+    for (int q = 0; q < 4; ++q) std::copy(b1.begin(), b1.end(), hb.begin() + (size_t)q * cw);   // (columns past Cout: zero)
+    // the kernel's form is chosen from the sizes and from which input channels have a weight that is not zero
+    std::vector<unsigned char> live(Cin, 0);
+    for (int c = 0; c < Cin; ++c)
+        for (int i = 0; i < Cout * 4 && !live[c]; ++i) live[c] = hw[(size_t)c * Cout * 4 + i] != 0.f;
+    DeconvK2S2Params kp{};
+    kp.B = B; kp.H = H; kp.W = W; kp.Cin = Cin; kp.in_ld = in_ld; kp.Kpad = round_up(Cin, 32);
+    kp.ld = ld; kp.coff = coff; kp.cw = cw;
+    if (!deconv_k2s2_prepare(kp, live.data()))
+        return ccvpe_fail(CCVPE_EINVAL, "deconv_k2s2_kernel does not take these sizes (cw a multiple of 16 up to 80, in_ld, ld and coff multiples of 4, coff + cw <= ld, "
+                                        "at most 192 live input channels, weights of two taps within the LDS)");
+    ccvpe_handle_s tmp;   // only its dev_allocs list and packer switches are used by the packer
+    tmp.sw = read_switches();
+    PackedConv pc;
+    // ConvTranspose2d weight [Cin][Cout][2][2] -> rows n = (dy*2+dx)*cw + o of a 1x1 GEMM, zero rows past Cout: as build_decoder packs a level
+    int rc = pack_conv(&tmp, pc, 4 * cw, 1, Cin, Cin, identity_map(Cin),
+                       [&](int n, int, int c) { const int q = n / cw, o = n % cw; return o < Cout ? hw[((size_t)c * Cout + o) * 4 + q] : 0.f; }, hb, 1, 1);
+    auto cleanup = [&]() { for (void* p : tmp.dev_allocs) (void)hipFree(p); };
+    if (rc) { cleanup(); return rc; }
+    if (pc.Kpad < Cin || pc.N != 4 * cw) { cleanup(); return ccvpe_fail(CCVPE_ESTATE, "unexpected packed form"); }
+    kp.Kpad = pc.Kpad;
+    kp.x = in; kp.wpk = pc.w; kp.bias = pc.bias; kp.out = out;
+    hipStream_t st = (hipStream_t)stream;
+    launch_deconv_k2s2(kp, st);
+    hipError_t e = hipGetLastError();
+    hipError_t e2 = hipStreamSynchronize(st);
+    cleanup();
+    if (e != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "transposed-conv launch failed: %s", hipGetErrorString(e));
+    if (e2 != hipSuccess) return ccvpe_fail(CCVPE_EHIP, "transposed-conv execution failed: %s", hipGetErrorString(e2));
+    return kp.taps;
 }
 
 }  // extern "C"

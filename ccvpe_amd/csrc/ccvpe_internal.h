@@ -128,6 +128,10 @@ struct Switches {
     // inverse transform) where the composed level 6 runs.  unset = plans of at least LEVEL6_SPLIT_MIN_BATCH samples, 0 = never (the tiled
     // launches and their reductions), 1 = every plan that runs the composed level 6; 2 / 3 = as 1, conv6.2 only / the skip half only
     std::optional<int> split_l6;
+    // CCVPE_DECONV_K2S2: the decoder's transposed convs on deconv_k2s2_kernel (kernels_deconv.hip).  unset = fp32 plans of
+    // at least DECONV_K2S2_MIN_BATCH samples on level 2, DECONV_K2S2_MIN_BATCH_L3 on level 3; 0 = never (the tiled launches); 1 = every fp32 plan, on
+    // every level whose shapes the kernel takes
+    std::optional<int> deconv_k2s2;
     // CCVPE_WINOGRAD=0 keeps the decoder 3x3 layers on the implicit GEMM.  The Winograd kernels serve fp32 plans only: bf16x3 plans keep the
     // decoder tensors as split bf16 planes, which only the bf16x3 tiles read
     bool wino = true;
@@ -240,6 +244,11 @@ struct Level6W {
 static constexpr int LEVEL6_AUTO_MIN_BATCH = 8;   // the smallest batch at which the composed path measured faster (8, 16, 32 tried)
 static constexpr int LEVEL6_SPLIT_MIN_BATCH = 8;  // ... and the split form of conv6.2 / the skip half (8, 16, 32 tried)
 enum { SPLIT6_CONV_B = 1, SPLIT6_SKIP = 2 };      // Plan::l6_split
+// deconv_k2s2_kernel under the automatic rule (profiles/deconv_k2s2_trace_b32_fp32.md): the smallest batch at which it
+// measured faster than the tiled launches (8, 16, 32 tried) - level 2 from 8 samples, level 3 (a tie at 8) from 16; level 4 and up are
+// wider than the kernel's slices
+static constexpr int DECONV_K2S2_MIN_BATCH = 8;
+static constexpr int DECONV_K2S2_MIN_BATCH_L3 = 16;
 struct ccvpe_handle_s;
 struct DecoderW;
 // sizes of a decoder's composed level 6 from its packed descriptors (no device work); != 0: these weights cannot be composed

@@ -517,6 +517,25 @@ static void plan_level6_composed(ccvpe_handle_s* h, Plan& pl, int B, const Level
     }, 0.0, 4.0 * ((double)Mp.numel() + 2.0 * (double)mid.numel()));
 }
 
+// Does the transposed conv of decoder level 6-j run on deconv_k2s2_kernel (CCVPE_DECONV_K2S2)?  fp32 plans whose tensors
+// are fp32, of at least DECONV_K2S2_MIN_BATCH samples (level 3: DECONV_K2S2_MIN_BATCH_L3), where the kernel takes the sizes; fills kp (all
+// but its pointers).  The live input channels follow from the packed layout, not from the weights' values (no device work here): either
+// every channel of the layer, or - a scored level, [score | 7 unused | C] - channel 0 and the channels from 8 on (build_decoder's cmap).
+static bool deconv_k2s2_planned(const ccvpe_handle_s* h, int B, int j, const PackedConv& pc, const DecLevel& l, const Tensor& din, const Tensor& cat, int cw,
+                                DeconvK2S2Params& kp) {
+    if (h->cfg.reserved[0] != 0 || din.split || cat.split || j < 2 || j > 4) return false;   // levels 4 .. 2 (level 1 is fused; levels 6 and 5: the wide tiles)
+    const int sw = h->sw.deconv_k2s2 ? *h->sw.deconv_k2s2 : -1;
+    if (sw == 0 || (sw < 0 && (j < 3 || B < (j == 3 ? DECONV_K2S2_MIN_BATCH_L3 : DECONV_K2S2_MIN_BATCH)))) return false;   // automatic: levels 3 and 2
+    if (pc.N != 4 * cw || pc.cinp <= 0 || pc.cinp > din.C || pc.KH != 1 || pc.KW != 1) return false;
+    std::vector<unsigned char> live(pc.cinp, 1);
+    if (pc.cinp == l.din + score_pad(1) - 1) { for (int c = 1; c < score_pad(1); ++c) live[c] = 0; }
+    else if (pc.cinp != l.din) return false;
+    const int hin = 8 << j;
+    kp.B = B; kp.H = hin; kp.W = hin; kp.Cin = pc.cinp; kp.in_ld = din.C; kp.Kpad = pc.Kpad;
+    kp.ld = cat.C; kp.coff = 0; kp.cw = cw;
+    return deconv_k2s2_prepare(kp, live.data());
+}
+
 // Decoder level 6-j of decoder `dw`: deconv into the concat buffer `cat` (whose skip half the aerial side wrote), conv_a, conv_b.
 // Level 1 (j == 5) returns conv_a's output: its tail conv is the caller's.
 static Tensor plan_level(ccvpe_handle_s* h, Plan& pl, int B, const Level6Form& l6, const DecoderW& dw, const DecLevel* lv, int j, Tensor din, Tensor cat,
@@ -527,7 +546,20 @@ static Tensor plan_level(ccvpe_handle_s* h, Plan& pl, int B, const Level6Form& l
     if (j == 0 && l6.wm) {
         plan_level6_composed(h, pl, B, l6, dw, l, din, mid, tag);
     } else {
-        {
+        const PackedConv* pcd = &dw.deconv[j];
+        const int cwd = deconv_width(l, h->sw.pad_concat);
+        DeconvK2S2Params kp{};
+        const double dflops = 2.0 * B * hin * hin * (double)l.din * 4 * l.dout, dbytes = 4.0 * B * hin * hin * ((double)din.C + 4.0 * l.dout);
+        if (deconv_k2s2_planned(h, B, j, *pcd, l, din, cat, cwd, kp)) {
+            // the transposed conv on its own kernel (kernels_deconv.hip): the launch's name, tensors, FLOPs and bytes are
+            // the tiled launch's; not a registry tile - the tuner and the tuning table do not see it
+            pl.add(tag + ".deconv", {din, cat}, [=](const Ctx& c) {
+                DeconvK2S2Params q = kp;
+                q.x = c.ptr(din); q.wpk = pcd->w; q.bias = pcd->bias; q.out = c.ptr(cat);
+                launch_deconv_k2s2(q, c.stream);
+            }, dflops, dbytes);
+            pl.ops.back().form = "conv_pw_k2s2";
+        } else {
             const PackedConv* pc = &dw.deconv[j];
             const int cout = deconv_width(l, h->sw.pad_concat);   // (columns past l.dout: zero weights and biases, written as zeros)
             pl.add_conv(tag + ".deconv", {din, cat}, B * hin * hin, pc->N, pc->Kpad, [=](const Ctx& c, int tile) {

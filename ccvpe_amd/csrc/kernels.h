@@ -420,6 +420,32 @@ void launch_split6_inverse(const Split6Params& p, hipStream_t s);
 // F(4x4,3x3) filter transform of one (output, input) channel pair in double: u[6 r + q] = (G g G^T)[r][q] (kernels_wino4.hip)
 void conv_wino4_filter(const double g[3][3], double u[36]);
 
+// The decoder's ConvTranspose2d(k2, s2) on a kernel of its own (kernels_deconv.hip): a wave owns 16 input pixels and
+// all four taps (or the two taps of one dy), so every input row is read once (twice); output pixel (2y + dy, 2x + dx) receives tap
+// q = 2 dy + dx.  The K loop walks a host-made list of 4-channel groups: groups whose weights are all zero are not in it, and channels
+// of a listed group whose weights are zero are masked out of the input (whatever they hold) and out of the weights.
+struct DeconvK2S2Params {
+    static constexpr int MAX_GROUPS = 48;   // 192 live input channels
+    const float* x;            // NHWC [B, H, W, in_ld], the first Cin channels used
+    int B, H, W, Cin, in_ld;   // Cin, in_ld: multiples of 4
+    const float* wpk;          // packed weights [>= 4 cw][Kpad], row q * cw + o, column = input channel (PackedConv::w of a 1x1 GEMM)
+    int Kpad;
+    const float* bias;         // [4 cw]
+    float* out;                // NHWC [B, 2H, 2W, ld]: channels [coff, coff + cw) are written
+    int ld, coff, cw;          // ld, coff: multiples of 4; cw: a multiple of 16
+    // deconv_k2s2_prepare:
+    int ngroups;               // listed groups, a multiple of 4 (padded with masked groups)
+    unsigned jmasked;          // bit j: one of the groups 4j .. 4j + 3 has a masked channel
+    unsigned short gch[MAX_GROUPS];   // first channel of group g
+    unsigned char gmask[MAX_GROUPS];  // bit i: channel gch[g] + i is live
+    int taps;                  // 4: one workgroup holds all the weights; 2: those of one dy (grid y = 2)
+    unsigned fdw_mul, fdw_shift, fdh_mul, fdh_shift;   // m / W and (m / W) / H by multiply-shift
+};
+// Fills the group list from live[Cin] (live[c] != 0: some weight of input channel c is not zero; null: every channel is) and chooses
+// the form; false: the kernel does not take these sizes (pointers are not looked at)
+bool deconv_k2s2_prepare(DeconvK2S2Params& p, const unsigned char* live);
+void launch_deconv_k2s2(const DeconvK2S2Params& p, hipStream_t s);
+
 // the angle of the test loops (train_VIGOR.py:307-311) in the fp32 form the post-processing kernels write
 __device__ __forceinline__ float pose_angle_deg(float cs, float sn) {
     float ang = acosf(fminf(fmaxf(cs, -1.f), 1.f)) * 57.29577951308232f;

@@ -1023,6 +1023,17 @@ int ccvpe_op_conv2d_ex(const ccvpe_op_conv_desc* d, void* stream);
 int ccvpe_op_level1(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t score, const float* wd, const float* bd,
                     const float* wa, const float* ba, const float* wt, const float* bt, int32_t Cout, int32_t tile, float* out, void* stream);
 
+/* Kernel-level hook for parity tests (not on the product path): deconv_k2s2_kernel on its own - ConvTranspose2d(k2, s2, Cin -> Cout) of
+ * in [B, H, W, in_ld] (device, NHWC; the first Cin channels are the layer's input, in_ld >= Cin) into channels [coff, coff + cw) of out
+ * [B, 2H, 2W, ld] (device, NHWC; nothing else of it is written).  cw >= Cout: the channels from coff + Cout on are written as zeros, as
+ * a plan's concat buffer has them.  w [Cin,Cout,2,2] and bias [Cout] (or null) in the reference's layouts, host or device; they are
+ * packed by the code that serves ccvpe_create.  Input channels whose weights are all zero are never multiplied: whatever `in` holds
+ * there (NaN included) leaves the result alone.  Sizes the kernel does not take (Cin a multiple of 8; cw a multiple of 16 up to 80; in_ld,
+ * ld, coff multiples of 4; at most 192 input channels with a weight that is not zero; the weights of two taps within the LDS) are
+ * refused with CCVPE_EINVAL.  Returns the taps a workgroup holds (4: every input row is read once; 2: twice), or a negative error code. */
+int ccvpe_op_deconv_k2s2(const float* in, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t in_ld, const float* w, const float* bias, int32_t Cout,
+                         float* out, int32_t ld, int32_t coff, int32_t cw, void* stream);
+
 /* Kernel-level hook (tests): the launches ccvpe_localize runs behind its decoders - softmax partials, the argmax without a prior,
  * posterior or summary, the orientation gather - on logits [batch][512*512] and ori [batch][2][512][512] the caller holds: rows
  * [batch][5], DEVICE memory, the bits ccvpe_postprocess_rows gives on ccvpe_forward's heatmap of those logits.  ccvpe_postprocess_prior
