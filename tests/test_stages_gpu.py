@@ -45,18 +45,28 @@ def stage_check(cfg, batch, precision="fp32", samples=None):
     tiles, names = tiles_and_names(m, g, s)
     print(f"\n{cfg['variant']} circular={cfg['circular']} ori_noise={cfg['ori_noise']} batch={batch} precision={precision} samples={samples}")
     print(sr.format_table(results))
+    assert_global_bounds(results, tiles, precision)
+    return m, g, s, tiles, names
+
+
+def stage_tiles(r, tiles):
+    """(launch name -> tile of the launches of a stage, whether one of them ran an F(4x4) Winograd tile)."""
+    mine = {op: t for op, t in tiles.items() if op in sr.launches_of(r, list(tiles))}
+    return mine, any("wino4" in t for t in mine.values())
+
+
+def assert_global_bounds(results, tiles, precision="fp32"):
+    """Every row of a full stage table under its bound; `tiles`: launch name -> tile of the plan that computed it."""
     # every row of the stage table: 2 x (16 blocks + head), 6 + 1 descriptors, 6 matching levels (ms + max + loc_in, + ori_in6 at level 1),
     # 6 localisation levels, softmax (twice), 6 orientation levels, normalise
     assert len({r.name for r in results}) == len(results) == 2 * 17 + 7 + (6 * 3 + 1) + 6 + 2 + 6 + 1
     bad = []
     for r in results:
-        mine = {op: t for op, t in tiles.items() if op in sr.launches_of(r, list(tiles))}
-        f4 = any("wino4" in t for t in mine.values())
+        mine, f4 = stage_tiles(r, tiles)
         b = sr.bound(r, f4=f4, bf16x3=precision == "bf16x3", factor=FACTORS.get(r.name, sr.REF_FACTOR))
         if not r.e_dev <= b:
             bad.append(f"{r.name} {r.shape}: e_dev {r.e_dev:.3g} > {b:.3g} (e_ref {r.e_ref:.3g}) worst at {r.worst_index}, launches {mine}")
     assert not bad, "\n".join(bad)
-    return m, g, s, tiles, names
 
 
 @pytest.mark.parametrize("name,batch", [("oxford", 1), ("oxford", 3), ("kitti", 2), ("vigor_circ", 1), ("vigor_prior72_fov108", 1),
