@@ -1594,6 +1594,92 @@ int ccvpe_track_joint_smooth(ccvpe_handle h, const float* joint, const float* sm
     return launch_status("track_joint_smooth launch");
 }
 
+// The MAP trajectory of a joint stream: four launches of kernels_track_joint.hip's first kernel and
+// kernels_track_joint_viterbi.hip per frame of the forward sweep (two for a stream's first frame), one per backtracked link, on the
+// caller's stream; the refusals are the joint smoother's, and like it nothing of the handle is used but its device.
+size_t ccvpe_track_joint_viterbi_work_bytes(int32_t batch, int32_t nb) {
+    return batch > 0 && nb >= JOINT_MIN_BINS && nb <= JOINT_MAX_BINS && (int64_t)batch * nb <= JOINT_MAX_SLICES ? track_joint_viterbi_work_bytes(batch, nb) : 0;
+}
+
+// the ranges the step and the link share behind their pointer checks
+static int check_joint_viterbi_motion(int32_t batch, int32_t nb, int32_t taps_stride, int32_t radius, int32_t htaps_stride, int32_t hradius) {
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if (hradius < 0 || hradius > TRACK_MAX_R || 2 * hradius + 1 > nb)
+        return ccvpe_fail(CCVPE_EINVAL, "hradius must be in 0 .. %d with 2 hradius + 1 <= nb = %d, got %d", TRACK_MAX_R, nb, hradius);
+    if (htaps_stride != 0 && htaps_stride != hradius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "htaps_stride must be 0 (one set of taps) or hradius + 1 = %d (one per query), got %d", hradius + 1,
+                          htaps_stride);
+    return 0;
+}
+
+int ccvpe_track_joint_viterbi(ccvpe_handle h, const float* joint, const float* joint_prev, const float* score_prev, const float* prev_stats,
+                              int32_t batch, int32_t nb, const float* shift, const float* taps, int32_t taps_stride, int32_t radius,
+                              const float* turn_deg, const float* htaps, int32_t htaps_stride, int32_t hradius, const float* floor,
+                              void* work, float* score, float* stats, void* stream) {
+    if (!joint) return ccvpe_fail(CCVPE_EINVAL, "null joint");
+    const int given = (joint_prev != nullptr) + (score_prev != nullptr) + (prev_stats != nullptr) + (shift != nullptr);
+    if (given != 0 && given != 4)
+        return ccvpe_fail(CCVPE_EINVAL, "joint_prev, score_prev, prev_stats and shift must be all null (a stream's first frame) or all given");
+    const bool first = given == 0;
+    if (!first) {
+        if (int rc = check_predict_ptrs(joint, "joint", shift, "shift", taps, floor, score, "score")) return rc;
+        if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+        if (!htaps) return ccvpe_fail(CCVPE_EINVAL, "null htaps");
+    }
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (!score) return ccvpe_fail(CCVPE_EINVAL, "null score");
+    if (!stats) return ccvpe_fail(CCVPE_EINVAL, "null stats");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (!first) {
+        if (int rc = check_joint_viterbi_motion(batch, nb, taps_stride, radius, htaps_stride, hradius)) return rc;
+    }
+    const void* in[] = {joint, joint_prev, score_prev, prev_stats, shift, taps, turn_deg, htaps, floor, work};
+    for (const void* q : in)
+        if (q && (q == (const void*)score || q == (const void*)stats))
+            return ccvpe_fail(CCVPE_EINVAL, "score and stats must not alias an input or work");
+    if (score == stats) return ccvpe_fail(CCVPE_EINVAL, "score and stats must not alias each other");
+    if ((const void*)joint == work || (joint_prev && (const void*)joint_prev == work) || (score_prev && (const void*)score_prev == work))
+        return ccvpe_fail(CCVPE_EINVAL, "joint, joint_prev, score_prev and work must not alias each other");
+    if (((uintptr_t)joint | (uintptr_t)joint_prev | (uintptr_t)score_prev | (uintptr_t)work | (uintptr_t)score) & 15)
+        return ccvpe_fail(CCVPE_EINVAL, "joint, joint_prev, score_prev, work and score must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackJointViterbiParams p{};
+    p.joint = joint; p.joint_prev = joint_prev; p.score_prev = score_prev; p.prev_stats = prev_stats; p.shift = shift;
+    if (!first) {
+        p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.turn_deg = turn_deg; p.htaps = htaps; p.htaps_stride = htaps_stride;
+        p.hradius = hradius; p.floor = floor;
+    }
+    p.work = (float*)work; p.score = score; p.stats = stats; p.B = batch; p.nb = nb;
+    launch_track_joint_viterbi(p, (hipStream_t)stream);
+    return launch_status("track_joint_viterbi launch");
+}
+
+int ccvpe_track_joint_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell, const int32_t* bin,
+                                   int32_t batch, int32_t nb, const float* shift, const float* taps, int32_t taps_stride, int32_t radius,
+                                   const float* turn_deg, const float* htaps, int32_t htaps_stride, int32_t hradius, const float* floor,
+                                   int32_t* back, void* stream) {
+    if (int rc = check_predict_ptrs(score_prev, "score_prev", shift, "shift", taps, floor, back, "back")) return rc;
+    if (!prev_stats) return ccvpe_fail(CCVPE_EINVAL, "null prev_stats");
+    if (!cell) return ccvpe_fail(CCVPE_EINVAL, "null cell");
+    if (!bin) return ccvpe_fail(CCVPE_EINVAL, "null bin");
+    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+    if (!htaps) return ccvpe_fail(CCVPE_EINVAL, "null htaps");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (int rc = check_joint_viterbi_motion(batch, nb, taps_stride, radius, htaps_stride, hradius)) return rc;
+    if ((const void*)back == score_prev || (const void*)back == prev_stats || back == cell || back == bin)
+        return ccvpe_fail(CCVPE_EINVAL, "back must not alias score_prev, prev_stats, cell or bin");
+    if ((uintptr_t)score_prev & 15) return ccvpe_fail(CCVPE_EINVAL, "score_prev must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackJointViterbiBackParams p{};
+    p.score_prev = score_prev; p.prev_stats = prev_stats; p.cell = cell; p.bin = bin; p.shift = shift; p.taps = taps; p.taps_stride = taps_stride;
+    p.radius = radius; p.turn_deg = turn_deg; p.htaps = htaps; p.htaps_stride = htaps_stride; p.hradius = hradius; p.floor = floor;
+    p.back = back; p.B = batch; p.nb = nb;
+    launch_track_joint_viterbi_back(p, (hipStream_t)stream);
+    return launch_status("track_joint_viterbi_back launch");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Credible regions: the radix select of kernels_credible.hip over a stored map (ccvpe_belief_credible, on the prior
 // scratch), behind the logits tail on the prior scratch (ccvpe_postprocess_credible), or as pose.credible behind pose.argmax in

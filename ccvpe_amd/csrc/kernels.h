@@ -942,6 +942,55 @@ static constexpr int JOINT_SMOOTH_COLS = 5;
 size_t track_joint_smooth_work_bytes(int B, int nb);
 void launch_track_joint_smooth(const TrackJointSmoothParams& p, hipStream_t s);
 
+// MAP trajectory of a joint stream (ccvpe_track_joint_viterbi, DESIGN.md 4.29, kernels_track_joint_viterbi.hip): per query the
+// max-product score joint of frame t from its filter joint J, the joint J- and the score joint v- of frame t - 1 and the arguments of
+// the launch_track_joint_predict call between the two.  joint_prev, score_prev, prev_stats and shift all null: the first frame of a
+// stream, score = J.  Four launches - launch_track_joint_xy on J-, the win (256 tiles, B * nb), the mix (1024 groups, B), the scale
+// (16 parts, B * nb) - that hand over through `work`: A, win, then the groups' pairs; the first frame runs the last two alone.
+static constexpr int JOINT_VITERBI_COLS = 5;
+struct TrackJointViterbiParams {
+    const float* joint;        // [B][nb][512*512] J
+    const float* joint_prev;   // [B][nb][512*512] J- or null
+    const float* score_prev;   // [B][nb][512*512] v- or null
+    const float* prev_stats;   // [B][JOINT_VITERBI_COLS], the stats of the call that made score_prev, or null
+    const float* shift;        // as TrackJointPredictParams, from here ... (null in the first-frame form)
+    const float* taps;
+    int taps_stride;
+    int radius;
+    const float* turn_deg;
+    const float* htaps;
+    int htaps_stride;
+    int hradius;
+    const float* floor;        // ... to here
+    float* work;               // track_joint_viterbi_work_bytes(B, nb) bytes, written before it is read: any contents
+    float* score;              // [B][nb][512*512], aliasing no input
+    float* stats;              // [B][JOINT_VITERBI_COLS] = (index, bin, peak, exponent, restarted)
+    int B, nb;
+};
+size_t track_joint_viterbi_work_bytes(int B, int nb);
+void launch_track_joint_viterbi(const TrackJointViterbiParams& p, hipStream_t s);
+
+// One link of its backtrack (ccvpe_track_joint_viterbi_back): per query the (cell, bin) of frame t - 1 that the path's (cell, bin) of
+// frame t came from and the link's kind.  One launch, grid (B).
+struct TrackJointViterbiBackParams {
+    const float* score_prev;   // [B][nb][512*512]
+    const float* prev_stats;   // [B][JOINT_VITERBI_COLS]
+    const int* cell;           // [B]; outside [0, 512*512): the backtrack starts here
+    const int* bin;            // [B]; outside [0, nb): likewise
+    const float* shift;        // as TrackJointPredictParams, from here ...
+    const float* taps;
+    int taps_stride;
+    int radius;
+    const float* turn_deg;
+    const float* htaps;
+    int htaps_stride;
+    int hradius;
+    const float* floor;        // ... to here
+    int* back;                 // [B][3] = (previous cell or -1, previous bin or -1, ViterbiLink)
+    int B, nb;
+};
+void launch_track_joint_viterbi_back(const TrackJointViterbiBackParams& p, hipStream_t s);
+
 struct PoseOut { int32_t index; float prob, cos_v, sin_v, angle_deg; };
 static constexpr int PP_MAX_BATCH = 4096;           // samples per launch_postprocess call
 size_t postprocess_scratch_bytes(int B);            // partial (max, index) pairs + one ticket counter per sample (the counters zero before the first launch)

@@ -825,6 +825,76 @@ int ccvpe_track_joint_smooth(ccvpe_handle h, const float* joint, const float* sm
                              int32_t htaps_stride, int32_t hradius, const float* floor, void* work, float* smoothed, float* marginal,
                              float* hist, float* stats, void* stream);
 
+/* The MAP trajectory of a joint stream: the one most probable sequence of (cell, heading bin) - a full (x, y, heading) track, which
+ * neither the argmaxes of T smoothed marginals nor "the best bin there" are.  The model is the joint filter's own transition read as
+ * a latent choice per link: the source bin offset d (which of the 2 hradius + 2 merged circle weights M[d] carried the mass), the
+ * window position under the source bin's shift (as in ccvpe_track_viterbi), or a JUMP through the floor to any state.  One call of
+ * ccvpe_track_joint_viterbi per frame, from the first frame on, builds the score joints; one call of
+ * ccvpe_track_joint_viterbi_back per link, from the last frame back, reads the path off them.  All joints DEVICE float32
+ * [batch][nb][512*512], n = 512*512: `joint` (J) the filter joint of frame t (ccvpe_track_joint_update_logits' joint_out),
+ * `joint_prev` (J-) that of frame t - 1, `score_prev` (v-) the score joint of frame t - 1 and `prev_stats`
+ * [batch][CCVPE_JOINT_VITERBI_COLS] the stats of the call that made it, `score` out.  shift [batch][nb][2], taps, taps_stride,
+ * radius, turn_deg, htaps, htaps_stride, hradius, floor: the arguments of the ccvpe_track_joint_predict call that carried J- into
+ * frame t, with its ranges.  With P(m; d), o, f and M[d] as in that call and ux, uy the merged weights of ccvpe_track_viterbi under
+ * shift[k'], per query, fl() one float32 rounding:
+ *     A(k')      = P(J-[k']; shift[k'])                                  the predict's first launch, unchanged
+ *     prior(k,i) = (fmaf chain of M[d] A((k + o + d) mod nb, i), ascending d) + floor     the bits the predict stores
+ *     lik(k,i)   = J(k,i) > 0 ? J(k,i) / prior(k,i) : 0                  NaN and negative J are not taken
+ *     (jk, j)    = ((int) prev_stats[1], (int) prev_stats[0]) when 0 <= prev_stats[0] < n and 0 <= prev_stats[1] < nb, else none
+ *     win(k',i)  = max over ky of fl(uy[ky] * max over kx of fl(ux[kx] * v-(k', source cell)))      per SOURCE bin, under shift[k']
+ *     mix(k,i)   = max over d = -hradius..hradius+1 of fl(M[d] * win((k + o + d) mod nb, i))
+ *     m(k,i)     = max(mix(k,i), fl(floor * v-(jk, j)))                  move or jump (the jump enters when it is strictly larger)
+ *     w(k,i)     = fl(lik * m);  a w that is not > 0 (NaN included) counts and is stored as 0
+ *     W          = max over (k, i) of w at its first flat index k n + i;  e = the integer with W * 2^-e in [1, 2): one per query
+ *     score      = ldexpf(w, -e)                                         exact unless the result is subnormal
+ *     stats      = (i*, k*, score(k*, i*), e, restarted)                 float32 [5]: cell and bin are separate columns, the flat
+ *                                                                        index reaches 18.9 M at nb 72 and float32 cannot hold that
+ * Every maximum takes its candidates as `c > acc ? c : acc` from acc = 0, so NaN and negatives never enter.  When 2 hradius + 1 == nb
+ * two offsets d reach one source bin with different weights; the maximum takes the larger.
+ *   - First frame: joint_prev, score_prev, prev_stats and shift all NULL.  w = J for J > 0, else 0; the other motion arguments are
+ *     not looked at and may be NULL or 0; restarted = 1.
+ *   - Restart: (jk, j) is none, or v-(jk, j) is not > 0 (the zero joint behind a frame without a finite posterior).  m = 1, so
+ *     w = lik, and restarted = 1; otherwise restarted = 0.
+ *   - Degenerate: W is not > 0 or not finite.  An all-zero score joint and stats (-1, -1, NaN, NaN, restarted).
+ * The recursion has no sum of its own beyond the prior's, and the normalisation is by a power of two.  Relative error against a
+ * float64 evaluation on the same float32 inputs, first order, u = 2^-24: the prior (4 radius + 2 hradius + 18) u, lik one more, a
+ * window candidate 6 u, M[d] 3 u, a mix candidate 10 u, the jump 1 u, w (4 radius + 2 hradius + 30) u; the scaling adds none
+ * (DESIGN.md 4.29).  Queries are independent: a query under any of the rules leaves its neighbours' bits unchanged; no launch reads
+ * outside its tensors whatever the inputs hold (the predict's clamps of the shifts and of the turn's integer part, and a guarded
+ * (jk, j)); the same inputs give the same bits on every call, alone as in a batch.  `work`:
+ * ccvpe_track_joint_viterbi_work_bytes(batch, nb) bytes of DEVICE memory (pure host arithmetic; 0 outside the ranges), 16-byte
+ * aligned, any contents: two joint-sized buffers (A and win) and the 1024 group maxima per query.  Four launches per step - the
+ * predict's first launch on J-, the window maxima, the mix, the scale - and two, the last two, in the first-frame form; the joint
+ * moves through memory ten times (2 + 2 + 4 + 2).  The call allocates nothing, synchronises nothing and uses no scratch of the
+ * handle.  CCVPE_EINVAL, nothing launched, checked before the handle is used: a null joint, work, score or stats; a mix of NULL and
+ * non-NULL among joint_prev, score_prev, prev_stats and shift; outside the first-frame form a null taps, turn_deg, htaps or floor,
+ * radius or hradius out of range, a bad taps_stride or htaps_stride; nb outside 4..72, batch * nb above 32768; score or stats
+ * equal to an input, to work or to each other (the step reads halos of its inputs: it cannot run in place); a joint or work that
+ * is not 16-byte aligned.
+ *
+ * Backtrack of one link: `cell`, `bin` DEVICE int32 [batch], the path's pair at frame t; back DEVICE int32 [batch][3] out =
+ * (previous cell, previous bin, kind), kind MOVE = 0, JUMP = 1, START = 2; the other arguments as above.
+ *   - cell outside [0, n) or bin outside [0, nb): (j, jk, START), or (-1, -1, START) where (jk, j) is none - the end of a
+ *     backtrack, or the frame behind a broken one.
+ *   - otherwise (jk, j) none: (-1, -1, START).
+ *   - otherwise the candidates are fl(M[d] * fl(uy * fl(ux * v-(k', g)))) over d and the (2 radius + 2)^2 source cells g of `cell`
+ *     in the window of k' = (bin + o + d) mod nb under shift[k'] that lie inside the grid; the largest wins, the smallest flat source
+ *     index k' n + g on ties, NaN never; jump = fl(floor * v-(jk, j)).  Neither the best candidate nor jump > 0: (j, jk, START).
+ *     jump strictly larger than the best candidate: (j, jk, JUMP).  Otherwise (g, k', MOVE) of the best candidate.
+ * Rounding is monotone and all factors are non-negative, so the best candidate's value is mix(bin, cell) bit for bit.  One launch,
+ * one workgroup per query, every read guarded.  CCVPE_EINVAL as above: a null pointer, the range and stride rules, back equal to
+ * an input, a score_prev that is not 16-byte aligned. */
+#define CCVPE_JOINT_VITERBI_COLS 5
+size_t ccvpe_track_joint_viterbi_work_bytes(int32_t batch, int32_t nb);
+int ccvpe_track_joint_viterbi(ccvpe_handle h, const float* joint, const float* joint_prev, const float* score_prev,
+                              const float* prev_stats, int32_t batch, int32_t nb, const float* shift, const float* taps,
+                              int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps, int32_t htaps_stride,
+                              int32_t hradius, const float* floor, void* work, float* score, float* stats, void* stream);
+int ccvpe_track_joint_viterbi_back(ccvpe_handle h, const float* score_prev, const float* prev_stats, const int32_t* cell,
+                                   const int32_t* bin, int32_t batch, int32_t nb, const float* shift, const float* taps,
+                                   int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps,
+                                   int32_t htaps_stride, int32_t hradius, const float* floor, int32_t* back, void* stream);
+
 /* Credible regions: the smallest set of cells holding a share of the posterior (the highest-density region of a histogram
  * posterior).  Per query, over the n = 512 * 512 cells of a float32 map h - ccvpe_belief_credible: the map given; the other forms:
  * the posterior h' of the prior forms, the map ccvpe_track_update* stores (all zero for a query without a finite posterior):
