@@ -140,6 +140,9 @@ SYMBOLS = [
     ("ccvpe_track_joint_work_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
     ("ccvpe_track_joint_predict", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("ccvpe_track_joint_predict_affine", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
     ("ccvpe_track_joint_update_logits", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ccvpe_track_joint_smooth_work_bytes", C.c_size_t, [C.c_int32, C.c_int32]),

@@ -904,3 +904,99 @@ class JointTracker:
         if credible_levels is not None:
             res += (model.belief_credible(marginal, credible_levels),)
         return res
+
+
+# ---- the joint filter across rotated or rescaled frames -----------------------------------------------------------
+
+def matrix_rotation_deg(matrix) -> np.ndarray:
+    """rigid_matrix's rotation_deg recovered from an OUTPUT -> SOURCE index map ([6] -> a float64 number, [B,6] -> [B]), in
+    (-180, 180]: atan2(m3 - m1, m0 + m4), the content's counter-clockwise turn as displayed.  Exact (to rounding) for similarities -
+    rigid_matrix with any scale and shift, kitti_track_matrix.  For a sheared or unevenly scaled matrix of positive determinant it
+    is the rotation of the polar part: the linear part factors into a rotation times a symmetric positive definite stretch, and this
+    is that rotation's angle - the turn nearest to the map.  A matrix whose m3 - m1 and m0 + m4 are both zero (the zero matrix, a
+    pure reflection) has no such angle and gives 0."""
+    m = _affine(matrix)
+    return np.degrees(np.arctan2(m[..., 3] - m[..., 1], m[..., 0] + m[..., 4])) + 0.0
+
+
+def joint_matrix_table(matrix, shift_table) -> np.ndarray:
+    """The matrix table of model.track_joint_predict_affine, float64 [B, nb, 6], from the frame change and a body-frame motion.
+    matrix ([6] or [B,6]): this frame's pixel index -> the position in the LAST frame's grid it shows - rigid_matrix or
+    kitti_track_matrix with the vehicle's own motion left out, the frame change alone.  shift_table [B, nb, 2] ([nb, 2]: one
+    query): joint_shift_table's output in the LAST frame's pixels and heading labels.  Content with source heading k sits at p_old
+    in the old grid and moves to p_old + d[k] there, so the source of an output pixel is M(p_out) - d[k]: entries 2 and 5 become
+    m2 - dx[k] and m5 - dy[k], the other four are copied."""
+    m = _affine(matrix)
+    d = np.asarray(shift_table, dtype=np.float64)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3 or d.shape[-1] != 2:
+        raise ValueError(f"shift_table must be [B,nb,2], got {d.shape}")
+    if not np.isfinite(d).all():
+        raise ValueError("shift_table must be finite")
+    m = m.reshape(-1, 6)
+    B = max(m.shape[0], d.shape[0])
+    if m.shape[0] not in (1, B) or d.shape[0] not in (1, B):
+        raise ValueError(f"matrix holds {m.shape[0]} rows, shift_table {d.shape[0]}: 1 or {B} each")
+    out = np.broadcast_to(m[:, None, :], (B, d.shape[1], 6)).copy()
+    out[..., 2] -= d[..., 0]
+    out[..., 5] -= d[..., 1]
+    return out
+
+
+class AffineJointTracker:
+    """JointTracker for frames whose aerial grids differ by more than a translation (KITTI's heading-up tiles): holds the joint
+    posterior of the last frame (a device tensor [B,nb,512,512]).  step() = the forward, model.track_joint_predict_affine (every
+    heading bin read through the frame change and moved by the body-frame odometry as that heading sees it, the bins turned, both
+    blurred, floored) and model.track_joint_update_logits; the first step has no prior."""
+
+    def __init__(self):
+        self.joint = None     # joint posterior of the last frame, or None before the first step
+
+    def reset(self) -> None:
+        self.joint = None
+
+    def step(self, model, grd, emission, matrix, forward_px, left_px, turn_deg, taps, heading_taps, floor, sat=None, cache=None,
+             tile_index=None, zero_deg: float = 0.0, clockwise: bool = False, summary_radius=None, credible_levels=None):
+        """One frame of B parallel streams.  The aerial side is sat (model.forward) or cache / tile_index (model.forward_cached).
+        matrix [6] or [B,6]: this frame's pixel index -> the position in the LAST frame's grid it shows, the frame change alone
+        (rigid_matrix, kitti_track_matrix with the vehicle's own motion left out; ignored by the first step).  forward_px, left_px
+        (numbers or [B]): the body-frame motion since the last step in pixels of the LAST frame's grid, as the last frame's heading
+        labels see it - the predict reads every source bin through joint_matrix_table(matrix, joint_shift_table(forward_px,
+        left_px, nb, zero_deg, clockwise)).  turn_deg (a number or [B]): the vehicle's change of heading label ALONE.  The
+        orientation field is expressed in each frame's own grid, so the labels also change by the rotation between the two grids;
+        this step adds that part itself, + matrix_rotation_deg(matrix) for counter-clockwise labels and - for clockwise ones.  That
+        differs from AffineTracker.step, whose heading_turn_deg must already be the sum: do not add the grid's rotation here.
+        emission, taps, heading_taps, floor, zero_deg, clockwise, summary_radius, credible_levels: as JointTracker.step.  Returns
+        what JointTracker.step returns: (rows [B,5], marginal [B,512,512], hist [B,nb]), then model.belief_summary and
+        model.belief_credible of the marginal where asked for."""
+        if (sat is None) == (cache is None):
+            raise ValueError("give this frame's aerial side as sat or as cache, one of the two")
+        if sat is not None and tile_index is not None:
+            raise ValueError("tile_index belongs to a cache")
+        B = grd.shape[0]
+        nb = int(np.shape(emission)[-1]) - 1
+        out = model.forward(grd, sat) if cache is None else model.forward_cached(grd, cache, tile_index=tile_index)
+        logits, ori = out[0], out[2]
+        prior = None
+        if self.joint is not None:
+            if tuple(self.joint.shape[:2]) != (B, nb):
+                raise ValueError(f"the tracker holds a joint of shape {tuple(self.joint.shape[:2])}, this step has {B} streams of {nb} bins")
+            table = joint_matrix_table(matrix, joint_shift_table(forward_px, left_px, nb, zero_deg, clockwise))
+            grid = matrix_rotation_deg(matrix)
+            grid = -grid if clockwise else grid
+            if hasattr(turn_deg, "data_ptr"):            # a tensor: the sum is formed where it lives
+                import torch
+                turn = turn_deg + torch.as_tensor(grid, dtype=turn_deg.dtype, device=turn_deg.device)
+            else:
+                turn = np.asarray(turn_deg, dtype=np.float64) + grid
+                turn = float(turn) if turn.ndim == 0 else turn
+            prior = model.track_joint_predict_affine(self.joint, np.broadcast_to(table, (B, nb, 6)), taps, floor, turn, heading_taps)
+        # in place: the prior is this step's alone
+        rows, self.joint, marginal, hist = model.track_joint_update_logits(logits, ori, emission, prior, out=prior)
+        res = (rows, marginal, hist)
+        if summary_radius is not None:
+            res += (model.belief_summary(marginal, summary_radius),)
+        if credible_levels is not None:
+            res += (model.belief_credible(marginal, credible_levels),)
+        return res

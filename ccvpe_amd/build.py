@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libccvpe_hip.so")
 STAMP = os.path.join(CSRC, ".libccvpe_hip.stamp")
-SOURCES = ["ccvpe_api.hip", "ccvpe_weights.hip", "ccvpe_plan.hip", "ccvpe_tune.hip", "kernels_igemm.hip", "kernels_igemm_bf16x3.hip", "kernels_wino.hip", "kernels_wino4.hip", "kernels_wino4x.hip", "kernels_encoder.hip", "kernels_match.hip", "kernels_tail.hip", "kernels_heading.hip", "kernels_hprior.hip", "kernels_credible.hip", "kernels_track.hip", "kernels_track_affine.hip", "kernels_track_smooth.hip", "kernels_track_smooth_affine.hip", "kernels_track_link.hip", "kernels_track_viterbi.hip", "kernels_track_viterbi_affine.hip", "kernels_track_joint.hip", "kernels_track_joint_smooth.hip", "kernels_track_joint_viterbi.hip", "kernels_level1.hip", "kernels_level6.hip", "kernels_mbconv.hip", "kernels_preproc.hip", "kernels_warp.hip", "kernels_pw.hip", "kernels_deconv.hip", "kernels_proj.hip", "kernels_mbimg.hip"]
+SOURCES = ["ccvpe_api.hip", "ccvpe_weights.hip", "ccvpe_plan.hip", "ccvpe_tune.hip", "kernels_igemm.hip", "kernels_igemm_bf16x3.hip", "kernels_wino.hip", "kernels_wino4.hip", "kernels_wino4x.hip", "kernels_encoder.hip", "kernels_match.hip", "kernels_tail.hip", "kernels_heading.hip", "kernels_hprior.hip", "kernels_credible.hip", "kernels_track.hip", "kernels_track_affine.hip", "kernels_track_smooth.hip", "kernels_track_smooth_affine.hip", "kernels_track_link.hip", "kernels_track_viterbi.hip", "kernels_track_viterbi_affine.hip", "kernels_track_joint.hip", "kernels_track_joint_smooth.hip", "kernels_track_joint_viterbi.hip", "kernels_track_joint_affine.hip", "kernels_level1.hip", "kernels_level6.hip", "kernels_mbconv.hip", "kernels_preproc.hip", "kernels_warp.hip", "kernels_pw.hip", "kernels_deconv.hip", "kernels_proj.hip", "kernels_mbimg.hip"]
 HEADERS = ["kernels.h", "ticket.h", "tail_shared.h", "track_blur.h", "track_maxmul.h", "track_smooth_work.h", "igemm_common.h", "ccvpe_internal.h", "kernels_level1_tile.inc", os.path.join("..", "..", "include", "ccvpe.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  kernels_match.hip: hipcc's SLP vectoriser fuses the dot-product and norm accumulators of match_kernel
@@ -29,14 +29,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # form (fewer instructions, no moves) is the faster one.
 # kernels_level6.hip: its transform kernels are the same kind of code as kernels_wino4.hip's.
 # kernels_track.hip, kernels_track_affine.hip, kernels_track_smooth.hip, kernels_track_smooth_affine.hip, kernels_track_link.hip,
-# kernels_track_viterbi.hip, kernels_track_viterbi_affine.hip, kernels_track_joint.hip, kernels_track_joint_smooth.hip, kernels_track_joint_viterbi.hip (the ten files that include track_blur.h): the SLP vectoriser
+# kernels_track_viterbi.hip, kernels_track_viterbi_affine.hip, kernels_track_joint.hip, kernels_track_joint_smooth.hip, kernels_track_joint_viterbi.hip, kernels_track_joint_affine.hip (the eleven files that include track_blur.h): the SLP vectoriser
 # packs the blur passes' accumulators into v_pk_fma_f32 with the op_sel encoding above.
 EXTRA_FLAGS = {"kernels_match.hip": ["-fno-slp-vectorize"], "kernels_track.hip": ["-fno-slp-vectorize"], "kernels_track_affine.hip": ["-fno-slp-vectorize"],
                "kernels_track_smooth.hip": ["-fno-slp-vectorize"], "kernels_track_smooth_affine.hip": ["-fno-slp-vectorize"],
                "kernels_track_link.hip": ["-fno-slp-vectorize"],
                "kernels_track_viterbi.hip": ["-fno-slp-vectorize"], "kernels_track_viterbi_affine.hip": ["-fno-slp-vectorize"],
                "kernels_track_joint.hip": ["-fno-slp-vectorize"], "kernels_track_joint_smooth.hip": ["-fno-slp-vectorize"],
-               "kernels_track_joint_viterbi.hip": ["-fno-slp-vectorize"],
+               "kernels_track_joint_viterbi.hip": ["-fno-slp-vectorize"], "kernels_track_joint_affine.hip": ["-fno-slp-vectorize"],
                "kernels_wino4.hip": ["-fno-slp-vectorize"], "kernels_wino4x.hip": ["-fno-slp-vectorize"], "kernels_level6.hip": ["-fno-slp-vectorize"]}
 
 

@@ -1509,6 +1509,34 @@ int ccvpe_track_joint_predict(ccvpe_handle h, const float* joint, int32_t batch,
     return launch_status("track_joint_predict launch");
 }
 
+// The same step under an affine map per source heading bin: the checks of ccvpe_track_joint_predict in their order, the
+// matrix in the shift's place; always the affine kernel, as ccvpe_track_predict_affine.
+int ccvpe_track_joint_predict_affine(ccvpe_handle h, const float* joint, int32_t batch, int32_t nb, const double* matrix, const float* taps,
+                                     int32_t taps_stride, int32_t radius, const float* turn_deg, const float* htaps, int32_t htaps_stride,
+                                     int32_t hradius, const float* floor, void* work, float* prior, void* stream) {
+    if (int rc = check_predict_ptrs(joint, "joint", matrix, "matrix", taps, floor, prior, "prior")) return rc;
+    if (!turn_deg) return ccvpe_fail(CCVPE_EINVAL, "null turn_deg");
+    if (!htaps) return ccvpe_fail(CCVPE_EINVAL, "null htaps");
+    if (!work) return ccvpe_fail(CCVPE_EINVAL, "null work");
+    if (int rc = check_joint_shape(batch, nb)) return rc;
+    if (int rc = check_predict_blur(radius, taps_stride, batch)) return rc;
+    if (hradius < 0 || hradius > TRACK_MAX_R || 2 * hradius + 1 > nb)
+        return ccvpe_fail(CCVPE_EINVAL, "hradius must be in 0 .. %d with 2 hradius + 1 <= nb = %d, got %d", TRACK_MAX_R, nb, hradius);
+    if (htaps_stride != 0 && htaps_stride != hradius + 1)
+        return ccvpe_fail(CCVPE_EINVAL, "htaps_stride must be 0 (one set of taps) or hradius + 1 = %d (one per query), got %d", hradius + 1,
+                          htaps_stride);
+    if (prior == joint || (const void*)prior == work || (const void*)joint == work)
+        return ccvpe_fail(CCVPE_EINVAL, "joint, work and prior must not alias each other");
+    if (((uintptr_t)joint | (uintptr_t)work | (uintptr_t)prior) & 15) return ccvpe_fail(CCVPE_EINVAL, "joint, work and prior must be 16-byte aligned");
+    if (!h) return ccvpe_fail(CCVPE_EINVAL, "null handle");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    TrackJointPredictAffineParams p{};
+    p.joint = joint; p.matrix = matrix; p.taps = taps; p.taps_stride = taps_stride; p.radius = radius; p.turn_deg = turn_deg; p.htaps = htaps;
+    p.htaps_stride = htaps_stride; p.hradius = hradius; p.floor = floor; p.work = (float*)work; p.prior = prior; p.B = batch; p.nb = nb;
+    launch_track_joint_predict_affine(p, (hipStream_t)stream);
+    return launch_status("track_joint_predict_affine launch");
+}
+
 int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const float* ori, int32_t batch, const float* prior,
                                     const float* emission, int32_t emission_stride, int32_t nb, float* rows, float* joint_out,
                                     float* marginal, float* hist, void* stream) {

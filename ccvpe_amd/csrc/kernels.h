@@ -915,6 +915,30 @@ void launch_track_joint_update(const TrackJointUpdateParams& p, hipStream_t s);
 // bits.  p.prior is not used.
 void launch_track_joint_xy(const TrackJointPredictParams& p, hipStream_t s);
 
+// The second launch of the predict alone, on a `work` that already holds A: the affine predict (kernels_track_joint_affine.hip) ends
+// with it, so its heading mix is the predict's bit for bit.  p.joint, p.shift, p.taps, p.taps_stride and p.radius are not used.
+void launch_track_joint_mix(const TrackJointPredictParams& p, hipStream_t s);
+
+// The predict under an affine map per SOURCE heading bin (ccvpe_track_joint_predict_affine, DESIGN.md 4.30,
+// kernels_track_joint_affine.hip): launch_track_predict_affine's c of every slice under its own matrix into `work` - grid (256 tiles,
+// B * nb) - then launch_track_joint_mix.  Two launches.
+struct TrackJointPredictAffineParams {
+    const float* joint;        // [B][nb][512*512]
+    const double* matrix;      // [B][nb][6] output index -> source index position of every SOURCE bin
+    const float* taps;         // as TrackPredictParams
+    int taps_stride;
+    int radius;                // 0 .. TRACK_MAX_R
+    const float* turn_deg;     // as TrackJointPredictParams, from here ...
+    const float* htaps;
+    int htaps_stride;
+    int hradius;
+    const float* floor;
+    float* work;
+    float* prior;              // ... to here
+    int B, nb;
+};
+void launch_track_joint_predict_affine(const TrackJointPredictAffineParams& p, hipStream_t s);
+
 // The backward step of the joint filter (ccvpe_track_joint_smooth, DESIGN.md 4.27, kernels_track_joint_smooth.hip): the smoothed joint
 // of frame t from the stored filter joint J, the smoothed joint s' of frame t + 1 and the arguments of the predict that carried J
 // into frame t + 1.  Five launches - launch_track_joint_xy, the ratio (1024 groups, B), the weight (256 tiles, B * nb), the scale

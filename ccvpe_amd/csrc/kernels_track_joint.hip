@@ -123,6 +123,15 @@ void launch_track_joint_xy(const TrackJointPredictParams& p, hipStream_t s) {
     CCVPE_LAUNCH(track_joint_xy_kernel, dim3(TRACK_TILES, p.B * p.nb), dim3(256), lds, s, p);
 }
 
+void launch_track_joint_mix(const TrackJointPredictParams& p, hipStream_t s) {
+    const size_t mix_lds = joint_mix_lds_bytes(p.nb, p.hradius);
+    // the kernel's largest size, asked for on every call: launch_track_joint_predict keeps a record of its own for this kernel, so a
+    // smaller request from either side after a larger one from the other would leave a record stale
+    LdsAttr mix_attr;
+    ensure_dynamic_lds(mix_attr, reinterpret_cast<const void*>(track_joint_mix_kernel), joint_mix_lds_bytes(JOINT_MAX_BINS, TRACK_MAX_R));
+    CCVPE_LAUNCH(track_joint_mix_kernel, dim3(JOINT_MIX_GROUPS, p.B), dim3(256), mix_lds, s, p);
+}
+
 // ---- update ----------------------------------------------------------------------------------------------------------------------
 
 size_t track_joint_scratch_bytes(int B) {

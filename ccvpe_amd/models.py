@@ -323,6 +323,62 @@ class _JointFilter:
                             (joint, B, nb, sh, tp, stride, radius, tn, ht, (rh + 1) if len(hshape) == 2 else 0, rh, fl, work),
                             _JointResults((_slot(nb, *spec.OUT_HW),), {0: out}))
 
+    def track_joint_predict_affine(self, joint: torch.Tensor, matrix, taps, floor, turn_deg, heading_taps, out: Optional[torch.Tensor] = None
+                                   ) -> torch.Tensor:
+        """track_joint_predict across frames whose grids differ by more than a translation: the map of every SOURCE
+        heading bin k is read through its own affine map matrix[b, k] - OUTPUT pixel index -> SOURCE index position, bilinear
+        weights, times |m0 m4 - m1 m3|, as track_predict_affine reads a belief - in place of a shift; the xy blur, the turn of the
+        bins, the blur on the circle and the floor are track_joint_predict's (the definition in include/ccvpe.h,
+        ccvpe_track_joint_predict_affine).  matrix is [B, nb, 6], or [nb, 6] for one table shared by every query
+        (aerial.joint_matrix_table): host data, which must be finite, or a float64 tensor on the joint's device, which is not looked
+        at (non-finite entries there may give NaN, never a read outside the joint).  joint, taps, floor, turn_deg, heading_taps and
+        out as in track_joint_predict; turn_deg is the change of the heading label between the two grids, the rotation of the grid
+        included (aerial.AffineJointTracker adds it).  Two launches, always the affine kernel: the matrices (1, 0, -dx, 0, 1, -dy)
+        are track_joint_predict's shifts (dx, dy), bit for bit at integer shifts."""
+        self._require_eval()
+        B, nb = self._joint_maps(joint, "joint")
+        tshape, stride, radius, number = self._blur_checks(taps, floor, B)
+        hshape = tuple(heading_taps.shape) if isinstance(heading_taps, (torch.Tensor, np.ndarray)) else np.shape(heading_taps)
+        if len(hshape) not in (1, 2) or hshape[-1] < 1 or (len(hshape) == 2 and hshape[0] != B):
+            raise ValueError(f"heading_taps must be [rh+1] or [{B}, rh+1], got {tuple(hshape)}")
+        rh = int(hshape[-1]) - 1
+        if rh > 32 or 2 * rh + 1 > nb:
+            raise ValueError(f"heading_taps give radius {rh}, must be in 0..32 with 2 radius + 1 <= nb = {nb}")
+        if out is not None:
+            self._joint_maps(out, "out", nb, B)
+            if out.data_ptr() == joint.data_ptr():
+                raise ValueError("out must not be the joint")
+        dev = joint.device
+        # shapes and values first (so that they are refused without a device), then the copies
+        on_device = isinstance(matrix, torch.Tensor) and matrix.device.type != "cpu"
+        if on_device:
+            mt = matrix.detach()
+            if mt.dtype != torch.float64:
+                raise ValueError(f"matrix on the device must be float64, got {mt.dtype}")
+        else:
+            # (a copy: a broadcast table, as aerial.AffineJointTracker passes one, is a read-only view)
+            mt = torch.as_tensor(np.array(matrix.detach().numpy() if isinstance(matrix, torch.Tensor) else matrix, dtype=np.float64))
+        if tuple(mt.shape) not in ((nb, 6), (B, nb, 6)):
+            raise ValueError(f"matrix must be [{nb}, 6] or [{B}, {nb}, 6], got {tuple(mt.shape)}")
+        if not on_device and not bool(torch.isfinite(mt).all()):
+            raise ValueError("matrix must be finite")
+        tp = self._track_vec(taps, "taps", tshape, dev)
+        ht = self._track_vec(heading_taps, "heading_taps", hshape, dev)
+        tn = self._per_query(turn_deg, np.ndim(turn_deg) == 0 and not isinstance(turn_deg, torch.Tensor), "turn_deg", B, dev)
+        fl = self._per_query(floor, number, "floor", B, dev)
+        if not joint.is_cuda:
+            raise ValueError(f"joint must be a cuda tensor, not a {joint.device.type} tensor")
+        if out is not None and out.device != dev:
+            raise ValueError(f"out is on {out.device}, joint on {dev}")
+        if on_device and mt.device != dev:
+            raise ValueError(f"matrix is on {mt.device}, joint on {dev}")
+        mt = mt.expand(B, nb, 6).to(dev).contiguous()
+        self._ensure_handle(dev)
+        work = self._joint_work(dev, _lib.load().ccvpe_track_joint_work_bytes(B, nb))
+        return self._launch("track_joint_predict_affine", dev, B,
+                            (joint, B, nb, mt, tp, stride, radius, tn, ht, (rh + 1) if len(hshape) == 2 else 0, rh, fl, work),
+                            _JointResults((_slot(nb, *spec.OUT_HW),), {0: out}))
+
     def track_joint_update_logits(self, logits: torch.Tensor, ori: torch.Tensor, emission, prior: Optional[torch.Tensor] = None,
                                   out: Optional[torch.Tensor] = None):
         """The update half of a joint filter step, from forward outputs the caller holds (logits [B, 512*512], ori [B, 2, 512, 512]):

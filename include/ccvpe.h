@@ -779,6 +779,28 @@ int ccvpe_track_joint_update_logits(ccvpe_handle h, const float* logits, const f
                                     const float* emission, int32_t emission_stride, int32_t nb, float* rows, float* joint_out,
                                     float* marginal, float* hist, void* stream);
 
+/* The joint predict across frames whose grids differ by more than a translation (KITTI's heading-up tiles): every SOURCE heading bin
+ * is carried through an affine map of its own.  matrix is float64 DEVICE memory [batch][nb][6]: matrix[b][k'] maps an OUTPUT pixel
+ * index to the SOURCE index position that bin k' reads, in the convention of ccvpe_track_predict_affine.  In the intended use the
+ * matrices of a query share their linear part - the frame change - and differ in the translation column alone - the motion as each
+ * heading sees it; nothing here assumes that.  Every other argument, with its range, is ccvpe_track_joint_predict's; work is
+ * ccvpe_track_joint_work_bytes(batch, nb) bytes; prior aliases neither joint nor work.  Per query
+ *     A(k', .)   = the map c of ccvpe_track_predict_affine for the belief joint[k'], the matrix matrix[k'] and taps
+ *                  (|det| included, the same arithmetic, before floor and log)
+ *     prior(k,i) = ccvpe_track_joint_predict's C(k, i) + floor over these A: o, f, M[d], the fmaf chain in ascending d, unchanged
+ * so the matrices (1, 0, -dx[k'], 0, 1, -dy[k']) with integer shifts give ccvpe_track_joint_predict's bits, and one matrix for every
+ * bin with hradius 0, turn 0 and htaps (1) gives exp of ccvpe_track_predict_affine's map, slice by slice.  Every term is
+ * non-negative: prior is within (4 radius + 2 hradius + 18) * 2^-24 of the exact value on the same float32 inputs, plus
+ * ccvpe_track_predict_affine's coordinate term 2^-38 max(joint of the query).  No matrix, NaN included, moves a read outside joint:
+ * the integer parts are clamped before they are converted and every read is bounds-checked; the turn is clamped as above.  A
+ * singular matrix gives A = 0 for its bin.  Two launches on the caller's stream - the affine sampling and the xy blur of every
+ * slice, grid (256 tiles, batch * nb), then ccvpe_track_joint_predict's heading mix -, no atomics: the same inputs give the same
+ * bits, alone as in a batch.  CCVPE_EINVAL as ccvpe_track_joint_predict, in its order, `matrix` in the place of `shift`. */
+int ccvpe_track_joint_predict_affine(ccvpe_handle h, const float* joint, int32_t batch, int32_t nb, const double* matrix,
+                                     const float* taps, int32_t taps_stride, int32_t radius, const float* turn_deg,
+                                     const float* htaps, int32_t htaps_stride, int32_t hradius, const float* floor,
+                                     void* work, float* prior, void* stream);
+
 /* Smoothing a joint stream: the backward half of the joint filter.  One call per frame, from the last frame back, turns the stored
  * joints into p(cell, heading bin | frames 1..T).  `joint` J is the stored filter joint of frame t (ccvpe_track_joint_update_logits'
  * joint_out), `smoothed_next` s' the smoothed joint of frame t + 1 (for the last frame but one: the last frame's own J), both DEVICE
